@@ -18,6 +18,16 @@ Prints ONE JSON line on rank 0 with the contract's fields plus
                  clock); the headline fields are those of the dominant kernel
   cpu_baseline : the CPU oracle (C port of the reference path) on a bounded sample of the same workload
   parity       : HIP vs that CPU render of the same pixels/samples/seed (per-pixel L2 -> relMSE, max abs)
+
+`--dump-outputs DIR` writes, after the timed steps, what a caller of the timed renderer receives from it (rank 0, whole film):
+  image.npy    : (W, H, 3) float32, linear radiance = accumulation / samples per pixel (`Renderer.pixels.to_numpy()`)
+  accum.npy    : (W, H, 3) float32, the accumulation itself (`Renderer.color.to_numpy()`)
+  counters.npy : (9,) float64, the path's event counts summed over ranks, in the order of COUNTER_KEYS
+  nonfinite.npy: (W, H, 3) float32, 1 where image / accum held a non-finite value, which is written there as 0
+The path keeps upstream's +-inf samples (the zero-pdf knife edge): a few components of a long render are infinite, and the
+dump records where instead of writing them, so that every file is finite and two builds compare entry for entry.
+The timed region starts from a cleared renderer (sample counter 0, seed 0), so with the same arguments the inputs are identical from
+run to run, whatever `--warmup` is.  The largest film (c5, 1280x720) makes 33 MB.
 """
 import argparse
 import glob
@@ -39,6 +49,7 @@ BAND_WIDTH = 4
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 ROUND = 6                       # profiles/r0<ROUND>_<config>_counters.json: PMC figures of THIS round's kernels
 STAGES = ("extend", "shade", "shadow")
+COUNTER_KEYS = ("n_samples", "n_extend", "n_shade", "n_shadow", "n_shadow_traced", "n_lit", "n_draws", "n_poisoned", "n_track")
 
 CONFIGS = {
     # name: (scene dir, file, width, height, spp, max_bounce, label)
@@ -69,6 +80,13 @@ def load_scene(sdir, sfile):
         return scene_parsing(os.path.join(ROOT, "scenes", sdir), sfile)
     finally:
         os.chdir(cwd)
+
+
+def finite_outputs(image, accum):
+    """--dump-outputs: (image, accum, nonfinite) with every component that is non-finite in either array set to 0 in both, and
+    the float32 mask of those components."""
+    bad = ~(np.isfinite(image) & np.isfinite(accum))
+    return np.where(bad, np.float32(0), image), np.where(bad, np.float32(0), accum), bad.astype(np.float32)
 
 
 def csrc_sha256():
@@ -216,11 +234,17 @@ def main():
     ap.add_argument("--no-profile", action="store_true", help="skip the repeat of the timed region with per-launch HIP events (the timed region itself never carries them) and the exclusive pass")
     ap.add_argument("--strict-profiles", action="store_true", help="fail if profiles/r0N_<config>_counters.json is missing or was taken on other kernels")
     ap.add_argument("--dump-image", default="", help="rank 0 writes the gathered (W, H, 3) accumulation of the timed region to this .npy file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write image.npy, accum.npy, counters.npy and nonfinite.npy of the timed renderer into DIR "
+                    "(see the module docstring)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for dry runs)")
     ap.add_argument("--single-device", action="store_true", help="dry run: every rank renders on cuda:0 (use with --backend gloo on a one-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dump_image:
         args.dump_image = os.path.abspath(args.dump_image)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     os.chdir(ROOT)                  # texture / .vol paths inside scene files are relative to the repository root (rocprofv3 runs from /tmp)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -338,6 +362,23 @@ def main():
             np.save(args.dump_image, assemble(rdr.plan, (g.cpu() if hasattr(g, "cpu") else g).numpy()))
         else:
             np.save(args.dump_image, rdr.tile_accum())
+    if args.dump_outputs:
+        counts = np.float64([st[k] for k in COUNTER_KEYS])
+        if dist is not None:
+            c = torch.from_numpy(counts).to(f"cuda:{local_rank}" if args.backend == "nccl" else "cpu")
+            dist.all_reduce(c)
+            counts = c.cpu().numpy()
+        if rank == 0:
+            if world > 1:
+                g = gathered[0]
+                accum = assemble(rdr.plan, (g.cpu() if hasattr(g, "cpu") else g).numpy())
+                image = accum / np.float32(rdr.cnt[None])            # what Renderer.pixels gives a sharded caller (tiles.gather_image)
+            else:
+                accum, image = rdr.color.to_numpy(), rdr.pixels.to_numpy()
+            image, accum, nonfinite = finite_outputs(image, accum)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in (("image", image), ("accum", accum), ("counters", counts), ("nonfinite", nonfinite)):
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
     # ---- what this process cannot measure from inside: HBM-side bytes and issued VALU instructions per queue unit, from the
     # rocprofv3 PMC passes of THIS round's kernels (tools/pmc_round.sh -> profiles/r0N_<config>_counters.json)

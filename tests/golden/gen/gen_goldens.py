@@ -75,6 +75,41 @@ def dump_parse(scene_dir, xml, tag):
     print(f"parse_{tag}: {arr['primitives'].shape[0]} prims, {len(objs)} objects, {len(emitters)} emitters")
 
 
+FLAT_KEYS = ("prims", "normals", "v_normals", "obj_info", "obj_aabb", "emitter_id", "bxdf_i", "bxdf_f", "src_i", "src_f")
+
+
+def dump_ref_parser_objects(scene_dir, xml, tag):
+    """The host objects the reference's scene_parsing returns, packed by adapt_amd.scene_pack.pack_scene (INTEGRATION.md option A)."""
+    sys.path.insert(0, refenv.REPO)
+    from parsers.xml_parser import scene_parsing
+    from adapt_amd.scene_pack import pack_scene
+    fs = pack_scene(*scene_parsing(os.path.join(refenv.REFERENCE, "scenes", scene_dir), xml))
+    out = {k: getattr(fs, k) for k in FLAT_KEYS}
+    out.update(world_ior=np.float32(fs.world_ior), has_vertex_normal=np.int32(fs.has_vertex_normal))
+    np.savez_compressed(os.path.join(OUT, f"refparser_{tag}.npz"), **out)
+    print(f"refparser_{tag}: {fs.prims.shape[0]} prims, {fs.obj_info.shape[0]} objects")
+
+
+def dump_ref_parser_textures():
+    """The reference's parser on scenes/test/textured.xml, packed: uv coordinates, texture records, and the texels behind every record
+    (texels_<object>_<map>; the atlas itself is not stored, its layout depends on the packer)."""
+    sys.path.insert(0, refenv.REPO)
+    from parsers.xml_parser import scene_parsing
+    from adapt_amd.scene_pack import pack_scene
+    cwd = os.getcwd()
+    os.chdir(refenv.REPO)                               # texture paths in the scene file are relative to the repository root
+    try:
+        fs = pack_scene(*scene_parsing(os.path.join(refenv.REPO, "scenes", "test"), "textured.xml"))
+    finally:
+        os.chdir(cwd)
+    out = {"uvs": fs.uvs, "tex_i": fs.tex_i, "tex_f": fs.tex_f}
+    for o, m in zip(*np.nonzero(fs.tex_i[:, :, 0] > -255)):
+        _, x, y, w, h = fs.tex_i[o, m]
+        out[f"texels_{o}_{m}"] = fs.atlas[m][y:y + h, x:x + w]
+    np.savez_compressed(os.path.join(OUT, "refparser_textured.npz"), **out)
+    print(f"refparser_textured: {len(out) - 3} texture records")
+
+
 # ------------------------------------------------------------- function vectors
 def gen_functions():
     from bxdf.brdf import BRDF
@@ -685,7 +720,7 @@ REF_SCENES = [("cbox", "cbox-point.xml"), ("cbox", "cbox-vn.xml"), ("cbox", "sma
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="all")
-    ap.add_argument("--out", default="", help="write the fixtures into this directory instead of tests/golden/ (tests/test_fixture_freshness.py)")
+    ap.add_argument("--out", default="", help="write the fixtures into this directory instead of tests/golden/ (check_freshness.py)")
     a = ap.parse_args()
     if a.out:
         OUT = os.path.abspath(a.out)
@@ -700,6 +735,10 @@ if __name__ == "__main__":
         dump_parse("cbox", "cbox.xml", "cbox")
         dump_parse("csphere", "balls-mono.xml", "balls_mono")
         dump_parse("cbox", "complex.xml", "complex")
+        dump_ref_parser_objects("cbox", "cbox.xml", "cbox")
+        dump_ref_parser_objects("csphere", "balls-mono.xml", "balls_mono")
+        dump_ref_parser_objects("cbox", "complex.xml", "glass_box")
+        dump_ref_parser_textures()
     if a.only in ("all", "func"):
         gen_functions()
     if a.only in ("all", "image"):

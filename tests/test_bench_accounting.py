@@ -68,3 +68,18 @@ def test_region_roofline_carries_traffic_and_valu_next_to_the_credited_bytes():
     sh = per["shade"]
     assert sh["traffic"] == int(120.0 * 4480 / 8) and sh["traffic_over_algorithmic"] < 1.0            # the fused kernel moves less than it is credited with
     assert abs(sh["valu"]["busy_frac"] - 22.0 * 4480 / 10e-3 / (1024 * 2400e6 / 4)) < 1e-4
+
+
+def test_dumped_outputs_are_finite_and_say_where_they_were_not():
+    """--dump-outputs writes finite arrays: a component that is +-inf or NaN in the image or the accumulation (upstream's zero-pdf knife edge
+    lets +-inf samples through) is written as 0 in both and marked 1 in `nonfinite`; every other component is written unchanged."""
+    import numpy as np
+    accum = np.float32(np.arange(24).reshape(2, 4, 3))
+    accum[0, 1, 2], accum[1, 3, 0] = np.inf, -np.inf
+    image = accum / np.float32(4)
+    image[1, 0, 1] = np.nan
+    img, acc, bad = bench.finite_outputs(image, accum)
+    assert img.dtype == acc.dtype == bad.dtype == np.float32 and np.isfinite(img).all() and np.isfinite(acc).all()
+    assert sorted(map(tuple, np.argwhere(bad == 1))) == [(0, 1, 2), (1, 0, 1), (1, 3, 0)] and set(np.unique(bad)) == {0.0, 1.0}
+    ok = bad == 0
+    assert np.array_equal(img[ok], image[ok]) and np.array_equal(acc[ok], accum[ok]) and not img[~ok].any() and not acc[~ok].any()

@@ -942,6 +942,34 @@ def test_plain_bench_gpus_2_launches_itself(tmp_path):
     assert np.array_equal(imgs[1], imgs[2])
 
 
+def test_bench_dump_outputs_are_the_timed_steps_and_do_not_depend_on_warmup(tmp_path):
+    """`bench.py --dump-outputs DIR`: the timed renderer's image, accumulation and event counts after exactly `--steps` timed steps, all
+    finite (non-finite components marked in nonfinite.npy); two runs that differ only in `--warmup` write the same arrays bit for bit, and the result line carries `steps` and `ms_per_step`."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    for warmup in (0, 2):
+        d = tmp_path / f"w{warmup}"
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--config", "c1", "--steps", "3", "--warmup", str(warmup), "--spp", "2",
+               "--no-cpu-baseline", "--no-profile", "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        out[warmup] = {k: np.load(d / f"{k}.npy") for k in ("image", "accum", "counters", "nonfinite")}
+    a = out[0]
+    assert all(np.isfinite(v).all() for v in a.values())
+    assert a["image"].dtype == a["accum"].dtype == a["nonfinite"].dtype == np.float32
+    assert a["image"].shape == a["accum"].shape == a["nonfinite"].shape == (256, 256, 3)
+    assert a["counters"].dtype == np.float64 and a["counters"][0] == 256 * 256 * 2 * 3           # n_samples: the three timed steps only
+    fin = a["nonfinite"] == 0
+    assert fin.mean() > 0.99 and np.allclose(a["image"][fin], a["accum"][fin] / np.float32(6), rtol=1e-6, atol=0)
+    for k in ("image", "accum", "counters", "nonfinite"):
+        assert np.array_equal(a[k], out[2][k]), k
+
+
 def test_nine_material_classes_on_the_tree_lose_no_hits(monkeypatch):
     """with all nine surface-model classes in one scene (the microfacet switch on) there are more classes than class
     queues, the scene renders unsorted through the all-models kernel - and the leaf-slot word of the product build's tree must not carry
