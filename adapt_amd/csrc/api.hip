@@ -29,7 +29,6 @@
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIP_TRY_VOID(expr) do { hipError_t e__ = (expr); (void)e__; } while (0)
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -132,10 +131,15 @@ struct DevBuf {
     hipError_t alloc(size_t n) { if (p) (void)hipFree(p); p = nullptr; bytes = n; return hipMalloc(&p, n ? n : 4); }
     template <class T> T* as() const { return (T*)p; }
 };
-template <class T> static hipError_t upload(DevBuf& b, const std::vector<T>& v) {
-    hipError_t e = b.alloc(v.size() * sizeof(T));
-    if (e != hipSuccess) return e;
-    return v.empty() ? hipSuccess : hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+template <class T> static hipError_t upload(DevBuf& b, const T* v, size_t n) {
+    hipError_t e = b.alloc(n * sizeof(T));
+    return (e != hipSuccess || n == 0) ? e : hipMemcpy(b.p, v, n * sizeof(T), hipMemcpyHostToDevice);
+}
+template <class T> static hipError_t upload(DevBuf& b, const std::vector<T>& v) { return upload(b, v.data(), v.size()); }
+template <class... V> static bool put(const char* what, DevBuf& b, const V&... v) {      // upload(b, ...), failing with "upload <what>: <hip error>"
+    const hipError_t e = upload(b, v...);
+    if (e != hipSuccess) fail(APT_E_HIP, std::string("upload ") + what + ": " + hipGetErrorString(e));
+    return e == hipSuccess;
 }
 
 struct apt_bvh { apt::BvhData data; apt::BvhData bin3; apt::WideBvhData wide; };     // data: the exported binary tree (leaves <= 4); bin3 (single-primitive leaves) -> wide: what the kernels walk
@@ -143,23 +147,18 @@ struct apt_bvh { apt::BvhData data; apt::BvhData bin3; apt::WideBvhData wide; };
 struct apt_scene {
     int device = 0;
     DevScene dev{};
-    apt::BvhData bvh;                    // binary SAH tree (leaves of <= 3 primitives): the intermediate of the build
-    apt::WideBvhData wide;               // 8-wide quantised tree: what the kernels walk
-    DevBuf nodes, prims, slot_prim, normals, vnormals, precom, prim_obj, prim_class, obj_info, emitter_id, bxdf, src, sweep_recs, sweep_tab, obj_aabb;
-    DevBuf flat_pairs;                   // the flat records two by two (traverse.hpp FlatScene::pairs)
-    DevBuf flat_recs, flat_tab;          // flat sweep (fast build, small scenes): records and the per-record table (traverse.hpp FlatScene)
+    int bvh_levels = 0;                  // levels of the 8-wide tree the kernels walk (the renderers size their traversal stacks by it)
+    DevBuf nodes, prims, slot_prim, normals, vnormals, precom, prim_obj, prim_class, obj_info, emitter_id, bxdf, src, sweep_recs, sweep_tab;
+    DevBuf flat_recs, flat_tab, flat_pairs;     // flat sweep (fast build, small scenes): records, the per-record table, the records two by two (traverse.hpp FlatScene)
     bool has_flat = false;
     DevBuf uvs, tex_i, tex_f, atlas[3];      // image textures (empty when the scene has none)
     DevBuf prim_shade;                   // per-primitive shading records (stages.hpp DevScene::prim_shade)
     DevBuf med;                          // participating media, n_objects + 1 rows (volumetric path tracer)
     DevBuf vol_grid;                     // grid volume densities
     bool has_volume = false;
-    bool gpu_built = false;              // the binary tree came from the device builder (bvh_gpu.hip)
-    bool world_scattering = false;       // the world medium scatters (rays that hit nothing still take part, vpt.py:176-181)
     bool has_null_surface = false;       // some object carries a null BSDF (rays pass, vpt.py:189-191)
     std::vector<int> obj_class;          // per object: compact material class
     std::vector<uint8_t> obj_null;       // per object: null BSDF (never shaded)
-    bool phong_no_lobe = true;           // every Blinn-Phong material has k_s = 0 and finite k_g >= 0
     float box_min[3] = {1e3f, 1e3f, 1e3f}, box_max[3] = {-1e3f, -1e3f, -1e3f};    // union of the object boxes (path_tracer.py:130-134)
     int n_classes = 0;                   // material classes present (compact ids 0..n_classes-1)
     int class_def[APT_N_CLASS_DEFS] = {};   // compact id -> class definition
@@ -270,7 +269,7 @@ APT_EXPORT int apt_flat_records(const float* prims, int32_t n_prims, const int32
                                 float* stream, int32_t stream_cap, float* tab, int32_t tab_cap, int32_t* n_stream, int32_t* n_tab) {
     if (!prims || !obj_info || !counts || n_prims <= 0 || n_objects <= 0 || !n_stream || !n_tab) return fail(APT_E_INVALID, "apt_flat_records: bad argument");
     std::vector<float> st, tb; int c[7];
-    if (apt::build_flat(prims, n_prims, obj_info, n_objects, nullptr, nullptr, st, tb, c) != 0) return fail(APT_E_INVALID, "apt_flat_records: obj_info range outside the primitive array");
+    if (apt::build_flat(prims, n_prims, obj_info, n_objects, nullptr, st, tb, c) != 0) return fail(APT_E_INVALID, "apt_flat_records: obj_info range outside the primitive array");
     for (int k = 0; k < 7; k++) counts[k] = c[k];
     *n_stream = (int32_t)st.size(); *n_tab = (int32_t)tb.size();
     if (stream) { if (stream_cap < (int32_t)st.size()) return fail(APT_E_INVALID, "apt_flat_records: stream buffer too small"); memcpy(stream, st.data(), st.size() * 4); }
@@ -326,67 +325,108 @@ APT_EXPORT int apt_linear_bvh_export(const apt_linear_bvh* b, float* bvh_minmax,
 }
 APT_EXPORT void apt_linear_bvh_free(apt_linear_bvh* b) { delete b; }
 
-// ---- scene
-APT_EXPORT int apt_scene_create(const apt_scene_desc* d, int32_t device, apt_scene** out) {
-    if (!d || !out) return fail(APT_E_INVALID, "apt_scene_create: null argument");
-    if (d->n_prims <= 0 || d->n_objects <= 0 || d->n_sources <= 0 || !d->prims || !d->normals || !d->obj_info || !d->emitter_id ||
-        !d->bxdf_i || !d->bxdf_f || !d->src_i || !d->src_f)
-        return fail(APT_E_INVALID, "apt_scene_create: incomplete scene description");
-    int ndev = 0;
-    if (int rc = count_device(&ndev)) return rc;
-    if (device < 0 || device >= ndev) return fail(APT_E_INVALID, "apt_scene_create: device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-    std::unique_ptr<apt_scene> s(new apt_scene());     // every early return below frees what was uploaded so far
-    s->device = device;
-    const int N = d->n_prims, O = d->n_objects, S = d->n_sources;
-    // the 64-byte nodes of the walk hold child and primitive indices in 24 bits (bvh_wide.cpp); records are addressed with 32-bit byte offsets
-    if (N >= (1 << 24)) return fail(APT_E_INVALID, "apt_scene_create: more than 16 777 215 primitives (24-bit indices in the 64-byte tree nodes)");
-    s->n_prims = N; s->n_objects = O; s->n_sources = S;
-    const bool timing = getenv("APT_SCENE_TIMING") != nullptr;      // stderr: where apt_scene_create spends its time
-    auto t_prev = std::chrono::steady_clock::now();
-    auto tick = [&](const char* what) {
-        if (!timing) return;
+// ---- scene: apt_scene_create in steps, each packing its tables, uploading them and binding their DevScene fields
+struct SceneTimer {         // APT_SCENE_TIMING: stderr lines saying where apt_scene_create spends its time
+    const bool on = getenv("APT_SCENE_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    void tick(const char* what) {
+        if (!on) return;
         const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[scene timing] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+        fprintf(stderr, "[scene timing] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - prev).count()); prev = now;
+    }
+};
+// primitive -> object and sphere flag.  Every primitive an object names must exist: the later steps index by these ranges.
+static int map_objects(const apt_scene_desc* d, std::vector<int>& prim_obj, std::vector<uint8_t>& sphere) {
+    prim_obj.assign((size_t)d->n_prims, 0); sphere.assign((size_t)d->n_prims, 0);
+    for (int o = 0; o < d->n_objects; o++)
+        for (int k = d->obj_info[3 * o]; k < d->obj_info[3 * o] + d->obj_info[3 * o + 1]; k++) {
+            if (k < 0 || k >= d->n_prims) return fail(APT_E_INVALID, "apt_scene_create: obj_info range outside the primitive array");
+            prim_obj[(size_t)k] = o; sphere[(size_t)k] = d->obj_info[3 * o + 2] != 0;
+        }
+    return APT_OK;
+}
+// The 8-wide tree the kernels walk, collapsed from a binary tree of single-primitive leaves.  Builder: binned SAH on the host (best tree) below a million primitives, PLOC on the device above (scene-load time); APT_BVH_BUILDER=sah|ploc|lbvh overrides.
+// Measured on one MI355X (Msamples/s, C4 95 k / C5 285 k triangles): SAH 1303 / 1216, PLOC 1287 / 1157, LBVH 1186 / 1048; apt_scene_create at 1.14 M
+// primitives: SAH ~800 ms, PLOC or LBVH ~500 ms (what is left is the 8-wide collapse and the table uploads, shared by all three)
+static int build_tree(const apt_scene_desc* d, int device, apt::WideBvhData& wide, SceneTimer& timer) {
+    const int N = d->n_prims, O = d->n_objects;
     const int max_leaf = 1;               // primitives per leaf of the binary tree: the 64-byte node's leaf child IS one primitive (measured 1 / 2 / 3 per leaf on the 80-byte node, rounds 2 and 5: C4 1274 / 1236 / 1228, C5 1117 / 1073 / 1043 Msamples/s; C4 extend 34.1 / 33.5 / 33.5 ms, C5's any-hit walk 25.7 / 27.9 / 28.9)
-    // builder: binned SAH on the host (best tree) below a million primitives, PLOC on the device above (scene-load time); APT_BVH_BUILDER=sah|ploc|lbvh overrides.
-    // Measured on one MI355X (Msamples/s, C4 95 k / C5 285 k triangles): SAH 1303 / 1216, PLOC 1287 / 1157, LBVH 1186 / 1048; apt_scene_create at 1.14 M
-    // primitives: SAH ~800 ms, PLOC or LBVH ~500 ms (what is left is the 8-wide collapse and the table uploads, shared by all three)
     bool gpu_build = N >= 1000000;
     int gpu_algo = 1;                     // 0 LBVH (radix tree), 1 PLOC (nearest-neighbour merging by box area)
     if (const char* bb = getenv("APT_BVH_BUILDER")) { gpu_build = (!strcmp(bb, "lbvh") || !strcmp(bb, "ploc")) && N >= 2; gpu_algo = !strcmp(bb, "ploc") ? 1 : 0; }
-    s->gpu_built = false;
-    if (gpu_build) {
-        const int rc_ = apt::build_bvh_gpu(d->prims, N, d->obj_info, O, device, s->bvh, gpu_algo);
-        if (rc_ != 0) {                                      // a valid scene must load: the host builder takes over (slower, never fails on valid input)
-            fprintf(stderr, "adapt_mi: device BVH build failed (%d), falling back to the host SAH builder\n", rc_);
-            if (apt::build_bvh(d->prims, N, d->obj_info, O, s->bvh, max_leaf) != 0) return fail(APT_E_INVALID, "apt_scene_create: BVH build failed");
-            gpu_build = false;
-        } else s->gpu_built = true;
-    } else if (apt::build_bvh(d->prims, N, d->obj_info, O, s->bvh, max_leaf) != 0) return fail(APT_E_INVALID, "apt_scene_create: BVH build failed");
-    tick(gpu_build ? (gpu_algo ? "binary tree (PLOC, device)" : "binary tree (LBVH, device)") : "binary tree (SAH, host)");
-    if (apt::build_wide_bvh(s->bvh, s->wide) != 0) return fail(APT_E_INVALID, "apt_scene_create: BVH collapse failed");
-    tick("8-wide collapse");
-
-    std::vector<int> prim_obj((size_t)N, 0);
-    std::vector<uint8_t> sphere((size_t)N, 0);
-    for (int o = 0; o < O; o++)
-        for (int k = d->obj_info[3 * o]; k < d->obj_info[3 * o] + d->obj_info[3 * o + 1]; k++) {
-            if (k < 0 || k >= N) return fail(APT_E_INVALID, "apt_scene_create: obj_info range outside the primitive array");
-            prim_obj[(size_t)k] = o; sphere[(size_t)k] = d->obj_info[3 * o + 2] != 0;
+    apt::BvhData bvh;
+    int rc = 0;
+    if (gpu_build && (rc = apt::build_bvh_gpu(d->prims, N, d->obj_info, O, device, bvh, gpu_algo)) != 0) {    // a valid scene must load: the host builder takes over (slower, never fails on valid input)
+        fprintf(stderr, "adapt_mi: device BVH build failed (%d), falling back to the host SAH builder\n", rc);
+        gpu_build = false;
+    }
+    if (!gpu_build && apt::build_bvh(d->prims, N, d->obj_info, O, bvh, max_leaf) != 0) return fail(APT_E_INVALID, "apt_scene_create: BVH build failed");
+    timer.tick(gpu_build ? (gpu_algo ? "binary tree (PLOC, device)" : "binary tree (LBVH, device)") : "binary tree (SAH, host)");
+    if (apt::build_wide_bvh(bvh, wide) != 0) return fail(APT_E_INVALID, "apt_scene_create: BVH collapse failed");
+    timer.tick("8-wide collapse");
+    return APT_OK;
+}
+// Materials (DevBxdf, bx_mask) and the classes present in this scene -> compact ids, per object and per primitive (the sorting extend).
+// Blinn-Phong objects without a specular lobe (the diffuse walls of most scenes) get a class of their own, whose kernel carries no double-precision
+// pow - unless that would need more class queues than there are (APT_MAX_CLASSES), then they stay with the other Blinn-Phong objects.
+static int pack_materials(const apt_scene_desc* d, apt_scene* s, const std::vector<int>& prim_obj, std::vector<int>& prim_class) {
+    const int O = s->n_objects;
+    std::vector<DevBxdf> bx((size_t)O);
+    std::vector<uint8_t> no_lobe((size_t)O, 0);
+    for (int o = 0; o < O; o++) {
+        const int32_t* bi = d->bxdf_i + 4 * o; const float* bf = d->bxdf_f + 13 * o;
+        DevBxdf& b = bx[(size_t)o]; memset(&b, 0, sizeof(b));
+        b.type = bi[0]; b.is_delta = bi[1]; b.is_bsdf = bi[2];
+        s->bx_mask |= b.is_bsdf ? (b.type == 0 ? 0x100 : (b.type == 1 ? 0x200 : 0x400)) : (1 << (b.type & 7));
+        b.k_d = mk3(bf[0], bf[1], bf[2]); b.k_s = mk3(bf[3], bf[4], bf[5]); b.k_g = mk3(bf[6], bf[7], bf[8]); b.mean = mk3(bf[9], bf[10], bf[11]); b.ior = bf[12];
+        bool lean = !b.is_bsdf && b.type == 0;      // Blinn-Phong without a specular lobe: k_s = +0, finite k_g >= 0
+        for (int a = 0; a < 3; a++) lean = lean && bf[3 + a] == 0.f && !std::signbit(bf[3 + a]) && bf[6 + a] >= 0.f && std::isfinite(bf[6 + a]);
+        no_lobe[(size_t)o] = lean ? 1 : 0;
+        s->obj_null.push_back((b.is_bsdf && b.type < 0) ? 1 : 0);
+        s->has_null_surface = s->has_null_surface || s->obj_null.back();
+    }
+    int compact[APT_N_CLASS_DEFS]; s->obj_class.resize((size_t)O);
+    for (int split = 1; split >= 0; split--) {
+        for (int c = 0; c < APT_N_CLASS_DEFS; c++) compact[c] = -1;
+        s->n_classes = 0;
+        for (int o = 0; o < O; o++) {
+            const int c = class_of(bx[(size_t)o].is_bsdf, bx[(size_t)o].type, split && no_lobe[(size_t)o]);
+            if (compact[c] < 0) { compact[c] = s->n_classes; s->class_def[s->n_classes++] = c; }
+            s->obj_class[(size_t)o] = compact[c];
         }
-    // primitive records in BVH order + precom rows (tracer_base.py:117-134)
-    std::vector<float> prec((size_t)N * 9), recs((size_t)N * 12, 0.f);
-    const int host_thr = apt::host_threads();           // per-primitive loops below: independent rows, chunked over host threads (bvh_build.hpp)
+        if (s->n_classes <= APT_MAX_CLASSES) break;
+    }
+    for (int o : prim_obj) prim_class.push_back(s->obj_class[(size_t)o]);
+    if (!put("bxdf", s->bxdf, bx) || !put("prim_class", s->prim_class, prim_class)) return APT_E_HIP;
+    s->dev.bxdf = s->bxdf.as<DevBxdf>(); s->dev.prim_class = s->prim_class.as<int>();
+    return APT_OK;
+}
+// Per-primitive tables (precom rows: tracer_base.py:117-134), leaf records and leaf-slot words in tree order, obj_info / emitter_id, the tree.
+static int pack_primitives(const apt_scene_desc* d, apt_scene* s, const apt::WideBvhData& wide, const std::vector<uint8_t>& sphere,
+                           const std::vector<int>& prim_obj, const std::vector<int>& prim_class, std::vector<float>& prec) {
+    const int N = s->n_prims, O = s->n_objects;
+    const int host_thr = apt::host_threads();           // per-primitive loops: independent rows, chunked over host threads (bvh_build.hpp)
+    prec.resize((size_t)N * 9);
+    std::vector<float> ps((size_t)N * 8, 0.f), vn((size_t)N * 12, 0.f);     // shading records (stages.hpp DevScene::prim_shade); vertex normals, three 16-byte records per primitive
     apt::parallel_for(N, host_thr, [&](int k) {
-        const float* v = d->prims + 9 * (size_t)k; float* pc = prec.data() + 9 * (size_t)k;
+        const float* v = d->prims + 9 * (size_t)k; float* pc = prec.data() + 9 * (size_t)k; float* r = ps.data() + 8 * (size_t)k;
         if (sphere[(size_t)k]) { for (int a = 0; a < 6; a++) pc[a] = v[a]; for (int a = 0; a < 3; a++) pc[6 + a] = v[a]; }
         else for (int a = 0; a < 3; a++) { pc[a] = v[3 + a] - v[a]; pc[3 + a] = v[6 + a] - v[a]; pc[6 + a] = v[a]; }
+        const int o = prim_obj[(size_t)k];
+        int32_t code = sphere[(size_t)k] ? ~o : o, light = d->emitter_id[o];
+        const float* src3 = sphere[(size_t)k] ? pc : d->normals + 3 * (size_t)k;      // centre | n_g
+        r[0] = src3[0]; r[1] = src3[1]; r[2] = src3[2];
+        memcpy(&r[3], &code, 4); memcpy(&r[4], &light, 4);
+        r[5] = d->bxdf_f[13 * o]; r[6] = d->bxdf_f[13 * o + 1]; r[7] = d->bxdf_f[13 * o + 2];
+        if (d->v_normals) for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) vn[12 * (size_t)k + 4 * j + a] = d->v_normals[9 * (size_t)k + 3 * j + a];
     });
+    // Leaf-slot word: primitive | material class << 28 (traverse.hpp walk_info).  Three class bits (28..30), so that the word stays non-negative:
+    // k_extend_dyn reads a negative word as "nothing hit".  A scene with more classes than class queues (all nine surface models + the lobe-free
+    // walls) renders unsorted through the all-models kernel, nobody reads the class then, and none is packed (a compact id of 8 would have set the sign bit: every closest hit on the ninth class lost).
+    const bool pack_cls = s->n_classes <= APT_MAX_CLASSES;
+    std::vector<float> recs((size_t)N * 12, 0.f); std::vector<int> slot_info((size_t)N);
     apt::parallel_for(N, host_thr, [&](int slot) {
-        int k = s->wide.prim_order[(size_t)slot];
+        int k = wide.prim_order[(size_t)slot];
         const float* v = d->prims + 9 * (size_t)k; const float* pc = prec.data() + 9 * (size_t)k; float* r = recs.data() + 12 * (size_t)slot;
         int32_t kid = k, flag = sphere[(size_t)k] ? 1 : 0;
 #if APT_FAST_LEAVES
@@ -399,28 +439,39 @@ APT_EXPORT int apt_scene_create(const apt_scene_desc* d, int32_t device, apt_sce
         else { r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = pc[0]; r[4] = pc[1]; r[5] = pc[2]; r[6] = pc[3]; r[7] = pc[4]; r[8] = pc[5]; }
         memcpy(&r[9], &kid, 4); memcpy(&r[10], &flag, 4);
 #endif
+        slot_info[(size_t)slot] = (int)((uint32_t)k | ((pack_cls ? (uint32_t)prim_class[(size_t)k] : 0u) << 28));
     });
-    tick("primitive records");
-    // sweep stream in scene order (layout: traverse.hpp SweepScene); the t-row cofactors of [e1 e2 .] are
-    // ray-independent, so they are computed once here with the same float operations the device would use
-    std::vector<float> sw;
-    std::vector<int> sw_tab((size_t)O * 4, 0);
-    s->has_sweep = N < 65536;            // larger scenes always walk the BVH (and would pay 48 B per primitive and their share of the load time for a stream nobody reads)
+    if (!put("nodes", s->nodes, wide.nodes) || !put("prims", s->prims, recs) || !put("slot_prim", s->slot_prim, slot_info) || !put("normals", s->normals, d->normals, (size_t)N * 3) ||
+        !put("vnormals", s->vnormals, vn) || !put("precom", s->precom, prec) || !put("prim_obj", s->prim_obj, prim_obj) || !put("prim_shade", s->prim_shade, ps) ||
+        !put("obj_info", s->obj_info, d->obj_info, (size_t)O * 3) || !put("emitter_id", s->emitter_id, d->emitter_id, (size_t)O)) return APT_E_HIP;
+    DevScene& ds = s->dev;
+    ds.bvh.nodes = s->nodes.as<uint4>(); ds.bvh.prims = s->prims.as<float4>(); ds.bvh.slot_prim = s->slot_prim.as<int>(); ds.bvh.n_nodes = wide.n_nodes(); ds.bvh.n_prims = N;
+    for (int a = 0; a < 3; a++) { ds.bvh.gmin[a] = wide.frame.gmin[a]; ds.bvh.gstep[a] = wide.frame.gstep[a]; ds.bvh.ginv[a] = 1.0f / wide.frame.gstep[a]; }
+    s->bvh_levels = wide.max_depth;
+    ds.normals = s->normals.as<float>(); ds.vnormals = s->vnormals.as<float4>(); ds.precom = s->precom.as<float>(); ds.flat.precom = ds.precom;
+    ds.prim_obj = s->prim_obj.as<int>(); ds.obj_info = s->obj_info.as<int>(); ds.emitter_id = s->emitter_id.as<int>(); ds.prim_shade = s->prim_shade.as<float4>();
+    return APT_OK;
+}
+// Sweep stream in scene order (layout: traverse.hpp SweepScene) and its per-object table.  The t-row cofactors of [e1 e2 .] are
+// ray-independent, so they are computed once here with the same float operations the device would use.
+static int pack_sweep(const apt_scene_desc* d, apt_scene* s, const std::vector<float>& prec) {
+    const int O = s->n_objects;
+    std::vector<float> sw; std::vector<int> sw_tab((size_t)O * 4, 0);
+    s->has_sweep = s->n_prims < 65536;   // larger scenes always walk the BVH (and would pay 48 B per primitive and their share of the load time for a stream nobody reads)
+    s->has_aabb = d->obj_aabb != nullptr;
     for (int o = 0; o < O; o++) {
         const int first = d->obj_info[3 * o], count = d->obj_info[3 * o + 1], is_sphere = d->obj_info[3 * o + 2] != 0;
         if (!is_sphere) s->max_obj_prims = std::max(s->max_obj_prims, count);
         if (!s->has_sweep) continue;
         sw_tab[4 * (size_t)o] = (int)sw.size(); sw_tab[4 * (size_t)o + 1] = count; sw_tab[4 * (size_t)o + 2] = is_sphere; sw_tab[4 * (size_t)o + 3] = first;
-        size_t base = sw.size();
-        sw.resize(base + 8, 0.f);
+        size_t base = sw.size(); sw.resize(base + 8, 0.f);
         if (d->obj_aabb) for (int a = 0; a < 3; a++) { sw[base + 2 * a] = d->obj_aabb[6 * o + a]; sw[base + 2 * a + 1] = d->obj_aabb[6 * o + 3 + a]; }
         if (is_sphere) {
             size_t at = sw.size(); sw.resize(at + 8, 0.f);
             for (int a = 0; a < 4; a++) sw[at + a] = d->prims[9 * (size_t)first + a];
             continue;
         }
-        const int n_pairs = (count + 1) / 2;
-        size_t at = sw.size(); sw.resize(at + (size_t)n_pairs * 24, 0.f);
+        size_t at = sw.size(); sw.resize(at + (size_t)((count + 1) / 2) * 24, 0.f);      // pairs of triangles
         for (int k = 0; k < count; k++) {
             const float* v = d->prims + 9 * (size_t)(first + k); const float* pc = prec.data() + 9 * (size_t)(first + k);
             float* r = sw.data() + at + 24 * (size_t)(k / 2) + (k & 1);
@@ -430,204 +481,135 @@ APT_EXPORT int apt_scene_create(const apt_scene_desc* d, int32_t device, apt_sce
             r[18] = a10 * a21 - a20 * a11; r[20] = a20 * a01 - a00 * a21; r[22] = a00 * a11 - a10 * a01;
         }
     }
-    tick("sweep stream");
-    std::vector<float> aabb((size_t)O * 6, 0.f);
-    if (d->obj_aabb) aabb.assign(d->obj_aabb, d->obj_aabb + (size_t)O * 6);
-    std::vector<DevBxdf> bx((size_t)O);
-    std::vector<uint8_t> no_lobe((size_t)O, 0);
-    for (int o = 0; o < O; o++) {
-        const int32_t* bi = d->bxdf_i + 4 * o; const float* bf = d->bxdf_f + 13 * o;
-        DevBxdf& b = bx[(size_t)o]; memset(&b, 0, sizeof(b));
-        b.type = bi[0]; b.is_delta = bi[1]; b.is_bsdf = bi[2];
-        s->bx_mask |= b.is_bsdf ? (b.type == 0 ? 0x100 : (b.type == 1 ? 0x200 : 0x400)) : (1 << (b.type & 7));
-        b.k_d = mk3(bf[0], bf[1], bf[2]); b.k_s = mk3(bf[3], bf[4], bf[5]); b.k_g = mk3(bf[6], bf[7], bf[8]); b.mean = mk3(bf[9], bf[10], bf[11]); b.ior = bf[12];
-        no_lobe[(size_t)o] = 0;
-        if (!b.is_bsdf && b.type == 0) {
-            bool lean = true;
-            for (int a = 0; a < 3; a++) if (!(bf[3 + a] == 0.f && !std::signbit(bf[3 + a]) && bf[6 + a] >= 0.f && std::isfinite(bf[6 + a]))) lean = false;
-            no_lobe[(size_t)o] = lean ? 1 : 0;
-            if (!lean) s->phong_no_lobe = false;
-        }
-    }
-#define UP(buf, vec) do { hipError_t e_ = upload(s->buf, vec); if (e_ != hipSuccess) return fail(APT_E_HIP, std::string("upload " #buf ": ") + hipGetErrorString(e_)); } while (0)
-    std::vector<int> pcls_host;
-    // material classes present in this scene -> compact ids; per-primitive class table for the sorting extend.  Blinn-Phong objects
-    // without a specular lobe (the diffuse walls of most scenes) get a class of their own, whose kernel carries no double-precision
-    // pow - unless that would need more class queues than there are (APT_MAX_CLASSES), then they stay with the other Blinn-Phong objects
-    {
-        int compact[APT_N_CLASS_DEFS];
-        std::vector<int> obj_cls((size_t)O);
-        for (int split = 1; split >= 0; split--) {
-            for (int c = 0; c < APT_N_CLASS_DEFS; c++) compact[c] = -1;
-            s->n_classes = 0;
-            for (int o = 0; o < O; o++) {
-                int c = class_of(bx[(size_t)o].is_bsdf, bx[(size_t)o].type, split && no_lobe[(size_t)o]);
-                if (compact[c] < 0) { compact[c] = s->n_classes; s->class_def[s->n_classes++] = c; }
-                obj_cls[(size_t)o] = compact[c];
-            }
-            if (s->n_classes <= APT_MAX_CLASSES) break;
-        }
-        s->obj_class = obj_cls;
-        s->obj_null.resize((size_t)O);
-        for (int o = 0; o < O; o++) s->obj_null[(size_t)o] = (bx[(size_t)o].is_bsdf && bx[(size_t)o].type < 0) ? 1 : 0;
-        std::vector<int> pcls((size_t)N);
-        for (int k = 0; k < N; k++) pcls[(size_t)k] = obj_cls[(size_t)prim_obj[(size_t)k]];
-        pcls_host = pcls;
-        UP(prim_class, pcls);
-        memset(&s->dev.flat, 0, sizeof(s->dev.flat));
+    if (!put("sweep_recs", s->sweep_recs, sw) || !put("sweep_tab", s->sweep_tab, sw_tab)) return APT_E_HIP;
+    s->dev.sweep = {s->sweep_recs.as<float>(), s->sweep_tab.as<int>(), s->prim_obj.as<int>(), O};
+    return APT_OK;
+}
 #if APT_FAST
-        if (N <= APT_FLAT_MAX_PRIMS && s->has_sweep && d->obj_aabb) {          // flat sweep records (traverse.hpp "Flat sweep"); the sweep stream serves its zero-component fallback
-            std::vector<float> fr, ft;
-            FlatScene& fl = s->dev.flat;
-            std::vector<uint8_t> trans((size_t)O);
-            for (int o = 0; o < O; o++) trans[(size_t)o] = bx[(size_t)o].is_bsdf ? 1 : 0;
-            int fc[7];
-            if (apt::build_flat(d->prims, N, d->obj_info, O, pcls.data(), trans.data(), fr, ft, fc) != 0) return fail(APT_E_INVALID, "apt_scene_create: flat records: obj_info range outside the primitive array");
-            fl.defer_all = getenv("APT_FLAT_DEFER_ALL") ? atoi(getenv("APT_FLAT_DEFER_ALL")) : 0;
-            fl.n_quads = fc[0]; fl.n_quads_tie = fc[1]; fl.n_gquads = fc[2]; fl.n_gquads_tie = fc[3]; fl.n_tris = fc[4]; fl.n_tris_tie = fc[5]; fl.n_spheres = fc[6];
-            hipError_t e1_ = upload(s->flat_recs, fr), e2_ = (e1_ == hipSuccess) ? upload(s->flat_tab, ft) : e1_;
-            if (e2_ != hipSuccess) return fail(APT_E_HIP, std::string("upload flat records: ") + hipGetErrorString(e2_));
-            fl.stream = s->flat_recs.as<float>(); fl.tab = s->flat_tab.as<float4>();
-            {   // the records two by two for the one-ray any-hit sweep (flat_any1): floats of records 2j, 2j + 1 interleaved; an odd tail repeats its record
-                std::vector<float> fp;
-                const float* src = fr.data();
-                auto section = [&](int n, int w) {
-                    for (int j = 0; 2 * j < n; j++) {
-                        const float* a = src + (size_t)(2 * j) * w; const float* b = (2 * j + 1 < n) ? a + w : a;
-                        for (int k = 0; k < w; k++) { fp.push_back(a[k]); fp.push_back(b[k]); }
-                    }
-                    src += (size_t)n * w;
-                };
-                section(fc[0] + fc[1], 12); section(fc[2] + fc[3], 18); section(fc[4] + fc[5], 12); section(fc[6], 4);
-                if (fp.empty()) fp.push_back(0.f);
-                hipError_t e3_ = upload(s->flat_pairs, fp);
-                if (e3_ != hipSuccess) return fail(APT_E_HIP, std::string("upload flat record pairs: ") + hipGetErrorString(e3_));
-                fl.pairs = s->flat_pairs.as<float>();
-            }
-            s->has_flat = true;
-            if (timing) fprintf(stderr, "[scene timing] flat records: %d + %d parallelograms, %d + %d convex quads, %d + %d triangles (plain + coplanar groups), %d spheres of %d primitives\n", fc[0], fc[1], fc[2], fc[3], fc[4], fc[5], fc[6], N);
-            tick("flat records");
-        }
+// Flat sweep (traverse.hpp "Flat sweep"; small scenes with object boxes): records, their table, the records two by two.  The sweep stream serves its zero-component fallback.
+static int pack_flat(const apt_scene_desc* d, apt_scene* s, const std::vector<int>& prim_class, SceneTimer& timer) {
+    const int N = s->n_prims;
+    if (N > APT_FLAT_MAX_PRIMS || !s->has_sweep || !d->obj_aabb) return APT_OK;
+    std::vector<float> fr, ft; int fc[7];
+    if (apt::build_flat(d->prims, N, d->obj_info, s->n_objects, prim_class.data(), fr, ft, fc) != 0) return fail(APT_E_INVALID, "apt_scene_create: flat records: obj_info range outside the primitive array");
+    if (!put("flat records", s->flat_recs, fr) || !put("flat records", s->flat_tab, ft) || !put("flat record pairs", s->flat_pairs, apt::flat_pairs(fr, fc))) return APT_E_HIP;
+    FlatScene& fl = s->dev.flat;
+    fl.stream = s->flat_recs.as<float>(); fl.tab = s->flat_tab.as<float4>(); fl.pairs = s->flat_pairs.as<float>();
+    fl.defer_all = getenv("APT_FLAT_DEFER_ALL") ? atoi(getenv("APT_FLAT_DEFER_ALL")) : 0;
+    fl.n_quads = fc[0]; fl.n_quads_tie = fc[1]; fl.n_gquads = fc[2]; fl.n_gquads_tie = fc[3]; fl.n_tris = fc[4]; fl.n_tris_tie = fc[5]; fl.n_spheres = fc[6];
+    s->has_flat = true;
+    if (timer.on) fprintf(stderr, "[scene timing] flat records: %d + %d parallelograms, %d + %d convex quads, %d + %d triangles (plain + coplanar groups), %d spheres of %d primitives\n", fc[0], fc[1], fc[2], fc[3], fc[4], fc[5], fc[6], N);
+    timer.tick("flat records");
+    return APT_OK;
+}
 #endif
-    }
-    std::vector<DevSrc> sr((size_t)S);
-    for (int k = 0; k < S; k++) {
+// Emitters: the DevSrc table and src_mask; an area emitter carries its object's primitive range.
+static int pack_emitters(const apt_scene_desc* d, apt_scene* s) {
+    std::vector<DevSrc> sr((size_t)s->n_sources);
+    for (int k = 0; k < s->n_sources; k++) {
         const int32_t* si = d->src_i + 4 * k; const float* sf = d->src_f + 11 * k;
         DevSrc& e = sr[(size_t)k]; memset(&e, 0, sizeof(e));
         e.type = si[0]; e.bool_bits = si[1]; e.obj_ref_id = si[2];
         s->src_mask |= 1 << (e.type & 7);
         e.intensity = mk3(sf[0], sf[1], sf[2]); e.dir = mk3(sf[3], sf[4], sf[5]); e.pos = mk3(sf[6], sf[7], sf[8]); e.inv_area = sf[9]; e.r = sf[10];
-        if (e.type == 1 && (e.obj_ref_id < 0 || e.obj_ref_id >= O)) return fail(APT_E_INVALID, "apt_scene_create: area emitter is not attached to an object");
+        if (e.type == 1 && (e.obj_ref_id < 0 || e.obj_ref_id >= s->n_objects)) return fail(APT_E_INVALID, "apt_scene_create: area emitter is not attached to an object");
         if (e.type == 1) { e.prim_first = d->obj_info[3 * e.obj_ref_id]; e.prim_count = d->obj_info[3 * e.obj_ref_id + 2] ? -1 : d->obj_info[3 * e.obj_ref_id + 1]; }
     }
-    std::vector<float> nrm(d->normals, d->normals + (size_t)N * 3);
-    std::vector<float> vn((size_t)N * 12, 0.f);           // three 16-byte records per primitive (DevScene::vnormals)
-    if (d->v_normals) for (size_t k = 0; k < (size_t)N * 3; k++) for (int a = 0; a < 3; a++) vn[4 * k + a] = d->v_normals[3 * k + a];
-    std::vector<int> oi(d->obj_info, d->obj_info + (size_t)O * 3), ei(d->emitter_id, d->emitter_id + (size_t)O);
-    std::vector<int> slot_info((size_t)N);                // leaf slot -> primitive | material class << 28 (traverse.hpp walk_info)
-    {
-        // Three class bits (28..30), so that the word stays non-negative: k_extend_dyn reads a negative word as "nothing hit".  A scene
-        // with more classes than class queues (all nine surface models + the lobe-free walls) renders unsorted through the all-models
-        // kernel, nobody reads the class then, and none is packed (a compact id of 8 would have set the sign bit: every closest hit on
-        // the ninth class lost).
-        if (N >= (1 << 28)) return fail(APT_E_INVALID, "apt_scene_create: more than 2^28 primitives");
-        const bool pack_cls = s->n_classes <= APT_MAX_CLASSES;
-        for (int slot = 0; slot < N; slot++) {
-            const int k = s->wide.prim_order[(size_t)slot];
-            const uint32_t c = pack_cls ? (uint32_t)pcls_host[(size_t)k] : 0u;
-            if (c >= (uint32_t)APT_MAX_CLASSES) return fail(APT_E_INVALID, "apt_scene_create: material class id does not fit the leaf-slot word");
-            slot_info[(size_t)slot] = (int)((uint32_t)k | (c << 28));
-        }
+    if (!put("src", s->src, sr)) return APT_E_HIP;
+    s->dev.src = s->src.as<DevSrc>();
+    return APT_OK;
+}
+// Image textures: uvs, the per-object map tables and the atlases (all left null when the scene has none).
+static int pack_textures(const apt_scene_desc* d, apt_scene* s) {
+    const int O = s->n_objects;
+    if (!d->tex_i || !d->tex_f || !d->uvs) return APT_OK;
+    for (int o = 0; o < O; o++) for (int m = 0; m < 3; m++) {
+        const int32_t* t = d->tex_i + 15 * o + 5 * m;
+        if (t[0] <= -255) continue;
+        if (d->obj_info[3 * o + 2]) return fail(APT_E_INVALID, "apt_scene_create: textured spheres are not supported");
+        if (!d->atlas[m] || t[3] < 2 || t[4] < 2 || t[1] < 0 || t[2] < 0 || t[1] + t[3] > d->atlas_w[m] || t[2] + t[4] > d->atlas_h[m])
+            return fail(APT_E_INVALID, "apt_scene_create: texture rectangle outside its atlas (or smaller than 2 x 2)");
     }
-    UP(nodes, s->wide.nodes); UP(prims, recs); UP(slot_prim, slot_info); UP(normals, nrm); UP(vnormals, vn); UP(precom, prec); UP(prim_obj, prim_obj);
-    UP(obj_info, oi); UP(emitter_id, ei); UP(bxdf, bx); UP(src, sr); UP(sweep_recs, sw); UP(sweep_tab, sw_tab); UP(obj_aabb, aabb);
-    DevScene& ds = s->dev;
-    ds.bvh.nodes = s->nodes.as<uint4>(); ds.bvh.prims = s->prims.as<float4>(); ds.bvh.slot_prim = s->slot_prim.as<int>(); ds.bvh.n_nodes = s->wide.n_nodes(); ds.bvh.n_prims = N;
-    for (int a = 0; a < 3; a++) { ds.bvh.gmin[a] = s->wide.frame.gmin[a]; ds.bvh.gstep[a] = s->wide.frame.gstep[a]; ds.bvh.ginv[a] = 1.0f / s->wide.frame.gstep[a]; }
-    ds.sweep.stream = s->sweep_recs.as<float>(); ds.sweep.obj_tab = s->sweep_tab.as<int>(); ds.sweep.prim_obj = s->prim_obj.as<int>(); ds.sweep.n_objects = O;
-    s->has_aabb = d->obj_aabb != nullptr;
-    ds.normals = s->normals.as<float>(); ds.vnormals = s->vnormals.as<float4>(); ds.precom = s->precom.as<float>();
-    ds.flat.precom = ds.precom;
-    ds.prim_obj = s->prim_obj.as<int>(); ds.prim_class = s->prim_class.as<int>(); ds.obj_info = s->obj_info.as<int>(); ds.emitter_id = s->emitter_id.as<int>();
-    ds.bxdf = s->bxdf.as<DevBxdf>(); ds.src = s->src.as<DevSrc>();
-    ds.n_prims = N; ds.n_objects = O; ds.n_sources = S; ds.has_vn = d->has_vertex_normal; ds.world_ior = d->world_ior;
-    ds.uvs = nullptr; ds.tex_i = nullptr; ds.tex_f = nullptr;
-    for (int m = 0; m < 3; m++) { ds.atlas[m] = nullptr; ds.atlas_w[m] = 0; }
-    if (d->tex_i && d->tex_f && d->uvs) {
-        for (int o = 0; o < O; o++) for (int m = 0; m < 3; m++) {
-            const int32_t* t = d->tex_i + 15 * o + 5 * m;
-            if (t[0] <= -255) continue;
-            if (d->obj_info[3 * o + 2]) return fail(APT_E_INVALID, "apt_scene_create: textured spheres are not supported");
-            if (!d->atlas[m] || t[3] < 2 || t[4] < 2 || t[1] < 0 || t[2] < 0 || t[1] + t[3] > d->atlas_w[m] || t[2] + t[4] > d->atlas_h[m])
-                return fail(APT_E_INVALID, "apt_scene_create: texture rectangle outside its atlas (or smaller than 2 x 2)");
-        }
-        std::vector<float> uv(d->uvs, d->uvs + (size_t)N * 6), tf(d->tex_f, d->tex_f + (size_t)O * 6);
-        std::vector<int> ti(d->tex_i, d->tex_i + (size_t)O * 15);
-        UP(uvs, uv); UP(tex_i, ti); UP(tex_f, tf);
-        ds.uvs = s->uvs.as<float>(); ds.tex_i = s->tex_i.as<int>(); ds.tex_f = s->tex_f.as<float>();
-        for (int m = 0; m < 3; m++) if (d->atlas[m]) {
-            std::vector<float> img(d->atlas[m], d->atlas[m] + (size_t)d->atlas_w[m] * (size_t)d->atlas_h[m] * 3);
-            UP(atlas[m], img);
-            ds.atlas[m] = s->atlas[m].as<float>(); ds.atlas_w[m] = d->atlas_w[m];
-        }
+    if (!put("uvs", s->uvs, d->uvs, (size_t)s->n_prims * 6) || !put("tex_i", s->tex_i, d->tex_i, (size_t)O * 15) || !put("tex_f", s->tex_f, d->tex_f, (size_t)O * 6)) return APT_E_HIP;
+    s->dev.uvs = s->uvs.as<float>(); s->dev.tex_i = s->tex_i.as<int>(); s->dev.tex_f = s->tex_f.as<float>();
+    for (int m = 0; m < 3; m++) if (d->atlas[m]) {
+        if (!put("atlas[m]", s->atlas[m], d->atlas[m], (size_t)d->atlas_w[m] * (size_t)d->atlas_h[m] * 3)) return APT_E_HIP;
+        s->dev.atlas[m] = s->atlas[m].as<float>(); s->dev.atlas_w[m] = d->atlas_w[m];
     }
-    {   // per-primitive shading records
-        std::vector<float> ps((size_t)N * 8, 0.f);
-        apt::parallel_for(N, host_thr, [&](int k) {
-            float* r = ps.data() + 8 * (size_t)k;
-            const int o = prim_obj[(size_t)k];
-            int32_t code = sphere[(size_t)k] ? ~o : o, light = d->emitter_id[o];
-            const float* src3 = sphere[(size_t)k] ? prec.data() + 9 * (size_t)k : d->normals + 3 * (size_t)k;      // centre | n_g
-            r[0] = src3[0]; r[1] = src3[1]; r[2] = src3[2];
-            memcpy(&r[3], &code, 4); memcpy(&r[4], &light, 4);
-            r[5] = d->bxdf_f[13 * o]; r[6] = d->bxdf_f[13 * o + 1]; r[7] = d->bxdf_f[13 * o + 2];
-        });
-        UP(prim_shade, ps);
-        ds.prim_shade = s->prim_shade.as<float4>();
+    return APT_OK;
+}
+// Participating media, n_objects + 1 rows (transparent unless the description carries the tables); the union of the object boxes (path_tracer.py:130-134).
+static int pack_media(const apt_scene_desc* d, apt_scene* s) {
+    const int O = s->n_objects;
+    std::vector<DevMedium> md((size_t)O + 1);
+    for (int o = 0; o <= O; o++) {
+        DevMedium& m = md[(size_t)o]; memset(&m, 0, sizeof(m));
+        if (d->med_i && d->med_f) {
+            const float* f = d->med_f + 16 * (size_t)o;
+            m.type = d->med_i[o]; m.ior = f[0];
+            m.u_s = mk3(f[1], f[2], f[3]); m.u_a = mk3(f[4], f[5], f[6]); m.u_e = mk3(f[7], f[8], f[9]);
+            m.par = mk3(f[10], f[11], f[12]); m.pdf = mk3(f[13], f[14], f[15]);
+            if (m.type < -1 || m.type > 3) return fail(APT_E_INVALID, "apt_scene_create: unknown medium type");
+        } else { m.type = -1; m.ior = (o < O) ? d->bxdf_f[13 * o + 12] : d->world_ior; m.pdf = mk3(1.f, 0.f, 0.f); }
     }
-    {   // participating media: transparent everywhere unless the description carries the tables
-        std::vector<DevMedium> md((size_t)O + 1);
-        for (int o = 0; o <= O; o++) {
-            DevMedium& m = md[(size_t)o]; memset(&m, 0, sizeof(m));
-            if (d->med_i && d->med_f) {
-                const float* f = d->med_f + 16 * (size_t)o;
-                m.type = d->med_i[o]; m.ior = f[0];
-                m.u_s = mk3(f[1], f[2], f[3]); m.u_a = mk3(f[4], f[5], f[6]); m.u_e = mk3(f[7], f[8], f[9]);
-                m.par = mk3(f[10], f[11], f[12]); m.pdf = mk3(f[13], f[14], f[15]);
-                if (m.type < -1 || m.type > 3) return fail(APT_E_INVALID, "apt_scene_create: unknown medium type");
-            } else { m.type = -1; m.ior = (o < O) ? bx[(size_t)o].ior : d->world_ior; m.pdf = mk3(1.f, 0.f, 0.f); }
-        }
-        UP(med, md);
-        ds.med = s->med.as<DevMedium>();
-        s->world_scattering = md[(size_t)O].type >= 0;
-        for (int o = 0; o < O; o++) {
-            if (bx[(size_t)o].is_bsdf && bx[(size_t)o].type < 0) s->has_null_surface = true;
-            if (d->obj_aabb) for (int a = 0; a < 3; a++) {
-                s->box_min[a] = std::min(s->box_min[a], d->obj_aabb[6 * o + a]); s->box_max[a] = std::max(s->box_max[a], d->obj_aabb[6 * o + 3 + a]);
-            }
-        }
-    }
-    memset(&ds.vol, 0, sizeof(ds.vol));
-    if (d->vol_i && d->vol_f && d->vol_grid && d->vol_i[0] != 0) {
-        const int32_t* vi = d->vol_i; const float* f = d->vol_f;
-        if (vi[0] != 2) return fail(APT_E_INVALID, "apt_scene_create: only RGB grid volumes (type 2) exist upstream");
-        if (vi[1] <= 0 || vi[2] <= 0 || vi[3] <= 0 || vi[4] < -1 || vi[4] > 3) return fail(APT_E_INVALID, "apt_scene_create: bad grid volume shape or phase type");
-        if (!(f[21] > 0.f && f[22] > 0.f && f[23] > 0.f)) return fail(APT_E_INVALID, "apt_scene_create: grid volume majorants must be positive");
-        std::vector<float> grid(d->vol_grid, d->vol_grid + (size_t)vi[1] * (size_t)vi[2] * (size_t)vi[3] * 3);
-        UP(vol_grid, grid);
-        DevVolume& vo = ds.vol;
-        vo.type = vi[0]; vo.xres = vi[1]; vo.yres = vi[2]; vo.zres = vi[3];
-        vo.albedo = mk3(f[0], f[1], f[2]);
-        vo.inv_r0 = mk3(f[3], f[4], f[5]); vo.inv_r1 = mk3(f[6], f[7], f[8]); vo.inv_r2 = mk3(f[9], f[10], f[11]);
-        vo.trans = mk3(f[12], f[13], f[14]); vo.mini = mk3(f[15], f[16], f[17]); vo.maxi = mk3(f[18], f[19], f[20]);
-        vo.majorant = mk3(f[21], f[22], f[23]); vo.pdf = mk3(f[24], f[25], f[26]);
-        vo.ph.type = vi[4]; vo.ph.par = mk3(f[27], f[28], f[29]); vo.ph.pdf = mk3(f[30], f[31], f[32]);
-        vo.grid = s->vol_grid.as<float>();
-        s->has_volume = true;
-    }
-#undef UP
-    tick("tables + uploads");
-    *out = s.release();
+    if (!put("med", s->med, md)) return APT_E_HIP;
+    s->dev.med = s->med.as<DevMedium>();
+    if (d->obj_aabb) for (int o = 0; o < O; o++) for (int a = 0; a < 3; a++)
+        { s->box_min[a] = std::min(s->box_min[a], d->obj_aabb[6 * o + a]); s->box_max[a] = std::max(s->box_max[a], d->obj_aabb[6 * o + 3 + a]); }
+    return APT_OK;
+}
+// Grid volume of the volumetric tracer (DevVolume stays zero when the scene declares none).
+static int pack_volume(const apt_scene_desc* d, apt_scene* s) {
+    if (!d->vol_i || !d->vol_f || !d->vol_grid || d->vol_i[0] == 0) return APT_OK;
+    const int32_t* vi = d->vol_i; const float* f = d->vol_f;
+    if (vi[0] != 2) return fail(APT_E_INVALID, "apt_scene_create: only RGB grid volumes (type 2) exist upstream");
+    if (vi[1] <= 0 || vi[2] <= 0 || vi[3] <= 0 || vi[4] < -1 || vi[4] > 3) return fail(APT_E_INVALID, "apt_scene_create: bad grid volume shape or phase type");
+    if (!(f[21] > 0.f && f[22] > 0.f && f[23] > 0.f)) return fail(APT_E_INVALID, "apt_scene_create: grid volume majorants must be positive");
+    if (!put("vol_grid", s->vol_grid, d->vol_grid, (size_t)vi[1] * (size_t)vi[2] * (size_t)vi[3] * 3)) return APT_E_HIP;
+    DevVolume& vo = s->dev.vol;
+    vo.type = vi[0]; vo.xres = vi[1]; vo.yres = vi[2]; vo.zres = vi[3]; vo.albedo = mk3(f[0], f[1], f[2]);
+    vo.inv_r0 = mk3(f[3], f[4], f[5]); vo.inv_r1 = mk3(f[6], f[7], f[8]); vo.inv_r2 = mk3(f[9], f[10], f[11]);
+    vo.trans = mk3(f[12], f[13], f[14]); vo.mini = mk3(f[15], f[16], f[17]); vo.maxi = mk3(f[18], f[19], f[20]);
+    vo.majorant = mk3(f[21], f[22], f[23]); vo.pdf = mk3(f[24], f[25], f[26]);
+    vo.ph.type = vi[4]; vo.ph.par = mk3(f[27], f[28], f[29]); vo.ph.pdf = mk3(f[30], f[31], f[32]);
+    vo.grid = s->vol_grid.as<float>();
+    s->has_volume = true;
+    return APT_OK;
+}
+APT_EXPORT int apt_scene_create(const apt_scene_desc* d, int32_t device, apt_scene** out) {
+    if (!d || !out) return fail(APT_E_INVALID, "apt_scene_create: null argument");
+    if (d->n_prims <= 0 || d->n_objects <= 0 || d->n_sources <= 0 || !d->prims || !d->normals || !d->obj_info || !d->emitter_id ||
+        !d->bxdf_i || !d->bxdf_f || !d->src_i || !d->src_f)
+        return fail(APT_E_INVALID, "apt_scene_create: incomplete scene description");
+    int ndev = 0;
+    if (int rc = count_device(&ndev)) return rc;
+    if (device < 0 || device >= ndev) return fail(APT_E_INVALID, "apt_scene_create: device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    // the 64-byte nodes of the walk hold child and primitive indices in 24 bits (bvh_wide.cpp); records are addressed with 32-bit byte offsets
+    if (d->n_prims >= (1 << 24)) return fail(APT_E_INVALID, "apt_scene_create: more than 16 777 215 primitives (24-bit indices in the 64-byte tree nodes)");
+    std::unique_ptr<apt_scene> owner(new apt_scene());     // every early return below frees what was uploaded so far
+    apt_scene* s = owner.get();
+    s->device = device; s->n_prims = d->n_prims; s->n_objects = d->n_objects; s->n_sources = d->n_sources;
+    s->dev.n_prims = d->n_prims; s->dev.n_objects = d->n_objects; s->dev.n_sources = d->n_sources; s->dev.has_vn = d->has_vertex_normal; s->dev.world_ior = d->world_ior;
+    SceneTimer timer;
+    std::vector<int> prim_obj, prim_class; std::vector<uint8_t> sphere; std::vector<float> prec;     // per primitive: object, material class, sphere flag, precom row
+    apt::WideBvhData wide;
+    if (int rc = map_objects(d, prim_obj, sphere)) return rc;
+    if (int rc = build_tree(d, device, wide, timer)) return rc;
+    if (int rc = pack_materials(d, s, prim_obj, prim_class)) return rc;
+    if (int rc = pack_primitives(d, s, wide, sphere, prim_obj, prim_class, prec)) return rc;
+    timer.tick("primitive records");
+    if (int rc = pack_sweep(d, s, prec)) return rc;
+    timer.tick("sweep stream");
+#if APT_FAST
+    if (int rc = pack_flat(d, s, prim_class, timer)) return rc;
+#endif
+    if (int rc = pack_emitters(d, s)) return rc;
+    if (int rc = pack_textures(d, s)) return rc;
+    if (int rc = pack_media(d, s)) return rc;
+    if (int rc = pack_volume(d, s)) return rc;
+    timer.tick("tables + uploads");
+    *out = owner.release();
     return APT_OK;
 }
 APT_EXPORT void apt_scene_destroy(apt_scene* s) { if (s) { (void)hipSetDevice(s->device); delete s; } }
@@ -865,7 +847,7 @@ static int plan_lds_and_grids(apt_renderer* r) {
     // LDS plan of the BVH walk: the per-lane stack of 8-byte groups.  A node visit leaves at most one group behind (the rest of its
     // hit children), so the stack never holds more groups than the tree has levels.
     LdsPlan pl{};
-    const int full_depth = sc->wide.max_depth + 2;
+    const int full_depth = sc->bvh_levels + 2;
     int lds_levels = 7;                                  // 14 KiB per 256-thread workgroup (measured: 6, 10 and 14 levels run alike - the 8-wide tree is at most 8-9 levels deep; 8 through round 5: the eighth level's 2 KiB hold the walk's permutation table now, seven workgroups per CU as before)
     if (const char* sd = getenv("APT_BVH_LDS_LEVELS")) lds_levels = std::max(2, atoi(sd));
     pl.stack_depth = std::min(full_depth, lds_levels);   // deeper levels spill to per-lane global columns (traverse.hpp TravStack)

@@ -73,6 +73,7 @@ int build_linear_bvh(const float* prims, int n_prims, const int32_t* obj_prim_cn
 // flat_build.cpp: the records of the flat sweep (traverse.hpp FlatScene): precomputed-transform planar primitives (parallelograms merged),
 // spheres, and the per-record table that maps a winning record back to its triangle and barycentrics
 void planar_rows(const float* tri9, float out12[12]);      // one triangle: corner + rows U, V, T of [e1 e2 n]^-1 (the product build's BVH leaf record)
-int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, const int32_t* prim_class, const uint8_t* transmissive,
+int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, const int32_t* prim_class,
                std::vector<float>& stream, std::vector<float>& tab, int counts[7]);      // counts: parallelograms, convex quads, triangles - each plain, then in coplanar groups - and spheres
+std::vector<float> flat_pairs(const std::vector<float>& stream, const int counts[7]);      // the stream's records two by two (FlatScene::pairs)
 }  // namespace apt

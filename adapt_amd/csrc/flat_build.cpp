@@ -93,6 +93,7 @@ bool convex_overlap(const Poly& A, const Poly& B, const float plane[4]) {
     }
     return true;
 }
+const int kRecordFloats[4] = {12, 18, 12, 4};      // stream floats per record: parallelogram, convex quad, triangle, sphere (layout: build_flat)
 }  // namespace
 
 // One triangle as the BVH walk of the product build reads it (traverse.hpp tri_two): corner p0, rows U, V, T of [e1 e2 n]^-1, 12 floats.
@@ -110,10 +111,10 @@ void planar_rows(const float* tri9, float out12[12]) {
 // coplanar groups] x 12, [spheres] x 4; a planar record = corner p0, rows U, V, T (3 floats each); a convex quad appends its two far
 // edges as functions a u + b v + c of the record's (u, v) that are >= 0 inside.  tab: 28 floats per record, in stream order (7 float4: (U, p0.x), (V, p0.y), (prim_a, prim_b, class_a,
 // class_b), map_a, map_b, (p0.z, -, -, -)).
-// prim_class: material class per primitive (sorted shading) or null.  transmissive: per object, 1 when rays can travel inside it (a BSDF).
+// prim_class: material class per primitive (sorted shading) or null.
 // A record joins a coplanar group when another record lies in the same plane (to 2e-5) and their outlines overlap - the configurations in
 // which upstream's answer hangs on the last bit of two distances (traverse.hpp flat_tie_break): a glass box resting on the floor, a decal on a wall.
-int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, const int32_t* prim_class, const uint8_t* transmissive,
+int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, const int32_t* prim_class,
                std::vector<float>& stream, std::vector<float>& tab, int counts[7]) {
     std::vector<Planar> quads, gquads, tris;
     std::vector<int> spheres;
@@ -205,7 +206,7 @@ int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_o
             bool same_plane = std::fabs((double)a.T[3] - (double)b.T[3]) <= 2e-5 * (1.0 + std::fabs((double)a.T[3]));
             for (int c = 0; c < 3; c++) if (std::fabs((double)a.T[c] - (double)b.T[c]) > 1e-5) same_plane = false;
             if (!same_plane) continue;
-            (void)transmissive;      // (opaque pairs too: a decal on a wall is coplanar geometry seen from outside, and upstream's picture of it is decided by the same last bits)
+            // (opaque pairs too: a decal on a wall is coplanar geometry seen from outside, and upstream's picture of it is decided by the same last bits)
             bool overlap = convex_overlap(poly(a), poly(b), a.T);
             if (overlap) { a.tie = true; b.tie = true; }
         }
@@ -221,7 +222,7 @@ int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_o
     counts[0] = (int)quads.size() - nq_tie; counts[1] = nq_tie; counts[2] = (int)gquads.size() - ng_tie; counts[3] = ng_tie;
     counts[4] = (int)tris.size() - nt_tie; counts[5] = nt_tie; counts[6] = (int)spheres.size();
     const int n_quads = (int)quads.size(), n_gquads = (int)gquads.size(), n_tris = (int)tris.size(), n_spheres = (int)spheres.size();
-    stream.assign((size_t)(n_quads + n_tris) * 12 + (size_t)n_gquads * 18 + (size_t)n_spheres * 4 + 4, 0.f);
+    stream.assign((size_t)n_quads * kRecordFloats[0] + (size_t)n_gquads * kRecordFloats[1] + (size_t)n_tris * kRecordFloats[2] + (size_t)n_spheres * kRecordFloats[3] + 4, 0.f);
     tab.assign((size_t)(n_quads + n_gquads + n_tris + n_spheres) * 28, 0.f);
     size_t at = 0, rec = 0;
     auto cls_of = [&](int k) -> int32_t { return (prim_class && k >= 0) ? prim_class[k] : -1; };
@@ -234,15 +235,15 @@ int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_o
                 for (int c = 0; c < 3; c++) { r[c] = p.P0[c]; r[3 + c] = p.U[c]; r[6 + c] = p.V[c]; r[9 + c] = p.T[c]; e[c] = p.U[c]; e[4 + c] = p.V[c]; }
                 e[3] = p.P0[0]; e[7] = p.P0[1]; e[24] = p.P0[2];
                 memcpy(e + 12, p.map_a, 24); memcpy(e + 18, p.map_b, 24);
-                if (stride == 18) memcpy(r + 12, p.far_edges, 24);
+                if (stride == kRecordFloats[1]) memcpy(r + 12, p.far_edges, 24);
             }                                                    // a degenerate triangle keeps its slot with all-zero rows: t = -0 / 0 = NaN, which no comparison accepts
             memcpy(e + 8, ids, 16);
             at += (size_t)stride; rec++;
         }
     };
-    put_planar(quads, 12);
-    put_planar(gquads, 18);
-    put_planar(tris, 12);
+    put_planar(quads, kRecordFloats[0]);
+    put_planar(gquads, kRecordFloats[1]);
+    put_planar(tris, kRecordFloats[2]);
     for (int k : spheres) {
         float* r = stream.data() + at;
         float* e = tab.data() + 28 * rec;
@@ -251,8 +252,23 @@ int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_o
         int32_t ids[4] = {k, -1, cls_of(k), -1};
         memcpy(e + 8, ids, 16);
         memcpy(e + 12, ident, 24); memcpy(e + 18, ident, 24);
-        at += 4; rec++;
+        at += kRecordFloats[3]; rec++;
     }
     return 0;
+}
+
+// The stream two records at a time, for the one-ray any-hit sweep (traverse.hpp FlatScene::pairs): in each section the floats of records
+// 2j and 2j + 1 interleaved; an odd tail repeats its record.
+std::vector<float> flat_pairs(const std::vector<float>& stream, const int counts[7]) {
+    const int n[4] = {counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6]};
+    std::vector<float> out;
+    const float* src = stream.data();
+    for (int sec = 0; sec < 4; src += (size_t)n[sec] * kRecordFloats[sec], sec++)
+        for (int j = 0, w = kRecordFloats[sec]; 2 * j < n[sec]; j++) {
+            const float* a = src + (size_t)(2 * j) * w; const float* b = (2 * j + 1 < n[sec]) ? a + w : a;
+            for (int k = 0; k < w; k++) { out.push_back(a[k]); out.push_back(b[k]); }
+        }
+    if (out.empty()) out.push_back(0.f);
+    return out;
 }
 }  // namespace apt

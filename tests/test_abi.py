@@ -64,6 +64,69 @@ def test_render_path_fails_loudly_without_a_device(flat):
         load_renderer(os.path.join(ROOT, "scenes", "cbox"), "c2_cbox.xml")
 
 
+def _bad_scene(case, fs, a):
+    """Corrupt one field of the balls_mono scene (meshes 0..5, spheres 6..11, an area emitter on object 0): changes `a`, copies of the
+    scene's arrays, in place and returns (further description fields, the message of the apt_scene_create check that refuses it)."""
+    O, N = fs.n_objects, fs.n_prims
+    volume = {"vol_i": np.int32([2, 2, 2, 2, 0]), "vol_f": np.zeros(33, np.float32), "vol_grid": np.zeros(2 * 2 * 2 * 3, np.float32)}
+    volume["vol_f"][21:24] = 1                                  # majorants
+    textures = {"uvs": np.zeros(N * 6, np.float32), "tex_i": np.full((O, 3, 5), -255, np.int32), "tex_f": np.zeros(O * 6, np.float32)}
+    if case == "too_many_prims":                                # the count alone: the check comes before any array is read
+        return {"n_prims": 1 << 24}, b"more than 16 777 215 primitives"
+    if case == "obj_info_range":
+        a["obj_info"][O - 1, 1] += 1
+        return {}, b"obj_info range outside the primitive array"
+    if case == "area_emitter_unattached":
+        a["src_i"][0, 2] = O
+        return {}, b"area emitter is not attached to an object"
+    if case == "textured_sphere":
+        textures["tex_i"][6, 0] = (0, 0, 0, 2, 2)
+        return textures, b"textured spheres are not supported"
+    if case == "texture_outside_atlas":
+        textures["tex_i"][1, 0] = (0, 0, 0, 4, 4)
+        return {**textures, "atlas": np.zeros(2 * 2 * 3, np.float32)}, b"texture rectangle outside its atlas"     # a 2 x 2 atlas
+    if case == "unknown_medium":
+        return {"med_i": np.int32([4] + [-1] * O), "med_f": np.zeros((O + 1) * 16, np.float32)}, b"unknown medium type"
+    if case == "volume_type":
+        volume["vol_i"][0] = 1
+        return volume, b"only RGB grid volumes (type 2) exist upstream"
+    if case in ("volume_shape", "volume_phase"):
+        volume["vol_i"][1 if case == "volume_shape" else 4] = 0 if case == "volume_shape" else 4
+        return volume, b"bad grid volume shape or phase type"
+    assert case == "volume_majorant"
+    volume["vol_f"][22] = 0
+    return volume, b"grid volume majorants must be positive"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["too_many_prims", "obj_info_range", "area_emitter_unattached", "textured_sphere", "texture_outside_atlas",
+                                  "unknown_medium", "volume_type", "volume_shape", "volume_phase", "volume_majorant"])
+def test_scene_create_rejects_a_bad_description(case, flat):
+    """Each check apt_scene_create makes after the device check refuses its corrupted field with APT_E_INVALID and its message; a valid
+    scene still creates afterwards."""
+    lib = _lib.load()
+    fs = flat("balls_mono")
+    names = ("prims", "normals", "v_normals", "obj_info", "obj_aabb", "emitter_id", "bxdf_i", "bxdf_f", "src_i", "src_f")
+    a = {k: np.array(getattr(fs, k), copy=True) for k in names}
+    extra, message = _bad_scene(case, fs, a)
+    desc, keep = _scene_desc(type("FS", (), {"n_prims": fs.n_prims, "n_objects": fs.n_objects, "n_sources": fs.n_sources, **a})())
+    for name, v in extra.items():
+        keep.append(v)
+        if name == "atlas":
+            desc.atlas[0], desc.atlas_w[0], desc.atlas_h[0] = v.ctypes.data_as(_lib.f32p), 2, 2
+        elif isinstance(v, np.ndarray):
+            setattr(desc, name, v.ctypes.data_as(_lib.i32p if v.dtype == np.int32 else _lib.f32p))
+        else:
+            setattr(desc, name, v)
+    h = C.c_void_p()
+    rc = lib.apt_scene_create(C.byref(desc), 0, C.byref(h))
+    assert rc == -1 and message in lib.apt_last_error() and not h.value, (rc, lib.apt_last_error())
+    desc, keep = _scene_desc(fs)
+    _lib.check(lib.apt_scene_create(C.byref(desc), 0, C.byref(h)), "apt_scene_create")
+    assert h.value
+    lib.apt_scene_destroy(h)
+
+
 def test_bad_arguments_are_rejected():
     lib = _lib.load()
     h = C.c_void_p()
