@@ -44,7 +44,8 @@ class RenderCfg(C.Structure):
                 ("cam_r", C.c_float * 9), ("cam_t", C.c_float * 3),
                 ("inv_focal", C.c_float), ("half_w", C.c_float), ("half_h", C.c_float), ("seed", C.c_uint32),
                 ("band_width", C.c_int32), ("rank", C.c_int32), ("world_size", C.c_int32),
-                ("spp_per_batch", C.c_int32), ("device", C.c_int32), ("profile", C.c_int32), ("volumetric", C.c_int32)]
+                ("spp_per_batch", C.c_int32), ("device", C.c_int32), ("profile", C.c_int32), ("volumetric", C.c_int32),
+                ("transient_bins", C.c_int32), ("transient_min_time", C.c_float), ("transient_interval", C.c_float)]
 
 
 class Stats(C.Structure):
@@ -86,6 +87,8 @@ SYMBOLS = {
     "apt_get_accum": (C.c_int, [C.c_void_p, f32p, i32p]),
     "apt_set_accum": (C.c_int, [C.c_void_p, f32p, C.c_int32]),
     "apt_reset": (C.c_int, [C.c_void_p]),
+    "apt_read_transient": (C.c_int, [C.c_void_p, f32p]),
+    "apt_set_transient": (C.c_int, [C.c_void_p, f32p]),
     "apt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "apt_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), i32p]),
     "apt_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -11,6 +11,9 @@ square crops - a deliberate deviation.
 Differences: there is no GUI and no Taichi (`--arch` is accepted and ignored unless it is not
 one of the known names), only `--type pt` and `--type vpt` exist (homogeneous media), the "RENDERED WITH AdaPT" watermark is not
 stamped (`--no_watermark` is accepted), PNG/BMP are written by a small built-in encoder.
+`--transient` (with `--type pt`): time-resolved rendering with the sensor's `sample_count` / `min_time` / `interval`; the frames are
+written as upstream's `export_transient_profile` writes them (render.py:36-56,166): `<output_path>/<scene file stem>/img_001.<ext>` ...,
+`--normalize` applied as one quantile over the whole cube, and the cube itself as `transient.npy` (n_bins, w, h, 3) next to them.
 """
 from __future__ import annotations
 
@@ -57,6 +60,8 @@ def get_options(argv=None):
     p.add_argument("--width", default=None, type=int)
     p.add_argument("--height", default=None, type=int)
     p.add_argument("--max_bounce", default=None, type=int)
+    p.add_argument("--spp_per_batch", default=0, type=int, help="samples per wavefront batch (0: automatic)")
+    p.add_argument("--transient", default=False, action="store_true", help="time-resolved output (pt only; the sensor's sample_count / min_time / interval)")
     argv = list(sys.argv[1:] if argv is None else argv)
     pre, _ = p.parse_known_args(argv)
     if pre.config:
@@ -105,6 +110,21 @@ def write_image(img: np.ndarray, path: str):
         f.write(blob)
 
 
+def export_transient(rdr, out_path: str, out_name: str, out_ext: str, normalize: float = 0.) -> str:
+    """render.py:36-56 export_transient_profile: one image per time bin, img_001.<ext> ..., normalised by ONE quantile of the whole
+    cube when normalize > 0.9; the cube (n_bins, w, h, 3) is also saved as transient.npy.  Returns the folder."""
+    folder = _folder(os.path.join(out_path, out_name))
+    cube = rdr.transient()
+    np.save(os.path.join(folder, "transient.npy"), cube)
+    frames = cube[:, rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y, :] if rdr.do_crop else cube
+    if normalize > 0.9:
+        frames = frames / np.quantile(frames, normalize)
+    for i in range(frames.shape[0]):
+        write_image(frames[i], os.path.join(folder, f"img_{i + 1:03d}.{out_ext}"))
+    print(f"[adapt_amd] wrote {frames.shape[0]} transient frames and transient.npy to {folder}")
+    return folder
+
+
 def _folder(path: str) -> str:
     os.makedirs(path, exist_ok=True)
     return path
@@ -115,6 +135,9 @@ def main(argv=None) -> int:
     if opts.type not in ("pt", "vpt"):
         print(f"--type {opts.type}: only the `pt` and `vpt` renderers exist in this build (bdpt/ao are outside its scope)", file=sys.stderr)
         return 2
+    if opts.transient and opts.type != "pt":
+        print(f"--transient: time-resolved output exists for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
+        return 2
     from .parsers.xml_parser import scene_parsing
     from .renderer import Renderer, VolumeRenderer
     if opts.type == "vpt":                      # render.py:33 rdr_mapping: "vpt" -> VolumeRenderer
@@ -124,7 +147,8 @@ def main(argv=None) -> int:
     print(f"[adapt_amd] scene '{opts.scene}/{opts.name}': {array_info['primitives'].shape[0]} primitives, {len(objs)} objects, "
           f"{len(emitters)} emitters, parsed in {time.time() - t0:.3f} s")
     rdr = Renderer(emitters, array_info, objs, cfg, device=opts.device, seed=opts.seed, profile=opts.profile,
-                   width=opts.width, height=opts.height, max_bounce=opts.max_bounce)
+                   width=opts.width, height=opts.height, max_bounce=opts.max_bounce, spp_per_batch=opts.spp_per_batch,
+                   transient=True if opts.transient else None)
     stem = opts.name[:-4]
     max_iter = (opts.iter_num if opts.iter_num > 0 else cfg.get("iter_num", 2000)) + 1          # render.py:80-81
     chk_file = os.path.join(_folder(opts.chkpt_path), f"{opts.img_name}-{stem}-{opts.type}.pkl")
@@ -176,6 +200,8 @@ def main(argv=None) -> int:
         out = os.path.join(_folder(opts.output_path), f"{opts.img_name}-{stem}-{opts.type}.{opts.img_ext}")
         write_image(img, out)
         print(f"[adapt_amd] wrote {out}")
+    if opts.transient:
+        export_transient(rdr, opts.output_path, stem, opts.img_ext, opts.normalize)      # render.py:166: folder named after the scene file
     rdr.close()
     return 0
 

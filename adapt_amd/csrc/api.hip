@@ -45,14 +45,15 @@ typedef void (*shade_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int)
 #define APT_FUSED_FN(...) nullptr         // rays traced by the shade kernel: a product-build path (it rides on the flat sweep's records)
 #endif
 typedef void (*shade_traced_fn)(DevScene, Params, Queues, Counters*, int, int);
-struct ShadeVariant { int bm, sm; shade_fn fn; const char* name; shade_traced_fn traced; };      // traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced: flat sweep, one light sample per vertex)
+typedef void (*shade_tr_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int, TransQ);
+struct ShadeVariant { int bm, sm; shade_fn fn; const char* name; shade_traced_fn traced; shade_tr_fn transient; };      // traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced: flat sweep, one light sample per vertex); transient: fn's time-resolved twin (k_shade_tr)
 static const ShadeVariant kShadeVariants[] = {
-    {0x002, 0x01, k_shade<0x002, 0x01>, "lambertian/point", APT_FUSED_FN(k_shade_traced_lean<0x002, 0x01>)},
-    {0x003, 0x03, k_shade<0x003, 0x03>, "phong+lambertian/point+area", APT_FUSED_FN(k_shade_traced<0x003, 0x03>)},
-    {0x107, 0x03, k_shade<0x107, 0x03>, "phong+lambertian+mirror+glass/point+area", APT_FUSED_FN(k_shade_traced<0x107, 0x03>)},
-    {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL>, "all models", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL>)},
+    {0x002, 0x01, k_shade<0x002, 0x01>, "lambertian/point", APT_FUSED_FN(k_shade_traced_lean<0x002, 0x01>), k_shade_tr<0x002, 0x01>},
+    {0x003, 0x03, k_shade<0x003, 0x03>, "phong+lambertian/point+area", APT_FUSED_FN(k_shade_traced<0x003, 0x03>), k_shade_tr<0x003, 0x03>},
+    {0x107, 0x03, k_shade<0x107, 0x03>, "phong+lambertian+mirror+glass/point+area", APT_FUSED_FN(k_shade_traced<0x107, 0x03>), k_shade_tr<0x107, 0x03>},
+    {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL>, "all models", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL>},
 };
-static const ShadeVariant kTexturedShade = {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL, 1>, "all models + image textures", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL, 1>)};
+static const ShadeVariant kTexturedShade = {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL, 1>, "all models + image textures", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL, 1>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL, 1>};
 // Material classes for sorted shading: (class mask) x (emitter mask: point+area | all)
 // A kernel's register allocation is the maximum over the models it contains, so the classes are as fine as the models'
 // footprints differ: Lambertian alone runs at 4 waves per SIMD, together with Blinn-Phong (three double pows) at 2-3.
@@ -82,6 +83,9 @@ static const int kClassSlot[APT_N_CLASS_DEFS] = {0, 0, 1, 1, 4, 5, 2, 2, 3, 3}; 
 #define APT_GROUP_ROW(SM) {k_shade_group<SM, APT_GROUP0_WAVES, 0x002, 0x504, 0x200, 0x801>, k_shade_group<SM, 4, 0x001, 0x040, 0x080, 0x008, 0x010, 0x020>}
 // (group 0 at five waves: 93 VGPRs with point + spot lights, 96 and one 8-byte scratch slot with area lights; at four it took 99)
 static const group_fn kGroupShade[3][APT_N_GROUPS] = {APT_GROUP_ROW(0x03), APT_GROUP_ROW(APT_SRC_ALL), APT_GROUP_ROW(0x05)};      // [emitter set: point + area | all | point + spot (no area light: no emission code, no pdf in the record, both Philox blocks up front)][group]
+typedef void (*group_tr_fn)(DevScene, Params, Queues, Counters*, GroupIn, int, int, TransQ);
+#define APT_GROUP_TR_ROW(SM) {k_shade_group_tr<SM, 0x002, 0x504, 0x200, 0x801>, k_shade_group_tr<SM, 0x001, 0x040, 0x080, 0x008, 0x010, 0x020>}
+static const group_tr_fn kGroupShadeTr[3][APT_N_GROUPS] = {APT_GROUP_TR_ROW(0x03), APT_GROUP_TR_ROW(APT_SRC_ALL), APT_GROUP_TR_ROW(0x05)};      // the same, transient renders
 #define APT_CLASS_PHONG 1
 #define APT_CLASS_PHONG_NO_LOBE 9
 static int class_of(int is_bsdf, int type, bool no_lobe) {
@@ -228,6 +232,11 @@ struct apt_renderer {
     double render_ms = 0.0;
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
     bool render_pending = false;
+    // transient render (apt_render_cfg.transient_bins > 0; stages.hpp TransQ): one render lane, the staged pipeline
+    int transient = 0;
+    TransQ tq{};
+    DevBuf tr_pool, tr_bins;              // per-path time / record arrays (cap-sized), the bins (n_bins x owned pixels float4)
+    group_tr_fn group_tr_[APT_N_GROUPS] = {};
 };
 
 static int count_device(int* n) {
@@ -631,6 +640,7 @@ static int plan_film(apt_renderer* r) {
     if (r->npix <= 0) { return fail(APT_E_INVALID, "apt_renderer_create: this rank owns no pixels"); }
     r->n_lanes = 3;   // measured on C2: 1 lane 1 827, 2 lanes 2 196, 3 lanes 2 268, 4 lanes 2 178 Msamples/s (round 2, 64 spp per lane-batch); round 5, 32 Mi paths per lane-batch: C2 4 559 / 4 590 / 4 287 with 2 / 3 / 4, C5 1 844 / 2 028 / 2 129 with 1 / 2 / 3; volumetric scenes with null surfaces ran four lanes in rounds 3-4 (the fourth hid the host read-backs of their tails): at this batch size V1 1 374 with three, 1 299 with four
     if (const char* nl = getenv("APT_LANES")) r->n_lanes = std::min(4, std::max(1, atoi(nl)));
+    if (c.transient_bins > 0) r->n_lanes = 1;      // the bins are shared by every batch and added to per bounce: one lane keeps the adds in order
     if (const char* e = getenv("APT_NQ")) r->nq = std::min(APT_MAX_NQ, std::max(1, atoi(e)));      // tuning knob: sub-queues per queue
     const size_t nq = (size_t)r->nq;
     // queue capacity of a batch of b: whole waves, dealt over the sub-queues (generate: wave w -> sub-queue w % nq)
@@ -731,6 +741,10 @@ static int pick_shading(apt_renderer* r) {
         p.fused = (want >= 2 && can_fuse) ? 2 : 0;
     }
     if (p.fused == 2) { p.nee_vm = 0; p.l_planes = 1; }      // no shadow queue: a vertex's light samples are summed in registers
+    if (c.transient_bins > 0) {                                // transient: the staged pipeline, one radiance plane per light sample (S <= 4)
+        p.fused = 0; p.nee_vm = 0; p.l_planes = (S >= 2 && S <= 4) ? S : 1;
+        r->transient = 1;
+    }
     if (r->volumetric) {
         if (c.max_bounce > 255) { return fail(APT_E_INVALID, "apt_renderer_create: the volumetric tracer keeps the bounce count in 8 bits (max_bounce <= 255)"); }
         if (!sc->has_aabb) { return fail(APT_E_INVALID, "apt_renderer_create: the volumetric tracer needs the object boxes (world bound)"); }
@@ -757,6 +771,7 @@ static int pick_shading(apt_renderer* r) {
         const int smi = ((sc->src_mask & ~0x03) == 0) ? 0 : (((sc->src_mask & ~0x05) == 0) ? 2 : 1);
         for (int g = 0; g < APT_N_GROUPS; g++) { r->group_fn_[g] = kGroupShade[smi][g]; for (int k = 0; k < APT_GROUP_SLOTS; k++) r->group_cls[g][k] = -1; }
         r->shade_name = "sorted, launched in register-footprint groups:";
+        for (int g = 0; g < APT_N_GROUPS; g++) r->group_tr_[g] = kGroupShadeTr[smi][g];
         for (int c = 0; c < sc->n_classes; c++) {
             r->group_cls[kClassGroup[sc->class_def[c]]][kClassSlot[sc->class_def[c]]] = c;
             r->shade_name += std::string(c ? "+" : "") + kClassName[sc->class_def[c]];
@@ -765,6 +780,7 @@ static int pick_shading(apt_renderer* r) {
         r->shade_name = r->shade->name;
         if (p.fused == 2) r->shade_name += " [rays traced in place]";
     }
+    if (r->transient) r->shade_name += " [transient]";
     // (sorted: extend appends every hit path's record to the packed queue of its material class, Queues::cq)
     r->extend = r->dyn_fetch ? kExtendDyn[r->sorted] : (r->trace_mode == 3 ? kExtendFlatHot[r->sorted] : kExtend[r->trace_mode][r->sorted]);
     r->fix = kFixFlat[r->sorted];
@@ -830,6 +846,26 @@ static int make_lanes(apt_renderer* r) {
     }
     HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
     HIP_TRY(hipEventCreate(&r->ev_r0)); HIP_TRY(hipEventCreate(&r->ev_r1));
+    return APT_OK;
+}
+
+// Transient render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the bins, all zero-filled.
+static int make_transient(apt_renderer* r) {
+    if (!r->transient) return APT_OK;
+    const apt_render_cfg& c = r->cfg;
+    const size_t cap = r->par.cap, planes = (size_t)r->par.l_planes;
+    const size_t words = cap + 4 * cap + planes * cap, bins = (size_t)c.transient_bins * (size_t)r->npix * 4;
+    hipError_t e;
+    if ((e = r->tr_pool.alloc(words * 4)) != hipSuccess || (e = r->tr_bins.alloc(bins * 4)) != hipSuccess)
+        return fail(APT_E_NOMEM, std::string("transient bins: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(r->tr_pool.p, 0, words * 4, r->stream()));
+    HIP_TRY(hipMemsetAsync(r->tr_bins.p, 0, bins * 4, r->stream()));
+    float* base = r->tr_pool.as<float>();
+    TransQ& t = r->tq;
+    t.t_path = base; t.emit = reinterpret_cast<float4*>(base + cap); t.t_light = base + 5 * cap;
+    t.bins = r->tr_bins.as<float4>();
+    t.n_bins = c.transient_bins; t.min_time = c.transient_min_time; t.interval = c.transient_interval;
+    t.max_time = (float)((double)c.transient_min_time + (double)c.transient_interval * (double)c.transient_bins);
     return APT_OK;
 }
 
@@ -945,6 +981,14 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     if (c.band_width <= 0) c.band_width = c.width;
     if (c.rank < 0 || c.rank >= c.world_size) return fail(APT_E_INVALID, "apt_renderer_create: rank outside world_size");
     if (c.device != sc->device) return fail(APT_E_INVALID, "apt_renderer_create: renderer and scene must live on the same device");
+    if (c.transient_bins < 0) return fail(APT_E_INVALID, "apt_renderer_create: transient_bins must be >= 0 (0 = steady state)");
+    if (c.transient_bins > 0) {
+        if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: transient rendering is a surface-renderer mode (volumetric = 0)");
+        if (c.num_shadow_ray > 4) return fail(APT_E_INVALID, "apt_renderer_create: transient rendering takes at most 4 light samples per vertex (num_shadow_ray <= 4)");
+        if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: transient rendering runs on one rank (world_size = 1)");
+        if (!(c.transient_interval > 0.f) || !std::isfinite(c.transient_interval) || !std::isfinite(c.transient_min_time))
+            return fail(APT_E_INVALID, "apt_renderer_create: transient_interval must be positive and finite, transient_min_time finite");
+    }
     HIP_TRY(hipSetDevice(c.device));
     apt_renderer* r = new apt_renderer();
     struct Owner { apt_renderer* r; ~Owner() { if (r) apt_renderer_destroy(r); } } owner{r};     // every early return below releases streams, events and queue pools
@@ -953,6 +997,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     pick_traversal(r);
     if (int rc = pick_shading(r)) return rc;
     if (int rc = make_lanes(r)) return rc;
+    if (int rc = make_transient(r)) return rc;
     if (int rc = plan_lds_and_grids(r)) return rc;
     if (int rc = make_overflow_stacks(r)) return rc;
     for (Lane& ln : r->lanes) HIP_TRY(hipStreamSynchronize(ln.stream));
@@ -1160,21 +1205,29 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
 #endif
         {
         { LaunchTimer t(r, 0, st); hipLaunchKernelGGL(k_generate, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, cnt); }
+        // transient: a bounce's records are binned once its light samples are all settled - after its shadow launch, or with the flat sweep
+        // after the next bounce's fix-up launch (it serves the deferred ones) - and before the next shade launch writes new ones
+        auto bin = [&]() { LaunchTimer t(r, 4, st, false); hipLaunchKernelGGL(k_bin_transient, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->accum.as<float>()); };
         int cur = 0;
         for (int b = 0; b < p.max_bounce; b++) {
             // (the walk kernels reset each other's work counters - k_shadow_dyn the next bounce's closest-hit counter, k_extend_dyn this bounce's any-hit counter; without light samples the host does)
             if (r->dyn_fetch && !(p.S > 0)) { unchain(r, st); HIP_TRY(hipMemsetAsync(cnt->n_work[0], 0, sizeof(cnt->n_work[0]), st)); }
             launch_extend(r, ln, p, total, cur);
+            if (r->transient && r->trace_mode == 3 && b > 0) bin();
             if (!r->sorted) {
                 ShadeIn in = {q.ray_o[cur], q.ray_d[cur], q.thr[cur], q.id[cur], q.meta[cur], q.pdf[cur],
                               q.hit_t, q.hit_prim, q.hit_u, q.hit_v, (const uint32_t*)cnt->n_active[cur]};
-                LaunchTimer t(r, 2, st); hipLaunchKernelGGL(r->shade->fn, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, in, cur, b);
+                LaunchTimer t(r, 2, st);
+                if (r->transient) hipLaunchKernelGGL(r->shade->transient, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, in, cur, b, r->tq);
+                else hipLaunchKernelGGL(r->shade->fn, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, in, cur, b);
             } else {
                 for (int g = 0; g < APT_N_GROUPS; g++) {       // one launch per register-footprint group: its workgroups walk the member classes' queues one after the other
                     GroupIn gi; bool any = false;
                     for (int k = 0; k < APT_GROUP_SLOTS; k++) { const int c = r->group_cls[g][k]; gi.cls[k] = c; gi.counts[k] = c >= 0 ? (const uint32_t*)cnt->n_cls[c] : nullptr; any = any || c >= 0; }
                     if (!any) continue;
-                    LaunchTimer t(r, 2, st); hipLaunchKernelGGL(r->group_fn_[g], dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, gi, cur, b);
+                    LaunchTimer t(r, 2, st);
+                    if (r->transient) hipLaunchKernelGGL(r->group_tr_[g], dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, gi, cur, b, r->tq);
+                    else hipLaunchKernelGGL(r->group_fn_[g], dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, gi, cur, b);
                 }
                 if (p.S <= 0) { unchain(r, st); HIP_TRY(hipMemsetAsync(cnt->n_cls, 0, sizeof(cnt->n_cls), st)); }      // normally k_shadow recycles these
             }
@@ -1184,11 +1237,13 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
                 p.fix_par = cur;
                 LaunchTimer t(r, 3, st); hipLaunchKernelGGL(kShadow[r->trace_mode], dim3(grid_for(total * (size_t)p.S, r->grid_shadow, nq, r->trace_items)), dim3(r->trace_nt), r->lds_bytes_any, st, sc, p, q, cnt, ln.plan);
             }
+            if (r->transient && r->trace_mode != 3) bin();
             cur ^= 1;
         }
         if (r->trace_mode == 3 && p.S > 0 && p.max_bounce > 0) {     // the last bounce's shadow list (the extend list of this parity is empty)
             LaunchTimer t(r, 3, st, false); hipLaunchKernelGGL(r->fix, dim3(r->grid_fix), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, (const uint32_t*)cnt->n_active[cur], ln.plan);
         }
+        if (r->transient && r->trace_mode == 3 && p.max_bounce > 0) bin();
         }
         if (int rc = finalize_batch(r, ln, p, prev_fin)) return rc;
         r->cnt += B; done += B; batch++;
@@ -1256,10 +1311,25 @@ APT_EXPORT int apt_set_accum(apt_renderer* r, const float* in, int32_t cnt) {
     r->cnt = cnt;
     return resolve_events(r);
 }
+APT_EXPORT int apt_read_transient(apt_renderer* r, float* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_read_transient: bad argument");
+    if (!r->transient) return fail(APT_E_STATE, "apt_read_transient: the renderer was created with transient_bins = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(out, r->tr_bins.p, r->tr_bins.bytes, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
+APT_EXPORT int apt_set_transient(apt_renderer* r, const float* in) {
+    if (!r || !in) return fail(APT_E_INVALID, "apt_set_transient: bad argument");
+    if (!r->transient) return fail(APT_E_STATE, "apt_set_transient: the renderer was created with transient_bins = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(r->tr_bins.p, in, r->tr_bins.bytes, hipMemcpyHostToDevice, r->stream()));
+    return resolve_events(r);
+}
 APT_EXPORT int apt_reset(apt_renderer* r) {
     if (!r) return fail(APT_E_INVALID, "apt_reset: null handle");
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
+    if (r->transient) HIP_TRY(hipMemsetAsync(r->tr_bins.p, 0, r->tr_bins.bytes, r->stream()));
     for (Lane& ln : r->lanes) HIP_TRY(hipMemsetAsync(ln.counters.p, 0, sizeof(Counters), r->stream()));      // lanes are idle between render calls
     r->cnt = 0;
     if (int rc = resolve_events(r)) return rc;

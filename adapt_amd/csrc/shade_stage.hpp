@@ -444,8 +444,11 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
 // TEX: image-texture lookups.  Only the all-models kernel is instantiated with TEX = 1 (textured scenes run unsorted through
 // it): inlined into the specialised kernels the lookup costs e.g. the mod-Phong class kernel its fourth wave per SIMD
 // (126 -> 129 VGPRs) in every scene WITHOUT textures, and out of line it costs a call frame in scratch.
-template <int BM, int SM, int TEX, bool CQ>
-APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur, int bounce) {
+// TR: transient render (stages.hpp TransQ): the vertex's optical length is carried by slot, each light sample's time is kept next to its
+// radiance plane, and the emitter-hit contribution goes to the slot's record with its time instead of into L.  TR = false is the steady
+// kernel, unchanged.
+template <int BM, int SM, int TEX, bool CQ, bool TR = false>
+APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur, int bounce, TransQ tq = TransQ{}) {
     const ShadeArgs3* A_ = args_fresh(A0);                      // scene, parameters, queues: read through the kernel-argument segment, re-fetched per phase (APT_ARGS_PHASE)
     const int nxt = cur ^ 1;
     const SubLoop sl = sub_loop((A_->p).nq);
@@ -505,6 +508,13 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
         t_near += wave_count(alive && bounce > 0 && vx.it.min_depth < 2e-3f);
 #endif
         if (alive) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
+        // the vertex's time: the segment that ends here adds length * ior, the ior of the world's medium when the ray arrives from outside
+        // (n_g . d < 0), else that of the hit object's medium (path_tracer.py get_ior, accumulated as in bdpt.py:253); the camera is at 0
+        float t_vx = 0.f;
+        if constexpr (TR) if (alive) {
+            const float ior = (dot(vx.it.n_g, vx.d) < 0.f) ? (A_->sc).world_ior : (A_->sc).med[vx.it.obj_id].ior;
+            t_vx = ((bounce == 0) ? 0.f : tq.t_path[vx.l_off >> 2]) + vx.it.min_depth * ior;
+        }
 
         APT_ARGS_PHASE();
         // ---- next-event estimation: one shadow-queue entry per useful light sample
@@ -529,6 +539,9 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
                     const uint32_t so = (sh_qbase + spos) << 2;
                     shadow_store((A_->q), so, vx.hit_point, ls.dir, ls.dist, ls.contrib);
                     stq((A_->q).sh_id, so, vx.l_off | (((A_->p).l_planes > 1) ? (uint32_t)s : 0u));
+                    // its time: the vertex's plus the connection segment's length in the world's medium (an unoccluded segment crosses no
+                    // surface: bdpt.py:372,397 with vpt.py track_ray); kept by radiance plane, which only this sample adds into this bounce
+                    if constexpr (TR) tq.t_light[(size_t)(((A_->p).l_planes > 1) ? s : 0) * (A_->p).cap + (vx.l_off >> 2)] = t_vx + ls.dist * (A_->sc).world_ior;
                 }
             }
         }
@@ -538,8 +551,10 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
         f3 new_d = mk3(0.f, 1.f, 0.f);
         float new_pdf = 1.f;
         if (alive) {
-            new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { add_radiance((A_->q).L, (A_->p).cap, vx.l_off, add, true); });      // (nothing else touches the path's slot while its shade kernel runs)
+            if constexpr (TR) new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { tq.emit[vx.l_off >> 2] = make_float4(add.x, add.y, add.z, t_vx); });      // binned at the vertex's time (k_bin_transient)
+            else new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { add_radiance((A_->q).L, (A_->p).cap, vx.l_off, add, true); });      // (nothing else touches the path's slot while its shade kernel runs)
             cont = (bounce + 1) < (A_->p).max_bounce;
+            if constexpr (TR) if (cont) tq.t_path[vx.l_off >> 2] = t_vx;
         }
         if (rng.draw != vx.draw0) atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);      // also paths that died in the roulette
         APT_ARGS_PHASE();
@@ -562,6 +577,10 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
 template <int BM, int SM, int TEX = 0>
 __global__ void __launch_bounds__(BLOCK) k_shade(DevScene sc, Params p, Queues q, Counters* cnt, ShadeIn in, int cur, int bounce) {
     shade_staged<BM, SM, TEX, false>(kernel_args3(), cnt, in, cur, bounce);
+}
+template <int BM, int SM, int TEX = 0>
+__global__ void __launch_bounds__(BLOCK) k_shade_tr(DevScene sc, Params p, Queues q, Counters* cnt, ShadeIn in, int cur, int bounce, TransQ tq) {
+    shade_staged<BM, SM, TEX, false, true>(kernel_args3(), cnt, in, cur, bounce, tq);
 }
 #if APT_FAST
 template <int BM, int SM, int TEX = 0>
@@ -603,4 +622,15 @@ __global__ void __launch_bounds__(BLOCK, WAVES) k_shade_group(DevScene sc, Param
     if constexpr (B4 != 0) if (g.cls[4] >= 0) { in.counts = g.counts[4]; in.cls = g.cls[4]; shade_staged<B4, SM, 0, true>(kernel_args3(), cnt, in, cur, bounce); }
     if constexpr (B5 != 0) if (g.cls[5] >= 0) { in.counts = g.counts[5]; in.cls = g.cls[5]; shade_staged<B5, SM, 0, true>(kernel_args3(), cnt, in, cur, bounce); }
     if constexpr (B3 != 0) if (g.cls[3] >= 0) { in.counts = g.counts[3]; in.cls = g.cls[3]; shade_staged<B3, SM, 0, true>(kernel_args3(), cnt, in, cur, bounce); }
+}
+// ... and their transient twins (no occupancy bound: the time words cost a few registers and this mode sets no speed target)
+template <int SM, int B0, int B1, int B2, int B3, int B4 = 0, int B5 = 0>
+__global__ void __launch_bounds__(BLOCK) k_shade_group_tr(DevScene sc, Params p, Queues q, Counters* cnt, GroupIn g, int cur, int bounce, TransQ tq) {
+    ShadeIn in = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    if constexpr (B0 != 0) if (g.cls[0] >= 0) { in.counts = g.counts[0]; in.cls = g.cls[0]; shade_staged<B0, SM, 0, true, true>(kernel_args3(), cnt, in, cur, bounce, tq); }
+    if constexpr (B1 != 0) if (g.cls[1] >= 0) { in.counts = g.counts[1]; in.cls = g.cls[1]; shade_staged<B1, SM, 0, true, true>(kernel_args3(), cnt, in, cur, bounce, tq); }
+    if constexpr (B2 != 0) if (g.cls[2] >= 0) { in.counts = g.counts[2]; in.cls = g.cls[2]; shade_staged<B2, SM, 0, true, true>(kernel_args3(), cnt, in, cur, bounce, tq); }
+    if constexpr (B4 != 0) if (g.cls[4] >= 0) { in.counts = g.counts[4]; in.cls = g.cls[4]; shade_staged<B4, SM, 0, true, true>(kernel_args3(), cnt, in, cur, bounce, tq); }
+    if constexpr (B5 != 0) if (g.cls[5] >= 0) { in.counts = g.counts[5]; in.cls = g.cls[5]; shade_staged<B5, SM, 0, true, true>(kernel_args3(), cnt, in, cur, bounce, tq); }
+    if constexpr (B3 != 0) if (g.cls[3] >= 0) { in.counts = g.counts[3]; in.cls = g.cls[3]; shade_staged<B3, SM, 0, true, true>(kernel_args3(), cnt, in, cur, bounce, tq); }
 }

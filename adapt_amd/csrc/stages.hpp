@@ -137,6 +137,24 @@ struct Queues {
     int n_classes;
 };
 #define APT_MAX_CLASSES 8
+// Transient (time-resolved) rendering, surface tracer, staged pipeline only (DESIGN.md "Transient rendering").  Its buffers are a kernel
+// argument of their own, behind the steady ones, so Params and Queues - and with them every steady kernel's code - stay as they are.
+// Like L, the per-path arrays are indexed by the path's radiance slot (sample in batch * npix + local pixel), not by queue position: the
+// extend kernels that move and sort path records need not carry anything more, and only the shade kernel of a path touches them.
+struct TransQ {
+    float* t_path;            // per slot: optical length from the camera to the path's latest vertex (written when the path continues)
+    float4* emit;             // per slot: this bounce's emitter-hit contribution (rgb) and its time (w); zero when there is none
+    float* t_light;           // per radiance plane and slot (l_planes * cap): the time of light sample s of this bounce's vertex
+    float4* bins;             // [bin][local pixel]: summed rgb of the contributions that landed in the bin, and their number
+    int n_bins;
+    float min_time, interval, max_time;      // max_time = min_time + interval * n_bins, rounded to float as upstream stores it (bdpt.py:99)
+};
+// bdpt.py:164-165: a contribution at time t lands in bin int((t - min_time) / interval) when min_time < t < max_time (float32, IEEE
+// division in both builds); -1: outside the window.  The clamp keeps a t that rounds up to the window's end inside the last bin.
+APT_D int transient_bin(const TransQ& tq, float t) {
+    if (!(t > tq.min_time && t < tq.max_time)) return -1;
+    return min((int)((t - tq.min_time) / tq.interval), tq.n_bins - 1);
+}
 // what one shade launch reads: either ray queue `cur` + the hit arrays (unsorted) or one class queue (sorted)
 struct ShadeIn {
     const float* ray_o; const float* ray_d; const float* thr; const uint32_t* id; const uint32_t* meta; const float* pdf;
@@ -1048,6 +1066,41 @@ __global__ void __launch_bounds__(BLOCK) k_finalize(Params p, Queues q, float* a
             r += isnan(cr) ? 0.f : cr; g += isnan(cg) ? 0.f : cg; b += isnan(cb) ? 0.f : cb;
         }
         accum[3 * lp] = r; accum[3 * lp + 1] = g; accum[3 * lp + 2] = b;
+    }
+}
+
+// ------------------------------------------------------------ transient bins
+// Once per bounce, after that bounce's light samples are settled (flat sweep: after the next bounce's fix-up launch, which serves the
+// deferred ones): one thread per owned pixel walks the batch's samples in order and, per sample, the emitter-hit record and the radiance
+// planes of the light samples; every non-zero contribution (NaN components dropped, as k_finalize drops them) is added to its time bin
+// and to the steady framebuffer, and the record is cleared for the next bounce.  The pixel owns its bins and its framebuffer entry: no
+// atomics, and the order of the adds depends on the batch split only.  (Binning at batch end instead would keep every bounce's records:
+// cap x bounces x (1 + S) float4.)  The render runs one lane in this mode, so no other batch adds to the bins meanwhile.
+__global__ void __launch_bounds__(BLOCK) k_bin_transient(Params p, Queues q, TransQ tq, float* accum) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride) {
+        f3 sum = splat3(0.f);
+        auto land = [&](float4 c, float t) {
+            const f3 v = mk3(isnan(c.x) ? 0.f : c.x, isnan(c.y) ? 0.f : c.y, isnan(c.z) ? 0.f : c.z);
+            if (v.x == 0.f && v.y == 0.f && v.z == 0.f) return;
+            sum = sum + v;
+            const int b = transient_bin(tq, t);
+            if (b < 0) return;
+            float4* bin = tq.bins + (size_t)b * (size_t)p.npix + lp;
+            const float4 a = *bin;
+            *bin = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + 1.f);
+        };
+        for (int s = 0; s < p.spp_batch; s++) {
+            const uint32_t slot = (uint32_t)s * (uint32_t)p.npix + lp;
+            const float4 e = tq.emit[slot];
+            if (e.x != 0.f || e.y != 0.f || e.z != 0.f) { land(e, e.w); tq.emit[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }      // (NaN != 0: cleared too)
+            for (int pl = 0; pl < p.l_planes; pl++) {      // light samples in sample order
+                float4* l4 = reinterpret_cast<float4*>(L_slot(q.L, p.cap, (slot << 2) | (uint32_t)pl));
+                const float4 c = *l4;
+                if (c.x != 0.f || c.y != 0.f || c.z != 0.f) { land(c, tq.t_light[(size_t)pl * p.cap + slot]); *l4 = make_float4(0.f, 0.f, 0.f, 0.f); }
+            }
+        }
+        if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
     }
 }
 

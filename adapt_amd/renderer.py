@@ -10,6 +10,12 @@ Mirrors the contract `render.py` drives in the reference (referen
     rdr.cnt[None], rdr.color.to_numpy(), rdr.w, rdr.h, rdr.do_crop, rdr.start_x ... rdr.end_y
     rdr.get_check_point() / rdr.load_check_point(d), rdr.reset(), rdr.summary()
 
+Transient (time-resolved) output, `pt` only (DESIGN.md "Transient rendering"): `Renderer(..., transient=True)` bins every path
+contribution by its optical length, camera to emitter, as AdaPT's BDPT does in TRANSIENT_CAM mode (bdpt.py:164-165):
+
+    rdr.transient()                # (n_bins, w, h, 3) float32 [t, x, y]: summed radiance of bin t / cnt
+    rdr.transient_counts()         # (n_bins, w, h) float32: contributions per bin (upstream's time_cnts)
+
 Extensions (keyword-only, all optional): `n_spp=` on render() to queue many samples per
 call (the wavefront batches them), `device/rank/world_size/band_width` for image-tile
 sharding across GPUs, `seed`, `spp_per_batch`, `profile`, and film/bounce overrides so the
@@ -147,7 +153,9 @@ class Renderer:
                  seed: int = 0, spp_per_batch: int = 0, profile: bool = False,
                  width: Optional[int] = None, height: Optional[int] = None,
                  max_bounce: Optional[int] = None, num_shadow_ray: Optional[int] = None, volumetric: Optional[bool] = None,
-                 exact: Optional[bool] = None):
+                 exact: Optional[bool] = None, transient=None):
+        # transient = None / False: steady state; True: time bins from the sensor's sample_count / min_time / interval; a dict overrides them
+        # (scene_pack.transient_config).  Surface renderer, at most 4 light samples per vertex, one rank: apt_renderer_create refuses the rest.
         # exact = True: the bit-parity build (the reference's float32 arithmetic operation for operation; debugging and the exact
         # parity tests), False: the fast build, None: whatever adapt_amd._lib currently hands out (fast unless APT_EXACT=1)
         self.lib = _lib.load(None if exact is None else ("exact" if exact else "fast"))
@@ -156,7 +164,7 @@ class Renderer:
             volumetric = self.VOLUMETRIC
         self.flat: FlatScene = pack_scene(emitters, array_info, objects, prop)
         self.rc: RenderConfig = make_config(prop, width=width, height=height, max_bounce=max_bounce,
-                                            num_shadow_ray=num_shadow_ray, seed=seed, volumetric=bool(volumetric))
+                                            num_shadow_ray=num_shadow_ray, seed=seed, volumetric=bool(volumetric), transient=transient)
         self.volumetric = bool(volumetric)
         rc = self.rc
         # attributes the reference's callers read (watermark.py:23-30, render.py:129, path_tracer.py:181-193)
@@ -188,6 +196,8 @@ class Renderer:
         cfg.band_width, cfg.rank, cfg.world_size = self.plan.band_width, self.rank, self.world_size
         cfg.spp_per_batch, cfg.device, cfg.profile = int(spp_per_batch), self.device, int(bool(profile))
         cfg.volumetric = int(self.volumetric)
+        cfg.transient_bins, cfg.transient_min_time, cfg.transient_interval = int(rc.transient_bins), float(rc.transient_min_time), float(rc.transient_interval)
+        self.n_bins, self.min_time, self.interval = rc.transient_bins, rc.transient_min_time, rc.transient_interval
         h = C.c_void_p()
         _lib.check(self.lib.apt_renderer_create(self.scene.handle, C.byref(cfg), C.byref(h)), "apt_renderer_create", self.lib)
         self.handle = h
@@ -213,7 +223,7 @@ class Renderer:
         """No-op, exactly like the reference (`TracerBase.reset` is an empty kernel, tracer_base.py:284-286)."""
 
     def clear(self):
-        """Zero the accumulation, the sample counter and the statistics."""
+        """Zero the accumulation, the sample counter, the statistics and the transient bins."""
         _lib.check(self.lib.apt_reset(self.handle), "apt_reset", self.lib)
         self._cnt = 0
 
@@ -236,6 +246,32 @@ class Renderer:
             return tile
         from .tiles import gather_image
         return gather_image(self, normalised)
+
+    # ----------------------------------------------------------- transient
+    def _need_transient(self):
+        if not self.n_bins:
+            raise RuntimeError("this renderer was created without transient=...: there are no time bins")
+
+    def tile_transient(self) -> np.ndarray:
+        """This rank's raw bins, (n_bins, n_cols, h, 4) float32: summed r, g, b and the number of contributions."""
+        self._need_transient()
+        out = np.empty((self.n_bins, self.n_cols, self.h, 4), np.float32)
+        _lib.check(self.lib.apt_read_transient(self.handle, _fp(out)), "apt_read_transient", self.lib)
+        return out
+
+    def transient(self) -> np.ndarray:
+        """(n_bins, w, h, 3) float32, index [t, x, y]: the radiance that arrived in time bin t, divided by the sample count like `pixels`.
+        With a window that holds every path the bins sum to the steady image."""
+        cube = self.tile_transient()[..., :3]
+        return cube / np.float32(self._cnt if self._cnt > 0 else 1)
+
+    def transient_counts(self) -> np.ndarray:
+        """(n_bins, w, h) float32: the number of contributions per bin (divide transient() * cnt by it for bdpt.py's copy_average)."""
+        return np.ascontiguousarray(self.tile_transient()[..., 3])
+
+    def _set_transient(self, cube: np.ndarray):
+        cube = np.ascontiguousarray(cube, np.float32)
+        _lib.check(self.lib.apt_set_transient(self.handle, _fp(cube)), "apt_set_transient", self.lib)
 
     def _set_cnt(self, v: int):
         self._set_accum(self.tile_accum(), v)
@@ -302,11 +338,12 @@ class Renderer:
         return {"w": self.w, "h": self.h, "crop_x": self.crop_x, "crop_y": self.crop_y, "crop_rx": self.crop_rx,
                 "crop_ry": self.crop_ry, "focal": self.focal, "num_objects": self.num_objects, "num_prims": self.num_prims,
                 "cam_orient": np.array(self.cam_orient), "src_num": self.src_num, "cam_t": np.array(self.cam_t),
-                "accumulation": self.color.to_numpy(), "counter": self._cnt}
+                "accumulation": self.color.to_numpy(), "counter": self._cnt,
+                **({"transient_bins": self.tile_transient()} if self.n_bins else {})}
 
     def load_check_point(self, check_point: dict):
         for key, val in check_point.items():
-            if key in ("accumulation", "counter"):
+            if key in ("accumulation", "counter", "transient_bins"):
                 continue
             if key in ("cam_t", "cam_orient"):
                 ok = np.abs(np.asarray(val) - np.asarray(getattr(self, key))).max() < 1e-4
@@ -315,6 +352,9 @@ class Renderer:
             if not ok:
                 raise ValueError(f"'{key}' from the checkpoint is different.")
         self._set_accum(np.asarray(check_point["accumulation"], np.float32), int(check_point["counter"]))
+        cube = check_point.get("transient_bins")
+        if self.n_bins and cube is not None and np.shape(cube) == (self.n_bins, self.n_cols, self.h, 4):
+            self._set_transient(cube)           # (a checkpoint of another bin layout, or of a steady render, leaves the bins as they are)
 
     def summary(self) -> str:
         self.synchronize()

@@ -15,7 +15,7 @@ from typing import List, Optional
 import numpy as np
 from scipy.spatial.transform import Rotation
 
-__all__ = ["FlatScene", "RenderConfig", "pack_scene", "pack_source", "pack_bxdf", "make_config", "fov2focal", "np_rotation_between"]
+__all__ = ["FlatScene", "RenderConfig", "pack_scene", "pack_source", "pack_bxdf", "make_config", "transient_config", "transient_bin_index", "fov2focal", "np_rotation_between"]
 
 
 def fov2focal(fov: float, img_size) -> float:
@@ -113,6 +113,9 @@ class RenderConfig:
     crop_y: int = 0
     crop_rx: int = 0
     crop_ry: int = 0
+    transient_bins: int = 0           # 0: steady state; > 0: time-resolved bins (transient_config)
+    transient_min_time: float = 0.0
+    transient_interval: float = 0.0
 
 
 _SRC_IDS = {"point": 0, "area": 1, "spot": 2, "collimated": 4}
@@ -229,11 +232,50 @@ def pack_scene(emitters: List, array_info: dict, objects: List, prop: dict) -> F
                      world_ior=float(prop["world"].medium.ior), med_i=med_i, med_f=med_f, **vol, **tex)
 
 
+def transient_config(prop: dict, transient=None) -> tuple:
+    """-> (bins, min_time, interval) of a transient render, (0, 0.0, 0.0) for a steady one.
+
+    transient = None / False: steady state, whatever the sensor says (upstream's `decomposition` key alone never turns the mode on);
+    True: `sample_count`, `min_time` and `interval` from the sensor dict, with upstream's defaults 1, 0.0, 0.1 (bdpt.py:47,98-99);
+    a dict: those keys override the sensor's.  interval <= 0 raises ValueError, as bdpt.py:107-108 does."""
+    if transient is None or transient is False:
+        return 0, 0.0, 0.0
+    if transient is True:
+        over = {}
+    elif isinstance(transient, dict):
+        unknown = set(transient) - {"sample_count", "min_time", "interval"}
+        if unknown:
+            raise ValueError(f"unknown transient setting(s): {sorted(unknown)}")
+        over = transient
+    else:
+        raise TypeError("transient must be None, a bool or a dict of sample_count / min_time / interval")
+    bins = int(over.get("sample_count", prop.get("sample_count", 1)))
+    min_time = float(over.get("min_time", prop.get("min_time", 0.0)))
+    interval = float(over.get("interval", prop.get("interval", 0.1)))
+    if not interval > 0:
+        raise ValueError("Transient interval must be positive. Otherwise, meaningful or futile.")
+    if bins < 1:
+        raise ValueError(f"transient sample_count must be >= 1, got {bins}")
+    return bins, min_time, interval
+
+
+def transient_bin_index(t, min_time: float, interval: float, n_bins: int) -> np.ndarray:
+    """Host mirror of the device binning (stages.hpp transient_bin; bdpt.py:164-165) in float32: the bin of each time in `t`,
+    -1 outside min_time < t < min_time + interval * n_bins."""
+    t = np.asarray(t, np.float32)
+    lo, step = np.float32(min_time), np.float32(interval)
+    hi = np.float32(float(lo) + float(step) * n_bins)
+    with np.errstate(invalid="ignore"):
+        idx = np.minimum(((t - lo) / step).astype(np.int64), n_bins - 1)
+        return np.where((t > lo) & (t < hi), idx, -1)
+
+
 def make_config(prop: dict, *, width: Optional[int] = None, height: Optional[int] = None,
                 max_bounce: Optional[int] = None, num_shadow_ray: Optional[int] = None,
-                seed: int = 0, use_bvh: Optional[bool] = None, volumetric: bool = False) -> RenderConfig:
+                seed: int = 0, use_bvh: Optional[bool] = None, volumetric: bool = False, transient=None) -> RenderConfig:
     """Sensor dict -> RenderConfig.  Keyword overrides exist because the BASELINE
-    configs differ from the values stored in the scene files."""
+    configs differ from the values stored in the scene files.  `transient`: see transient_config."""
+    t_bins, t_min, t_int = transient_config(prop, transient)
     film = prop["film"]
     w = int(width if width is not None else film["width"])
     h = int(height if height is not None else film["height"])
@@ -259,4 +301,5 @@ def make_config(prop: dict, *, width: Optional[int] = None, height: Optional[int
         use_bvh=bool(use_bvh), rr_bounce_th=int(prop.get("rr_bounce_th", 4)), rr_threshold=float(prop.get("rr_threshold", 0.1)),
         cam_r=np.ascontiguousarray(cam_r, np.float32), cam_t=np.float32(prop["transform"][1]), cam_orient=orient,
         focal=float(focal), inv_focal=float(1. / focal), half_w=w / 2, half_h=h / 2, seed=int(seed), volumetric=bool(volumetric),
-        crop_x=crop_x, crop_y=crop_y, crop_rx=crop_rx, crop_ry=crop_ry)
+        crop_x=crop_x, crop_y=crop_y, crop_rx=crop_rx, crop_ry=crop_ry,
+        transient_bins=t_bins, transient_min_time=t_min, transient_interval=t_int)

@@ -16,6 +16,7 @@
  *                                   VolumeRenderer.render (one launch == one spp there; here `n_spp` samples per call, cnt += n_spp)
  *   apt_read_pixels                `rdr.pixels.to_numpy()` (utils/watermark.py:23): color / cnt, layout [x][y][rgb]
  *   apt_get_accum / apt_set_accum  tracer/path_tracer.py:181-211  get_check_point / load_check_point
+ *   apt_read_transient             renderer/bdpt.py:57-58,164-166  time_bins / time_cnts (TRANSIENT_CAM), for the `pt` renderer
  *   apt_get_stats                  (none; the reference only has ti.profiler, render.py:154-160)
  *   apt_device_ptr                 (none; hands the tile framebuffer to RCCL for the multi-GPU gather)
  *
@@ -102,6 +103,12 @@ typedef struct apt_render_cfg {
     int32_t volumetric;                           /* 0 = Renderer.render (renderer/vanilla_renderer.py:32-120); 1 = VolumeRenderer.render
                                                      (renderer/vpt.py:145-258): free-path sampling in homogeneous media, null surfaces,
                                                      transmittance-tracked light samples */
+    /* Transient (time-resolved) rendering, surface renderer only (DESIGN.md "Transient rendering"): every path contribution is also
+       added to a time bin by its optical length, camera to emitter (bdpt.py:164-165, TRANSIENT_CAM).  0 = off (steady state).  Needs
+       volumetric = 0, num_shadow_ray <= 4 and world_size = 1; runs the staged pipeline on one render lane. */
+    int32_t transient_bins;                       /* number of bins (upstream's sample_count) */
+    float   transient_min_time;                   /* a contribution at time t counts when min_time < t < min_time + interval * bins ... */
+    float   transient_interval;                   /* ... in bin int((t - min_time) / interval); must be > 0 */
 } apt_render_cfg;
 
 #define APT_N_KERNELS 5   /* generate, extend, shade, shadow, finalize */
@@ -175,7 +182,11 @@ int apt_tile_shape(const apt_renderer*, int32_t* n_cols, int32_t* height);   /* 
 int apt_read_pixels(apt_renderer*, float* out);           /* owned tile, [local col][y][rgb], color / cnt */
 int apt_get_accum(apt_renderer*, float* out, int32_t* cnt);
 int apt_set_accum(apt_renderer*, const float* in, int32_t cnt);
-int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0 */
+int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0, transient bins = 0 */
+/* transient renders: the owned tile's bins, [bin][local col][y][rgba] - summed r, g, b (divide by cnt for radiance, as pixels) and the
+   number of contributions (a); transient_bins * n_cols * height * 4 floats.  apt_set_transient restores them (checkpoints). */
+int apt_read_transient(apt_renderer*, float* out);
+int apt_set_transient(apt_renderer*, const float* in);
 int apt_get_stats(apt_renderer*, apt_stats* out);
 int apt_device_ptr(apt_renderer*, void** accum_dev, int32_t* cnt); /* device float[n_cols*height*3] accumulation buffer */
 int apt_stream(apt_renderer*, void** hip_stream);         /* the hipStream_t every kernel of this renderer runs on */
