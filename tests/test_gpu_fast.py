@@ -128,6 +128,36 @@ def test_fix_up_lists_carry_every_ray_when_asked_to(tag, kw, renderer, monkeypat
     assert m["frac_within"] >= 0.95 and abs(np.nanmean(img) - np.nanmean(ref)) <= 0.02 * np.nanmean(ref), m
 
 
+@pytest.mark.parametrize("tag,kw", [("cbox", {}), ("glass_box", {}), ("balls_mono", {}), ("balls_mono", {"num_shadow_ray": 1}), ("features_b", {}), ("textured", {"num_shadow_ray": 3})])
+def test_fix_up_lists_match_the_reference_order_sweep_of_the_same_build(tag, kw, renderer, monkeypatch):
+    """The sibling of the test above inside the product build: every ray through the fix-up lists (APT_FLAT_DEFER_ALL=1) against the
+    same library with its traversal forced to the reference-order mode the exact build picks for the scene (`sweep`, or `tile` where
+    an object has 6 primitives).  Both resolve every ray with the reference-order intersector and shade with the same arithmetic, so
+    the path statistics agree to the last count; the image is bit-equal with one light sample per vertex and, with several, equal up
+    to the association of the light-sample sum (rtol 4 ulp)."""
+    w, h, spp = 48, 40, 6
+    mode = renderer(tag, width=8, height=8, exact=True, **kw).info()["traversal"]
+    assert mode in ("sweep", "tile")
+    monkeypatch.setenv("APT_TRAVERSAL", mode)
+    s = renderer(tag, width=w, height=h, **kw)
+    assert s.info()["traversal"] == mode and s.info()["arithmetic"] == "fast"
+    s.render(n_spp=spp); ref = s.color.to_numpy(); sst = s.stats()
+    monkeypatch.delenv("APT_TRAVERSAL")
+    monkeypatch.setenv("APT_FLAT_DEFER_ALL", "1")
+    f = renderer(tag, width=w, height=h, **kw)
+    assert f.info()["traversal"] == "flat" and f.info()["arithmetic"] == "fast"
+    f.render(n_spp=spp); img = f.color.to_numpy(); st = f.stats()
+    for k in ("n_samples", "n_extend", "n_shade", "n_shadow", "n_shadow_traced", "n_lit", "n_draws"):
+        assert st[k] == sst[k], (k, st[k], sst[k])
+    if f.num_shadow_ray == 1:
+        assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))
+    same = (img == ref) | (np.isnan(img) & np.isnan(ref))
+    rel = np.abs(img.astype(np.float64) - ref) / np.maximum(np.abs(ref.astype(np.float64)), np.finfo(np.float32).tiny)
+    record_metric(f"fix-up lists vs reference-order sweep, product build {tag} {kw}",
+                  {"mode": mode, "bit_equal_frac": float(same.mean()), "max_rel": float(np.where(same, 0.0, rel).max())})
+    assert np.all(same | (rel <= 4 * 2.0 ** -23))
+
+
 @pytest.mark.parametrize("tag,kw", [("cbox", {}), ("cbox", {"max_bounce": 1}), ("glass_box", {"num_shadow_ray": 1}), ("balls_mono", {"num_shadow_ray": 1}), ("textured", {"num_shadow_ray": 1})])
 def test_rays_traced_in_place_render_the_staged_pipeline_s_image(tag, kw, renderer, monkeypatch):
     """Unsorted flat-sweep renders with one light sample per vertex run ONE launch per bounce (shade_stage.hpp "rays traced in place",
