@@ -849,6 +849,13 @@ static int make_lanes(apt_renderer* r) {
     return APT_OK;
 }
 
+// The time window of a transient render (TransQ): max_time = min_time + interval * n_bins in double, rounded to float as upstream
+// stores it (bdpt.py:99).  The renderer and apt_transient_bin_probe both set it up here.
+static void transient_window(TransQ& t, int32_t n_bins, float min_time, float interval) {
+    t.n_bins = n_bins; t.min_time = min_time; t.interval = interval;
+    t.max_time = (float)((double)min_time + (double)interval * (double)n_bins);
+}
+
 // Transient render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the bins, all zero-filled.
 static int make_transient(apt_renderer* r) {
     if (!r->transient) return APT_OK;
@@ -864,8 +871,7 @@ static int make_transient(apt_renderer* r) {
     TransQ& t = r->tq;
     t.t_path = base; t.emit = reinterpret_cast<float4*>(base + cap); t.t_light = base + 5 * cap;
     t.bins = r->tr_bins.as<float4>();
-    t.n_bins = c.transient_bins; t.min_time = c.transient_min_time; t.interval = c.transient_interval;
-    t.max_time = (float)((double)c.transient_min_time + (double)c.transient_interval * (double)c.transient_bins);
+    transient_window(t, c.transient_bins, c.transient_min_time, c.transient_interval);
     return APT_OK;
 }
 
@@ -1475,6 +1481,22 @@ APT_EXPORT int apt_bxdf_probe(int32_t device, int32_t n, const int32_t* bxdf_i, 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * per * 4, hipMemcpyDeviceToHost));
+    return APT_OK;
+}
+APT_EXPORT int apt_transient_bin_probe(int32_t device, int32_t n, const float* t, float min_time, float interval, int32_t n_bins, int32_t* out) {
+    if (n <= 0 || !t || !out || n_bins <= 0) return fail(APT_E_INVALID, "apt_transient_bin_probe: bad argument");
+    int ndev = 0;
+    if (int rc = count_device(&ndev)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    TransQ tq{};
+    transient_window(tq, n_bins, min_time, interval);
+    std::vector<float> in(t, t + (size_t)n);
+    DevBuf din, dout;
+    HIP_TRY(upload(din, in)); HIP_TRY(dout.alloc((size_t)n * 4));
+    hipLaunchKernelGGL(k_transient_bin_probe, dim3((n + 63) / 64), dim3(64), 0, 0, tq, n, din.as<float>(), dout.as<int>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return APT_OK;
 }
 APT_EXPORT int apt_medium_probe(int32_t device, int32_t n, const int32_t* med_i, const float* med_f, int32_t mode, const float* in7, uint32_t seed, float* out8) {

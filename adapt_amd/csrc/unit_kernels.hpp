@@ -70,6 +70,12 @@ __global__ void k_texture_probe(DevScene sc, int n, const int* map_obj, const fl
     f3 r = texture_query(sc, map_obj[2 * k], map_obj[2 * k + 1], uv[2 * k], uv[2 * k + 1]);
     out3[3 * k] = r.x; out3[3 * k + 1] = r.y; out3[3 * k + 2] = r.z;
 }
+// stages.hpp transient_bin on explicit times (the window as make_transient sets it up)
+__global__ void k_transient_bin_probe(TransQ tq, int n, const float* t, int* out) {
+    int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    out[k] = transient_bin(tq, t[k]);
+}
 // emitter sample_hit / eval_le / solid_angle_pdf on explicit inputs: in = src index, hit_pos, normal, ray_d, min_depth (11 floats)
 __global__ void k_emitter_probe(DevScene sc, int n, const float* in, uint32_t seed, float* out12) {
     int k = blockIdx.x * blockDim.x + threadIdx.x;

@@ -69,9 +69,17 @@ def lib():
         _lib.orc_scene_destroy.argtypes = [C.c_void_p]
         _lib.orc_texture_query.argtypes = [C.c_void_p, C.c_int, i32p, f32p, f32p]
         _lib.orc_render.argtypes = [C.c_void_p, C.POINTER(Cfg), f32p, i32p, C.c_int, C.c_int, C.POINTER(Stats)]
+        _lib.orc_render_contributions.restype = C.c_longlong
+        _lib.orc_render_contributions.argtypes = [C.c_void_p, C.POINTER(Cfg), C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, f32p, C.POINTER(Stats)]
         _lib.orc_fresnel_equation.restype = C.c_float
         _lib.orc_fresnel_equation.argtypes = [C.c_float] * 4
     return _lib
+
+
+# one record of orc_render_contributions (pt_oracle.c orc_contrib)
+CONTRIB_DTYPE = np.dtype([("pixel", np.int32), ("sample", np.int32), ("bounce", np.int32), ("kind", np.int32), ("rgb", np.float32, 3),
+                          ("t32", np.float32), ("t64", np.float64), ("t_scale", np.float64), ("t_dir", np.float64)])
+assert CONTRIB_DTYPE.itemsize == 56
 
 
 def _fp(a):
@@ -158,6 +166,27 @@ class OracleScene:
         st = Stats()
         lib().orc_render(self.handle, C.byref(cfg), _fp(accum), C.byref(c), int(n_spp), int(threads), C.byref(st))
         return accum, c.value, st.as_dict()
+
+    def contributions(self, rc, n_spp: int, cnt: int = 0, threads: int = 0):
+        """The per-contribution log of render(rc, n_spp) on the same stream (samples cnt + 1 .. cnt + n_spp), one record per path
+        contribution as the transient renderer bins it: CONTRIB_DTYPE, sorted by pixel (i * height + j), sample, bounce
+        and kind (0 the emitter hit of the vertex, 1 + s its light sample s).  Returns (records, per_sample, stats): per_sample is
+        (w, h, n_spp, 5) float32: the sample's steady colour, its number of NaN MIS weights, and 1 where its colour was NaN before
+        vanilla_renderer.py:119 zeroed it (the steady image drops such a sample whole; the log keeps its other terms)."""
+        L = lib()
+        cfg = make_cfg(rc)
+        per = np.zeros((rc.width, rc.height, int(n_spp), 5), np.float32)
+        st = Stats()
+        cap = max(1024, rc.width * rc.height * int(n_spp) * 2)
+        while True:
+            out = np.zeros(cap, CONTRIB_DTYPE)
+            n = L.orc_render_contributions(self.handle, C.byref(cfg), int(cnt), int(n_spp), int(threads), cap, out.ctypes.data_as(C.c_void_p),
+                                           _fp(per), C.byref(st))
+            if n < 0:
+                raise MemoryError("orc_render_contributions: out of memory")
+            if n <= cap:
+                return out[:n], per, st.as_dict()
+            cap = int(n)
 
     def trace_sample(self, rc, i, j, cnt, script=None, max_events=64):
         cfg = make_cfg(rc)
@@ -307,3 +336,50 @@ def medium_probe(med_type, med_f16, mode, vec, key=0, seed=0):
     out = np.zeros((6, 8, 4)[mode], np.float32)
     L.orc_medium_probe(int(med_type), _fp(f), int(mode), _fp(x), C.c_uint32(key), C.c_uint32(seed), _fp(out))
     return out
+
+
+def transient_max_time(min_time, interval, n_bins) -> np.float32:
+    """the window's end as the device stores it: min_time + interval * n_bins in double, rounded to float"""
+    return np.float32(float(np.float32(min_time)) + float(np.float32(interval)) * float(n_bins))
+
+
+def transient_bin_index(t, min_time, interval, n_bins) -> np.ndarray:
+    """stages.hpp transient_bin restated in numpy: the bin of float32 time t, -1 outside the window.  A time counts when
+    min_time < t < max_time (float32); its bin is int(float32(t - min_time) / interval) (IEEE float32 division, truncated), and a
+    quotient that rounds up to n_bins stays in the last bin."""
+    t = np.asarray(t, np.float32)
+    lo, step = np.float32(min_time), np.float32(interval)
+    inside = (t > lo) & (t < transient_max_time(lo, step, n_bins))
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.where(inside, (t - lo) / step, np.float32(0))
+    return np.where(inside, np.minimum(q.astype(np.int64), int(n_bins) - 1), -1)
+
+
+def transient_bins(records, n_pixels, min_time, interval, n_bins, near_rel=2e-5):
+    """Bin a contribution log (OracleScene.contributions) as the transient renderer does: (sums, counts, near_cnt, near_energy).
+    sums (n_bins, n_pixels, 3) float64 and counts (n_bins, n_pixels) int64 use each record's float32 time t32; near_cnt / near_energy
+    (n_bins + 1, n_pixels[, 3]) are the number and the |rgb| of the records whose time lies within near_rel * t of edge k
+    (min_time + k * interval, in double): the ones another build's time, a few ulp or a slightly different hit away, may put into the
+    neighbouring bin.  The time is t32 taken exactly: t64 differs from it by t_dir as well (a direction's length), which moves no bin of
+    a device that carries t32."""
+    recs = np.asarray(records)
+    b = transient_bin_index(recs["t32"], min_time, interval, n_bins)
+    rgb = recs["rgb"].astype(np.float64)
+    pix = recs["pixel"].astype(np.int64)
+    sums = np.zeros((n_bins, n_pixels, 3))
+    counts = np.zeros((n_bins, n_pixels), np.int64)
+    m = b >= 0
+    np.add.at(sums, (b[m], pix[m]), rgb[m])
+    np.add.at(counts, (b[m], pix[m]), 1)
+    near_cnt = np.zeros((n_bins + 1, n_pixels), np.int64)
+    near_energy = np.zeros((n_bins + 1, n_pixels, 3))
+    t = recs["t32"].astype(np.float64)
+    lo, step = float(np.float32(min_time)), float(np.float32(interval))
+    with np.errstate(invalid="ignore"):
+        k = np.rint((t - lo) / step)                            # the nearest edge
+    ok = np.isfinite(k) & (k >= 0) & (k <= n_bins)
+    ok[ok] &= np.abs(t[ok] - (lo + k[ok] * step)) <= near_rel * np.abs(t[ok])
+    ki = k[ok].astype(np.int64)
+    np.add.at(near_cnt, (ki, pix[ok]), 1)
+    np.add.at(near_energy, (ki, pix[ok]), np.abs(rgb[ok]))
+    return sums, counts, near_cnt, near_energy

@@ -1606,7 +1606,48 @@ static void process_ns(const scene_t* sc, isect_t* it) {
     if (get_uv_item(sc, 2, it, &t)) { m3 R; it->n_s = delocalize_rotate(it->n_s, t, &R); }
 }
 
-static v3 render_sample(const ctx_t* c, int i, int j, int cnt, rng_t* rng, orc_stats* st, trace_t* tr) {
+/* Per-contribution log of one pixel-sample (orc_render_contributions: the transient renderer's binning).  One record
+ * per path contribution in the form the device bins it: the emitter hit of a vertex (kind 0) at the vertex's time, light sample s of a
+ * vertex (kind 1 + s) at the vertex's time plus the connection segment's length times the world's ior.  t32 is the float32 optical
+ * length the device carries (t += min_depth * ior, the world's ior when n_g . d < 0, else the hit object's medium's); t64 is the same
+ * length in double, taken between the float32 vertex positions; t_scale is the sum of the magnitudes t32 is rounded against (t_seg).
+ * t_dir is the part of t32 - t64 that is no rounding: the device measures a segment by its ray parameter min_depth, and a sampled
+ * direction is of unit length only to a few 1e-5 (the frames of la/cam_transform.py), so it sums ior * min_depth * ||d| - 1|. */
+typedef struct {
+    int32_t pixel, sample, bounce, kind;
+    float r, g, b, t32;
+    double t64, t_scale, t_dir;
+} orc_contrib;
+typedef struct {
+    orc_contrib* rec; int n, cap, failed;
+    int pixel, sample, n_poisoned, nan_colour;
+    float t32; double t64, t_scale, t_dir; v3 prev;
+} clog_t;
+static void clog_push(clog_t* cl, int bounce, int kind, v3 c, float t32, double t64, double t_scale, double t_dir) {
+    if (isnan(c.x)) c.x = 0.f;
+    if (isnan(c.y)) c.y = 0.f;
+    if (isnan(c.z)) c.z = 0.f;
+    if (c.x == 0.f && c.y == 0.f && c.z == 0.f) return;      /* k_bin_transient counts no such contribution */
+    if (cl->n == cl->cap) {
+        int cap = cl->cap ? 2 * cl->cap : 64;
+        orc_contrib* p = realloc(cl->rec, sizeof(orc_contrib) * (size_t)cap);
+        if (!p) { cl->failed = 1; return; }
+        cl->rec = p; cl->cap = cap;
+    }
+    orc_contrib* e = &cl->rec[cl->n++];
+    e->pixel = cl->pixel; e->sample = cl->sample; e->bounce = bounce; e->kind = kind;
+    e->r = c.x; e->g = c.y; e->b = c.z; e->t32 = t32; e->t64 = t64; e->t_scale = t_scale; e->t_dir = t_dir;
+}
+static inline double amax3(v3 a) { return fmax(fabs((double)a.x), fmax(fabs((double)a.y), fabs((double)a.z))); }
+static inline double dlen(v3 a, v3 b) {
+    double x = (double)a.x - (double)b.x, y = (double)a.y - (double)b.y, z = (double)a.z - (double)b.z;
+    return sqrt(x * x + y * y + z * z);
+}
+/* what a segment's float32 time is rounded against: its length and the coordinates of both ends (the float32 vertex o + d * t and the
+ * float32 distance carry rounding relative to those, not to the length), times the ior */
+static inline double t_seg(double len, v3 a, v3 b, float ior) { return (double)ior * (len + amax3(a) + amax3(b)); }
+
+static v3 render_sample(const ctx_t* c, int i, int j, int cnt, rng_t* rng, orc_stats* st, trace_t* tr, clog_t* cl) {
     const orc_cfg* g = c->cfg; const scene_t* sc = c->sc;
     v3 ray_d = pix2ray(c, i, j, cnt, rng);
     v3 ray_o = c->cam_t;
@@ -1630,37 +1671,62 @@ static v3 render_sample(const ctx_t* c, int i, int j, int cnt, rng_t* rng, orc_s
         st->n_shade++;
         v3 hit_point = vadd(vscale(ray_d, it.min_depth), ray_o);
         float direct_pdf = 1.0f, emitter_pdf = 1.0f;
+        if (cl) {                                  /* the vertex's time (device: shade_stage.hpp, TR) */
+            const float ior = (vdot(it.n_g, ray_d) < 0.f) ? sc->world_ior : sc->med[it.obj_id].ior;
+            const double len = dlen(hit_point, cl->prev);
+            cl->t32 = cl->t32 + it.min_depth * ior;
+            cl->t64 += len * (double)ior;
+            cl->t_scale += t_seg(len, hit_point, cl->prev, ior);
+            cl->t_dir += (double)ior * fabs((double)it.min_depth) * fabs(sqrt((double)ray_d.x * ray_d.x + (double)ray_d.y * ray_d.y + (double)ray_d.z * ray_d.z) - 1.0);
+            cl->prev = hit_point;
+        }
         int break_flag = 0;
         v3 shadow_int = ZERO3, direct_int = ZERO3, direct_spec = V(1.f, 1.f, 1.f);
         get_uv_item(sc, 0, &it, &it.tex);          /* vanilla_renderer.py:66 */
         for (int s = 0; s < g->num_shadow_ray; s++) {
             int emitter_valid;
             const src_t* emitter = pt_sample_light(c, hit_light, rng, &emitter_pdf, &emitter_valid);
-            v3 light_dir = ZERO3;
+            v3 light_dir = ZERO3, emit_pos = ZERO3;
+            float emitter_d = 0.f;
             if (emitter_valid) {
-                v3 emit_pos = src_sample_hit(c, emitter, hit_point, rng, &shadow_int, &direct_pdf);
+                emit_pos = src_sample_hit(c, emitter, hit_point, rng, &shadow_int, &direct_pdf);
                 v3 to_emitter = vsub(emit_pos, hit_point);
-                float emitter_d = vnorm(to_emitter);
+                emitter_d = vnorm(to_emitter);
                 light_dir = vdivs(to_emitter, emitter_d);
                 st->n_shadow++;
                 if (pt_does_intersect(c, light_dir, hit_point, emitter_d)) shadow_int = ZERO3;
                 else { direct_spec = pt_eval(c, &it, ray_d, light_dir); st->n_lit++; }
             } else { break_flag = 1; break; }
             float light_pdf = emitter_pdf * direct_pdf;
+            v3 term;
             if (g->use_mis) {
                 float mis_w = 1.0f;
                 if (!(emitter->bool_bits & 0x01)) {
                     float bsdf_pdf_v = pt_surface_pdf(c, &it, light_dir, ray_d);
                     mis_w = balance_heuristic(light_pdf, bsdf_pdf_v);
                 }
-                direct_int = vadd(direct_int, vdivs(vscale(vmul(direct_spec, shadow_int), mis_w), emitter_pdf));
+                if (cl && isnan(mis_w)) cl->n_poisoned++;
+                term = vdivs(vscale(vmul(direct_spec, shadow_int), mis_w), emitter_pdf);
             } else {
-                direct_int = vadd(direct_int, vdivs(vmul(direct_spec, shadow_int), emitter_pdf));
+                term = vdivs(vmul(direct_spec, shadow_int), emitter_pdf);
+            }
+            direct_int = vadd(direct_int, term);
+            if (cl) {                                  /* light sample s: its own term, weighted as shade_stage.hpp sample_light weights it */
+                const double len = dlen(emit_pos, hit_point);
+                clog_push(cl, bounce, 1 + s, vmul(vscale(term, c->inv_num_shadow_ray), contribution), cl->t32 + emitter_d * sc->world_ior,
+                          cl->t64 + len * (double)sc->world_ior, cl->t_scale + t_seg(len, emit_pos, hit_point, sc->world_ior), cl->t_dir);
             }
         }
         if (!break_flag) direct_int = vscale(direct_int, c->inv_num_shadow_ray);
         v3 emit_int = ZERO3;
         if (hit_light >= 0) emit_int = src_eval_le(&sc->src[hit_light], vsub(hit_point, ray_o), it.n_s);
+        if (cl && hit_light >= 0) {                /* the emitter hit, at the vertex's time: kind 0, ahead of the vertex's light samples */
+            const int n0 = cl->n;
+            clog_push(cl, bounce, 0, vmul(vscale(emit_int, emission_weight), contribution), cl->t32, cl->t64, cl->t_scale, cl->t_dir);
+            for (int k = n0; cl->n > n0 && k > 0 && cl->rec[k - 1].sample == cl->sample && cl->rec[k - 1].bounce == bounce; k--) {
+                orc_contrib t = cl->rec[k - 1]; cl->rec[k - 1] = cl->rec[k]; cl->rec[k] = t;
+            }
+        }
         v3 indirect_spec; float ray_pdf; int is_specular;
         v3 new_d = pt_sample_new_ray(c, &it, ray_d, rng, &indirect_spec, &ray_pdf, &is_specular);
         if (tr && tr->n_events < tr->max_events) {
@@ -1688,6 +1754,7 @@ static v3 render_sample(const ctx_t* c, int i, int j, int cnt, rng_t* rng, orc_s
         }
     }
     st->n_draws += rng->draw;
+    if (cl) cl->nan_colour = isnan(color.x) || isnan(color.y) || isnan(color.z);
     if (isnan(color.x)) color.x = 0.f;
     if (isnan(color.y)) color.y = 0.f;
     if (isnan(color.z)) color.z = 0.f;
@@ -2084,7 +2151,7 @@ ORC_API int orc_render(const scene_t* sc, const orc_cfg* cfg, float* accum, int*
             if (cfg->do_crop && !(i >= cfg->start_x && i < cfg->end_x && j >= cfg->start_y && j < cfg->end_y)) continue;
             rng_t rng; rng_seed(&rng, (uint32_t)p, cfg->seed, (uint32_t)cur);
             orc_stats st; memset(&st, 0, sizeof(st));
-            v3 col = cfg->volumetric ? render_sample_vpt(&c, i, j, cur, &rng, &st, NULL) : render_sample(&c, i, j, cur, &rng, &st, NULL);
+            v3 col = cfg->volumetric ? render_sample_vpt(&c, i, j, cur, &rng, &st, NULL) : render_sample(&c, i, j, cur, &rng, &st, NULL, NULL);
             float* px = accum + 3 * (size_t)p;
             px[0] += col.x; px[1] += col.y; px[2] += col.z;
             a0 += st.n_samples; a1 += st.n_shade; a2 += st.n_shadow; a3 += st.n_lit; a4 += st.n_draws; a5 += st.n_extend; a6 += st.n_track;
@@ -2097,6 +2164,54 @@ ORC_API int orc_render(const scene_t* sc, const orc_cfg* cfg, float* accum, int*
     return 0;
 }
 
+/* The per-contribution log of Renderer.render x n_spp (orc_render's samples cnt0 + 1 .. cnt0 + n_spp, the same Philox stream):
+ * the records of every pixel-sample (orc_contrib, sorted by pixel, sample, bounce, kind whatever the thread count), the sample's
+ * steady colour, its number of NaN MIS weights and whether its colour was NaN before zeroing (then the steady image drops it whole)
+ * in sample_out[(p * n_spp + s) * 5 ..], the statistics in *stats.  Up to max_records
+ * records go to out; returns the total number (more than max_records: call again with a bigger buffer), -1 when memory runs out. */
+ORC_API long long orc_render_contributions(const scene_t* sc, const orc_cfg* cfg, int cnt0, int n_spp, int n_threads, long long max_records,
+                                           orc_contrib* out, float* sample_out, orc_stats* stats) {
+    ctx_t c; make_ctx(&c, sc, cfg);
+#ifdef _OPENMP
+    if (n_threads > 0) omp_set_num_threads(n_threads);
+#endif
+    (void)n_threads;
+    const int W = cfg->width, H = cfg->height, NP = W * H;
+    clog_t* logs = calloc((size_t)(NP > 0 ? NP : 1), sizeof(clog_t));
+    if (!logs) return -1;
+    long long a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0;
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : a0, a1, a2, a3, a4, a5, a6)
+    for (int p = 0; p < NP; p++) {
+        int i = p / H, j = p % H;
+        clog_t* cl = &logs[p];
+        cl->pixel = p;
+        if (cfg->do_crop && !(i >= cfg->start_x && i < cfg->end_x && j >= cfg->start_y && j < cfg->end_y)) continue;
+        for (int s = 0; s < n_spp; s++) {
+            const int cur = cnt0 + s + 1;
+            rng_t rng; rng_seed(&rng, (uint32_t)p, cfg->seed, (uint32_t)cur);
+            orc_stats st; memset(&st, 0, sizeof(st));
+            cl->sample = cur; cl->n_poisoned = 0;
+            cl->t32 = 0.f; cl->t64 = 0.0; cl->t_scale = 0.0; cl->t_dir = 0.0; cl->prev = c.cam_t;
+            v3 col = render_sample(&c, i, j, cur, &rng, &st, NULL, cl);
+            float* so = sample_out + 5 * ((size_t)p * (size_t)n_spp + (size_t)s);
+            so[0] = col.x; so[1] = col.y; so[2] = col.z; so[3] = (float)cl->n_poisoned; so[4] = (float)cl->nan_colour;
+            a0 += st.n_samples; a1 += st.n_shade; a2 += st.n_shadow; a3 += st.n_lit; a4 += st.n_draws; a5 += st.n_extend; a6 += st.n_track;
+        }
+    }
+    long long total = 0; int failed = 0;
+    for (int p = 0; p < NP; p++) {
+        failed |= logs[p].failed;
+        for (int k = 0; k < logs[p].n; k++, total++) if (total < max_records) out[total] = logs[p].rec[k];
+        free(logs[p].rec);
+    }
+    free(logs);
+    if (stats) {
+        stats->n_samples = a0; stats->n_shade = a1; stats->n_shadow = a2; stats->n_lit = a3; stats->n_draws = a4;
+        stats->n_extend = a5; stats->n_track = a6;
+    }
+    return failed ? -1 : total;
+}
+
 /* One pixel-sample with a per-bounce event trace and either RNG mode (script != NULL -> scripted). */
 ORC_API int orc_trace_sample(const scene_t* sc, const orc_cfg* cfg, int i, int j, int cnt, const double* script, int script_n,
                              float color_out[3], float* events, int max_events, int* n_events, int* n_draws) {
@@ -2106,7 +2221,7 @@ ORC_API int orc_trace_sample(const scene_t* sc, const orc_cfg* cfg, int i, int j
     orc_stats st; memset(&st, 0, sizeof(st));
     trace_t tr = {max_events, 0, events};
     v3 col = cfg->volumetric ? render_sample_vpt(&c, i, j, cnt, &rng, &st, events ? &tr : NULL)
-                             : render_sample(&c, i, j, cnt, &rng, &st, events ? &tr : NULL);
+                             : render_sample(&c, i, j, cnt, &rng, &st, events ? &tr : NULL, NULL);
     color_out[0] = col.x; color_out[1] = col.y; color_out[2] = col.z;
     if (n_events) *n_events = tr.n_events;
     if (n_draws) *n_draws = (int)rng.draw;

@@ -134,6 +134,10 @@ def test_bad_arguments_are_rejected():
     assert lib.apt_scene_create(None, 0, C.byref(h)) == -1
     assert lib.apt_render(None, 1) == -1 and lib.apt_get_stats(None, None) == -1
     assert b"apt_get_stats" in lib.apt_last_error()
+    t, out = np.float32([1.0]), np.zeros(1, np.int32)
+    fp, ip = t.ctypes.data_as(_lib.f32p), out.ctypes.data_as(_lib.i32p)
+    assert lib.apt_transient_bin_probe(0, 0, fp, 0.0, 1.0, 4, ip) == -1 and lib.apt_transient_bin_probe(0, 1, fp, 0.0, 1.0, 0, ip) == -1
+    assert b"apt_transient_bin_probe" in lib.apt_last_error()
 
 
 def build_bvh(fs):
