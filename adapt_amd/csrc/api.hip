@@ -154,6 +154,7 @@ struct apt_scene {
     int bvh_levels = 0;                  // levels of the 8-wide tree the kernels walk (the renderers size their traversal stacks by it)
     DevBuf nodes, prims, slot_prim, normals, vnormals, precom, prim_obj, prim_class, obj_info, emitter_id, bxdf, src, sweep_recs, sweep_tab;
     DevBuf flat_recs, flat_tab, flat_pairs;     // flat sweep (fast build, small scenes): records, the per-record table, the records two by two (traverse.hpp FlatScene)
+    DevBuf flat_occ, flat_occ_tab;              // ... per emitter, the records that can block its light samples, two by two, and their table
     bool has_flat = false;
     DevBuf uvs, tex_i, tex_f, atlas[3];      // image textures (empty when the scene has none)
     DevBuf prim_shade;                   // per-primitive shading records (stages.hpp DevScene::prim_shade)
@@ -283,6 +284,19 @@ APT_EXPORT int apt_flat_records(const float* prims, int32_t n_prims, const int32
     *n_stream = (int32_t)st.size(); *n_tab = (int32_t)tb.size();
     if (stream) { if (stream_cap < (int32_t)st.size()) return fail(APT_E_INVALID, "apt_flat_records: stream buffer too small"); memcpy(stream, st.data(), st.size() * 4); }
     if (tab) { if (tab_cap < (int32_t)tb.size()) return fail(APT_E_INVALID, "apt_flat_records: table buffer too small"); memcpy(tab, tb.data(), tb.size() * 4); }
+    return APT_OK;
+}
+APT_EXPORT int apt_flat_occluders(const float* prims, int32_t n_prims, const int32_t* obj_info, int32_t n_objects, const int32_t* src_i, const float* src_f, int32_t n_sources,
+                                  int32_t cull, int32_t* table, int32_t* keep, int32_t keep_cap, float* pairs, int32_t pairs_cap, int32_t* n_records, int32_t* n_pairs) {
+    if (!prims || !obj_info || !src_i || !src_f || n_prims <= 0 || n_objects <= 0 || n_sources <= 0 || !n_records || !n_pairs) return fail(APT_E_INVALID, "apt_flat_occluders: bad argument");
+    std::vector<float> st, tb, pts, pr; std::vector<int32_t> off, tab8; std::vector<uint8_t> kp; int c[7];
+    if (apt::build_flat(prims, n_prims, obj_info, n_objects, nullptr, st, tb, c) != 0) return fail(APT_E_INVALID, "apt_flat_occluders: obj_info range outside the primitive array");
+    apt::emitter_points(prims, obj_info, n_objects, src_i, src_f, n_sources, pts, off);
+    if (apt::flat_occluders(prims, n_prims, st, tb, c, pts.data(), off.data(), n_sources, cull != 0, pr, tab8, kp) != 0) return fail(APT_E_INVALID, "apt_flat_occluders: bad record");
+    *n_records = (int32_t)(kp.size() / (size_t)n_sources); *n_pairs = (int32_t)pr.size();
+    if (table) memcpy(table, tab8.data(), tab8.size() * 4);
+    if (keep) { if (keep_cap < (int32_t)kp.size()) return fail(APT_E_INVALID, "apt_flat_occluders: keep buffer too small"); for (size_t k = 0; k < kp.size(); k++) keep[k] = kp[k]; }
+    if (pairs) { if (pairs_cap < (int32_t)pr.size()) return fail(APT_E_INVALID, "apt_flat_occluders: pairs buffer too small"); memcpy(pairs, pr.data(), pr.size() * 4); }
     return APT_OK;
 }
 APT_EXPORT int apt_bvh_wide_counts(const apt_bvh* b, int32_t* n_nodes, int32_t* n_levels) {
@@ -502,12 +516,20 @@ static int pack_flat(const apt_scene_desc* d, apt_scene* s, const std::vector<in
     std::vector<float> fr, ft; int fc[7];
     if (apt::build_flat(d->prims, N, d->obj_info, s->n_objects, prim_class.data(), fr, ft, fc) != 0) return fail(APT_E_INVALID, "apt_scene_create: flat records: obj_info range outside the primitive array");
     if (!put("flat records", s->flat_recs, fr) || !put("flat records", s->flat_tab, ft) || !put("flat record pairs", s->flat_pairs, apt::flat_pairs(fr, fc))) return APT_E_HIP;
+    // per emitter, the records that can block its light samples (flat_build.cpp flat_occluders); APT_SHADOW_CULL=0: the full stream for every emitter
+    const bool cull = !(getenv("APT_SHADOW_CULL") && atoi(getenv("APT_SHADOW_CULL")) == 0);
+    std::vector<float> pts, op; std::vector<int32_t> off, ot; std::vector<uint8_t> keep;
+    apt::emitter_points(d->prims, d->obj_info, s->n_objects, d->src_i, d->src_f, s->n_sources, pts, off);
+    if (apt::flat_occluders(d->prims, N, fr, ft, fc, pts.data(), off.data(), s->n_sources, cull, op, ot, keep) != 0) return fail(APT_E_INVALID, "apt_scene_create: flat records: bad record");
+    if (!put("occluder lists", s->flat_occ, op) || !put("occluder lists", s->flat_occ_tab, ot)) return APT_E_HIP;
     FlatScene& fl = s->dev.flat;
     fl.stream = s->flat_recs.as<float>(); fl.tab = s->flat_tab.as<float4>(); fl.pairs = s->flat_pairs.as<float>();
+    fl.occ_pairs = s->flat_occ.as<float>(); fl.occ_tab = s->flat_occ_tab.as<int>();
     fl.defer_all = getenv("APT_FLAT_DEFER_ALL") ? atoi(getenv("APT_FLAT_DEFER_ALL")) : 0;
     fl.n_quads = fc[0]; fl.n_quads_tie = fc[1]; fl.n_gquads = fc[2]; fl.n_gquads_tie = fc[3]; fl.n_tris = fc[4]; fl.n_tris_tie = fc[5]; fl.n_spheres = fc[6];
     s->has_flat = true;
     if (timer.on) fprintf(stderr, "[scene timing] flat records: %d + %d parallelograms, %d + %d convex quads, %d + %d triangles (plain + coplanar groups), %d spheres of %d primitives\n", fc[0], fc[1], fc[2], fc[3], fc[4], fc[5], fc[6], N);
+    if (timer.on) for (int e = 0; e < s->n_sources; e++) fprintf(stderr, "[scene timing] occluders of emitter %d: %d parallelograms, %d convex quads, %d triangles, %d spheres\n", e, ot[8 * (size_t)e + 1], ot[8 * (size_t)e + 2], ot[8 * (size_t)e + 3], ot[8 * (size_t)e + 4]);
     timer.tick("flat records");
     return APT_OK;
 }

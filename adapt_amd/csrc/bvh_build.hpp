@@ -76,4 +76,13 @@ void planar_rows(const float* tri9, float out12[12]);      // one triangle: corn
 int build_flat(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, const int32_t* prim_class,
                std::vector<float>& stream, std::vector<float>& tab, int counts[7]);      // counts: parallelograms, convex quads, triangles - each plain, then in coplanar groups - and spheres
 std::vector<float> flat_pairs(const std::vector<float>& stream, const int counts[7]);      // the stream's records two by two (FlatScene::pairs)
+// Occluder lists of the light samples: the points each emitter can be sampled at (pts: xyz; emitter e owns points
+// off[e] .. off[e + 1] - 1; none: the emitter gets the full stream), and per emitter the records a segment from the scene to one of those
+// points can block, two by two as FlatScene::pairs.  table: 8 ints per emitter (offset into `pairs` in floats, records per section:
+// parallelograms, convex quads, triangles, spheres, then 0 0 0); keep: n_records flags per emitter, in stream order.  cull = false: every
+// emitter's list is the full stream.
+void emitter_points(const float* prims, const int32_t* obj_info, int n_objects, const int32_t* src_i, const float* src_f, int n_sources,
+                    std::vector<float>& pts, std::vector<int32_t>& off);
+int flat_occluders(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7],
+                   const float* pts, const int32_t* off, int n_emit, bool cull, std::vector<float>& pairs, std::vector<int32_t>& table, std::vector<uint8_t>& keep);
 }  // namespace apt

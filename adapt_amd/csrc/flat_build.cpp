@@ -8,6 +8,8 @@
 // the shared edge, edge, edge): a parallelogram (inside <=> u, v in [0, 1]) or a general convex quadrilateral (u, v >= 0 and two more edge
 // functions of (u, v)); which triangle a hit belongs to is u + v <= 1, and each triangle's own barycentrics are an affine map of the
 // record's (u, v) (coefficients in {-1, 0, 1} for a parallelogram).  Degenerate triangles get a record no ray can hit (upstream: det = 0 -> non-finite barycentrics -> never accepted).
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 
@@ -270,5 +272,136 @@ std::vector<float> flat_pairs(const std::vector<float>& stream, const int counts
         }
     if (out.empty()) out.push_back(0.f);
     return out;
+}
+
+// The points an emitter's light samples aim at (shading.hpp emitter_sample_hit): point and spot lights their position, an area light on a
+// mesh every vertex of the mesh (a sample is a convex combination of them), an area light on a sphere the sphere's box, padded.  Any other
+// emitter gets no points - and with them the full stream.
+void emitter_points(const float* prims, const int32_t* obj_info, int n_objects, const int32_t* src_i, const float* src_f, int n_sources,
+                    std::vector<float>& pts, std::vector<int32_t>& off) {
+    pts.clear(); off.assign(1, 0);
+    for (int e = 0; e < n_sources; e++) {
+        const int type = src_i[4 * e], obj = src_i[4 * e + 2];
+        const float* pos = src_f + 11 * e + 6;
+        if (type == 0 || type == 2) pts.insert(pts.end(), pos, pos + 3);
+        else if (type == 1 && obj >= 0 && obj < n_objects) {
+            const int first = obj_info[3 * obj], count = obj_info[3 * obj + 1];
+            if (obj_info[3 * obj + 2]) {
+                const float* c = prims + 9 * (size_t)first; const double r = std::fabs((double)c[3]) * (1.0 + 1e-3) + 1e-6 * (1.0 + std::fabs((double)c[0]) + std::fabs((double)c[1]) + std::fabs((double)c[2]));
+                for (int k = 0; k < 8; k++) for (int a = 0; a < 3; a++) pts.push_back((float)((double)c[a] + (((k >> a) & 1) ? r : -r)));
+            } else for (int k = first; k < first + count; k++) pts.insert(pts.end(), prims + 9 * (size_t)k, prims + 9 * (size_t)k + 9);
+        }
+        off.push_back((int32_t)(pts.size() / 3));
+    }
+}
+
+// Which records can block a light sample (traverse.hpp flat_any1).  A record R blocks a shadow ray only where
+// flat_blocks() accepts it: inside R, t > 1e-4, t < dist - 1e-4.  h(x) = T . (x - p0) is the height over R's plane exactly as the
+// kernel computes it (its stored rows), oriented so that the emitter's points are on the positive side, at height >= delta > 0.  If every
+// vertex of the scene (and every sphere's padded box) is at height >= h_min, every shadow-ray origin - a hit point on some record S, off S
+// by the rounding of its intersector - is at height >= h_min - eta, and h is affine along the ray, so the segment from an origin to the
+// light crosses R's plane at most once, at t <= (eta - h_min) maxdist / delta (maxdist: the farthest light point from any vertex), and
+// nowhere if the origin is above the plane.  The kernel's own t adds its rounding (e_o below).  If that bound stays below HALF the 1e-4
+// floor, R can only ever be "hit" as a self-intersection that flat_blocks() already rejects: R is left out of the emitter's list.
+// Rounding, with u = 2^-24, ext = the extent of scene and lights per axis, L = |ext|, M = the largest |coordinate| per axis:
+//  * height of a hit point x over its own record S's plane (planar_solve: t = -T.s * rcp(T.d), s = o - p0 and the products rounded, the
+//    rcp within 1 ulp, |t| <= L):  7 u sum|T_S| ext + 3 u L;
+//  * how far outside S's outline the inside test may accept x: an edge function g = a u + b v + c, with u, v from U . P, V . P at
+//    P = fma(t, d, s), is off by 5 u (|a| sum|U| ext + |b| sum|V| ext) - divided by |a U + b V| a distance in the plane;
+//  * x itself, d * t + o rounded per component: u (L + |M|);
+//  * R's own t: T_R . s to 4 u sum|T_R| ext, T_R . d >= delta / maxdist.
+// The reference-order code that serves the rare deferred rays (prim_test, sweep) rounds its hit points to the same order; the factor 2 of
+// the floor covers it.  Spheres keep their records (their hit points enter through their padded boxes).
+int flat_occluders(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7],
+                   const float* pts, const int32_t* off, int n_emit, bool cull, std::vector<float>& pairs, std::vector<int32_t>& table, std::vector<uint8_t>& keep) {
+    const double u = std::ldexp(1.0, -24);
+    const int nsec[4] = {counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6]};
+    const int n_rec = nsec[0] + nsec[1] + nsec[2] + nsec[3];
+    struct Rec { int sec; size_t at; std::vector<D3> vs; };
+    std::vector<Rec> recs;
+    std::vector<D3> geo;                                    // every vertex of the scene, every sphere's padded box
+    {
+        size_t at = 0;
+        for (int sec = 0, r = 0; sec < 4; sec++) for (int j = 0; j < nsec[sec]; j++, r++, at += (size_t)kRecordFloats[sec]) {
+            int32_t ids[2]; memcpy(ids, tab.data() + 28 * (size_t)r + 8, 8);
+            Rec rc; rc.sec = sec; rc.at = at;
+            if (ids[0] < 0 || ids[0] >= n_prims || ids[1] >= n_prims) return -1;
+            if (sec < 3) { for (int k : {ids[0], ids[1]}) if (k >= 0) for (int v = 0; v < 3; v++) rc.vs.push_back(vtx(prims, k, v)); }
+            else {
+                const float* c = prims + 9 * (size_t)ids[0];
+                const double rr = std::fabs((double)c[3]);
+                // a grazing sphere hit is off by up to ~sqrt(u) L along the ray (a difference of squares): pad the box by more than that
+                const double pad = 1e-3 * rr + 1e-6 * (1.0 + std::fabs((double)c[0]) + std::fabs((double)c[1]) + std::fabs((double)c[2])) + 1e-3;
+                for (int k = 0; k < 8; k++) rc.vs.push_back({c[0] + (((k >> 0) & 1) ? rr + pad : -rr - pad), c[1] + (((k >> 1) & 1) ? rr + pad : -rr - pad), c[2] + (((k >> 2) & 1) ? rr + pad : -rr - pad)});
+            }
+            geo.insert(geo.end(), rc.vs.begin(), rc.vs.end());
+            recs.push_back(rc);
+        }
+    }
+    const int n_pts = n_emit > 0 ? off[n_emit] : 0;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, M[3] = {0, 0, 0};
+    auto grow = [&](D3 p) { const double c[3] = {p.x, p.y, p.z}; for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], c[a]); hi[a] = std::max(hi[a], c[a]); M[a] = std::max(M[a], std::fabs(c[a])); } };
+    for (const D3& p : geo) grow(p);
+    for (int k = 0; k < n_pts; k++) grow({pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]});
+    const D3 ext = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    const double L = std::sqrt(dot(ext, ext)), Mn = std::sqrt(M[0] * M[0] + M[1] * M[1] + M[2] * M[2]);
+    auto absdot = [](D3 a, D3 b) { return std::fabs(a.x) * b.x + std::fabs(a.y) * b.y + std::fabs(a.z) * b.z; };
+    auto row = [&](const Rec& r, int k) -> D3 { const float* p = stream.data() + r.at + 3 * k; return {p[0], p[1], p[2]}; };      // k: 0 p0, 1 U, 2 V, 3 T
+    // eta: how far below the outline of the record it lies on a shadow-ray origin can be, the worst over all planar records
+    double eta = 0.0;
+    for (const Rec& r : recs) {
+        if (r.sec == 3) continue;
+        const D3 U = row(r, 1), V = row(r, 2), T = row(r, 3);
+        if (dot(T, T) == 0.0) continue;                          // a degenerate triangle: never hit, never an origin
+        std::vector<std::array<double, 2>> edges = {{1, 0}, {0, 1}};
+        if (r.sec == 2) edges.push_back({1, 1});               // w = 1 - u - v (a parallelogram's u = 1, v = 1 have the gradients of u, v)
+        if (r.sec == 1) for (int e = 0; e < 2; e++) { const float* f = stream.data() + r.at + 12 + 3 * e; edges.push_back({f[0], f[1]}); }
+        double ovs = 0.0;
+        for (const auto& g : edges) {
+            const D3 grad = add({g[0] * U.x, g[0] * U.y, g[0] * U.z}, {g[1] * V.x, g[1] * V.y, g[1] * V.z});
+            const double gl = std::sqrt(dot(grad, grad));
+            if (!(gl > 0.0)) return -1;
+            ovs = std::max(ovs, 5.0 * u * (std::fabs(g[0]) * absdot(U, ext) + std::fabs(g[1]) * absdot(V, ext)) / gl);
+        }
+        eta = std::max(eta, 7.0 * u * absdot(T, ext) / std::sqrt(dot(T, T)) + 3.0 * u * L + ovs);
+    }
+    eta += u * (L + Mn);
+    keep.assign((size_t)n_emit * (size_t)n_rec, 1);
+    pairs.clear(); table.assign((size_t)n_emit * 8, 0);
+    for (int e = 0; e < n_emit; e++) {
+        uint8_t* kp = keep.data() + (size_t)e * n_rec;
+        const int p0 = off[e], p1 = off[e + 1];
+        if (cull && p1 > p0) for (int ri = 0; ri < n_rec; ri++) {
+            const Rec& r = recs[(size_t)ri];
+            if (r.sec == 3) continue;
+            const D3 P = row(r, 0), T = row(r, 3);
+            if (dot(T, T) == 0.0) continue;
+            auto h = [&](D3 x) { return dot(T, sub(x, P)); };
+            double lmin = 1e300, lmax = -1e300;
+            for (int k = p0; k < p1; k++) { const double v = h({pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]}); lmin = std::min(lmin, v); lmax = std::max(lmax, v); }
+            const double sgn = lmin > 0.0 ? 1.0 : (lmax < 0.0 ? -1.0 : 0.0);
+            if (sgn == 0.0) continue;                            // the emitter straddles (or touches) R's plane
+            const double delta = (sgn > 0 ? lmin : -lmax) - 4.0 * u * Mn;      // (an area-light sample is a rounded combination of its vertices)
+            double hmin = 1e300, maxdist = 0.0;
+            for (const D3& g : geo) hmin = std::min(hmin, sgn * h(g));
+            for (int k = p0; k < p1; k++) for (const D3& g : geo) { const D3 dd = sub({pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]}, g); maxdist = std::max(maxdist, std::sqrt(dot(dd, dd))); }
+            const double e_o = 4.0 * u * absdot(T, ext);
+            const double reach = (std::max(0.0, -hmin) + eta + e_o) * (maxdist + eta) / delta * (1.0 + 1e-3);
+            if (delta > 0.0 && reach <= 0.5e-4) kp[ri] = 0;
+        }
+        // the kept records, sections as in the stream (coplanar-group records inside their sections), two by two
+        std::vector<float> st; int c[7] = {0, 0, 0, 0, 0, 0, 0};
+        for (int ri = 0; ri < n_rec; ri++) if (kp[ri]) {
+            const Rec& r = recs[(size_t)ri];
+            st.insert(st.end(), stream.begin() + (long)r.at, stream.begin() + (long)(r.at + (size_t)kRecordFloats[r.sec]));
+            c[2 * r.sec]++;
+        }
+        int32_t* t = table.data() + 8 * (size_t)e;
+        t[0] = (int32_t)pairs.size(); t[1] = c[0]; t[2] = c[2]; t[3] = c[4]; t[4] = c[6];
+        std::vector<float> pr = flat_pairs(st, c);
+        pairs.insert(pairs.end(), pr.begin(), pr.end());
+    }
+    if (pairs.empty()) pairs.push_back(0.f);
+    return 0;
 }
 }  // namespace apt

@@ -229,10 +229,10 @@ APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, Philox& rng, int prim, 
 // the weight multiplies the sample even when the shadow ray is occluded, 0 * NaN, so it poisons the whole pixel-sample, which is zeroed
 // at the end - reproduced without tracing).  LANE_SRC: whole-record emitter loads (the class kernels only: in C2's traced kernel their
 // sixteen registers cost the fourth wave, 127 -> 132 VGPRs).
-struct LightSample { bool want, sampled, poisoned; f3 dir, contrib; float dist, mis_w; };
+struct LightSample { bool want, sampled, poisoned; f3 dir, contrib; float dist, mis_w; int src; };      // src: the emitter sampled
 template <int BM, int SM, bool LANE_SRC>
 APT_D LightSample sample_light(const ShadeArgs3* A_, Vertex& vx, Philox& rng, const EmitterGeom& geom, const DevSrc src_only, bool active, bool& break_flag) {
-    LightSample ls; ls.want = ls.sampled = ls.poisoned = false; ls.dir = ls.contrib = splat3(0.f); ls.dist = 0.f; ls.mis_w = 1.0f;
+    LightSample ls; ls.want = ls.sampled = ls.poisoned = false; ls.dir = ls.contrib = splat3(0.f); ls.dist = 0.f; ls.mis_w = 1.0f; ls.src = 0;
     if (!active || break_flag) return ls;
     const int ns = (A_->sc).n_sources;                    // wave-uniform: one light needs no modulo
     int sidx = rng_int(rng);                            // one int is always drawn
@@ -247,6 +247,7 @@ APT_D LightSample sample_light(const ShadeArgs3* A_, Vertex& vx, Philox& rng, co
     }
     DevSrc src = src_only;
     if (ns != 1) src = LANE_SRC ? ld_src_lane((A_->sc).src + sidx) : (A_->sc).src[sidx];
+    ls.src = sidx;
     f3 shadow_int; float direct_pdf;
     const f3 to_emitter = emitter_sample_hit<SM>(src, geom, vx.hit_point, rng, shadow_int, direct_pdf) - vx.hit_point;
     ls.dist = fnorm(to_emitter);
@@ -371,6 +372,18 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
         const LightSample f = sample_light<BM, SM, false>(A_, vx, rng, geom, src_only, alive, break_flag);      // (one light sample per vertex: api.hip, Params::fused)
         if (f.poisoned) Lc = splat3(f.mis_w);
         tl.shadow += wave_count(f.sampled); tl.poison += wave_count(f.poisoned);
+        // the records the row's light samples are swept against (traverse.hpp flat_occ_list): the occluder list of the emitter that every
+        // lane of the wave that wants a sample has sampled - the only one in a single-emitter scene - else the full stream (occ_e = -1).
+        // Decided here, wave-uniform (scalar registers), so that the emitter index is not held in a lane register until the sweep.
+        int occ_e = 0;
+        if ((A_->sc).n_sources != 1) {
+            const unsigned long long wm = __ballot(f.want);
+            occ_e = -1;
+            if (wm != 0ull) {
+                const int e0 = __builtin_amdgcn_readlane(f.src, __ffsll((long long)wm) - 1);
+                if (!__any(f.want && f.src != e0)) occ_e = e0;
+            }
+        }
         APT_ARGS_PHASE();
         // ---- emission of the surface we are on, then the continuation
         bool cont = false, is_spec = false;
@@ -401,7 +414,10 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
             // the row's light sample, swept in place; a ray that needs the reference-order sweep leaves as a shadow-queue entry for the next launch's prologue
             const bool defer = f.want && flat_needs_cull((A_->sc).flat, f.dir);
             bool occ = false;
-            if (__any(f.want && !defer)) occ = flat_any1((A_->sc).flat, vx.hit_point, f.dir, (f.dist > 0.0f) ? f.dist - 1e-4f : 1e7f);
+            if (__any(f.want && !defer)) {
+                const FlatList ls = (occ_e >= 0) ? flat_occ_list((A_->sc).flat, occ_e) : flat_full_list((A_->sc).flat);
+                occ = flat_any1(ls, vx.hit_point, f.dir, (f.dist > 0.0f) ? f.dist - 1e-4f : 1e7f);
+            }
             if (__any(defer)) {
                 const uint32_t spos = wave_append(defer, &cnt->n_fix_sh[cur][sl.q * CNT_PAD]);
                 if (defer && spos < (A_->q).sh_subcap) { const uint32_t so = (sh_qbase + spos) << 2; shadow_store((A_->q), so, vx.hit_point, f.dir, f.dist, f.contrib); stq((A_->q).sh_id, so, vx.l_off); }

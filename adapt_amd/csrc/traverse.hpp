@@ -648,6 +648,8 @@ struct FlatScene {
     const float* pairs;       // the same records two by two, every float of records 2j and 2j + 1 next to each other (an odd tail repeats its last record): the any-hit sweep of ONE ray per lane tests two records per packed instruction (flat_any1: shade kernels that trace their own light samples)
     int n_quads, n_quads_tie, n_gquads, n_gquads_tie, n_tris, n_tris_tie, n_spheres;
     int defer_all;            // test switch (APT_FLAT_DEFER_ALL=1 at scene creation): every ray takes the reference-order path - in the stage kernels, through the fix-up lists
+    const float* occ_pairs;   // per emitter, the records that can block its light samples, two by two as `pairs` (flat_build.cpp flat_occluders)
+    const int* occ_tab;       // 8 ints per emitter: offset into occ_pairs (floats), records per section - parallelograms, convex quads, triangles, spheres
 };
 #if APT_FAST
 struct FlatRays { v2f ox, oy, oz, dx, dy, dz; };           // two rays: .x = entry 2k, .y = entry 2k + 1
@@ -880,11 +882,25 @@ APT_D void flat_any2(const FlatScene& fl, const SweepScene& sw, f3 o0, f3 d0, f3
 APT_D void flat_any2(const FlatScene& fl, const SweepScene& sw, f3 o0, f3 d0, f3 o1, f3 d1, float lim0, float lim1, bool& occ0, bool& occ1) {
     bool a, b; flat_any2<false>(fl, sw, o0, d0, o1, d1, lim0, lim1, occ0, occ1, a, b);
 }
-// Occlusion of ONE ray per lane below `lim`: the lane's ray against two records per packed instruction (FlatScene::pairs) - the mirror
-// image of flat_loop<true>, for kernels that hold one path per lane (the shade kernel that traces its own rays: shade_stage.hpp
-// "rays traced in place").  Same arithmetic per (ray, record) as flat_loop: the two answers are the same bit for bit.
-APT_D bool flat_any1(const FlatScene& fl, f3 o, f3 d, float lim) {
-    cf_ptr at = (cf_ptr)fl.pairs;
+// A paired record stream for flat_any1 and its records per section (parallelograms, convex quads, triangles, spheres; coplanar-group
+// records inside their sections): the scene's full stream, or one emitter's occluder list.  Wave-uniform: the records stay scalar loads.
+struct FlatList { cf_ptr pairs; int nq, ng, nt, ns; };
+APT_D FlatList flat_full_list(const FlatScene& fl) {
+    FlatList l; l.pairs = (cf_ptr)fl.pairs;
+    l.nq = fl.n_quads + fl.n_quads_tie; l.ng = fl.n_gquads + fl.n_gquads_tie; l.nt = fl.n_tris + fl.n_tris_tie; l.ns = fl.n_spheres;
+    return l;
+}
+// the records that can block a light sample of emitter e (flat_build.cpp flat_occluders: the others can only be "hit" at t <= 1e-4)
+APT_D FlatList flat_occ_list(const FlatScene& fl, int e) {
+    const __attribute__((address_space(4))) int* t = (const __attribute__((address_space(4))) int*)fl.occ_tab + 8 * e;
+    FlatList l; l.pairs = (cf_ptr)fl.occ_pairs + t[0]; l.nq = t[1]; l.ng = t[2]; l.nt = t[3]; l.ns = t[4];
+    return l;
+}
+// Occlusion of ONE ray per lane below `lim`: the lane's ray against two records per packed instruction (a FlatList: FlatScene::pairs or
+// an emitter's occluder list) - the mirror image of flat_loop<true>, for kernels that hold one path per lane (the shade kernel that traces
+// its own rays: shade_stage.hpp "rays traced in place").  Same arithmetic per (ray, record) as flat_loop: the two answers are the same bit for bit.
+APT_D bool flat_any1(const FlatList& ls, f3 o, f3 d, float lim) {
+    cf_ptr at = ls.pairs;
     const v2f ox = sp2(o.x), oy = sp2(o.y), oz = sp2(o.z), dx = sp2(d.x), dy = sp2(d.y), dz = sp2(d.z);
     bool occ = false;
     auto solve = [&](cf_ptr r, v2f& t, v2f& u, v2f& v) {      // planar_solve() with the record pair in the halves and the ray broadcast
@@ -900,7 +916,7 @@ APT_D bool flat_any1(const FlatScene& fl, f3 o, f3 d, float lim) {
         u = fma2(ux, px, fma2(uy, py, uz * pz));
         v = fma2(vx, px, fma2(vy, py, vz * pz));
     };
-    const int nq = (fl.n_quads + fl.n_quads_tie + 1) >> 1, ng = (fl.n_gquads + fl.n_gquads_tie + 1) >> 1, nt = (fl.n_tris + fl.n_tris_tie + 1) >> 1, ns = (fl.n_spheres + 1) >> 1;
+    const int nq = (ls.nq + 1) >> 1, ng = (ls.ng + 1) >> 1, nt = (ls.nt + 1) >> 1, ns = (ls.ns + 1) >> 1;
     for (int j = 0; j < nq; j++, at += 24) {
         v2f t, u, v; solve(at, t, u, v);
         const v2f a = u - sp2(0.5f), b = v - sp2(0.5f);

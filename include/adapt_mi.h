@@ -8,6 +8,7 @@
  *                                   tracer/path_tracer.py:143-179 (bvh_process): the same four arrays in the same layout
  *   apt_bvh_build / apt_bvh_*      the same builder's role for this library's own kernels (binary SAH tree -> 8-wide quantised tree)
  *   apt_flat_records               tracer/tracer_base.py:117-134,184-212: the data of the brute-force intersector, as the flat sweep wants it
+ *   apt_flat_occluders             (no upstream counterpart) per emitter, the flat records that can block its light samples
  *   apt_scene_create               tracer/tracer_base.py:117-134 (load_primitives) +
  *                                   tracer/path_tracer.py:245-274 (initialze): numpy -> device fields
  *   apt_renderer_create            renderer/vanilla_renderer.py:26-30 / tracer_base.py:36-102 (film, crop, camera,
@@ -152,6 +153,15 @@ void apt_bvh_free(apt_bvh*);
  * class_a class_b as int32 | map_a[6] | map_b[6] | p0.z ...).  n_stream / n_tab: floats needed (always written). */
 int apt_flat_records(const float* prims /* n_prims*9 */, int32_t n_prims, const int32_t* obj_info /* n_objects*3 */, int32_t n_objects,
                      int32_t counts[7], float* stream, int32_t stream_cap, float* tab, int32_t tab_cap, int32_t* n_stream, int32_t* n_tab);
+/* Occluder lists of the light samples (csrc/flat_build.cpp flat_occluders): per emitter, the flat records a segment from
+ * the scene to a point the emitter can be sampled at may block - what the product build's traced shade kernel sweeps a light sample
+ * against.  src_i / src_f as in apt_scene_desc.  cull = 0: every list is the full stream.  table (may be NULL): 8 int32 per emitter (offset
+ * into pairs in floats, records per section: parallelograms, convex quads, triangles, spheres; 0 0 0); keep (may be NULL): n_records
+ * flags per emitter, 1 = in the list, records in apt_flat_records' stream order; pairs (may be NULL): the lists two records at a time
+ * (the layout of the flat sweep's paired stream).  n_records / n_pairs: always written. */
+int apt_flat_occluders(const float* prims /* n_prims*9 */, int32_t n_prims, const int32_t* obj_info /* n_objects*3 */, int32_t n_objects,
+                       const int32_t* src_i, const float* src_f, int32_t n_sources, int32_t cull, int32_t* table, int32_t* keep, int32_t keep_cap,
+                       float* pairs, int32_t pairs_cap, int32_t* n_records, int32_t* n_pairs);
 
 /* ---- BVH build, reference layout: the drop-in for the pybind11 module itself.
  * Replaces bvh_cpp.bvh_build(obj_array, obj_info, world_min, world_max) (tracer/bvh/bvh.cpp:274-296), whose four flat arrays
