@@ -18,6 +18,8 @@ LIB_PATH = LIB_PATHS[_variant]
 f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
 u32p = C.POINTER(C.c_uint32)
+u8p = C.POINTER(C.c_uint8)
+f64p = C.POINTER(C.c_double)
 APT_N_KERNELS = 5
 KERNEL_NAMES = ("generate", "extend", "shade", "shadow", "finalize")
 
@@ -45,6 +47,7 @@ class RenderCfg(C.Structure):
                 ("inv_focal", C.c_float), ("half_w", C.c_float), ("half_h", C.c_float), ("seed", C.c_uint32),
                 ("band_width", C.c_int32), ("rank", C.c_int32), ("world_size", C.c_int32),
                 ("spp_per_batch", C.c_int32), ("device", C.c_int32), ("profile", C.c_int32), ("volumetric", C.c_int32),
+                ("adaptive_threshold", C.c_float), ("adaptive_min_spp", C.c_int32), ("adaptive_step", C.c_int32),
                 ("transient_bins", C.c_int32), ("transient_min_time", C.c_float), ("transient_interval", C.c_float)]
 
 
@@ -90,6 +93,9 @@ SYMBOLS = {
     "apt_reset": (C.c_int, [C.c_void_p]),
     "apt_read_transient": (C.c_int, [C.c_void_p, f32p]),
     "apt_set_transient": (C.c_int, [C.c_void_p, f32p]),
+    "apt_read_sample_counts": (C.c_int, [C.c_void_p, i32p, u8p]),
+    "apt_read_moments": (C.c_int, [C.c_void_p, f64p]),
+    "apt_set_adaptive_state": (C.c_int, [C.c_void_p, i32p, f64p, u8p]),
     "apt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "apt_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), i32p]),
     "apt_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

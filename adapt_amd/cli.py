@@ -14,6 +14,9 @@ stamped (`--no_watermark` is accepted), PNG/BMP are written by a small built-in 
 `--transient` (with `--type pt`): time-resolved rendering with the sensor's `sample_count` / `min_time` / `interval`; the frames are
 written as upstream's `export_transient_profile` writes them (render.py:36-56,166): `<output_path>/<scene file stem>/img_001.<ext>` ...,
 `--normalize` applied as one quantile over the whole cube, and the cube itself as `transient.npy` (n_bins, w, h, 3) next to them.
+`--noise_threshold t` (with `--min_spp`, `--adaptive_step`): adaptive sampling; `--iter_num` is then the most samples
+any pixel gets, and the per-pixel sample counts are written as `<img_name>-<scene file stem>-<type>-spp.npy` (w, h) int32 next to the
+image (cropped like it).  Not with `--transient`.
 """
 from __future__ import annotations
 
@@ -62,6 +65,9 @@ def get_options(argv=None):
     p.add_argument("--max_bounce", default=None, type=int)
     p.add_argument("--spp_per_batch", default=0, type=int, help="samples per wavefront batch (0: automatic)")
     p.add_argument("--transient", default=False, action="store_true", help="time-resolved output (pt only; the sensor's sample_count / min_time / interval)")
+    p.add_argument("--noise_threshold", default=0., type=float, help="adaptive sampling: a pixel stops once the relative standard error of its mean is <= this (0: off)")
+    p.add_argument("--min_spp", default=64, type=int, help="adaptive sampling: no pixel stops before this many samples")
+    p.add_argument("--adaptive_step", default=32, type=int, help="adaptive sampling: pixels are retired at sample numbers that are multiples of this")
     argv = list(sys.argv[1:] if argv is None else argv)
     pre, _ = p.parse_known_args(argv)
     if pre.config:
@@ -138,6 +144,18 @@ def main(argv=None) -> int:
     if opts.transient and opts.type != "pt":
         print(f"--transient: time-resolved output exists for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
         return 2
+    adaptive = None
+    if opts.noise_threshold > 0:
+        if opts.transient:
+            print("--transient with --noise_threshold: time-resolved output needs every pixel's samples; adaptive sampling and --transient do not combine", file=sys.stderr)
+            return 2
+        if opts.min_spp <= 0 or opts.adaptive_step <= 0:
+            print("--min_spp and --adaptive_step must be > 0", file=sys.stderr)
+            return 2
+        adaptive = {"threshold": opts.noise_threshold, "min_spp": opts.min_spp, "step": opts.adaptive_step}
+    elif opts.noise_threshold < 0:
+        print("--noise_threshold must be >= 0 (0: every pixel takes every sample)", file=sys.stderr)
+        return 2
     from .parsers.xml_parser import scene_parsing
     from .renderer import Renderer, VolumeRenderer
     if opts.type == "vpt":                      # render.py:33 rdr_mapping: "vpt" -> VolumeRenderer
@@ -148,7 +166,7 @@ def main(argv=None) -> int:
           f"{len(emitters)} emitters, parsed in {time.time() - t0:.3f} s")
     rdr = Renderer(emitters, array_info, objs, cfg, device=opts.device, seed=opts.seed, profile=opts.profile,
                    width=opts.width, height=opts.height, max_bounce=opts.max_bounce, spp_per_batch=opts.spp_per_batch,
-                   transient=True if opts.transient else None)
+                   transient=True if opts.transient else None, adaptive=adaptive)
     stem = opts.name[:-4]
     max_iter = (opts.iter_num if opts.iter_num > 0 else cfg.get("iter_num", 2000)) + 1          # render.py:80-81
     chk_file = os.path.join(_folder(opts.chkpt_path), f"{opts.img_name}-{stem}-{opts.type}.pkl")
@@ -185,6 +203,14 @@ def main(argv=None) -> int:
     dt = time.time() - t1
     rdr.summary()
     n = rdr.w * rdr.h * done
+    spp_map = None
+    if adaptive:
+        spp_map = rdr.sample_counts()
+        if rdr.do_crop:
+            spp_map = spp_map[rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y]
+        n = int(rdr.stats()["n_samples"])
+        print(f"[adapt_amd] adaptive sampling: {100.0 * (1.0 - rdr.active_fraction()):.2f} % of the pixels converged, "
+              f"mean spp {spp_map.mean():.1f} (at most {done})")
     print(f"[adapt_amd] {n / max(dt, 1e-9) / 1e6:.1f} Msamples/s ({done} spp in {dt:.3f} s)")
     if opts.profile:
         st = rdr.stats()
@@ -200,6 +226,10 @@ def main(argv=None) -> int:
         out = os.path.join(_folder(opts.output_path), f"{opts.img_name}-{stem}-{opts.type}.{opts.img_ext}")
         write_image(img, out)
         print(f"[adapt_amd] wrote {out}")
+        if spp_map is not None:
+            out_spp = os.path.join(opts.output_path, f"{opts.img_name}-{stem}-{opts.type}-spp.npy")
+            np.save(out_spp, spp_map)
+            print(f"[adapt_amd] wrote {out_spp}")
     if opts.transient:
         export_transient(rdr, opts.output_path, stem, opts.img_ext, opts.normalize)      # render.py:166: folder named after the scene file
     rdr.close()

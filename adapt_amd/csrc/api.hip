@@ -238,6 +238,15 @@ struct apt_renderer {
     TransQ tq{};
     DevBuf tr_pool, tr_bins;              // per-path time / record arrays (cap-sized), the bins (n_bins x owned pixels float4)
     group_tr_fn group_tr_[APT_N_GROUPS] = {};
+    // adaptive sampling (apt_render_cfg.adaptive_threshold > 0; stages.hpp AdaptQ)
+    int adaptive = 0;
+    AdaptQ aq{};
+    DevBuf ad_n, ad_s2, ad_active, ad_live;
+    std::vector<uint8_t> ad_start;        // the mask of a fresh render: every owned pixel inside the crop window
+    uint32_t* ad_live_host = nullptr;     // pinned: the live count of the last decision ...
+    hipEvent_t ad_ev = nullptr;           // ... valid once this event has passed
+    bool ad_pending = false;
+    uint32_t n_live = 0;                  // active pixels of the coming round
 };
 
 static int count_device(int* n) {
@@ -803,6 +812,7 @@ static int pick_shading(apt_renderer* r) {
         if (p.fused == 2) r->shade_name += " [rays traced in place]";
     }
     if (r->transient) r->shade_name += " [transient]";
+    if (r->adaptive) r->shade_name += " [adaptive]";
     // (sorted: extend appends every hit path's record to the packed queue of its material class, Queues::cq)
     r->extend = r->dyn_fetch ? kExtendDyn[r->sorted] : (r->trace_mode == 3 ? kExtendFlatHot[r->sorted] : kExtend[r->trace_mode][r->sorted]);
     r->fix = kFixFlat[r->sorted];
@@ -879,6 +889,39 @@ static void transient_window(TransQ& t, int32_t n_bins, float min_time, float in
 }
 
 // Transient render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the bins, all zero-filled.
+// Adaptive sampling state: n_p = 0, S2 = 0 and every owned pixel inside the crop window active (a fresh render, apt_reset).
+static int adaptive_restart(apt_renderer* r) {
+    HIP_TRY(hipMemsetAsync(r->ad_n.p, 0, r->ad_n.bytes, r->stream()));
+    HIP_TRY(hipMemsetAsync(r->ad_s2.p, 0, r->ad_s2.bytes, r->stream()));
+    HIP_TRY(hipMemcpyAsync(r->ad_active.p, r->ad_start.data(), r->ad_start.size(), hipMemcpyHostToDevice, r->stream()));
+    HIP_TRY(hipStreamSynchronize(r->stream()));
+    r->n_live = 0;
+    for (uint8_t a : r->ad_start) r->n_live += a;
+    r->ad_pending = false;
+    return APT_OK;
+}
+static int make_adaptive(apt_renderer* r) {
+    if (!r->adaptive) return APT_OK;
+    const apt_render_cfg& c = r->cfg;
+    const size_t n = (size_t)r->npix;
+    hipError_t e;
+    if ((e = r->ad_n.alloc(n * 4)) != hipSuccess || (e = r->ad_s2.alloc(n * 3 * sizeof(double))) != hipSuccess ||
+        (e = r->ad_active.alloc(n)) != hipSuccess || (e = r->ad_live.alloc(4)) != hipSuccess)
+        return fail(APT_E_NOMEM, std::string("adaptive sampling state: ") + hipGetErrorString(e));
+    HIP_TRY(hipHostMalloc((void**)&r->ad_live_host, 4, hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&r->ad_ev, hipEventDisableTiming));
+    r->ad_start.assign(n, 1);
+    if (c.do_crop)
+        for (int lp = 0; lp < r->npix; lp++) {         // the crop test of generate_body, on the mapping of plan_film
+            const int lc = lp / c.height, j = lp % c.height, i = (lc / c.band_width * c.world_size + c.rank) * c.band_width + lc % c.band_width;
+            r->ad_start[(size_t)lp] = (i >= c.start_x && i < c.end_x && j >= c.start_y && j < c.end_y) ? 1 : 0;
+        }
+    AdaptQ& a = r->aq;
+    a.n = r->ad_n.as<int32_t>(); a.s2 = r->ad_s2.as<double>(); a.active = r->ad_active.as<uint8_t>(); a.live = r->ad_live.as<uint32_t>();
+    a.threshold = (double)c.adaptive_threshold; a.min_spp = c.adaptive_min_spp;
+    return adaptive_restart(r);
+}
+
 static int make_transient(apt_renderer* r) {
     if (!r->transient) return APT_OK;
     const apt_render_cfg& c = r->cfg;
@@ -996,6 +1039,8 @@ APT_EXPORT void apt_renderer_destroy(apt_renderer* r) {
     for (auto& ev : r->free_events) (void)hipEventDestroy(ev);
     if (r->ev_r0) (void)hipEventDestroy(r->ev_r0);
     if (r->ev_r1) (void)hipEventDestroy(r->ev_r1);
+    if (r->ad_ev) (void)hipEventDestroy(r->ad_ev);
+    if (r->ad_live_host) (void)hipHostFree(r->ad_live_host);
     delete r;
 }
 APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cfg, apt_renderer** out) {
@@ -1017,15 +1062,24 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
         if (!(c.transient_interval > 0.f) || !std::isfinite(c.transient_interval) || !std::isfinite(c.transient_min_time))
             return fail(APT_E_INVALID, "apt_renderer_create: transient_interval must be positive and finite, transient_min_time finite");
     }
+    if (!std::isfinite(c.adaptive_threshold)) return fail(APT_E_INVALID, "apt_renderer_create: adaptive_threshold must be finite (> 0: adaptive sampling, <= 0: off)");
+    if (c.adaptive_threshold > 0.f) {
+        if (c.transient_bins > 0)
+            return fail(APT_E_INVALID, "apt_renderer_create: adaptive sampling and transient rendering do not combine (transient_bins must be 0 when adaptive_threshold > 0)");
+        if (c.adaptive_min_spp <= 0 || c.adaptive_step <= 0)
+            return fail(APT_E_INVALID, "apt_renderer_create: adaptive sampling needs adaptive_min_spp > 0 and adaptive_step > 0");
+    }
     HIP_TRY(hipSetDevice(c.device));
     apt_renderer* r = new apt_renderer();
     struct Owner { apt_renderer* r; ~Owner() { if (r) apt_renderer_destroy(r); } } owner{r};     // every early return below releases streams, events and queue pools
     r->scene = sc; r->cfg = c;
+    r->adaptive = c.adaptive_threshold > 0.f ? 1 : 0;
     if (int rc = plan_film(r)) return rc;
     pick_traversal(r);
     if (int rc = pick_shading(r)) return rc;
     if (int rc = make_lanes(r)) return rc;
     if (int rc = make_transient(r)) return rc;
+    if (int rc = make_adaptive(r)) return rc;
     if (int rc = plan_lds_and_grids(r)) return rc;
     if (int rc = make_overflow_stacks(r)) return rc;
     for (Lane& ln : r->lanes) HIP_TRY(hipStreamSynchronize(ln.stream));
@@ -1120,7 +1174,11 @@ static void launch_extend(apt_renderer* r, Lane& ln, const Params& p, size_t tot
 // ... and ends with the ordered finalize: the framebuffer is shared, so batch k's samples are added after batch k-1's, whichever lanes they ran on.
 static int finalize_batch(apt_renderer* r, Lane& ln, const Params& p, hipEvent_t& prev_fin) {
     if (prev_fin && r->n_lanes > 1) { unchain(r, ln.stream); HIP_TRY(hipStreamWaitEvent(ln.stream, prev_fin, 0)); }
-    { LaunchTimer t(r, 4, ln.stream); hipLaunchKernelGGL(k_finalize, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, ln.stream, p, ln.q, r->accum.as<float>()); }
+    {
+        LaunchTimer t(r, 4, ln.stream);
+        if (r->adaptive) hipLaunchKernelGGL(k_finalize_ad, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, ln.stream, p, ln.q, r->accum.as<float>(), r->aq);
+        else hipLaunchKernelGGL(k_finalize, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, ln.stream, p, ln.q, r->accum.as<float>());
+    }
     HIP_TRY(hipEventRecord(ln.fin, ln.stream));
     prev_fin = ln.fin;
     HIP_TRY(hipGetLastError());
@@ -1145,7 +1203,11 @@ static int render_volumetric(apt_renderer* r, int32_t n_spp) {
             Lane& ln = r->lanes[(size_t)li];
             Issued is; is.ln = &ln; is.cur = 0; is.p = r->par; is.p.cnt_base = r->cnt; is.p.spp_batch = B; is.total = (size_t)r->npix * (size_t)B;
             if (int rc = begin_batch(r, ln)) return rc;
-            { LaunchTimer t(r, 0, ln.stream); hipLaunchKernelGGL(k_generate, dim3(grid_for(is.total, r->grid_small, 1)), dim3(BLOCK), 0, ln.stream, is.p, ln.q, ln.cnt()); }
+            {
+                LaunchTimer t(r, 0, ln.stream);
+                if (r->adaptive) hipLaunchKernelGGL(k_generate_ad, dim3(grid_for(is.total, r->grid_small, 1)), dim3(BLOCK), 0, ln.stream, is.p, ln.q, ln.cnt(), (const uint8_t*)r->aq.active);
+                else hipLaunchKernelGGL(k_generate, dim3(grid_for(is.total, r->grid_small, 1)), dim3(BLOCK), 0, ln.stream, is.p, ln.q, ln.cnt());
+            }
             round.push_back(is);
             r->cnt += B; done += B;
         }
@@ -1222,7 +1284,11 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
         if (p.fused == 2) {
             // rays traced in place (shade_stage.hpp): generate and every bounce are ONE launch each; the rare rays that need the reference-order code
             // are served by the next launch's prologue, the last bounce's deferred light samples by one fix-up launch at the end
-            { LaunchTimer t(r, 0, st); hipLaunchKernelGGL(k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt); }
+            {
+                LaunchTimer t(r, 0, st);
+                if (r->adaptive) hipLaunchKernelGGL(k_generate_trace_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, (const uint8_t*)r->aq.active);
+                else hipLaunchKernelGGL(k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt);
+            }
             int cur = 0;
             for (int b = 0; b < p.max_bounce; b++) {
                 { LaunchTimer t(r, 2, st); hipLaunchKernelGGL(r->shade->traced, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, b); }      // (the records are Queues::tr[cur]: one queue for the scene)
@@ -1232,7 +1298,11 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
         } else
 #endif
         {
-        { LaunchTimer t(r, 0, st); hipLaunchKernelGGL(k_generate, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, cnt); }
+        {
+            LaunchTimer t(r, 0, st);
+            if (r->adaptive) hipLaunchKernelGGL(k_generate_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, cnt, (const uint8_t*)r->aq.active);
+            else hipLaunchKernelGGL(k_generate, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, cnt);
+        }
         // transient: a bounce's records are binned once its light samples are all settled - after its shadow launch, or with the flat sweep
         // after the next bounce's fix-up launch (it serves the deferred ones) - and before the next shade launch writes new ones
         auto bin = [&]() { LaunchTimer t(r, 4, st, false); hipLaunchKernelGGL(k_bin_transient, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->accum.as<float>()); };
@@ -1279,10 +1349,49 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
     return APT_OK;
 }
 
+// the live count of the last decision, once its read-back has landed
+static int adaptive_settle(apt_renderer* r) {
+    if (r->ad_pending) { HIP_TRY(hipEventSynchronize(r->ad_ev)); r->n_live = *r->ad_live_host; r->ad_pending = false; }
+    return APT_OK;
+}
+
+// Adaptive render: the call's samples in rounds that end at the decision points - global sample numbers that are multiples
+// of adaptive_step and >= adaptive_min_spp.  A round renders like a steady call over its fixed mask (generate and finalize take the mask;
+// every other kernel is the steady one); after its ordered finalize, on the main stream, k_adaptive_retire decides and the live count comes
+// back in one 4-byte copy, the only new synchronisation; the next round's launches wait on it.  A call that ends mid-round leaves the rest
+// of the round to the next call.  A round without active pixels launches nothing; cnt advances all the same.
+static int render_adaptive(apt_renderer* r, int32_t n_spp) {
+    const int64_t step = r->cfg.adaptive_step, min_spp = r->cfg.adaptive_min_spp;
+    int left = n_spp;
+    while (left > 0) {
+        if (int rc = adaptive_settle(r)) return rc;
+        const int64_t first = std::max<int64_t>(min_spp, (int64_t)r->cnt + 1);
+        const int64_t decide = ((first + step - 1) / step) * step;          // the next decision point
+        const int seg = (int)std::min<int64_t>(left, decide - (int64_t)r->cnt);
+        left -= seg;
+        if (r->n_live == 0) { r->cnt += seg; continue; }
+        if (int rc = r->volumetric ? render_volumetric(r, seg) : render_surface(r, seg)) return rc;        // (cnt += seg)
+        if ((int64_t)r->cnt != decide) continue;
+        hipStream_t st = r->stream();
+        for (size_t li = 1; li < r->lanes.size(); li++) {      // join: the decision follows every finalize of the round
+            unchain(r, st); HIP_TRY(hipEventRecord(r->lanes[li].fin, r->lanes[li].stream)); HIP_TRY(hipStreamWaitEvent(st, r->lanes[li].fin, 0));
+        }
+        unchain(r, st); HIP_TRY(hipMemsetAsync(r->ad_live.p, 0, 4, st));
+        { LaunchTimer t(r, 4, st, false); hipLaunchKernelGGL(k_adaptive_retire, dim3((r->npix + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, (uint32_t)r->npix, (const float*)r->accum.as<float>(), r->aq); }
+        unchain(r, st); HIP_TRY(hipMemcpyAsync(r->ad_live_host, r->ad_live.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(r->ad_ev, st));
+        r->ad_pending = true;
+        for (size_t li = 1; li < r->lanes.size(); li++) { unchain(r, r->lanes[li].stream); HIP_TRY(hipStreamWaitEvent(r->lanes[li].stream, r->ad_ev, 0)); }      // fork: the next round waits on the decision
+        HIP_TRY(hipGetLastError());
+    }
+    return APT_OK;
+}
+
 static int render_impl(apt_renderer* r, int32_t n_spp) {
     HIP_TRY(hipEventRecord(r->ev_r0, r->stream()));
     for (size_t li = 1; li < r->lanes.size(); li++) { unchain(r, r->lanes[li].stream); HIP_TRY(hipStreamWaitEvent(r->lanes[li].stream, r->ev_r0, 0)); }     // lanes start after whatever the main stream did before
-    if (int rc = r->volumetric ? render_volumetric(r, n_spp) : render_surface(r, n_spp)) return rc;
+    if (r->adaptive) { if (int rc = render_adaptive(r, n_spp)) return rc; }
+    else if (int rc = r->volumetric ? render_volumetric(r, n_spp) : render_surface(r, n_spp)) return rc;
     for (size_t li = 1; li < r->lanes.size(); li++) {      // join
         unchain(r, r->stream()); HIP_TRY(hipEventRecord(r->lanes[li].fin, r->lanes[li].stream)); HIP_TRY(hipStreamWaitEvent(r->stream(), r->lanes[li].fin, 0));
     }
@@ -1321,7 +1430,8 @@ APT_EXPORT int apt_read_pixels(apt_renderer* r, float* out) {
     HIP_TRY(hipSetDevice(r->cfg.device));
     const uint32_t n = (uint32_t)r->npix * 3u;
     const float inv = (float)(r->cnt > 0 ? r->cnt : 1);     // before the first sample the image is all zero
-    hipLaunchKernelGGL(k_divide, dim3((n + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), r->scratch.as<float>(), n, inv);
+    if (r->adaptive) hipLaunchKernelGGL(k_divide_ad, dim3((n + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), (const int32_t*)r->ad_n.p, r->scratch.as<float>(), n);
+    else hipLaunchKernelGGL(k_divide, dim3((n + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), r->scratch.as<float>(), n, inv);
     HIP_TRY(hipMemcpyAsync(out, r->scratch.p, (size_t)n * 4, hipMemcpyDeviceToHost, r->stream()));
     return resolve_events(r);
 }
@@ -1361,8 +1471,44 @@ APT_EXPORT int apt_reset(apt_renderer* r) {
     for (Lane& ln : r->lanes) HIP_TRY(hipMemsetAsync(ln.counters.p, 0, sizeof(Counters), r->stream()));      // lanes are idle between render calls
     r->cnt = 0;
     if (int rc = resolve_events(r)) return rc;
+    if (r->adaptive) { if (int rc = adaptive_restart(r)) return rc; }
     for (int k = 0; k < APT_N_KERNELS; k++) { r->kernel_ms[k] = 0; r->launches[k] = 0; }
     r->render_ms = 0;
+    return APT_OK;
+}
+APT_EXPORT int apt_read_sample_counts(apt_renderer* r, int32_t* counts, uint8_t* active) {
+    if (!r || !counts) return fail(APT_E_INVALID, "apt_read_sample_counts: bad argument");
+    if (!r->adaptive) return fail(APT_E_STATE, "apt_read_sample_counts: the renderer was created with adaptive_threshold = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(counts, r->ad_n.p, r->ad_n.bytes, hipMemcpyDeviceToHost, r->stream()));
+    if (active) HIP_TRY(hipMemcpyAsync(active, r->ad_active.p, r->ad_active.bytes, hipMemcpyDeviceToHost, r->stream()));
+    if (int rc = resolve_events(r)) return rc;
+    return adaptive_settle(r);
+}
+APT_EXPORT int apt_read_moments(apt_renderer* r, double* s2) {
+    if (!r || !s2) return fail(APT_E_INVALID, "apt_read_moments: bad argument");
+    if (!r->adaptive) return fail(APT_E_STATE, "apt_read_moments: the renderer was created with adaptive_threshold = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(s2, r->ad_s2.p, r->ad_s2.bytes, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
+APT_EXPORT int apt_set_adaptive_state(apt_renderer* r, const int32_t* counts, const double* s2, const uint8_t* active) {
+    if (!r || !counts || !s2 || !active) return fail(APT_E_INVALID, "apt_set_adaptive_state: bad argument");
+    if (!r->adaptive) return fail(APT_E_STATE, "apt_set_adaptive_state: the renderer was created with adaptive_threshold = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (int rc = resolve_events(r)) return rc;
+    if (int rc = adaptive_settle(r)) return rc;
+    uint32_t live = 0;
+    for (int lp = 0; lp < r->npix; lp++) {
+        if (counts[lp] < 0 || counts[lp] > r->cnt) return fail(APT_E_INVALID, "apt_set_adaptive_state: a sample count is negative or above the renderer's cnt");
+        live += active[lp] ? 1u : 0u;
+    }
+    std::vector<uint8_t> a((size_t)r->npix);
+    for (int lp = 0; lp < r->npix; lp++) a[(size_t)lp] = active[lp] ? 1 : 0;
+    HIP_TRY(hipMemcpy(r->ad_n.p, counts, r->ad_n.bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r->ad_s2.p, s2, r->ad_s2.bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r->ad_active.p, a.data(), a.size(), hipMemcpyHostToDevice));
+    r->n_live = live;
     return APT_OK;
 }
 APT_EXPORT int apt_get_stats(apt_renderer* r, apt_stats* out) {

@@ -400,8 +400,10 @@ APT_D SubLoop sub_loop(int nq, int nt = BLOCK) {
 // atomic-free unless a crop window makes some lanes inactive.
 // TRACE (rays traced in place, Params::fused == 2): the camera ray meets the scene's records here and the entry carries its hit record
 // (Queues::tr, parity 0, the queue of the hit primitive's class; counted in n_tr[0]); a ray that hits nothing is not queued at all.
-template <bool TRACE>
-APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, Counters* cnt) {
+// ADAPTIVE (adaptive sampling): a pixel that has stopped sampling (active[lp] == 0) is one more slot that is not alive;
+// the queue is compacted as for a crop window.
+template <bool TRACE, bool ADAPTIVE = false>
+APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, Counters* cnt, const uint8_t* active = nullptr) {
     const uint32_t total = (uint32_t)p.npix * (uint32_t)p.spp_batch;
     const uint32_t n_waves = (total + 63u) / 64u;
     const uint32_t wave_stride = gridDim.x * (BLOCK / 64);
@@ -417,6 +419,7 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
             int i, j; local_to_global(p, lp, i, j);
             for (int pl = 0; pl < p.l_planes; pl++) stL(q.L, p.cap, (idx << 2) | (uint32_t)pl, splat3(0.f));
             alive = !p.do_crop || (i >= p.sx && i < p.ex && j >= p.sy && j < p.ey);
+            if (ADAPTIVE) alive = alive && active[lp] != 0;
             if (alive) {
                 int sample_cnt = p.cnt_base + (int)s + 1;        // cnt is incremented before the pixel loop
                 Philox rng; rng_init(rng, (uint32_t)(i * p.H + j), p.seed, (uint32_t)sample_cnt, 0u);
@@ -442,7 +445,7 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
         uint32_t pos;
         uint32_t* q0_counter = &cnt->n_active[0][sq * CNT_PAD];
         if (TRACE) pos = 0;
-        else if (p.do_crop) pos = wave_append(alive, q0_counter);
+        else if (p.do_crop || ADAPTIVE) pos = wave_append(alive, q0_counter);
         else {
             pos = (w / (uint32_t)p.nq) * 64u + lane_id();
             unsigned long long m = __ballot(alive);
@@ -490,8 +493,10 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
     flush_stat(t_draws, &cnt->stats[sq0][ST_DRAWS]);
 }
 __global__ void __launch_bounds__(BLOCK) k_generate(Params p, Queues q, Counters* cnt) { generate_body<false>(nullptr, p, q, cnt); }
+__global__ void __launch_bounds__(BLOCK) k_generate_ad(Params p, Queues q, Counters* cnt, const uint8_t* active) { generate_body<false, true>(nullptr, p, q, cnt, active); }
 #if APT_FAST
 __global__ void __launch_bounds__(BLOCK) k_generate_trace(DevScene sc, Params p, Queues q, Counters* cnt) { generate_body<true>(&sc, p, q, cnt); }
+__global__ void __launch_bounds__(BLOCK) k_generate_trace_ad(DevScene sc, Params p, Queues q, Counters* cnt, const uint8_t* active) { generate_body<true, true>(&sc, p, q, cnt, active); }
 #endif
 
 // ------------------------------------------------------------------- extend
@@ -1067,6 +1072,80 @@ __global__ void __launch_bounds__(BLOCK) k_finalize(Params p, Queues q, float* a
         }
         accum[3 * lp] = r; accum[3 * lp + 1] = g; accum[3 * lp + 2] = b;
     }
+}
+
+// ------------------------------------------------------------ adaptive sampling
+// Per owned pixel: the samples it has taken (n_p), the float64 sums of its squared sample values per channel (S2; S1 is the framebuffer)
+// and whether it still samples.  A kernel argument of its own behind the steady ones, like TransQ: Params, Queues and every steady
+// kernel stay as they are.
+struct AdaptQ {
+    int32_t* n;               // n_p
+    double* s2;               // 3 per pixel: sum of c^2 over the samples k_finalize adds, NaN components dropped as it drops them
+    uint8_t* active;          // 1 = the pixel takes the next round's samples
+    uint32_t* live;           // k_adaptive_retire: active pixels left after the decision (zeroed by the host before it)
+    double threshold;         // e_p <= threshold retires the pixel ...
+    int min_spp;              // ... once it has at least min_spp samples
+};
+// The relative error of a pixel, e_p = max over channels of se / (mean + 1e-3), with mean = S1 / n, var = max(S2 / n - mean^2, 0) * n / (n - 1)
+// and se = sqrt(var / n), in float64.  Not finite (n < 2, an inf sample, a NaN): +inf, and the pixel keeps sampling.  The tests restate it
+// in numpy (tests/test_adaptive_host.py relative_error): one rule, two places.
+APT_D double adaptive_error(const float* s1, const double* s2, int n) {
+    if (n < 2) return __builtin_inf();
+    const double nd = (double)n;
+    double e = 0.0;
+    bool fin = true;
+    for (int c = 0; c < 3; c++) {
+        const double mean = (double)s1[c] / nd;
+        double v = s2[c] / nd - mean * mean;
+        v = (v < 0.0) ? 0.0 : v;                 // (a NaN stays NaN)
+        const double var = v * (nd / (nd - 1.0));
+        const double ratio = sqrt(var / nd) / (mean + 1e-3);
+        fin = fin && isfinite(ratio);
+        e = (ratio > e) ? ratio : e;
+    }
+    return fin ? e : __builtin_inf();
+}
+// k_finalize for adaptive renders: the active pixels only (the round's mask is fixed), the same float32 sum in the same order, S2 beside
+// it in float64, and n_p += the batch's samples.  A retired pixel's slots are all zero (generate stores L for every slot) and not read.
+__global__ void __launch_bounds__(BLOCK) k_finalize_ad(Params p, Queues q, float* accum, AdaptQ a) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride) {
+        if (!a.active[lp]) continue;
+        float r = accum[3 * lp], g = accum[3 * lp + 1], b = accum[3 * lp + 2];
+        double sr = a.s2[3 * lp], sg = a.s2[3 * lp + 1], sb = a.s2[3 * lp + 2];
+        for (int s = 0; s < p.spp_batch; s++) {
+            const uint32_t lo_ = ((uint32_t)s * (uint32_t)p.npix + lp) << 2;
+            f3 c_ = ldL(q.L, p.cap, lo_);
+            for (int pl = 1; pl < p.l_planes; pl++) c_ = c_ + ldL(q.L, p.cap, lo_ | (uint32_t)pl);
+            float cr = c_.x, cg = c_.y, cb = c_.z;
+            r += isnan(cr) ? 0.f : cr; g += isnan(cg) ? 0.f : cg; b += isnan(cb) ? 0.f : cb;
+            if (!isnan(cr)) sr += (double)cr * (double)cr;
+            if (!isnan(cg)) sg += (double)cg * (double)cg;
+            if (!isnan(cb)) sb += (double)cb * (double)cb;
+        }
+        accum[3 * lp] = r; accum[3 * lp + 1] = g; accum[3 * lp + 2] = b;
+        a.s2[3 * lp] = sr; a.s2[3 * lp + 1] = sg; a.s2[3 * lp + 2] = sb;
+        a.n[lp] += p.spp_batch;
+    }
+}
+// After a round's last finalize, at a decision point: one thread per owned pixel retires the active pixels with n_p >= min_spp and
+// e_p <= threshold, and counts the pixels that stay active (one atomic per wave) for the host's single read-back of the round.
+__global__ void __launch_bounds__(BLOCK) k_adaptive_retire(uint32_t npix, const float* accum, AdaptQ a) {
+    const uint32_t lp = blockIdx.x * BLOCK + threadIdx.x;
+    bool keep = false;
+    if (lp < npix && a.active[lp]) {
+        const int n = a.n[lp];
+        const bool retire = n >= a.min_spp && adaptive_error(accum + 3 * lp, a.s2 + 3 * lp, n) <= a.threshold;
+        if (retire) a.active[lp] = 0;
+        keep = !retire;
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane_id() == 0 && m) atomicAdd(a.live, (uint32_t)__popcll(m));
+}
+// pixels = color / n_p, 0 where the pixel has no sample
+__global__ void k_divide_ad(const float* accum, const int32_t* n, float* out, uint32_t n3) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n3) { const int c = n[i / 3u]; out[i] = c > 0 ? accum[i] / (float)c : 0.f; }
 }
 
 // ------------------------------------------------------------ transient bins

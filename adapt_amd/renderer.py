@@ -16,6 +16,15 @@ contribution by its optical length, camera to emitter, as AdaPT's BDPT does in T
     rdr.transient()                # (n_bins, w, h, 3) float32 [t, x, y]: summed radiance of bin t / cnt
     rdr.transient_counts()         # (n_bins, w, h) float32: contributions per bin (upstream's time_cnts)
 
+Adaptive sampling, `pt` and `vpt`: `Renderer(..., adaptive={"threshold": 0.02, "min_spp": 64, "step": 32})` retires a pixel
+once the relative standard error of its mean is at most `threshold`; decisions fall on global sample numbers that are multiples of `step`
+and >= `min_spp`.  `render(n)` still advances `cnt` by n (the most samples any pixel has); `pixels` divides by each pixel's own count:
+
+    rdr.sample_counts()            # (w, h) int32: n_p
+    rdr.std_error()                # (w, h, 3) float64: standard error of each pixel's mean
+    rdr.relative_error()           # (w, h) float64: e_p, the quantity the threshold is held against
+    rdr.active_fraction()          # share of this rank's sampled pixels that still sample
+
 Extensions (keyword-only, all optional): `n_spp=` on render() to queue many samples per
 call (the wavefront batches them), `device/rank/world_size/band_width` for image-tile
 sharding across GPUs, `seed`, `spp_per_batch`, `profile`, and film/bounce overrides so the
@@ -33,7 +42,48 @@ from . import _lib
 from .scene_pack import FlatScene, RenderConfig, make_config, pack_scene
 from .tiles import TilePlan
 
-__all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "rng_stream"]
+__all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error"]
+
+ADAPTIVE_DEFAULTS = {"min_spp": 64, "step": 32}
+
+
+def adaptive_config(adaptive) -> Optional[dict]:
+    """None / False -> None (uniform sampling); a dict with "threshold" (> 0) and optionally "min_spp" and "step" (> 0) -> the full dict."""
+    if adaptive is None or adaptive is False:
+        return None
+    if not isinstance(adaptive, dict):
+        raise TypeError("adaptive must be None or a dict {'threshold': t, 'min_spp': 64, 'step': 32}")
+    unknown = set(adaptive) - {"threshold", "min_spp", "step"}
+    if unknown:
+        raise ValueError(f"adaptive: unknown key(s) {sorted(unknown)}")
+    cfg = {"threshold": float(adaptive["threshold"]), **{k: int(adaptive.get(k, v)) for k, v in ADAPTIVE_DEFAULTS.items()}}
+    if not (np.isfinite(cfg["threshold"]) and cfg["threshold"] > 0):
+        raise ValueError("adaptive: threshold must be a finite number > 0")
+    if cfg["min_spp"] <= 0 or cfg["step"] <= 0:
+        raise ValueError("adaptive: min_spp and step must be > 0")
+    return cfg
+
+
+def _moments(s1, s2, n):
+    """(mean, standard error) per channel in float64; NaN where n < 2"""
+    s1 = np.asarray(s1, np.float64); s2 = np.asarray(s2, np.float64)
+    nd = np.asarray(n, np.float64)[..., None]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        mean = s1 / nd
+        v = s2 / nd - mean * mean
+        v = np.where(v < 0.0, 0.0, v)
+        se = np.sqrt(v * (nd / (nd - 1.0)) / nd)
+    return mean, np.where(nd >= 2, se, np.nan)
+
+
+def relative_error(s1, s2, n) -> np.ndarray:
+    """e_p = max over channels of se / (mean + 1e-3); +inf where that is not finite (n < 2, an inf sample).  The device's k_adaptive_retire
+    evaluates the same expressions in the same order."""
+    mean, se = _moments(s1, s2, n)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ratio = se / (mean + 1e-3)
+    fin = np.all(np.isfinite(ratio), axis=-1)
+    return np.where(fin, np.where(fin[..., None], ratio, 0.0).max(axis=-1), np.inf)
 
 
 def _fp(a):
@@ -72,6 +122,21 @@ def rng_stream(pixel: int, seed: int, sample: int, n: int, device: int = 0) -> n
     out = np.zeros(n, np.uint32)
     _lib.check(lib.apt_rng_stream(int(device), pixel & 0xffffffff, seed & 0xffffffff, sample & 0xffffffff, int(n),
                                   out.ctypes.data_as(_lib.u32p)), "apt_rng_stream")
+    return out
+
+
+def adaptive_segments(cnt: int, n_spp: int, min_spp: int, step: int) -> list:
+    """How one render call of an adaptive renderer at sample count `cnt` is split (api.hip render_adaptive does the same): a list of
+    (first sample, last sample, decides) per round piece - a piece ends at the next decision point (a multiple of `step` that is
+    >= `min_spp`), where the retirement rule runs, or where the call ends, and the next call continues the round."""
+    out, left = [], int(n_spp)
+    while left > 0:
+        first = max(int(min_spp), cnt + 1)
+        decide = -(-first // int(step)) * int(step)
+        seg = min(left, decide - cnt)
+        out.append((cnt + 1, cnt + seg, cnt + seg == decide))
+        cnt += seg
+        left -= seg
     return out
 
 
@@ -140,7 +205,7 @@ class _FieldView:
 
     def __init__(self, owner, normalised: bool): self._o, self._n = owner, normalised
     def to_numpy(self): return self._o._image(self._n)
-    def from_numpy(self, arr): self._o._set_accum(np.asarray(arr, np.float32), self._o._cnt)
+    def from_numpy(self, arr): self._o._steady_only("color.from_numpy"); self._o._set_accum(np.asarray(arr, np.float32), self._o._cnt)
     @property
     def shape(self): return (self._o.w, self._o.h)
 
@@ -153,11 +218,13 @@ class Renderer:
                  seed: int = 0, spp_per_batch: int = 0, profile: bool = False,
                  width: Optional[int] = None, height: Optional[int] = None,
                  max_bounce: Optional[int] = None, num_shadow_ray: Optional[int] = None, volumetric: Optional[bool] = None,
-                 exact: Optional[bool] = None, transient=None):
+                 exact: Optional[bool] = None, transient=None, adaptive=None):
         # transient = None / False: steady state; True: time bins from the sensor's sample_count / min_time / interval; a dict overrides them
         # (scene_pack.transient_config).  Surface renderer, at most 4 light samples per vertex, one rank: apt_renderer_create refuses the rest.
         # exact = True: the bit-parity build (the reference's float32 arithmetic operation for operation; debugging and the exact
         # parity tests), False: the fast build, None: whatever adapt_amd._lib currently hands out (fast unless APT_EXACT=1)
+        # adaptive = None: every pixel takes every sample; a dict {"threshold", "min_spp", "step"}: adaptive sampling (adaptive_config)
+        self.adaptive = adaptive_config(adaptive)
         self.lib = _lib.load(None if exact is None else ("exact" if exact else "fast"))
         self.arithmetic = _lib.arithmetic(self.lib)
         if volumetric is None:
@@ -198,6 +265,9 @@ class Renderer:
         cfg.volumetric = int(self.volumetric)
         cfg.transient_bins, cfg.transient_min_time, cfg.transient_interval = int(rc.transient_bins), float(rc.transient_min_time), float(rc.transient_interval)
         self.n_bins, self.min_time, self.interval = rc.transient_bins, rc.transient_min_time, rc.transient_interval
+        if self.adaptive:
+            cfg.adaptive_threshold = self.adaptive["threshold"]
+            cfg.adaptive_min_spp, cfg.adaptive_step = self.adaptive["min_spp"], self.adaptive["step"]
         h = C.c_void_p()
         _lib.check(self.lib.apt_renderer_create(self.scene.handle, C.byref(cfg), C.byref(h)), "apt_renderer_create", self.lib)
         self.handle = h
@@ -245,7 +315,7 @@ class Renderer:
         if self.world_size == 1:
             return tile
         from .tiles import gather_image
-        return gather_image(self, normalised)
+        return gather_image(self, normalised)          # (adaptive: divided by the gathered per-pixel counts)
 
     # ----------------------------------------------------------- transient
     def _need_transient(self):
@@ -274,7 +344,80 @@ class Renderer:
         _lib.check(self.lib.apt_set_transient(self.handle, _fp(cube)), "apt_set_transient", self.lib)
 
     def _set_cnt(self, v: int):
+        self._steady_only("cnt[None] = ...")
         self._set_accum(self.tile_accum(), v)
+
+    def _steady_only(self, what: str):
+        if self.adaptive:
+            raise RuntimeError(f"{what}: an adaptive renderer's per-pixel counts and moments would not follow; use load_check_point")
+
+    # ----------------------------------------------------------- adaptive sampling
+    def _need_adaptive(self):
+        if not self.adaptive:
+            raise RuntimeError("this renderer was created without adaptive=...: every pixel has cnt samples")
+
+    def tile_sample_counts(self, with_mask: bool = False):
+        """This rank's per-pixel sample counts, (n_cols, h) int32; with_mask: also the active flags, (n_cols, h) bool."""
+        self._need_adaptive()
+        n = np.empty((self.n_cols, self.h), np.int32)
+        act = np.empty((self.n_cols, self.h), np.uint8)
+        _lib.check(self.lib.apt_read_sample_counts(self.handle, _ip(n), act.ctypes.data_as(_lib.u8p)), "apt_read_sample_counts", self.lib)
+        return (n, act.astype(bool)) if with_mask else n
+
+    def tile_moments(self) -> np.ndarray:
+        """This rank's float64 sums of squared sample values, (n_cols, h, 3)."""
+        self._need_adaptive()
+        s2 = np.empty((self.n_cols, self.h, 3), np.float64)
+        _lib.check(self.lib.apt_read_moments(self.handle, s2.ctypes.data_as(_lib.f64p)), "apt_read_moments", self.lib)
+        return s2
+
+    def _tile_of(self, arr, tail, dtype):
+        arr = np.ascontiguousarray(arr, dtype)
+        if arr.shape == (self.n_cols, self.h) + tail:
+            return arr
+        if arr.shape == (self.w, self.h) + tail:
+            return np.ascontiguousarray(arr[self.plan.columns(self.rank)])
+        raise ValueError(f"expected ({self.w},{self.h}){tail} or the tile ({self.n_cols},{self.h}){tail}, got {arr.shape}")
+
+    def _set_adaptive_state(self, counts, s2, active):
+        n = self._tile_of(counts, (), np.int32)
+        m = self._tile_of(s2, (3,), np.float64)
+        a = self._tile_of(np.asarray(active).astype(np.uint8), (), np.uint8)
+        _lib.check(self.lib.apt_set_adaptive_state(self.handle, _ip(n), m.ctypes.data_as(_lib.f64p), a.ctypes.data_as(_lib.u8p)),
+                   "apt_set_adaptive_state", self.lib)
+
+    def _full(self, tile):
+        if self.world_size == 1:
+            return tile
+        from .tiles import gather_array
+        return gather_array(tile, self.plan, self.rank, self.world_size, device=self.device)
+
+    def sample_counts(self) -> np.ndarray:
+        """(w, h) int32: the samples each pixel has taken (0 outside a crop window); the largest is cnt."""
+        return self._full(self.tile_sample_counts())
+
+    def std_error(self) -> np.ndarray:
+        """(w, h, 3) float64: the standard error of each pixel's mean, per channel (NaN below two samples)."""
+        self._need_adaptive()
+        return _moments(self._full(self.tile_accum()), self._full(self.tile_moments()), self._full(self.tile_sample_counts()))[1]
+
+    def relative_error(self) -> np.ndarray:
+        """(w, h) float64: e_p, what the retirement rule holds against the threshold (+inf where not finite)."""
+        self._need_adaptive()
+        return relative_error(self._full(self.tile_accum()), self._full(self.tile_moments()), self._full(self.tile_sample_counts()))
+
+    def active_fraction(self) -> float:
+        """The share of this rank's sampled pixels (inside the crop window) that still take samples."""
+        n, act = self.tile_sample_counts(with_mask=True)
+        sampled = self._crop_mask().sum()
+        return float(act.sum()) / float(max(1, sampled))
+
+    def _crop_mask(self) -> np.ndarray:
+        cols = self.plan.columns(self.rank)[:, None]
+        rows = np.arange(self.h)[None, :]
+        if not self.do_crop:
+            return np.ones((self.n_cols, self.h), bool)
+        return (cols >= self.start_x) & (cols < self.end_x) & (rows >= self.start_y) & (rows < self.end_y)
 
     def _set_accum(self, arr: np.ndarray, cnt: int):
         arr = np.ascontiguousarray(arr, np.float32)
@@ -330,7 +473,8 @@ class Renderer:
         _lib.check(self.lib.apt_renderer_info(self.handle, C.byref(b), C.byref(nq), C.byref(qb), C.byref(lds), C.byref(name), C.byref(tm)), "apt_renderer_info", self.lib)
         return {"spp_per_batch": b.value, "n_subqueues": nq.value, "queue_bytes": qb.value, "lds_bytes": lds.value,
                 "shade_variant": name.value.decode() if name.value else "",
-                "traversal": {0: "bvh", 1: "sweep", 2: "tile", 3: "flat"}.get(tm.value, str(tm.value)), "arithmetic": self.arithmetic}
+                "traversal": {0: "bvh", 1: "sweep", 2: "tile", 3: "flat"}.get(tm.value, str(tm.value)), "arithmetic": self.arithmetic,
+                "sampling": "adaptive" if self.adaptive else "uniform", **({"adaptive": dict(self.adaptive)} if self.adaptive else {})}
 
     # ------------------------------------------------------------ checkpoint
     def get_check_point(self) -> dict:
@@ -339,11 +483,23 @@ class Renderer:
                 "crop_ry": self.crop_ry, "focal": self.focal, "num_objects": self.num_objects, "num_prims": self.num_prims,
                 "cam_orient": np.array(self.cam_orient), "src_num": self.src_num, "cam_t": np.array(self.cam_t),
                 "accumulation": self.color.to_numpy(), "counter": self._cnt,
-                **({"transient_bins": self.tile_transient()} if self.n_bins else {})}
+                **({"transient_bins": self.tile_transient()} if self.n_bins else {}),
+                **(self._adaptive_check_point() if self.adaptive else {})}
+
+    _ADAPTIVE_KEYS = ("adaptive", "sample_counts", "moments", "active")
+
+    def _adaptive_check_point(self) -> dict:
+        """this rank's tiles (the whole film with one rank): counts, moments and mask, and the settings they were made with"""
+        n, act = self.tile_sample_counts(with_mask=True)
+        return {"adaptive": dict(self.adaptive), "sample_counts": n, "moments": self.tile_moments(), "active": act}
 
     def load_check_point(self, check_point: dict):
+        if self.adaptive and "moments" not in check_point:
+            raise ValueError("this checkpoint has no per-pixel moments (a uniform render's): an adaptive renderer cannot continue it")
+        if not self.adaptive and any(k in check_point for k in self._ADAPTIVE_KEYS):
+            raise ValueError("this checkpoint is an adaptive render's: continue it with Renderer(..., adaptive=...)")
         for key, val in check_point.items():
-            if key in ("accumulation", "counter", "transient_bins"):
+            if key in ("accumulation", "counter", "transient_bins") + self._ADAPTIVE_KEYS:
                 continue
             if key in ("cam_t", "cam_orient"):
                 ok = np.abs(np.asarray(val) - np.asarray(getattr(self, key))).max() < 1e-4
@@ -352,6 +508,8 @@ class Renderer:
             if not ok:
                 raise ValueError(f"'{key}' from the checkpoint is different.")
         self._set_accum(np.asarray(check_point["accumulation"], np.float32), int(check_point["counter"]))
+        if self.adaptive:
+            self._set_adaptive_state(check_point["sample_counts"], check_point["moments"], check_point["active"])
         cube = check_point.get("transient_bins")
         if self.n_bins and cube is not None and np.shape(cube) == (self.n_bins, self.n_cols, self.h, 4):
             self._set_transient(cube)           # (a checkpoint of another bin layout, or of a steady render, leaves the bins as they are)
@@ -359,6 +517,9 @@ class Renderer:
     def summary(self) -> str:
         self.synchronize()
         msg = f"{'VPT' if self.volumetric else 'PT'} SPP = {self._cnt}. Rendering time: {time.time() - self._t0:.3f} s"
+        if self.adaptive:
+            n = self.tile_sample_counts()[self._crop_mask()]
+            msg += f". Adaptive: mean spp {n.mean() if n.size else 0.0:.1f}, {100.0 * (1.0 - self.active_fraction()):.1f} % of the pixels converged"
         print(msg)
         return msg
 

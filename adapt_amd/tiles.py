@@ -10,7 +10,9 @@ readback:
     image is identical to the single-GPU image bit for bit, whatever the partition.
   * gather: one `all_gather` of the per-rank (n_cols, H, 3) float32 tiles over
     torch.distributed (backend "nccl" == RCCL over xGMI on ROCm; "gloo" in the CPU tests),
-    ~1-2 MB per rank — latency-bound, not link-bound.  There is no other collective on the path.
+    ~1-2 MB per rank — latency-bound, not link-bound.  There is no other collective on the path,
+    except for adaptive renders: their per-pixel sample counts travel the same way
+    (`gather_array`), so that the assembled image and count map equal one rank's.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["TilePlan", "gather_tiles", "gather_tiles_device", "gather_image", "assemble", "device_tile"]
+__all__ = ["TilePlan", "gather_tiles", "gather_tiles_device", "gather_image", "gather_array", "assemble", "device_tile"]
 
 
 class TilePlan:
@@ -49,8 +51,11 @@ class TilePlan:
 
 
 def assemble(plan: TilePlan, tiles) -> np.ndarray:
-    """tiles[r] = (>= n_cols(r), H, 3) array of rank r  ->  (W, H, 3) image."""
-    img = np.zeros((plan.width, plan.height, 3), np.float32)
+    """tiles[r] = (>= n_cols(r), H, 3) array of rank r  ->  (W, H, 3) image.  (Other trailing shapes and dtypes - adaptive sample counts,
+    (n_cols, H) int32 - assemble the same way, into an array of the first tile's shape and dtype.)"""
+    t0 = np.asarray(tiles[0])
+    img = np.zeros((plan.width, plan.height, 3), np.float32) if t0.shape[2:] == (3,) and t0.dtype == np.float32 else \
+        np.zeros((plan.width, plan.height) + t0.shape[2:], t0.dtype)
     for r in range(plan.world_size):
         cols = plan.columns(r)
         img[cols] = np.asarray(tiles[r])[:len(cols)]
@@ -73,14 +78,15 @@ def gather_tiles_device(tile, plan: TilePlan, world_size: int, group=None):
     if not dist.is_initialized():
         raise RuntimeError("gather_tiles_device: torch.distributed is not initialised")
     mc = plan.max_cols()
+    ch = tuple(tile.shape[2:])                    # (3,) for the image tiles
     if tile.shape[0] == mc:
         padded = tile.contiguous()
     else:
-        padded = torch.zeros((mc, plan.height, 3), dtype=torch.float32, device=tile.device)
+        padded = torch.zeros((mc, plan.height) + ch, dtype=tile.dtype, device=tile.device)
         padded[:tile.shape[0]] = tile
-    out = torch.empty((world_size * mc, plan.height, 3), dtype=torch.float32, device=tile.device)    # rank-major concatenation
+    out = torch.empty((world_size * mc, plan.height) + ch, dtype=tile.dtype, device=tile.device)    # rank-major concatenation
     dist.all_gather_into_tensor(out, padded, group=group)
-    return out.view(world_size, mc, plan.height, 3)
+    return out.view((world_size, mc, plan.height) + ch)
 
 
 def gather_tiles(tile, plan: TilePlan, rank: int, world_size: int, group=None, force_collective: bool = False) -> np.ndarray:
@@ -95,6 +101,26 @@ def gather_tiles(tile, plan: TilePlan, rank: int, world_size: int, group=None, f
     import torch
     t = tile if isinstance(tile, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tile, np.float32))
     return assemble(plan, gather_tiles_device(t, plan, world_size, group).cpu().numpy())
+
+
+def gather_array(tile: np.ndarray, plan: TilePlan, rank: int, world_size: int, group=None, force_collective: bool = False,
+                 device: Optional[int] = None) -> np.ndarray:
+    """All-gather a per-rank (n_cols, H, ...) host array of any 4- or 8-byte dtype, moved as its bytes (float32 words), and assemble
+    (W, H, ...) on every rank.  On an RCCL group the words go through `device`'s memory."""
+    t = np.ascontiguousarray(tile)
+    if t.dtype.itemsize % 4:
+        raise ValueError("gather_array: the dtype must be a multiple of 4 bytes")
+    words = t.view(np.float32).reshape(t.shape[0], t.shape[1], -1)
+    if world_size == 1 and not force_collective:
+        full = assemble(plan, [words])
+    else:
+        import torch
+        import torch.distributed as dist
+        tt = torch.from_numpy(words)
+        if dist.get_backend(group) == "nccl":
+            tt = tt.to(torch.device(f"cuda:{device or 0}"))
+        full = assemble(plan, gather_tiles_device(tt, plan, world_size, group).cpu().numpy())
+    return np.ascontiguousarray(full).view(t.dtype).reshape((plan.width, plan.height) + t.shape[2:])
 
 
 _warned_staged = [False]
@@ -133,6 +159,10 @@ def gather_image(rdr, normalised: bool = True, group=None, force_collective: boo
     if tile is None:
         tile = rdr.tile_accum()
     img = gather_tiles(tile, rdr.plan, rdr.rank, rdr.world_size, group, force_collective)
+    if normalised and getattr(rdr, "adaptive", None):          # adaptive: each pixel divided by its own count, 0 where it has none
+        n = gather_array(rdr.tile_sample_counts(), rdr.plan, rdr.rank, rdr.world_size, group, force_collective, rdr.device)[..., None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, img / n.astype(np.float32), np.float32(0)).astype(np.float32)
     if normalised and rdr._cnt > 0:
         img = img / np.float32(rdr._cnt)
     return img

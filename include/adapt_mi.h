@@ -18,6 +18,7 @@
  *   apt_read_pixels                `rdr.pixels.to_numpy()` (utils/watermark.py:23): color / cnt, layout [x][y][rgb]
  *   apt_get_accum / apt_set_accum  tracer/path_tracer.py:181-211  get_check_point / load_check_point
  *   apt_read_transient             renderer/bdpt.py:57-58,164-166  time_bins / time_cnts (TRANSIENT_CAM), for the `pt` renderer
+ *   apt_read_sample_counts / apt_read_moments / apt_set_adaptive_state   (none; adaptive sampling)
  *   apt_get_stats                  (none; the reference only has ti.profiler, render.py:154-160)
  *   apt_device_ptr                 (none; hands the tile framebuffer to RCCL for the multi-GPU gather)
  *
@@ -104,6 +105,14 @@ typedef struct apt_render_cfg {
     int32_t volumetric;                           /* 0 = Renderer.render (renderer/vanilla_renderer.py:32-120); 1 = VolumeRenderer.render
                                                      (renderer/vpt.py:145-258): free-path sampling in homogeneous media, null surfaces,
                                                      transmittance-tracked light samples */
+    /* Adaptive sampling: a pixel stops sampling once its relative error e_p (max over channels of the standard error of
+       its mean / (mean + 1e-3)) is <= adaptive_threshold.  Decisions are made only at global sample numbers that are multiples of
+       adaptive_step and >= adaptive_min_spp; an active pixel takes every sample of a round, with the steady renderer's sample numbers, so
+       a pixel with n_p samples holds the steady renderer's accumulation after n_p spp bit for bit.  0 = off (steady state).  Not with
+       transient_bins > 0.  (These three sit before the transient block, which keeps the
+       last place it had when it was added.) */
+    float   adaptive_threshold;                   /* > 0 turns the mode on (finite) */
+    int32_t adaptive_min_spp, adaptive_step;      /* both > 0 when the mode is on (the Python layer's defaults: 64, 32) */
     /* Transient (time-resolved) rendering, surface renderer only (DESIGN.md "Transient rendering"): every path contribution is also
        added to a time bin by its optical length, camera to emitter (bdpt.py:164-165, TRANSIENT_CAM).  0 = off (steady state).  Needs
        volumetric = 0, num_shadow_ray <= 4 and world_size = 1; runs the staged pipeline on one render lane. */
@@ -189,14 +198,20 @@ void apt_renderer_destroy(apt_renderer*);
 int apt_render(apt_renderer*, int32_t n_spp);             /* accumulates n_spp more samples per owned pixel */
 int apt_synchronize(apt_renderer*);
 int apt_tile_shape(const apt_renderer*, int32_t* n_cols, int32_t* height);   /* owned framebuffer = n_cols*height*3 */
-int apt_read_pixels(apt_renderer*, float* out);           /* owned tile, [local col][y][rgb], color / cnt */
+int apt_read_pixels(apt_renderer*, float* out);           /* owned tile, [local col][y][rgb], color / cnt (adaptive: color / n_p, 0 where n_p = 0) */
 int apt_get_accum(apt_renderer*, float* out, int32_t* cnt);
 int apt_set_accum(apt_renderer*, const float* in, int32_t cnt);
-int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0, transient bins = 0 */
+int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0, transient bins = 0, adaptive state = start */
 /* transient renders: the owned tile's bins, [bin][local col][y][rgba] - summed r, g, b (divide by cnt for radiance, as pixels) and the
    number of contributions (a); transient_bins * n_cols * height * 4 floats.  apt_set_transient restores them (checkpoints). */
 int apt_read_transient(apt_renderer*, float* out);
 int apt_set_transient(apt_renderer*, const float* in);
+/* adaptive renders (adaptive_threshold > 0; APT_E_STATE otherwise), owned tile in [local col][y] order: the per-pixel sample counts n_p and
+   (active may be NULL) whether each pixel still samples; the float64 sums of squared sample values, 3 per pixel (S2; S1 is the accumulation).
+   apt_set_adaptive_state restores all three (checkpoints; after apt_set_accum). */
+int apt_read_sample_counts(apt_renderer*, int32_t* counts, uint8_t* active);
+int apt_read_moments(apt_renderer*, double* s2);
+int apt_set_adaptive_state(apt_renderer*, const int32_t* counts, const double* s2, const uint8_t* active);
 int apt_get_stats(apt_renderer*, apt_stats* out);
 int apt_device_ptr(apt_renderer*, void** accum_dev, int32_t* cnt); /* device float[n_cols*height*3] accumulation buffer */
 int apt_stream(apt_renderer*, void** hip_stream);         /* the hipStream_t every kernel of this renderer runs on */
