@@ -155,6 +155,7 @@ struct apt_scene {
     DevBuf nodes, prims, slot_prim, normals, vnormals, precom, prim_obj, prim_class, obj_info, emitter_id, bxdf, src, sweep_recs, sweep_tab;
     DevBuf flat_recs, flat_tab, flat_pairs;     // flat sweep (fast build, small scenes): records, the per-record table, the records two by two (traverse.hpp FlatScene)
     DevBuf flat_occ, flat_occ_tab;              // ... per emitter, the records that can block its light samples, two by two, and their table
+    std::vector<float> h_prims, h_flat_recs, h_flat_tab; int h_flat_counts[7] = {0, 0, 0, 0, 0, 0, 0};      // ... and what a renderer builds its camera strip lists from (flat_build.cpp camera_strips)
     bool has_flat = false;
     DevBuf uvs, tex_i, tex_f, atlas[3];      // image textures (empty when the scene has none)
     DevBuf prim_shade;                   // per-primitive shading records (stages.hpp DevScene::prim_shade)
@@ -197,6 +198,7 @@ struct apt_renderer {
     int n_lanes = 1;
     hipStream_t stream() const { return lanes[0].stream; }
     DevBuf accum, scratch, pix_key;
+    DevBuf cam_strips;            // rays traced in place: per 64 local pixels, the record pairs a camera ray can hit (flat_build.cpp camera_strips)
     Counters host_counters{};
     int grid_small = 0, grid_trace = 0, nq = APT_MAX_NQ;
     const ShadeVariant* shade = nullptr;
@@ -536,6 +538,7 @@ static int pack_flat(const apt_scene_desc* d, apt_scene* s, const std::vector<in
     fl.occ_pairs = s->flat_occ.as<float>(); fl.occ_tab = s->flat_occ_tab.as<int>();
     fl.defer_all = getenv("APT_FLAT_DEFER_ALL") ? atoi(getenv("APT_FLAT_DEFER_ALL")) : 0;
     fl.n_quads = fc[0]; fl.n_quads_tie = fc[1]; fl.n_gquads = fc[2]; fl.n_gquads_tie = fc[3]; fl.n_tris = fc[4]; fl.n_tris_tie = fc[5]; fl.n_spheres = fc[6];
+    s->h_prims.assign(d->prims, d->prims + 9 * (size_t)N); s->h_flat_recs = fr; s->h_flat_tab = ft; memcpy(s->h_flat_counts, fc, sizeof(fc));
     s->has_flat = true;
     if (timer.on) fprintf(stderr, "[scene timing] flat records: %d + %d parallelograms, %d + %d convex quads, %d + %d triangles (plain + coplanar groups), %d spheres of %d primitives\n", fc[0], fc[1], fc[2], fc[3], fc[4], fc[5], fc[6], N);
     if (timer.on) for (int e = 0; e < s->n_sources; e++) fprintf(stderr, "[scene timing] occluders of emitter %d: %d parallelograms, %d convex quads, %d triangles, %d spheres\n", e, ot[8 * (size_t)e + 1], ot[8 * (size_t)e + 2], ot[8 * (size_t)e + 3], ot[8 * (size_t)e + 4]);
@@ -819,6 +822,46 @@ static int pick_shading(apt_renderer* r) {
     return APT_OK;
 }
 
+// Rays traced in place: the strip lists of the camera rays (flat_build.cpp camera_strips) - per block of 64 local pixels
+// the record pairs k_generate_trace sweeps.  They depend on the scene's records, the camera, the film and this rank's bands, all fixed
+// for the life of a renderer: built once, here.  APT_CAMERA_CULL=0: every strip takes the full stream.
+static apt::CamFilm cam_film(const apt_render_cfg& c) {
+    apt::CamFilm cf;
+    memcpy(cf.cam_r, c.cam_r, sizeof(cf.cam_r)); memcpy(cf.cam_t, c.cam_t, sizeof(cf.cam_t));
+    cf.inv_focal = c.inv_focal; cf.half_w = c.half_w; cf.half_h = c.half_h;
+    cf.width = c.width; cf.height = c.height; cf.n_cols = owned_columns(c); cf.band_width = c.band_width; cf.rank = c.rank; cf.world = c.world_size;
+    return cf;
+}
+static int make_camera_strips(apt_renderer* r) {
+    if (r->par.fused != 2) return APT_OK;
+    const apt_scene* sc = r->scene;
+    const bool cull = !(getenv("APT_CAMERA_CULL") && atoi(getenv("APT_CAMERA_CULL")) == 0);
+    std::vector<uint64_t> masks;
+    if (apt::camera_strips(sc->h_prims.data(), sc->n_prims, sc->h_flat_recs, sc->h_flat_tab, sc->h_flat_counts, cam_film(r->cfg), cull, masks) != 0)
+        return fail(APT_E_INVALID, "apt_renderer_create: camera strip lists: bad record or film");
+    hipError_t e = upload(r->cam_strips, masks);
+    if (e != hipSuccess) return fail(APT_E_HIP, std::string("upload camera strip lists: ") + hipGetErrorString(e));
+    return APT_OK;
+}
+
+// ... and the same lists without a device, for the host tests (tests/test_camera_cull.py)
+APT_EXPORT int apt_camera_strips(const float* prims, int32_t n_prims, const int32_t* obj_info, int32_t n_objects, const apt_render_cfg* cfg, int32_t cull,
+                                 uint64_t* masks, int32_t masks_cap, int32_t* n_strips, int32_t* n_pairs) {
+    if (!prims || !obj_info || !cfg || n_prims <= 0 || n_objects <= 0 || !n_strips || !n_pairs) return fail(APT_E_INVALID, "apt_camera_strips: bad argument");
+    apt_render_cfg c = *cfg;                                                  // defaults as apt_renderer_create
+    if (c.world_size <= 0) { c.world_size = 1; c.rank = 0; }
+    if (c.band_width <= 0) c.band_width = c.width;
+    if (c.width <= 0 || c.height <= 0 || c.rank < 0 || c.rank >= c.world_size || owned_columns(c) <= 0) return fail(APT_E_INVALID, "apt_camera_strips: bad film or rank");
+    std::vector<float> st, tb; int cn[7];
+    if (apt::build_flat(prims, n_prims, obj_info, n_objects, nullptr, st, tb, cn) != 0) return fail(APT_E_INVALID, "apt_camera_strips: obj_info range outside the primitive array");
+    std::vector<uint64_t> m;
+    if (apt::camera_strips(prims, n_prims, st, tb, cn, cam_film(c), cull != 0, m) != 0) return fail(APT_E_INVALID, "apt_camera_strips: bad record or film");
+    *n_strips = (int32_t)m.size();
+    *n_pairs = (cn[0] + cn[1] + 1) / 2 + (cn[2] + cn[3] + 1) / 2 + (cn[4] + cn[5] + 1) / 2 + (cn[6] + 1) / 2;
+    if (masks) { if (masks_cap < (int32_t)m.size()) return fail(APT_E_INVALID, "apt_camera_strips: masks buffer too small"); memcpy(masks, m.data(), m.size() * 8); }
+    return APT_OK;
+}
+
 // The render lanes (queue pool, counters, stream, "finalize done" event each) and the framebuffer.
 static int make_lanes(apt_renderer* r) {
     const apt_scene* sc = r->scene;
@@ -1077,6 +1120,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     if (int rc = plan_film(r)) return rc;
     pick_traversal(r);
     if (int rc = pick_shading(r)) return rc;
+    if (int rc = make_camera_strips(r)) return rc;
     if (int rc = make_lanes(r)) return rc;
     if (int rc = make_transient(r)) return rc;
     if (int rc = make_adaptive(r)) return rc;
@@ -1286,8 +1330,9 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
             // are served by the next launch's prologue, the last bounce's deferred light samples by one fix-up launch at the end
             {
                 LaunchTimer t(r, 0, st);
-                if (r->adaptive) hipLaunchKernelGGL(k_generate_trace_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, (const uint8_t*)r->aq.active);
-                else hipLaunchKernelGGL(k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt);
+                const unsigned long long* strips = r->cam_strips.as<unsigned long long>();
+                if (r->adaptive) hipLaunchKernelGGL(k_generate_trace_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, (const uint8_t*)r->aq.active, strips);
+                else hipLaunchKernelGGL(k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips);
             }
             int cur = 0;
             for (int b = 0; b < p.max_bounce; b++) {

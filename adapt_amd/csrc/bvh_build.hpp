@@ -85,4 +85,13 @@ void emitter_points(const float* prims, const int32_t* obj_info, int n_objects, 
                     std::vector<float>& pts, std::vector<int32_t>& off);
 int flat_occluders(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7],
                    const float* pts, const int32_t* off, int n_emit, bool cull, std::vector<float>& pairs, std::vector<int32_t>& table, std::vector<uint8_t>& keep);
+// Strip lists of the camera rays: per block of 64 consecutive local pixels - what one wave of k_generate_trace holds - a
+// bit per record PAIR of FlatScene::pairs, in stream order: clear = no camera ray of the block can hit either record of the pair.
+// cull = false, or more than 64 pairs: every bit of every word set.
+#ifndef APT_FLAT_MAX_PRIMS
+#define APT_FLAT_MAX_PRIMS 96
+#endif
+struct CamFilm { float cam_r[9], cam_t[3], inv_focal, half_w, half_h; int width, height, n_cols, band_width, rank, world; };      // n_cols: the columns this rank owns
+int camera_strips(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7],
+                  const CamFilm& cf, bool cull, std::vector<uint64_t>& masks);
 }  // namespace apt

@@ -404,4 +404,136 @@ int flat_occluders(const float* prims, int n_prims, const std::vector<float>& st
     if (pairs.empty()) pairs.push_back(0.f);
     return 0;
 }
+
+// Which record PAIRS of FlatScene::pairs a camera ray of a pixel strip can hit (stages.hpp generate_body, traverse.hpp flat_closest1's
+// mask).  A wave of k_generate_trace holds 64 consecutive local pixels; block b = local pixels 64 b .. 64 b + 63.  Every
+// ray of the block leaves cam_t with a direction R (x, y, 1), (x, y) inside the rectangle that the block's pixels span on the image
+// plane - whatever the jitter, which stays in [0, 1] of its pixel - so it lies inside the pyramid with apex cam_t through that
+// rectangle.  masks[b] bit k is CLEAR when, for each record of pair k, all its vertices (a sphere: the corners of its padded box) are
+// outside ONE of the pyramid's four side planes by more than a margin; otherwise set.  cull = false: every bit set.
+//
+// Why a cleared record cannot change flat_closest1's answer.  flat_candidate() leaves the running best untouched unless
+// `inside && t > 1e-4`, so it is enough that this is false for every ray of the block, in the kernel's float32 arithmetic.  Let n be
+// the inward unit normal of the separating side plane: n . (x - cam_t) <= -margin for every vertex x, n . d >= 0 for every ray
+// (the rectangle is widened by `widen` pixels for the rounding of d, below).  Take the kernel's t and the exact point
+// X = cam_t + t d.  If t > 1e-4 then n . (X - cam_t) = t (n . d) >= 0.  If the inside test accepts, X is within eps of the record's
+// outline (below), hence n . (X - cam_t) <= -margin + eps < 0: both cannot hold.  Records BEHIND the camera drop out by the same test:
+// they are outside every side plane, their t is negative.  With u = 2^-24, ext = the extent per axis of scene and camera, L = |ext|:
+//  * height of X over the record's plane.  t = -fl(T . s) rcp(fl(T . d)), s = fl(o - p0): with e_o <= 4 u sum|T| ext the error of
+//    T . s, e_d <= 3 sqrt(3) u |T| that of T . d and 3 u for rcp and the product, T . (X - p0) = t t_d' (3 u) - e_o - t e_d
+//    (t_d' the computed T . d, |t t_d'| <= sum|T| ext), and |t| <= L + height because X is over the outline:
+//    height <= (7 u sum|T| ext + 6 u L) / |T|;
+//  * how far outside the outline the inside test may accept X: u, v come from U . P, V . P at P = fma(t, d, s), off by
+//    5 u sum|U| ext and 5 u sum|V| ext; an edge function g = a u + b v + c adds its own three roundings, 3 u (|a| + |b| + |c|)
+//    (the comparisons with 0 and 1/2 are exact) - divided by |a U + b V| a distance in the plane.
+//  eps is the sum of the two, and margin = 16 eps: the factor covers a corner where two edges meet at an angle (the distance to the
+//  outline is the overshoot over one edge divided by the sine) down to ~7 degrees and costs a strip nothing it could measure - 16 eps
+//  is ~1e-4 of the Cornell box, a hundredth of a pixel's footprint on its back wall.
+//  * spheres (flat_closest1's last loop): `c2ray < r2` is the squared distance of the centre from the LINE, off by <= 16 u D^2
+//    (D = |centre - cam_t|; |d|^2 - 1 <= 4 u included), and a camera with cn2 <= r2 + 1e-4 takes the far root.  The box is that of
+//    the radius sqrt(r^2 (1 + 4 u) + 1.1e-4 + 32 u D^2): it contains every point where an accepted line is closest to the centre, and
+//    a camera that is inside the sphere or within the 1e-4 rule (the apex is then not separable: kept).  Where the box is separated, the
+//    closest point has t < 0, the near root proj - cut is below proj <= -margin + 6 u D, and nothing is valid.
+//  * the direction: (half_w + vx - i) inv_focal, (j - half_h - vy) inv_focal, R ., normalize: four roundings of numbers up to
+//    W + H + 1 / inv_focal pixels in the image plane, then relative ones that keep the ray on its line (a positive scale) or move it by
+//    <= 3 u of |(x, y, 1)| per matrix row.  widen = 64 u (W + H + 1 / inv_focal) pixels (a few 1e-3 of a pixel) is ten times their sum.
+// Rays that flat_needs_cull() defers never use the sweep's answer (generate_body hands them to the reference-order code as before).
+int camera_strips(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7],
+                  const CamFilm& cf, bool cull, std::vector<uint64_t>& masks) {
+    static_assert((APT_FLAT_MAX_PRIMS + 4) / 2 <= 64, "a strip's pair list is one 64-bit word (four sections, each with at most one odd tail)");
+    const double u = std::ldexp(1.0, -24);
+    const int nsec[4] = {counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6]};
+    const int n_pairs = (nsec[0] + 1) / 2 + (nsec[1] + 1) / 2 + (nsec[2] + 1) / 2 + (nsec[3] + 1) / 2;
+    const int npix = cf.n_cols * cf.height, n_blocks = (npix + 63) / 64;
+    if (npix <= 0 || cf.height <= 0 || cf.band_width <= 0 || cf.world <= 0) return -1;
+    const uint64_t all = ~(uint64_t)0;
+    masks.assign((size_t)n_blocks, all);
+    if (!cull || n_pairs > 64) return 0;
+    const D3 cam = {cf.cam_t[0], cf.cam_t[1], cf.cam_t[2]};
+    struct Rec { int pair; std::vector<D3> vs; double margin; };
+    std::vector<Rec> recs;
+    double lo[3] = {cam.x, cam.y, cam.z}, hi[3] = {cam.x, cam.y, cam.z};
+    {
+        size_t at = 0; int pair0 = 0;
+        for (int sec = 0, r = 0; sec < 4; pair0 += (nsec[sec] + 1) / 2, sec++) for (int j = 0; j < nsec[sec]; j++, r++, at += (size_t)kRecordFloats[sec]) {
+            int32_t ids[2]; memcpy(ids, tab.data() + 28 * (size_t)r + 8, 8);
+            if (ids[0] < 0 || ids[0] >= n_prims || ids[1] >= n_prims) return -1;
+            Rec rc; rc.pair = pair0 + j / 2; rc.margin = 0.0;
+            if (sec < 3) { for (int k : {ids[0], ids[1]}) if (k >= 0) for (int v = 0; v < 3; v++) rc.vs.push_back(vtx(prims, k, v)); }
+            else {
+                const float* c = prims + 9 * (size_t)ids[0];
+                const D3 dc = sub({c[0], c[1], c[2]}, cam);
+                const double D2 = dot(dc, dc), rr = std::sqrt((double)c[3] * (double)c[3] * (1.0 + 4.0 * u) + 1.1e-4 + 32.0 * u * D2);
+                for (int k = 0; k < 8; k++) rc.vs.push_back({c[0] + ((k & 1) ? rr : -rr), c[1] + ((k & 2) ? rr : -rr), c[2] + ((k & 4) ? rr : -rr)});
+                rc.margin = 16.0 * 6.0 * u * (std::sqrt(D2) + rr);
+            }
+            for (const D3& p : rc.vs) { const double c[3] = {p.x, p.y, p.z}; for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], c[a]); hi[a] = std::max(hi[a], c[a]); } }
+            recs.push_back(rc);
+        }
+    }
+    const D3 ext = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    const double L = std::sqrt(dot(ext, ext));
+    auto absdot = [](D3 a, D3 b) { return std::fabs(a.x) * b.x + std::fabs(a.y) * b.y + std::fabs(a.z) * b.z; };
+    {
+        size_t at = 0;
+        for (int sec = 0, r = 0; sec < 3; sec++) for (int j = 0; j < nsec[sec]; j++, r++, at += (size_t)kRecordFloats[sec]) {
+            const float* p = stream.data() + at;
+            const D3 U = {p[3], p[4], p[5]}, V = {p[6], p[7], p[8]}, T = {p[9], p[10], p[11]};
+            if (dot(T, T) == 0.0) continue;                      // a degenerate triangle: t = NaN, never valid; its vertices still decide its bit (margin 0)
+            std::vector<std::array<double, 3>> edges = {{1, 0, 0}, {0, 1, 0}};
+            if (sec == 0) { edges.push_back({1, 0, 0.5}); edges.push_back({0, 1, 0.5}); }      // |u - 1/2| <= 1/2
+            if (sec == 2) edges.push_back({1, 1, 1});
+            if (sec == 1) for (int e = 0; e < 2; e++) edges.push_back({p[12 + 3 * e], p[13 + 3 * e], p[14 + 3 * e]});
+            double ovs = 0.0;
+            for (const auto& g : edges) {
+                const D3 grad = add({g[0] * U.x, g[0] * U.y, g[0] * U.z}, {g[1] * V.x, g[1] * V.y, g[1] * V.z});
+                const double gl = std::sqrt(dot(grad, grad));
+                if (!(gl > 0.0)) return -1;
+                ovs = std::max(ovs, (5.0 * u * (std::fabs(g[0]) * absdot(U, ext) + std::fabs(g[1]) * absdot(V, ext)) + 3.0 * u * (std::fabs(g[0]) + std::fabs(g[1]) + std::fabs(g[2]))) / gl);
+            }
+            recs[(size_t)r].margin = 16.0 * ((7.0 * u * absdot(T, ext) + 6.0 * u * L) / std::sqrt(dot(T, T)) + ovs);
+        }
+    }
+    const double widen = 64.0 * u * ((double)cf.width + (double)cf.height + 1.0 / std::fabs((double)cf.inv_focal));
+    auto world = [&](double x, double y) -> D3 {
+        const float* R = cf.cam_r;
+        return {R[0] * x + R[1] * y + R[2], R[3] * x + R[4] * y + R[5], R[6] * x + R[7] * y + R[8]};
+    };
+    for (int b = 0; b < n_blocks; b++) {
+        int i0 = 1 << 30, i1 = -(1 << 30), j0 = 1 << 30, j1 = -(1 << 30);
+        for (int lp = 64 * b; lp < std::min(npix, 64 * b + 64); lp++) {      // local_to_global (stages.hpp)
+            const int lc = lp / cf.height, j = lp % cf.height, i = (lc / cf.band_width * cf.world + cf.rank) * cf.band_width + lc % cf.band_width;
+            i0 = std::min(i0, i); i1 = std::max(i1, i); j0 = std::min(j0, j); j1 = std::max(j1, j);
+        }
+        // image-plane rectangle of the block: x = (half_w + vx - i) inv_focal, y = (j - half_h - vy) inv_focal, vx, vy in [0, 1]
+        const double f = cf.inv_focal;
+        double xa = ((double)cf.half_w - i1 - widen) * f, xb = ((double)cf.half_w + 1.0 - i0 + widen) * f;
+        double ya = ((double)j0 - cf.half_h - 1.0 - widen) * f, yb = ((double)j1 - cf.half_h + widen) * f;
+        if (xa > xb) std::swap(xa, xb);
+        if (ya > yb) std::swap(ya, yb);
+        const D3 c[4] = {world(xa, ya), world(xb, ya), world(xb, yb), world(xa, yb)}, mid = world(0.5 * (xa + xb), 0.5 * (ya + yb));
+        D3 n[4];
+        bool ok = true;
+        for (int k = 0; k < 4; k++) {
+            D3 m = cross(c[k], c[(k + 1) & 3]);
+            const double len = std::sqrt(dot(m, m));
+            if (!(len > 0.0) || !std::isfinite(len)) { ok = false; break; }
+            if (dot(m, mid) < 0.0) m = {-m.x, -m.y, -m.z};
+            n[k] = {m.x / len, m.y / len, m.z / len};
+        }
+        if (!ok) continue;                                       // (a singular camera matrix: the full stream)
+        uint64_t m = 0;
+        for (const Rec& r : recs) {
+            bool out = false;
+            for (int k = 0; k < 4 && !out; k++) {
+                double top = -1e300;
+                for (const D3& p : r.vs) top = std::max(top, dot(n[k], sub(p, cam)));
+                out = top < -r.margin;
+            }
+            if (!out) m |= (uint64_t)1 << r.pair;
+        }
+        masks[(size_t)b] = m;
+    }
+    return 0;
+}
 }  // namespace apt

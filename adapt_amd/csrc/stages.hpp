@@ -402,8 +402,11 @@ APT_D SubLoop sub_loop(int nq, int nt = BLOCK) {
 // (Queues::tr, parity 0, the queue of the hit primitive's class; counted in n_tr[0]); a ray that hits nothing is not queued at all.
 // ADAPTIVE (adaptive sampling): a pixel that has stopped sampling (active[lp] == 0) is one more slot that is not alive;
 // the queue is compacted as for a crop window.
+// strips (TRACE): per block of 64 consecutive local pixels, the record pairs a camera ray of the block can hit (flat_build.cpp
+// camera_strips).  A wave's 64 entries are consecutive local pixels modulo npix: they lie in the block of the first, the
+// block of the last before the film's end and - where the wave wraps into the next sample - block 0; the wave sweeps the union.
 template <bool TRACE, bool ADAPTIVE = false>
-APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, Counters* cnt, const uint8_t* active = nullptr) {
+APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, Counters* cnt, const uint8_t* active = nullptr, const unsigned long long* strips = nullptr) {
     const uint32_t total = (uint32_t)p.npix * (uint32_t)p.spp_batch;
     const uint32_t n_waves = (total + 63u) / 64u;
     const uint32_t wave_stride = gridDim.x * (BLOCK / 64);
@@ -455,7 +458,12 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
         if (TRACE) {
             const f3 cam_o = mk3(p.cam_t[0], p.cam_t[1], p.cam_t[2]);
             float tr_t = 0.f; int tr_run = -1, tr_idx = -1;
-            if (__any(alive)) tr_idx = flat_closest1(sc->flat, cam_o, dir, 1e7f, tr_t, tr_run);
+            if (__any(alive)) {
+                typedef const __attribute__((address_space(4))) unsigned long long* strip_ptr;      // wave-uniform: scalar loads
+                const uint32_t lp0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((w * 64u) % (uint32_t)p.npix)), lp1 = lp0 + 63u, last = (uint32_t)p.npix - 1u;
+                const unsigned long long mask = ((strip_ptr)strips)[lp0 >> 6] | ((strip_ptr)strips)[(lp1 < last ? lp1 : last) >> 6] | ((strip_ptr)strips)[lp1 > last ? 0u : (lp0 >> 6)];
+                tr_idx = flat_closest1<true>(sc->flat, cam_o, dir, 1e7f, tr_t, tr_run, mask);
+            }
             const bool defer = alive && (tr_run >= 0 || flat_needs_cull(sc->flat, dir));
             HitRec hr; hr.t = 1e7f; hr.prim = -1; hr.u = hr.v = 0.f;
             int hit_cls = 0;
@@ -495,8 +503,8 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
 __global__ void __launch_bounds__(BLOCK) k_generate(Params p, Queues q, Counters* cnt) { generate_body<false>(nullptr, p, q, cnt); }
 __global__ void __launch_bounds__(BLOCK) k_generate_ad(Params p, Queues q, Counters* cnt, const uint8_t* active) { generate_body<false, true>(nullptr, p, q, cnt, active); }
 #if APT_FAST
-__global__ void __launch_bounds__(BLOCK) k_generate_trace(DevScene sc, Params p, Queues q, Counters* cnt) { generate_body<true>(&sc, p, q, cnt); }
-__global__ void __launch_bounds__(BLOCK) k_generate_trace_ad(DevScene sc, Params p, Queues q, Counters* cnt, const uint8_t* active) { generate_body<true, true>(&sc, p, q, cnt, active); }
+__global__ void __launch_bounds__(BLOCK) k_generate_trace(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) { generate_body<true>(&sc, p, q, cnt, nullptr, strips); }
+__global__ void __launch_bounds__(BLOCK) k_generate_trace_ad(DevScene sc, Params p, Queues q, Counters* cnt, const uint8_t* active, const unsigned long long* strips) { generate_body<true, true>(&sc, p, q, cnt, active, strips); }
 #endif
 
 // ------------------------------------------------------------------- extend

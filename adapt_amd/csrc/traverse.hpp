@@ -951,7 +951,12 @@ APT_D bool flat_any1(const FlatList& ls, f3 o, f3 d, float lim) {
 // bit for bit.  A pair that straddles the border between a plain section and its coplanar-group section is treated as a group pair: its
 // plain record may then be remembered as a runner-up, which only sends the ray to the reference-order arithmetic a little more often.
 // Returns the winner's record index (-1: none); t = its distance, runner = a near-tied runner-up from a coplanar group (-1: none).
-APT_D int flat_closest1(const FlatScene& fl, f3 o, f3 d, float lim, float& t_out, int& runner) {
+// MASKED: bit k of the wave-uniform `mask` clear = pair k of the stream (counted across the sections) is skipped, record index and stream
+// position moving on as if it had been visited.  A pair may be skipped when neither of its records can be a valid candidate of any ray
+// of the wave (flat_build.cpp camera_strips): flat_candidate() leaves the running best untouched for such a record, so winner, distance
+// and runner-up are the same bit for bit.  (k & 63: a stream of more than 64 pairs comes with every bit set.)
+template <bool MASKED = false>
+APT_D int flat_closest1(const FlatScene& fl, f3 o, f3 d, float lim, float& t_out, int& runner, unsigned long long mask = ~0ull) {
     cf_ptr at = (cf_ptr)fl.pairs;
     const v2f ox = sp2(o.x), oy = sp2(o.y), oz = sp2(o.z), dx = sp2(d.x), dy = sp2(d.y), dz = sp2(d.z);
     FlatBest b; b.t = lim; b.idx = -1; b.runner = -1;
@@ -969,16 +974,20 @@ APT_D int flat_closest1(const FlatScene& fl, f3 o, f3 d, float lim, float& t_out
         v = fma2(vx, px, fma2(vy, py, vz * pz));
     };
     int idx = 0;                                             // wave-uniform index of the pair's first record
+    int k = 0;                                               // ... and of the pair itself
+    auto skip = [&](int pair) { return MASKED && ((mask >> (pair & 63)) & 1ull) == 0ull; };
     {   // parallelograms
         const int n = fl.n_quads + fl.n_quads_tie, n_plain = fl.n_quads >> 1;      // pairs whose records are both plain
         int j = 0;
-        for (; j < n_plain; j++, idx += 2, at += 24) {
+        for (; j < n_plain; j++, idx += 2, at += 24, k++) {
+            if (skip(k)) continue;
             v2f t, u, v; solve(at, t, u, v);
             const v2f a = u - sp2(0.5f), c = v - sp2(0.5f);
             b = flat_candidate<false>(b, fmaxf(fabsf(a.x), fabsf(c.x)) <= 0.5f, t.x, idx);
             b = flat_candidate<false>(b, fmaxf(fabsf(a.y), fabsf(c.y)) <= 0.5f, t.y, idx + 1);
         }
-        for (; 2 * j < n; j++, idx += 2, at += 24) {
+        for (; 2 * j < n; j++, idx += 2, at += 24, k++) {
+            if (skip(k)) continue;
             v2f t, u, v; solve(at, t, u, v);
             const v2f a = u - sp2(0.5f), c = v - sp2(0.5f);
             b = flat_candidate<true>(b, fmaxf(fabsf(a.x), fabsf(c.x)) <= 0.5f, t.x, idx);
@@ -989,13 +998,15 @@ APT_D int flat_closest1(const FlatScene& fl, f3 o, f3 d, float lim, float& t_out
     {   // convex quadrilaterals
         const int n = fl.n_gquads + fl.n_gquads_tie, n_plain = fl.n_gquads >> 1, first = idx;
         int j = 0;
-        for (; j < n_plain; j++, idx += 2, at += 36) {
+        for (; j < n_plain; j++, idx += 2, at += 36, k++) {
+            if (skip(k)) continue;
             v2f t, u, v; solve(at, t, u, v);
             const v2f e1 = fma2(ld2c(at + 24), u, fma2(ld2c(at + 26), v, ld2c(at + 28))), e2 = fma2(ld2c(at + 30), u, fma2(ld2c(at + 32), v, ld2c(at + 34)));
             b = flat_candidate<false>(b, fminf(fminf(u.x, v.x), fminf(e1.x, e2.x)) >= 0.f, t.x, idx);
             b = flat_candidate<false>(b, fminf(fminf(u.y, v.y), fminf(e1.y, e2.y)) >= 0.f, t.y, idx + 1);
         }
-        for (; 2 * j < n; j++, idx += 2, at += 36) {
+        for (; 2 * j < n; j++, idx += 2, at += 36, k++) {
+            if (skip(k)) continue;
             v2f t, u, v; solve(at, t, u, v);
             const v2f e1 = fma2(ld2c(at + 24), u, fma2(ld2c(at + 26), v, ld2c(at + 28))), e2 = fma2(ld2c(at + 30), u, fma2(ld2c(at + 32), v, ld2c(at + 34)));
             b = flat_candidate<true>(b, fminf(fminf(u.x, v.x), fminf(e1.x, e2.x)) >= 0.f, t.x, idx);
@@ -1006,13 +1017,15 @@ APT_D int flat_closest1(const FlatScene& fl, f3 o, f3 d, float lim, float& t_out
     {   // triangles
         const int n = fl.n_tris + fl.n_tris_tie, n_plain = fl.n_tris >> 1, first = idx;
         int j = 0;
-        for (; j < n_plain; j++, idx += 2, at += 24) {
+        for (; j < n_plain; j++, idx += 2, at += 24, k++) {
+            if (skip(k)) continue;
             v2f t, u, v; solve(at, t, u, v);
             const v2f w = (sp2(1.0f) - u) - v;
             b = flat_candidate<false>(b, fminf(fminf(u.x, v.x), w.x) >= 0.f, t.x, idx);
             b = flat_candidate<false>(b, fminf(fminf(u.y, v.y), w.y) >= 0.f, t.y, idx + 1);
         }
-        for (; 2 * j < n; j++, idx += 2, at += 24) {
+        for (; 2 * j < n; j++, idx += 2, at += 24, k++) {
+            if (skip(k)) continue;
             v2f t, u, v; solve(at, t, u, v);
             const v2f w = (sp2(1.0f) - u) - v;
             b = flat_candidate<true>(b, fminf(fminf(u.x, v.x), w.x) >= 0.f, t.x, idx);
@@ -1020,7 +1033,8 @@ APT_D int flat_closest1(const FlatScene& fl, f3 o, f3 d, float lim, float& t_out
         }
         idx = first + n;
     }
-    for (int j = 0; 2 * j < fl.n_spheres; j++, idx += 2, at += 8) {      // spheres: flat_loop's test (the reference's, tracer_base.py:184-199) on two spheres
+    for (int j = 0; 2 * j < fl.n_spheres; j++, idx += 2, at += 8, k++) {      // spheres: flat_loop's test (the reference's, tracer_base.py:184-199) on two spheres
+        if (skip(k)) continue;
         const v2f r2 = ld2c(at + 6);
         const v2f sx = ld2c(at) - ox, sy = ld2c(at + 2) - oy, sz = ld2c(at + 4) - oz;
         const v2f cn2 = (sx * sx + sy * sy) + sz * sz;

@@ -9,6 +9,7 @@
  *   apt_bvh_build / apt_bvh_*      the same builder's role for this library's own kernels (binary SAH tree -> 8-wide quantised tree)
  *   apt_flat_records               tracer/tracer_base.py:117-134,184-212: the data of the brute-force intersector, as the flat sweep wants it
  *   apt_flat_occluders             (no upstream counterpart) per emitter, the flat records that can block its light samples
+ *   apt_camera_strips              (no upstream counterpart) per 64 local pixels, the flat record pairs a camera ray can hit
  *   apt_scene_create               tracer/tracer_base.py:117-134 (load_primitives) +
  *                                   tracer/path_tracer.py:245-274 (initialze): numpy -> device fields
  *   apt_renderer_create            renderer/vanilla_renderer.py:26-30 / tracer_base.py:36-102 (film, crop, camera,
@@ -171,6 +172,13 @@ int apt_flat_records(const float* prims /* n_prims*9 */, int32_t n_prims, const 
 int apt_flat_occluders(const float* prims /* n_prims*9 */, int32_t n_prims, const int32_t* obj_info /* n_objects*3 */, int32_t n_objects,
                        const int32_t* src_i, const float* src_f, int32_t n_sources, int32_t cull, int32_t* table, int32_t* keep, int32_t keep_cap,
                        float* pairs, int32_t pairs_cap, int32_t* n_records, int32_t* n_pairs);
+
+/* Strip lists of the camera rays (host only): for the film, camera, crop-independent band plan (band_width, rank, world_size)
+ * of cfg, one 64-bit word per block of 64 consecutive local pixels (ceil(owned columns * height / 64) words): bit k set = a camera ray of
+ * the block can hit a record of pair k of the flat sweep's paired stream (pairs counted in stream order across the sections).  cull = 0:
+ * every bit of every word set (what APT_CAMERA_CULL=0 gives a renderer).  masks may be NULL; n_strips / n_pairs: always written. */
+int apt_camera_strips(const float* prims /* n_prims*9 */, int32_t n_prims, const int32_t* obj_info /* n_objects*3 */, int32_t n_objects,
+                      const apt_render_cfg* cfg, int32_t cull, uint64_t* masks, int32_t masks_cap, int32_t* n_strips, int32_t* n_pairs);
 
 /* ---- BVH build, reference layout: the drop-in for the pybind11 module itself.
  * Replaces bvh_cpp.bvh_build(obj_array, obj_info, world_min, world_max) (tracer/bvh/bvh.cpp:274-296), whose four flat arrays

@@ -1,0 +1,203 @@
+"""Strip lists of the camera rays (csrc/flat_build.cpp camera_strips, reached through apt_camera_strips) checked on the CPU.
+For every bundled scene small enough for the flat records and a set of film shapes, the camera rays of every block of 64 local pixels -
+the pyramid's corners and edge midpoints, and a few thousand jittered rays with the jitter pushed to its bounds - are generated with
+generate_body's float32 arithmetic (stages.hpp) and tested against the FULL record stream with a numpy float32 restatement of
+flat_closest1's per-record test (traverse.hpp), the reciprocal also moved by one ulp either way.  Every record that is a valid candidate
+of some ray (inside, t > 1e-4) - which includes every winner and every runner-up - has to sit in a pair of the block's list."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from adapt_amd import _lib
+from adapt_amd.scene_pack import make_config
+from conftest import ALL_TAGS
+from test_flat_records import flat_records
+from test_shadow_cull import _fma, sections
+
+FLAT_MAX_PRIMS = 96                     # traverse.hpp APT_FLAT_MAX_PRIMS: scenes up to here get flat records, and with them the traced kernel
+BENCH_BAND_WIDTH = 4                    # bench.py BAND_WIDTH
+
+# (width, height, crop (cx, cy, rx, ry) or None, world_size, rank)
+FILMS = {
+    "512x512": (512, 512, None, 1, 0),
+    "64x64": (64, 64, None, 1, 0),
+    "50x30": (50, 30, None, 1, 0),                           # npix = 1500: not a multiple of 64, and a block spans several columns
+    "96x100": (96, 100, None, 1, 0),                         # height not a multiple of 64: blocks straddle two columns
+    "crop": (128, 128, (70, 40, 30, 20), 1, 0),
+    "world2_rank1": (128, 64, None, 2, 1),
+}
+
+
+def _cfg(prop, film):
+    w, h, crop, world, rank = film
+    rc = make_config(prop, width=w, height=h)
+    cfg = _lib.RenderCfg()
+    cfg.width, cfg.height = w, h
+    if crop:
+        cx, cy, rx, ry = crop
+        cfg.do_crop, cfg.start_x, cfg.end_x, cfg.start_y, cfg.end_y = 1, cx - rx, cx + rx, cy - ry, cy + ry
+    else:
+        cfg.do_crop, cfg.start_x, cfg.end_x, cfg.start_y, cfg.end_y = 0, 0, w, 0, h
+    cfg.cam_r = (C.c_float * 9)(*np.float32(rc.cam_r).reshape(-1).tolist())
+    cfg.cam_t = (C.c_float * 3)(*np.float32(rc.cam_t).tolist())
+    cfg.inv_focal, cfg.half_w, cfg.half_h = float(rc.inv_focal), float(rc.half_w), float(rc.half_h)
+    cfg.band_width, cfg.rank, cfg.world_size = (BENCH_BAND_WIDTH if world > 1 else w), rank, world
+    return cfg
+
+
+def camera_strips(prims, obj_info, cfg, cull=1):
+    lib = _lib.load()
+    prims = np.ascontiguousarray(prims, np.float32).reshape(-1, 9); obj_info = np.ascontiguousarray(obj_info, np.int32).reshape(-1, 3)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)); ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    ns, npairs = C.c_int32(0), C.c_int32(0)
+    args = (fp(prims), prims.shape[0], ip(obj_info), obj_info.shape[0], C.byref(cfg), cull)
+    _lib.check(lib.apt_camera_strips(*args, None, 0, C.byref(ns), C.byref(npairs)), "apt_camera_strips", lib)
+    masks = np.zeros(ns.value, np.uint64)
+    _lib.check(lib.apt_camera_strips(*args, masks.ctypes.data_as(C.POINTER(C.c_uint64)), masks.size, C.byref(ns), C.byref(npairs)), "apt_camera_strips", lib)
+    return masks, npairs.value
+
+
+def local_pixels(cfg):
+    """local pixel -> (column i, row j): stages.hpp local_to_global"""
+    cols = [x for x in range(cfg.width) if (x // cfg.band_width) % cfg.world_size == cfg.rank]
+    lp = np.arange(len(cols) * cfg.height)
+    lc, j = lp // cfg.height, lp % cfg.height
+    i = (lc // cfg.band_width * cfg.world_size + cfg.rank) * cfg.band_width + lc % cfg.band_width
+    assert sorted(set(i.tolist())) == cols
+    return i.astype(np.int64), j.astype(np.int64)
+
+
+def pair_of_record(counts):
+    """record (stream order) -> its pair in flat_closest1's order: pairs are formed inside a section, an odd tail stands alone"""
+    n = [counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6]]
+    out, base = [], 0
+    for cnt in n:
+        out += [base + k // 2 for k in range(cnt)]
+        base += (cnt + 1) // 2
+    return np.array(out, np.int64), base
+
+
+def camera_dirs(cfg, i, j, vx, vy):
+    """generate_body's direction, operation for operation in float32"""
+    f = np.float32
+    R = np.array(list(cfg.cam_r), np.float32).reshape(3, 3)
+    x = ((f(cfg.half_w) + vx.astype(f)).astype(f) - i.astype(f)).astype(f) * f(cfg.inv_focal)
+    y = ((j.astype(f) - f(cfg.half_h)).astype(f) - vy.astype(f)).astype(f) * f(cfg.inv_focal)
+    z = np.ones_like(x)
+    d = np.stack([((R[a, 0] * x + R[a, 1] * y).astype(f) + R[a, 2] * z).astype(f) for a in range(3)], 1)
+    n2 = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).astype(f) + d[:, 2] * d[:, 2]).astype(f)
+    inv = (f(1) / np.sqrt(n2).astype(f)).astype(f)
+    return (d * inv[:, None]).astype(f)
+
+
+def valid_candidates(rec, sec, o, d):
+    """flat_candidate()'s `inside && t > 1e-4` of flat_closest1's test of one record, float32 as the kernel; the reciprocal as computed
+    and one ulp to either side: -> bool per ray (any of the three)"""
+    f = np.float32
+    r = rec.astype(f)
+    out = np.zeros(d.shape[0], bool)
+    with np.errstate(all="ignore"):
+        if sec == 3:                                         # spheres: flat_loop's test
+            s = (r[0:3] - o).astype(f)
+            cn2 = ((s[0] * s[0] + s[1] * s[1]).astype(f) + s[2] * s[2]).astype(f)
+            proj = ((d[:, 0] * s[0] + d[:, 1] * s[1]).astype(f) + d[:, 2] * s[2]).astype(f)
+            c2ray = (cn2 - (proj * proj).astype(f)).astype(f)
+            cut = np.sqrt((r[3] - c2ray).astype(f)).astype(f)
+            t = (proj + np.where(cn2 > f(r[3] + f(1e-4)), -cut, cut)).astype(f)
+            return (c2ray < r[3]) & (t > f(1e-4))
+        s = (o - r[0:3]).astype(f)
+        s = np.broadcast_to(s, d.shape)
+        t_o = _fma(r[9], s[:, 0], _fma(r[10], s[:, 1], r[11] * s[:, 2]))
+        t_d = _fma(r[9], d[:, 0], _fma(r[10], d[:, 1], (r[11] * d[:, 2]).astype(f)))
+        inv0 = (f(1) / t_d).astype(f)
+        for inv in (inv0, np.nextafter(inv0, f(np.inf)), np.nextafter(inv0, f(-np.inf))):
+            t = (-t_o * inv).astype(f)
+            p = [_fma(t, d[:, k], s[:, k]) for k in range(3)]
+            u = _fma(r[3], p[0], _fma(r[4], p[1], (r[5] * p[2]).astype(f)))
+            v = _fma(r[6], p[0], _fma(r[7], p[1], (r[8] * p[2]).astype(f)))
+            if sec == 0: inside = np.maximum(np.abs((u - f(0.5)).astype(f)), np.abs((v - f(0.5)).astype(f))) <= f(0.5)
+            elif sec == 2: inside = np.minimum(np.minimum(u, v), ((f(1) - u).astype(f) - v).astype(f)) >= 0
+            else:
+                e1 = _fma(r[12], u, _fma(r[13], v, r[14])); e2 = _fma(r[15], u, _fma(r[16], v, r[17]))
+                inside = np.minimum(np.minimum(u, v), np.minimum(e1, e2)) >= 0
+            out |= inside & (t > f(1e-4))
+    return out
+
+
+N_JITTER = 2048                         # jittered rays per block, besides the 8 corner / edge-midpoint rays
+_EDGE = np.float32([0.0, 1.0, 1.0 - 2.0 ** -24, 2.0 ** -24, 1e-4, 1.0 - 1e-4, 0.5])      # the jitter's bounds (the stratified one can round up to 1.0), and the centre
+
+
+def block_rays(cfg, i, j, blocks, rs):
+    """rays of the given blocks: -> block index per ray (into `blocks`), directions"""
+    npix = i.size
+    bi, pi, vx, vy = [], [], [], []
+    for k, b in enumerate(blocks):
+        lp = np.arange(64 * b, min(npix, 64 * b + 64))
+        ii, jj = i[lp], j[lp]
+        # corners and edge midpoints of the rectangle the block's pixels span (x = half_w + vx - i, y = j - half_h - vy)
+        for (ci, cvx) in ((ii.min(), 1.0), (ii.max(), 0.0), (None, 0.5)):
+            for (cj, cvy) in ((jj.min(), 1.0), (jj.max(), 0.0), (None, 0.5)):
+                if ci is None and cj is None: continue
+                c_i = ii[len(ii) // 2] if ci is None else ci; c_j = jj[len(jj) // 2] if cj is None else cj
+                bi.append(k); pi.append((c_i, c_j)); vx.append(cvx); vy.append(cvy)
+        pick = lp[rs.randint(0, lp.size, size=N_JITTER)]
+        a, c = rs.uniform(size=(2, N_JITTER)).astype(np.float32)
+        pa, pc = rs.randint(0, 3, size=(2, N_JITTER))            # a third of the rays: jitter on a bound, in x / in y independently
+        a = np.where(pa == 0, _EDGE[rs.randint(0, _EDGE.size, size=N_JITTER)], a); c = np.where(pc == 0, _EDGE[rs.randint(0, _EDGE.size, size=N_JITTER)], c)
+        bi += [k] * N_JITTER; pi += list(zip(i[pick].tolist(), j[pick].tolist())); vx += a.tolist(); vy += c.tolist()
+    pi = np.array(pi, np.int64)
+    return np.array(bi, np.int64), camera_dirs(cfg, pi[:, 0], pi[:, 1], np.float32(vx), np.float32(vy))
+
+
+def flat_tags(flat):
+    return [t for t in ALL_TAGS if flat(t).prims.reshape(-1, 9).shape[0] <= FLAT_MAX_PRIMS]
+
+
+@pytest.mark.parametrize("film", list(FILMS))
+def test_every_candidate_of_a_strip_is_in_its_list(film, flat, parsed):
+    tags = flat_tags(flat)
+    assert "cbox" in tags
+    n_culled = 0
+    for tag in tags:
+        fs = flat(tag)
+        prims = fs.prims.reshape(-1, 9)
+        cfg = _cfg(parsed(tag)[3], FILMS[film])
+        counts, stream, _ = flat_records(prims, fs.obj_info)
+        masks, n_pairs = camera_strips(prims, fs.obj_info, cfg)
+        pair, n_pairs_py = pair_of_record(counts)
+        assert n_pairs == n_pairs_py <= 64
+        i, j = local_pixels(cfg)
+        assert masks.size == (i.size + 63) // 64
+        if n_pairs < 64: assert not (masks >> np.uint64(n_pairs)).any()      # no bit beyond the stream's pairs
+        recs = sections(counts)
+        o = np.array(list(cfg.cam_t), np.float32)
+        rs = np.random.RandomState(11)
+        n_valid = 0
+        for first in range(0, masks.size, 256):
+            blocks = np.arange(first, min(masks.size, first + 256))
+            bi, d = block_rays(cfg, i, j, blocks, rs)
+            m = masks[blocks][bi]
+            for R, (sec, at) in enumerate(recs):
+                ok = valid_candidates(stream[at:at + (12, 18, 12, 4)[sec]], sec, o, d)
+                listed = ((m >> np.uint64(pair[R])) & np.uint64(1)).astype(bool)
+                n_valid += int(ok.sum())
+                bad = ok & ~listed
+                assert not bad.any(), (tag, film, R, int(bad.sum()), int(blocks[bi[np.flatnonzero(bad)[0]]]))
+        assert n_valid > 0, tag                             # the restatement sees hits at all
+        n_culled += int(sum(n_pairs - bin(int(x)).count("1") for x in masks))
+        # the cull off: every strip takes the full stream
+        masks0, _ = camera_strips(prims, fs.obj_info, cfg, cull=0)
+        assert masks0.size == masks.size and (masks0 == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
+    assert n_culled > 0
+
+
+def test_the_cornell_box_strips_are_shorter_than_the_stream(flat, parsed):
+    fs = flat("cbox")
+    cfg = _cfg(parsed("cbox")[3], FILMS["512x512"])
+    masks, n_pairs = camera_strips(fs.prims, fs.obj_info, cfg)
+    lengths = np.array([bin(int(x)).count("1") for x in masks])
+    assert masks.size == 4096 and n_pairs == 9
+    assert lengths.mean() < n_pairs, lengths.mean()
+    print(f"cbox 512x512: {lengths.mean():.2f} of {n_pairs} pairs per strip on average (min {lengths.min()}, max {lengths.max()})")
