@@ -602,20 +602,28 @@ static int pack_media(const apt_scene_desc* d, apt_scene* s) {
     return APT_OK;
 }
 // Grid volume of the volumetric tracer (DevVolume stays zero when the scene declares none).
-static int pack_volume(const apt_scene_desc* d, apt_scene* s) {
-    if (!d->vol_i || !d->vol_f || !d->vol_grid || d->vol_i[0] == 0) return APT_OK;
-    const int32_t* vi = d->vol_i; const float* f = d->vol_f;
-    if (vi[0] != 2) return fail(APT_E_INVALID, "apt_scene_create: only RGB grid volumes (type 2) exist upstream");
-    if (vi[1] <= 0 || vi[2] <= 0 || vi[3] <= 0 || vi[4] < -1 || vi[4] > 3) return fail(APT_E_INVALID, "apt_scene_create: bad grid volume shape or phase type");
-    if (!(f[21] > 0.f && f[22] > 0.f && f[23] > 0.f)) return fail(APT_E_INVALID, "apt_scene_create: grid volume majorants must be positive");
-    if (!put("vol_grid", s->vol_grid, d->vol_grid, (size_t)vi[1] * (size_t)vi[2] * (size_t)vi[3] * 3)) return APT_E_HIP;
-    DevVolume& vo = s->dev.vol;
+// The packed description (vol_i[5], vol_f[33]) -> DevVolume, without the grid pointer; refuses what the tracking loops cannot run on (a
+// majorant that is zero, negative, NaN or infinite: inv_maj = 0 leaves `t` where it is and the loops never end).  No device call in it.
+static int fill_volume(DevVolume& vo, const int32_t* vi, const float* f, const char* who) {
+    if (vi[0] != 2) return fail(APT_E_INVALID, std::string(who) + ": only RGB grid volumes (type 2) exist upstream");
+    if (vi[1] <= 0 || vi[2] <= 0 || vi[3] <= 0 || vi[4] < -1 || vi[4] > 3) return fail(APT_E_INVALID, std::string(who) + ": bad grid volume shape or phase type");
+    if (!(f[21] > 0.f && f[22] > 0.f && f[23] > 0.f)) return fail(APT_E_INVALID, std::string(who) + ": grid volume majorants must be positive");
+    if (!(std::isfinite(f[21]) && std::isfinite(f[22]) && std::isfinite(f[23]))) return fail(APT_E_INVALID, std::string(who) + ": grid volume majorants must be finite");
     vo.type = vi[0]; vo.xres = vi[1]; vo.yres = vi[2]; vo.zres = vi[3]; vo.albedo = mk3(f[0], f[1], f[2]);
     vo.inv_r0 = mk3(f[3], f[4], f[5]); vo.inv_r1 = mk3(f[6], f[7], f[8]); vo.inv_r2 = mk3(f[9], f[10], f[11]);
     vo.trans = mk3(f[12], f[13], f[14]); vo.mini = mk3(f[15], f[16], f[17]); vo.maxi = mk3(f[18], f[19], f[20]);
     vo.majorant = mk3(f[21], f[22], f[23]); vo.pdf = mk3(f[24], f[25], f[26]);
     vo.ph.type = vi[4]; vo.ph.par = mk3(f[27], f[28], f[29]); vo.ph.pdf = mk3(f[30], f[31], f[32]);
+    return APT_OK;
+}
+static int pack_volume(const apt_scene_desc* d, apt_scene* s) {
+    if (!d->vol_i || !d->vol_f || !d->vol_grid || d->vol_i[0] == 0) return APT_OK;
+    const int32_t* vi = d->vol_i;
+    DevVolume vo{};
+    if (int rc = fill_volume(vo, vi, d->vol_f, "apt_scene_create")) return rc;
+    if (!put("vol_grid", s->vol_grid, d->vol_grid, (size_t)vi[1] * (size_t)vi[2] * (size_t)vi[3] * 3)) return APT_E_HIP;
     vo.grid = s->vol_grid.as<float>();
+    s->dev.vol = vo;
     s->has_volume = true;
     return APT_OK;
 }
@@ -1728,6 +1736,30 @@ APT_EXPORT int apt_medium_probe(int32_t device, int32_t n, const int32_t* med_i,
     HIP_TRY(upload(dmed, md)); HIP_TRY(upload(din, in)); HIP_TRY(dout.alloc((size_t)n * 32));
     HIP_TRY(hipMemset(dout.p, 0, (size_t)n * 32));
     hipLaunchKernelGGL(k_medium_probe, dim3((n + 63) / 64), dim3(64), 0, 0, n, dmed.as<DevMedium>(), mode, din.as<float>(), seed, dout.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out8, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+    return APT_OK;
+}
+APT_EXPORT int apt_volume_probe(int32_t device, int32_t n, const int32_t* vol_i, const float* vol_f, const float* vol_grid, int32_t mode,
+                                const float* in10, uint32_t seed, float* out8) {
+    if (n <= 0 || !vol_i || !vol_f || !vol_grid || !in10 || !out8 || mode < 0 || mode > 3) return fail(APT_E_INVALID, "apt_volume_probe: bad argument");
+    DevVolume vo{};
+    if (int rc = fill_volume(vo, vol_i, vol_f, "apt_volume_probe")) return rc;
+    if (mode == 1) for (int k = 0; k < n; k++) {
+        const float ch = in10[10 * (size_t)k + 6];
+        if (!(ch == 0.f || ch == 1.f || ch == 2.f)) return fail(APT_E_INVALID, "apt_volume_probe: channel must be 0, 1 or 2");
+    }
+    int ndev = 0;
+    if (int rc = count_device(&ndev)) return rc;
+    if (device < 0 || device >= ndev) return fail(APT_E_INVALID, "apt_volume_probe: device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    std::vector<float> grid(vol_grid, vol_grid + (size_t)vo.xres * (size_t)vo.yres * (size_t)vo.zres * 3), in(in10, in10 + (size_t)n * 10);
+    DevBuf dgrid, din, dout;
+    HIP_TRY(upload(dgrid, grid)); HIP_TRY(upload(din, in)); HIP_TRY(dout.alloc((size_t)n * 32));
+    HIP_TRY(hipMemset(dout.p, 0, (size_t)n * 32));
+    vo.grid = dgrid.as<float>();
+    hipLaunchKernelGGL(k_volume_probe, dim3((n + 63) / 64), dim3(64), 0, 0, n, vo, mode, din.as<float>(), seed, dout.as<float>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out8, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));

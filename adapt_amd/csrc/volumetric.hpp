@@ -695,3 +695,26 @@ __global__ void k_medium_probe(int n, const DevMedium* med, int mode, const floa
         y[1] = tr.x; y[2] = tr.y; y[3] = tr.z;
     }
 }
+// Grid-volume functions on explicit inputs (parity probe): one volume, 10 input floats and 8 output floats per test; RNG as above.
+// mode 0 vol_intersect      in = o, d, -, max_t           out = hit, near_t, far_t
+// mode 1 vol_density        in = index, u, channel        out = the voxel value
+// mode 2 vol_sample_mfp     in = o, d, thp, max_t         out = hit_t, beta rgb, draws
+// mode 3 vol_transmittance  in = o, d, thp, max_t         out = transmittance rgb, draws
+__global__ void k_volume_probe(int n, DevVolume vo, int mode, const float* in10, uint32_t seed, float* out8) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const float* x = in10 + 10 * k; float* y = out8 + 8 * k;
+    Philox r; rng_init(r, (uint32_t)k, seed, 1u, 0u);
+    if (mode == 0) {
+        float near_t, far_t; const bool hit = vol_intersect(vo, ld3(x), ld3(x + 3), x[9], near_t, far_t);
+        y[0] = hit ? 1.f : 0.f; y[1] = near_t; y[2] = far_t;
+    } else if (mode == 1) {
+        y[0] = vol_density(vo, ld3(x), ld3(x + 3), (int)x[6]);
+    } else if (mode == 2) {
+        f3 beta; const float hit_t = vol_sample_mfp(vo, ld3(x), ld3(x + 3), ld3(x + 6), x[9], r, beta);
+        y[0] = hit_t; y[1] = beta.x; y[2] = beta.y; y[3] = beta.z; y[4] = (float)r.draw;
+    } else {
+        const f3 tr = vol_transmittance(vo, ld3(x), ld3(x + 3), ld3(x + 6), x[9], r);
+        y[0] = tr.x; y[1] = tr.y; y[2] = tr.z; y[3] = (float)r.draw;
+    }
+}

@@ -42,7 +42,7 @@ from . import _lib
 from .scene_pack import FlatScene, RenderConfig, make_config, pack_scene
 from .tiles import TilePlan
 
-__all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error"]
+__all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error"]
 
 ADAPTIVE_DEFAULTS = {"min_spp": 64, "step": 32}
 
@@ -114,6 +114,20 @@ def medium_probe(med_i, med_f, mode: int, in7, seed: int = 0, device: int = 0) -
     x = np.ascontiguousarray(in7, np.float32).reshape(-1, 7)
     out = np.zeros((x.shape[0], 8), np.float32)
     _lib.check(lib.apt_medium_probe(int(device), x.shape[0], _ip(mi), _fp(mf), int(mode), _fp(x), int(seed) & 0xffffffff, _fp(out)), "apt_medium_probe")
+    return out
+
+
+def volume_probe(vol_i, vol_f, vol_grid, mode: int, in10, seed: int = 0, device: int = 0) -> np.ndarray:
+    """apt_volume_probe: one packed grid volume (FlatScene.vol_i / vol_f / vol_grid) and 10 inputs per test -> (n, 8); mode 0 intersect,
+    1 density lookup, 2 sample_mfp (delta tracking), 3 transmittance (ratio tracking)"""
+    lib = _lib.load()
+    vi = np.ascontiguousarray(vol_i, np.int32).reshape(-1); vf = np.ascontiguousarray(vol_f, np.float32).reshape(-1)
+    vg = np.ascontiguousarray(vol_grid, np.float32).reshape(-1)
+    if vi.shape[0] != 5 or vf.shape[0] != 33 or vg.shape[0] != 3 * max(int(vi[1]), 0) * max(int(vi[2]), 0) * max(int(vi[3]), 0):
+        raise ValueError("volume_probe: vol_i (5,), vol_f (33,) and a vol_grid of zres * yres * xres * 3 values")
+    x = np.ascontiguousarray(in10, np.float32).reshape(-1, 10)
+    out = np.zeros((x.shape[0], 8), np.float32)
+    _lib.check(lib.apt_volume_probe(int(device), x.shape[0], _ip(vi), _fp(vf), _fp(vg), int(mode), _fp(x), int(seed) & 0xffffffff, _fp(out)), "apt_volume_probe")
     return out
 
 

@@ -242,6 +242,14 @@ int apt_texture_probe(const apt_scene*, int32_t n, const int32_t* map_obj, const
  * mode 2: Medium.eval + transmittance, in = incid xyz, out xyz, depth -> phase value, transmittance rgb.  RNG as above. */
 int apt_medium_probe(int32_t device, int32_t n, const int32_t* med_i, const float* med_f, int32_t mode, const float* in7,
                      uint32_t seed, float* out8);
+/* Grid-volume probe (volumetric tracer; bxdf/volume.py:268-463): one volume, packed as apt_scene_desc carries it (vol_i[5], vol_f[33],
+ * vol_grid), test k uses in10[10k..] and the Philox stream keyed (k, seed), sample 1.  The volume is checked as apt_scene_create checks it.
+ * mode 0: GridVolume.intersect_volume, in = o xyz, d xyz, -, -, -, max_t   -> out8[8k..] = hit, near_t, far_t
+ * mode 1: density_lookup_3d + channel, in = index xyz, u xyz, channel      -> the voxel value (0 outside the grid)
+ * mode 2: GridVolume.sample_mfp,       in = o xyz, d xyz, thp rgb, max_t   -> hit_t (-1: none), beta rgb, draws
+ * mode 3: GridVolume.transmittance,    in = o xyz, d xyz, thp rgb, max_t   -> transmittance rgb, draws */
+int apt_volume_probe(int32_t device, int32_t n, const int32_t* vol_i, const float* vol_f, const float* vol_grid, int32_t mode,
+                     const float* in10, uint32_t seed, float* out8);
 /* Emitter probe: in11[11k..] = source index, hit_pos, normal, ray_d, min_depth;
  * out12[12k..] = sampled pos, intensity (/pdf), pdf, draws, eval_le rgb, solid_angle_pdf; RNG as above. */
 int apt_emitter_probe(const apt_scene*, int32_t n, const float* in11, uint32_t seed, float* out12);

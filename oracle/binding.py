@@ -338,6 +338,22 @@ def medium_probe(med_type, med_f16, mode, vec, key=0, seed=0):
     return out
 
 
+def volume_probe(vol_i, vol_f, vol_grid, mode, in10, key0=0, seed=0):
+    """orc_volume_probe: the grid-volume functions on n rows of 10 floats -> (n, 8); row k draws from the stream (key0 + k, seed).
+    mode 0 intersect -> hit, near_t, far_t; 1 density (index, u, channel) -> value; 2 sample_mfp (o, d, thp, max_t) -> hit_t, beta rgb,
+    draws; 3 transmittance -> rgb, draws"""
+    L = lib()
+    L.orc_volume_probe.argtypes = [i32p, f32p, f32p, C.c_int, C.c_int, f32p, C.c_uint32, C.c_uint32, f32p]
+    L.orc_volume_probe.restype = None
+    vi = np.ascontiguousarray(vol_i, np.int32).reshape(5); vf = np.ascontiguousarray(vol_f, np.float32).reshape(33)
+    vg = np.ascontiguousarray(vol_grid, np.float32).reshape(-1)
+    assert vg.shape[0] == 3 * int(vi[1]) * int(vi[2]) * int(vi[3])
+    x = np.ascontiguousarray(in10, np.float32).reshape(-1, 10)
+    out = np.zeros((x.shape[0], 8), np.float32)
+    L.orc_volume_probe(_ip(vi), _fp(vf), _fp(vg), int(mode), x.shape[0], _fp(x), C.c_uint32(key0), C.c_uint32(seed), _fp(out))
+    return out
+
+
 def transient_max_time(min_time, interval, n_bins) -> np.float32:
     """the window's end as the device stores it: min_time + interval * n_bins in double, rounded to float"""
     return np.float32(float(np.float32(min_time)) + float(np.float32(interval)) * float(n_bins))

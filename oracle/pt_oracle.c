@@ -2291,6 +2291,40 @@ ORC_API void orc_medium_probe(int type, const float f[16], int mode, const float
         st3(out + 1, medium_transmittance(&m, in[6]));
     }
 }
+/* Grid-volume functions on explicit inputs (bxdf/volume.py:268-463), one volume (packed as orc_scene_desc carries it) and n rows of 10
+ * floats; row k draws from the Philox stream (key0 + k, seed), sample 1.  8 output floats per row.
+ * mode 0  intersect_volume   in = o, d, -, max_t       out = hit, near_t, far_t
+ * mode 1  density lookup     in = index, u, channel    out = the voxel value
+ * mode 2  sample_mfp         in = o, d, thp, max_t     out = hit_t, beta rgb, draws
+ * mode 3  transmittance      in = o, d, thp, max_t     out = transmittance rgb, draws */
+ORC_API void orc_volume_probe(const int vol_i[5], const float vol_f[33], const float* vol_grid, int mode, int n, const float* in10,
+                              uint32_t key0, uint32_t seed, float* out8) {
+    scene_t sc; memset(&sc, 0, sizeof(sc));
+    const float* f = vol_f;
+    sc.vol_type = vol_i[0]; sc.vol_res[0] = vol_i[1]; sc.vol_res[1] = vol_i[2]; sc.vol_res[2] = vol_i[3];
+    sc.vol_albedo = LD3(f);
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) sc.vol_inv_T.m[i][j] = f[3 + 3 * i + j];
+    sc.vol_trans = LD3(f + 12); sc.vol_mini = LD3(f + 15); sc.vol_maxi = LD3(f + 18);
+    sc.vol_majorant = LD3(f + 21); sc.vol_pdf = LD3(f + 24);
+    sc.vol_grid = (float*)vol_grid;                  /* read only */
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int k = 0; k < n; k++) {
+        const float* x = in10 + 10 * (size_t)k; float* y = out8 + 8 * (size_t)k;
+        memset(y, 0, 8 * sizeof(float));
+        rng_t r; unit_rng(&r, NULL, 0, key0 + (uint32_t)k, seed);
+        if (mode == 0) {
+            float near_t, far_t; int hit = vol_intersect(&sc, LD3(x), LD3(x + 3), x[9], &near_t, &far_t);
+            y[0] = (float)hit; y[1] = near_t; y[2] = far_t;
+        } else if (mode == 1) {
+            y[0] = rgb_select(vol_density_lookup(&sc, LD3(x), LD3(x + 3)), (int)x[6]);
+        } else if (mode == 2) {
+            v3 beta; float hit_t = vol_sample_mfp(&sc, LD3(x), LD3(x + 3), LD3(x + 6), x[9], &r, &beta);
+            y[0] = hit_t; st3(y + 1, beta); y[4] = (float)r.draw;
+        } else {
+            st3(y, vol_transmittance(&sc, LD3(x), LD3(x + 3), LD3(x + 6), x[9], &r)); y[3] = (float)r.draw;
+        }
+    }
+}
 ORC_API void orc_rotation_between(const float a[3], const float b[3], float R_out[9]) {
     m3 R; rotation_between(LD3(a), LD3(b), &R);
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R_out[3 * i + j] = R.m[i][j];

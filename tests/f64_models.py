@@ -671,6 +671,174 @@ def medium_mfp(med_type, mf, max_depth, words):
     return np.array([1.0, t] + [x * s / p for x, s in zip(tr, mf[1:4])]), mg
 
 
+# ------------------------------------------------------------------ grid volume (bxdf/volume.py:268-463 via volumetric.hpp vol_*)
+# Every decision of the grid-volume functions reports its distance to the branch in units of the float32 error of its operand, derived
+# from the operations on the chain (each rounding <= U relative; device logf and glibc logf within 2 U of the true logarithm): Margin.m
+# is the smallest such ratio a row met.  A float32 evaluation can take the other branch only where the ratio is below 1; the tests keep
+# rows above VOLUME_SAFE = 2 (the second unit is for the model's own operands, which are the float32 inputs taken exactly, against
+# intermediate values the float32 code has already rounded).
+VOLUME_SAFE = 2.0
+
+
+def _at_err(mg, x, thr, err):
+    """distance of x to thr in units of err (the float32 error bound of x - thr); an exact comparison (err = 0) has no knife edge"""
+    if math.isfinite(x) and math.isfinite(thr) and err > 0:
+        mg.m = min(mg.m, abs(x - thr) / err)
+
+
+def _nan_max(a):
+    return math.nan if any(math.isnan(x) for x in a) else max(a)
+
+
+def _nan_min(a):
+    return math.nan if any(math.isnan(x) for x in a) else min(a)
+
+
+def _fmax(a, b):                       # fmaxf / fminf: the non-NaN operand
+    return b if math.isnan(a) else (a if math.isnan(b) else max(a, b))
+
+
+def _fmin(a, b):
+    return b if math.isnan(a) else (a if math.isnan(b) else min(a, b))
+
+
+def volume_intersect(vf, row, mg=None):
+    """vol_intersect: (hit, near_t, far_t) and (float32 error bound of near_t, of far_t).  1 / d is +-inf for a zero component; an
+    origin on a face plane then gives 0 * inf = NaN for that face, which the element-wise min / max of the two slab distances drops: the
+    axis contributes the other face's +-inf to BOTH near and far, and the ray misses (upstream's behaviour, pinned by the fixture).
+    Vector.max() / .min() propagate a NaN that survives (both faces NaN), fmaxf / fminf with 0 / max_t drop it."""
+    vf = [float(x) for x in vf]
+    o, d, max_t = [float(x) for x in row[0:3]], [float(x) for x in row[3:6]], float(row[9])
+    lo_t, hi_t = [], []
+    for a in range(3):
+        inv = math.copysign(math.inf, d[a]) if d[a] == 0 else 1.0 / d[a]
+        t1 = (vf[15 + a] - o[a]) * inv if not (vf[15 + a] - o[a] == 0 and math.isinf(inv)) else math.nan
+        t2 = (vf[18 + a] - o[a]) * inv if not (vf[18 + a] - o[a] == 0 and math.isinf(inv)) else math.nan
+        lo_t.append(_fmin(t1, t2)); hi_t.append(_fmax(t1, t2))       # ti.min / ti.max of two vectors: element-wise fminf / fmaxf, which drop a NaN
+    near = _fmax(0.0, _nan_max(lo_t)) + float(F32(1e-5))
+    far = _fmin(max_t, _nan_min(hi_t)) - float(F32(1e-5))
+    # chain of a slab distance: subtraction, reciprocal, product (3 roundings, the subtraction's relative to its operands), then + 1e-5
+    mag = max(abs(o[a]) + max(abs(vf[15 + a]), abs(vf[18 + a])) for a in range(3))
+    slope = max((1.0 / abs(d[a]) if d[a] != 0 else 0.0) for a in range(3))
+    e_near = U * (mag * slope + 3.0 * abs(near)) if math.isfinite(near) else 0.0
+    e_far = U * (mag * slope + 3.0 * abs(far)) if math.isfinite(far) else 0.0
+    if mg is not None:
+        _at_err(mg, near, far, e_near + e_far)
+        _at_err(mg, far, 0.0, e_far)
+    hit = bool(near < far and far > 0.0)
+    return hit, near, far, e_near, e_far
+
+
+def volume_density(vi, grid, index, u, ch, mg=None, e_index=(0.0, 0.0, 0.0)):
+    """vol_density: the voxel floor(index + (u - 0.5)) of channel ch, 0 outside the grid.  u - 0.5 is exact in float32; the sum rounds
+    once (U |index|) on top of the index's own error e_index."""
+    res = (int(vi[1]), int(vi[2]), int(vi[3]))
+    cell = []
+    for a in range(3):
+        x = float(index[a]) + (float(u[a]) - 0.5)
+        if mg is not None:
+            _at_err(mg, x, round(x), e_index[a] + U * (abs(float(index[a])) + 0.5))
+        cell.append(math.floor(x))
+    if all(0 <= cell[a] < res[a] for a in range(3)):
+        return float(grid[cell[2], cell[1], cell[0], ch])
+    return 0.0
+
+
+def _volume_setup(vf, row, words, mg):
+    """the part sample_mfp and transmittance share: intersection, local ray, channel pick.  -> None (no hit) or a dict"""
+    vf = [float(x) for x in vf]
+    hit, near, far, e_near, e_far = volume_intersect(vf, row, mg)
+    if not hit:
+        return None
+    o, d, thp = [float(x) for x in row[0:3]], [float(x) for x in row[3:6]], [float(x) for x in row[6:9]]
+    rel = [o[a] - vf[12 + a] for a in range(3)]
+    ol = [sum(vf[3 + 3 * i + j] * rel[j] for j in range(3)) for i in range(3)]
+    dl = [sum(vf[3 + 3 * i + j] * d[j] for j in range(3)) for i in range(3)]
+    # local ray: one subtraction (relative to its operands), three products and two sums per component
+    e_ol = [U * sum(abs(vf[3 + 3 * i + j]) * (4.0 * abs(rel[j]) + abs(o[j]) + abs(vf[12 + j])) for j in range(3)) for i in range(3)]
+    e_dl = [U * 3.0 * sum(abs(vf[3 + 3 * i + j] * d[j]) for j in range(3)) for i in range(3)]
+    pdfs = [thp[c] * vf[24 + c] for c in range(3)]
+    tot = (pdfs[0] + pdfs[1]) + pdfs[2]
+    pdfs = [p / tot if tot != 0 else math.nan for p in pdfs]
+    val = _rf(words[0])
+    if math.isnan(pdfs[0]):
+        ch = 2                                           # every comparison with NaN is false (all-zero throughput)
+    else:
+        _at_err(mg, val, pdfs[0], 4.0 * U * pdfs[0]); _at_err(mg, val, pdfs[0] + pdfs[1], 5.0 * U * (pdfs[0] + pdfs[1]))
+        ch = 0 if val <= pdfs[0] else (1 if val <= pdfs[0] + pdfs[1] else 2)
+    return dict(vf=vf, near=near, far=far, e_near=e_near, e_far=e_far, ol=ol, dl=dl, e_ol=e_ol, e_dl=e_dl, ch=ch, pdf=pdfs[ch],
+                inv_maj=1.0 / vf[21 + ch])
+
+
+def _volume_step(st, t, e_t, word):
+    """t -= logf(1 - xi) * inv_maj: the new t and its error bound (logf 2 U, the reciprocal majorant and the product 1.5 U, the sum U |t|)"""
+    step = -math.log(1.0 - _rf(word)) * st["inv_maj"]
+    t = t + step
+    return t, e_t + U * (3.5 * step + abs(t))
+
+
+def _volume_lookup(st, vi, grid, t, e_t, words3, mg):
+    idx = [st["ol"][a] + st["dl"][a] * t for a in range(3)]
+    e_idx = [st["e_ol"][a] + st["e_dl"][a] * abs(t) + abs(st["dl"][a]) * e_t + U * (abs(st["ol"][a]) + 2.0 * abs(st["dl"][a] * t)) for a in range(3)]
+    return volume_density(vi, grid, idx, [_rf(w) for w in words3], st["ch"], mg, e_idx)
+
+
+def volume_sample_mfp(vi, vf, grid, row, words):
+    """apt_volume_probe mode 2 from its draws: (hit_t, beta rgb, draws) and the margin of every decision.  `words` is a callable
+    k -> the k-th 32-bit word of the row's Philox stream."""
+    mg = Margin()
+    st = _volume_setup(vf, row, [words(0)], mg)
+    if st is None:
+        return np.array([-1.0, 1.0, 1.0, 1.0, 0.0]), mg
+    k = 1
+    t, e_t = _volume_step(st, st["near"], st["e_near"], words(k)); k += 1
+    Tr, hit_t = 1.0, -1.0
+    while True:
+        _at_err(mg, t, st["far"], e_t + st["e_far"])
+        if not t < st["far"]:
+            break
+        n_t = _volume_lookup(st, vi, grid, t, e_t, [words(k), words(k + 1), words(k + 2)], mg); k += 3
+        p = n_t * st["inv_maj"]
+        xi = _rf(words(k)); k += 1
+        _at_err(mg, xi, p, 1.5 * U * p)
+        if xi < p:
+            Tr *= st["vf"][st["ch"]]; hit_t = t
+            break
+        t, e_t = _volume_step(st, t, e_t, words(k)); k += 1
+    beta = [0.0, 0.0, 0.0]
+    beta[st["ch"]] = Tr / st["pdf"]
+    return np.array([hit_t] + beta + [float(k)]), mg
+
+
+def volume_transmittance(vi, vf, grid, row, words):
+    """apt_volume_probe mode 3 from its draws: (transmittance rgb, draws) and the margin of every decision"""
+    mg = Margin()
+    st = _volume_setup(vf, row, [words(0)], mg)
+    if st is None:
+        return np.array([1.0, 1.0, 1.0, 0.0]), mg
+    k = 1
+    Tr, e_tr, t, e_t = 1.0, 0.0, st["near"], st["e_near"]
+    while True:
+        t, e_t = _volume_step(st, t, e_t, words(k)); k += 1
+        _at_err(mg, t, st["far"], e_t + st["e_far"])
+        if t >= st["far"]:
+            break
+        n_t = _volume_lookup(st, vi, grid, t, e_t, [words(k), words(k + 1), words(k + 2)], mg); k += 3
+        f = max(0.0, 1.0 - n_t * st["inv_maj"])
+        Tr, e_tr = Tr * f, e_tr * f + U * Tr * (1.5 * n_t * st["inv_maj"] + 1.0 + f)      # the factor's roundings (reciprocal, product, 1 - x) and the product's
+        _at_err(mg, Tr, float(F32(0.1)), e_tr)
+        if Tr < float(F32(0.1)):
+            xi = _rf(words(k)); k += 1
+            _at_err(mg, xi, Tr, e_tr)
+            if xi >= Tr:
+                Tr = 0.0
+                break
+            Tr, e_tr = 1.0, 0.0
+    out = [0.0, 0.0, 0.0]
+    out[st["ch"]] = Tr / st["pdf"]
+    return np.array(out + [float(k)]), mg
+
+
 # ------------------------------------------------------------------ emitters (emitters/abtract_source.py)
 def emitter_eval_le(src_type, intensity, inci_dir, normal):
     """(le rgb, margin): an area light's radiance toward a ray that arrives at its front side"""

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The committed fixtures are what the committed generator produces (needs the reference tree, see refenv.py).
 
-    python tests/golden/gen/check_freshness.py [section ...]        (default: func; `textured` adds the whole-kernel section, ~30 s)
+    python tests/golden/gen/check_freshness.py [section ...]        (default: func, which includes media and volfunc; `textured` adds the
+                                                                     whole-kernel section, ~30 s)
 
 `gen_goldens.py --only <section>` draws every fixture's random inputs from a stream seeded by the fixture's file name, so a section
 re-run must reproduce the committed arrays bit for bit.  Arrays are compared, not file bytes: the zip container stores timestamps.

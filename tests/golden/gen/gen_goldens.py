@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz from the reference's own source (authoring container only).
 
-    python tests/golden/gen/gen_goldens.py [--only parse|func|media|image|features|textured|refscenes|vpt|volgrid|bvh|microfacet]
+    python tests/golden/gen/gen_goldens.py [--only parse|func|media|volfunc|image|features|textured|refscenes|vpt|volgrid|bvh|microfacet]
 
 Every fixture is produced by calling UNMODIFIED reference code (/root/reference) under the
 float32 stand-in `taichi` package in shim/ (third-party taichi==1.6.0 is not installable
@@ -367,6 +367,55 @@ def gen_media_functions():
                         mfp_in=np.float32(mfp_in), mfp_out=np.float32(mfp_out), scat_in=np.float32(sc_in), scat_out=np.float32(sc_out),
                         eval_in=np.float32(ev_in), eval_out=np.float32(ev_out))
     print(f"media_functions: {len(objs)} media, {len(mfp_in)} vectors each; medium events {int(np.float32(mfp_out)[:, 0].sum())}")
+
+
+def gen_volume_functions():
+    """GridVolume.intersect_volume / density_lookup_3d / sample_mfp / transmittance (bxdf/volume.py:268-463) on the rows of
+    tests/volume_cases.py (the first VOLFUNC_PER rows of every volume x stratum), the reference object built from the packed arrays the
+    device and the oracle take.  Philox stream: key = row index within its array, seeds 881 (sample_mfp) / 882 (transmittance)."""
+    sys.path.insert(0, os.path.join(refenv.REPO, "tests"))
+    import volume_cases as VC
+    from taichi.math import mat3
+    from bxdf.volume import GridVolume
+    from bxdf.phase import PhaseFunction
+    vols, groups, dens = VC.same_stream_rows(VC.VOLFUNC_PER, VC.VOLFUNC_DENSITY)
+    names = list(vols)
+    objs, grids = {}, {}
+    for name, (vi, vf, vg) in vols.items():
+        grids[name] = ti.Vector.field(3, float, (int(vi[3]), int(vi[2]), int(vi[1])))
+        grids[name].from_numpy(vg)
+        objs[name] = GridVolume(_type=int(vi[0]), albedo=vec3(vf[0:3]), inv_T=mat3(vf[3:12].reshape(3, 3)), trans=vec3(vf[12:15]),
+                                mini=vec3(vf[15:18]), maxi=vec3(vf[18:21]), max_idxs=ti.math.ivec3([int(vi[1]) - 1, int(vi[2]) - 1, int(vi[3]) - 1]),
+                                majorant=vec3(vf[21:24]), pdf=vec3(vf[24:27]),
+                                ph=PhaseFunction(_type=int(vi[4]), par=vec3(vf[27:30]), pdf=vec3(vf[30:33])))
+    ray_vol, ray_in, isect, mfp, trn = [], [], [], [], []
+    for name, stratum, rows in groups:
+        gv, grid = objs[name], grids[name]
+        for x in rows:
+            k = len(ray_in)
+            o, d, thp, max_t = vec3(x[0:3]), vec3(x[3:6]), vec3(x[6:9]), np.float32(x[9])
+            with np.errstate(all="ignore"):
+                nf = gv.intersect_volume(o, d, max_t)
+                isect.append([float(bool(nf[0] < nf[1] and nf[1] > 0)), nf[0], nf[1]])
+                ti.RNG.set_philox(k, VC.SEED_MFP, 1)
+                r = gv.sample_mfp(grid, o, d, thp, max_t)
+                mfp.append([r[3], r[0], r[1], r[2], ti.RNG.draw])
+                ti.RNG.set_philox(k, VC.SEED_TR, 1)
+                t = gv.transmittance(grid, o, d, thp, max_t)
+                trn.append([t[0], t[1], t[2], ti.RNG.draw])
+            ray_vol.append(names.index(name)); ray_in.append(x)
+    den_vol, den_in, den_out = [], [], []
+    for name, rows in dens:
+        for x in rows:
+            v = objs[name].density_lookup_3d(grids[name], vec3(x[0:3]), vec3(x[3:6]))
+            den_vol.append(names.index(name)); den_in.append(x); den_out.append(v[int(x[6])])
+    arrays = dict(ray_vol=np.int32(ray_vol), ray_in=np.float32(ray_in), isect_out=np.float32(isect), mfp_out=np.float32(mfp),
+                  tr_out=np.float32(trn), den_vol=np.int32(den_vol), den_in=np.float32(den_in), den_out=np.float32(den_out))
+    for j, name in enumerate(names):
+        arrays[f"vol{j}_i"], arrays[f"vol{j}_f"], arrays[f"vol{j}_grid"] = vols[name]
+    np.savez_compressed(os.path.join(OUT, "volume_functions.npz"), **arrays)
+    print(f"volume_functions: {len(names)} volumes, {len(ray_in)} rays ({int(np.float32(isect)[:, 0].sum())} hit, "
+          f"{int((np.float32(mfp)[:, 0] > 0).sum())} collisions, most draws {int(np.float32(trn)[:, 3].max())}), {len(den_in)} lookups")
 
 
 def gen_scene(scene_dir, xml, tag, w, h, spp, overrides, seed=0, n_rays=192):
@@ -764,6 +813,8 @@ if __name__ == "__main__":
             gen_bvhref("bunnies3", sdir, xml, 800, 800, 0, 600, synth_check=synth4, extra_rays=disputed_rays_95k, brute_rays=-1, store_scene=False)
     if a.only in ("all", "func", "media"):
         gen_media_functions()
+    if a.only in ("all", "func", "volfunc"):
+        gen_volume_functions()
     if a.only in ("all", "vpt"):
         # the reference's volumetric scenes (homogeneous media) through its own VolumeRenderer.render
         for sdir, xml, ov in (("vpt", "cbox.xml", {}), ("vpt", "balls.xml", {"max_bounce": 12}), ("vpt", "volbox.xml", {})):

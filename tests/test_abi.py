@@ -140,6 +140,36 @@ def test_bad_arguments_are_rejected():
     assert b"apt_transient_bin_probe" in lib.apt_last_error()
 
 
+def test_volume_probe_checks_its_arguments_before_the_device():
+    """apt_volume_probe refuses a bad call before it looks for a device, with the checks apt_scene_create makes of a grid volume (one
+    shared helper fills DevVolume for both): type, shape, phase type, and majorants that are not positive or not finite.  A majorant
+    of +inf passes `> 0` and would make the tracking loops' step 1 / majorant zero."""
+    lib = _lib.load()
+    fp, ip = (lambda a: a.ctypes.data_as(_lib.f32p)), (lambda a: a.ctypes.data_as(_lib.i32p))
+    vi, vf, vg = np.int32([2, 2, 2, 2, 0]), np.zeros(33, np.float32), np.zeros(2 * 2 * 2 * 3, np.float32)
+    vf[21:24] = 1
+    x, out = np.zeros(10, np.float32), np.zeros(8, np.float32)
+    x[3:6] = (0, 0, 1)
+
+    def call(vi=vi, vf=vf, n=1, mode=0, grid=vg, rows=x):
+        return lib.apt_volume_probe(0, n, ip(vi), fp(vf), fp(grid) if grid is not None else None, mode, fp(rows), 0, fp(out))
+
+    for kw in ({"n": 0}, {"mode": -1}, {"mode": 4}, {"grid": None}):
+        assert call(**kw) == -1 and b"apt_volume_probe: bad argument" in lib.apt_last_error(), kw
+    bad = [(0, 1, b"only RGB grid volumes"), (1, 0, b"bad grid volume shape"), (3, -2, b"bad grid volume shape"), (4, 4, b"bad grid volume shape or phase type")]
+    for slot, value, message in bad:
+        w = vi.copy(); w[slot] = value
+        assert call(vi=w) == -1 and message in lib.apt_last_error() and b"apt_volume_probe: " in lib.apt_last_error(), (slot, value)
+    for slot in (21, 22, 23):
+        for value, message in ((0.0, b"must be positive"), (-1.0, b"must be positive"), (np.nan, b"must be positive"), (np.inf, b"majorants must be finite")):
+            w = vf.copy(); w[slot] = value
+            assert call(vf=w) == -1 and message in lib.apt_last_error(), (slot, value, lib.apt_last_error())
+    rows = x.copy(); rows[6] = 3
+    assert call(mode=1, rows=rows) == -1 and b"channel must be 0, 1 or 2" in lib.apt_last_error()
+    if not has_gpu():                               # a good call gets as far as the device check
+        assert call() == -2 and b"no HIP device" in lib.apt_last_error()
+
+
 def build_bvh(fs):
     lib = _lib.load()
     prims, info = np.ascontiguousarray(fs.prims), np.ascontiguousarray(fs.obj_info)
