@@ -45,15 +45,16 @@ typedef void (*shade_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int)
 #define APT_FUSED_FN(...) nullptr         // rays traced by the shade kernel: a product-build path (it rides on the flat sweep's records)
 #endif
 typedef void (*shade_traced_fn)(DevScene, Params, Queues, Counters*, int, int);
+typedef void (*shade_cam_fn)(DevScene, Params, Queues, Counters*, const unsigned long long*);
 typedef void (*shade_tr_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int, TransQ);
-struct ShadeVariant { int bm, sm; shade_fn fn; const char* name; shade_traced_fn traced; shade_tr_fn transient; };      // traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced: flat sweep, one light sample per vertex); transient: fn's time-resolved twin (k_shade_tr)
+struct ShadeVariant { int bm, sm; shade_fn fn; const char* name; shade_traced_fn traced; shade_tr_fn transient; shade_cam_fn traced_cam; };      // traced_cam: traced's camera-fed twin (k_shade_traced_cam: bounce 0 of a steady full-film batch, no k_generate_trace in front of it); traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced: flat sweep, one light sample per vertex); transient: fn's time-resolved twin (k_shade_tr)
 static const ShadeVariant kShadeVariants[] = {
-    {0x002, 0x01, k_shade<0x002, 0x01>, "lambertian/point", APT_FUSED_FN(k_shade_traced_lean<0x002, 0x01>), k_shade_tr<0x002, 0x01>},
-    {0x003, 0x03, k_shade<0x003, 0x03>, "phong+lambertian/point+area", APT_FUSED_FN(k_shade_traced<0x003, 0x03>), k_shade_tr<0x003, 0x03>},
-    {0x107, 0x03, k_shade<0x107, 0x03>, "phong+lambertian+mirror+glass/point+area", APT_FUSED_FN(k_shade_traced<0x107, 0x03>), k_shade_tr<0x107, 0x03>},
-    {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL>, "all models", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL>},
+    {0x002, 0x01, k_shade<0x002, 0x01>, "lambertian/point", APT_FUSED_FN(k_shade_traced_lean<0x002, 0x01>), k_shade_tr<0x002, 0x01>, APT_FUSED_FN(k_shade_traced_lean_cam<0x002, 0x01>)},
+    {0x003, 0x03, k_shade<0x003, 0x03>, "phong+lambertian/point+area", APT_FUSED_FN(k_shade_traced<0x003, 0x03>), k_shade_tr<0x003, 0x03>, APT_FUSED_FN(k_shade_traced_cam<0x003, 0x03>)},
+    {0x107, 0x03, k_shade<0x107, 0x03>, "phong+lambertian+mirror+glass/point+area", APT_FUSED_FN(k_shade_traced<0x107, 0x03>), k_shade_tr<0x107, 0x03>, APT_FUSED_FN(k_shade_traced_cam<0x107, 0x03>)},
+    {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL>, "all models", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL>, APT_FUSED_FN(k_shade_traced_cam<APT_BX_ALL, APT_SRC_ALL>)},
 };
-static const ShadeVariant kTexturedShade = {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL, 1>, "all models + image textures", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL, 1>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL, 1>};
+static const ShadeVariant kTexturedShade = {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL, 1>, "all models + image textures", APT_FUSED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL, 1>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL, 1>, APT_FUSED_FN(k_shade_traced_cam<APT_BX_ALL, APT_SRC_ALL, 1>)};
 // Material classes for sorted shading: (class mask) x (emitter mask: point+area | all)
 // A kernel's register allocation is the maximum over the models it contains, so the classes are as fine as the models'
 // footprints differ: Lambertian alone runs at 4 waves per SIMD, together with Blinn-Phong (three double pows) at 2-3.
@@ -199,6 +200,7 @@ struct apt_renderer {
     hipStream_t stream() const { return lanes[0].stream; }
     DevBuf accum, scratch, pix_key;
     DevBuf cam_strips;            // rays traced in place: per 64 local pixels, the record pairs a camera ray can hit (flat_build.cpp camera_strips)
+    int camera_fuse = 0;          // rays traced in place: 1 = the camera vertex is shaded by the kernel that traces the camera ray (k_shade_traced_cam; steady full-film renders with max_bounce >= 1, APT_CAMERA_FUSE=0 switches it off)
     Counters host_counters{};
     int grid_small = 0, grid_trace = 0, nq = APT_MAX_NQ;
     const ShadeVariant* shade = nullptr;
@@ -849,6 +851,10 @@ static int make_camera_strips(apt_renderer* r) {
         return fail(APT_E_INVALID, "apt_renderer_create: camera strip lists: bad record or film");
     hipError_t e = upload(r->cam_strips, masks);
     if (e != hipSuccess) return fail(APT_E_HIP, std::string("upload camera strip lists: ") + hipGetErrorString(e));
+    // the camera-fed bounce 0 (shade_stage.hpp shade_traced, CAM) wants every slot of the id space to be a live camera ray: an adaptive
+    // round's or a crop window's dead slots would sit as idle lanes through a whole shading row - those keep k_generate_trace's compaction
+    const bool want = !(getenv("APT_CAMERA_FUSE") && atoi(getenv("APT_CAMERA_FUSE")) == 0);
+    r->camera_fuse = (want && !r->adaptive && !r->par.do_crop && r->par.max_bounce >= 1 && r->shade->traced_cam != nullptr) ? 1 : 0;
     return APT_OK;
 }
 
@@ -1336,14 +1342,20 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
         if (p.fused == 2) {
             // rays traced in place (shade_stage.hpp): generate and every bounce are ONE launch each; the rare rays that need the reference-order code
             // are served by the next launch's prologue, the last bounce's deferred light samples by one fix-up launch at the end
-            {
+            const unsigned long long* strips = r->cam_strips.as<unsigned long long>();
+            int cur = 0, b0 = 0;
+            if (r->camera_fuse) {
+                // the camera vertex in one launch (no k_generate_trace, no record of the camera ray), then the ordinary bounce-0 launch for the
+                // handful of camera rays it staged for the reference-order code: that launch's prologue resolves them, its loop shades them
+                { LaunchTimer t(r, 2, st); hipLaunchKernelGGL(r->shade->traced_cam, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips); }
+                { LaunchTimer t(r, 2, st); hipLaunchKernelGGL(r->shade->traced, dim3(r->grid_fix), dim3(BLOCK), 0, st, sc, p, q, cnt, 0, 0); }
+                cur = 1; b0 = 1;
+            } else {
                 LaunchTimer t(r, 0, st);
-                const unsigned long long* strips = r->cam_strips.as<unsigned long long>();
                 if (r->adaptive) hipLaunchKernelGGL(k_generate_trace_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, (const uint8_t*)r->aq.active, strips);
                 else hipLaunchKernelGGL(k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips);
             }
-            int cur = 0;
-            for (int b = 0; b < p.max_bounce; b++) {
+            for (int b = b0; b < p.max_bounce; b++) {
                 { LaunchTimer t(r, 2, st); hipLaunchKernelGGL(r->shade->traced, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, b); }      // (the records are Queues::tr[cur]: one queue for the scene)
                 cur ^= 1;
             }
@@ -1819,6 +1831,11 @@ APT_EXPORT int apt_measure_sclk_mhz(int32_t device, float* mhz) {
     if (r.empty()) return fail(APT_E_STATE, "apt_measure_sclk_mhz: the wall clock did not advance");
     std::nth_element(r.begin(), r.begin() + r.size() / 2, r.end());
     *mhz = (float)r[r.size() / 2];
+    return APT_OK;
+}
+APT_EXPORT int apt_renderer_camera_fused(const apt_renderer* r, int32_t* fused) {
+    if (!r || !fused) return fail(APT_E_INVALID, "apt_renderer_camera_fused: null argument");
+    *fused = r->camera_fuse;
     return APT_OK;
 }
 APT_EXPORT int apt_renderer_info(const apt_renderer* r, int32_t* spp_batch, int32_t* n_subqueues, int64_t* queue_bytes, int32_t* lds_bytes, const char** shade_variant, int32_t* trace_mode) {

@@ -300,9 +300,19 @@ APT_D void tally_flush(const ShadeTally& t, const uint32_t* s_draws, Counters* c
 // here (one ray per lane against two records per packed instruction, traverse.hpp flat_any1), after the continuation has been sampled and
 // traced, when little else is live.  The rare rays whose answer needs the reference-order sweep (flat_needs_cull) still leave as
 // shadow-queue entries, counted by n_fix_sh[cur], and are served by the next launch's prologue.
-template <int BM, int SM, int TEX>
-APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
+//
+// CAM, the camera-fed form (steady full-film batches): bounce 0 with no queue in front of it.  Every slot of the id space is
+// a live camera ray then, so a row MAKES its 64 records instead of loading them - pixel, jitter, direction, the slot's radiance zeroed, the
+// sweep against the strip's records, all as k_generate_trace does them (stages.hpp camera_ray_dir / camera_strip_mask) - and shades the hits
+// in the same registers: the camera ray's 64-byte record is neither written nor read back, and k_generate_trace's launch is gone.  Row `pos`
+// of sub-queue q is id-space wave (pos / 64) * nq + q, the mapping of generate_body, so a wave holds 64 consecutive local pixels and the
+// strip-mask rule holds as it stands; the row count is a closed form, no counter is read.  Camera rays the sweep cannot settle are staged
+// exactly as k_generate_trace stages them (top of the sub-queue's region of tr[0], n_tr[0][ncls]); the ordinary bounce-0 launch that
+// follows resolves them in its prologue and shades that handful.  This kernel runs no prologue: nothing is listed before it.
+template <int BM, int SM, int TEX, bool CAM = false>
+APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, const unsigned long long* strips = nullptr) {
     const ShadeArgs3* A_ = args_fresh(A0);                      // scene, parameters, queues: read through the kernel-argument segment, re-fetched per phase (APT_ARGS_PHASE)
+    const int cur = CAM ? 0 : cur_, bounce = CAM ? 0 : bounce_;
     const int nxt = cur ^ 1;
     const SubLoop sl = sub_loop((A_->p).nq);
     const uint32_t qbase = (uint32_t)sl.q * (A_->p).subcap, sh_qbase = (uint32_t)sl.q * (A_->q).sh_subcap;
@@ -315,7 +325,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
     __shared__ uint32_t s_draws[BLOCK / 64];
     if (lane_id() == 0) s_draws[threadIdx.x >> 6] = 0;
     ShadeTally tl = {0u, 0u, 0u};
-    uint32_t t_traced = 0, t_lit = 0, t_extend = 0;
+    uint32_t t_traced = 0, t_lit = 0, t_extend = 0, t_samples = 0;
 #ifdef APT_NEAR_STATS
     uint32_t t_near = 0;
 #endif
@@ -323,11 +333,19 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
     // with its queue record instead of a round trip after it.  (Rounds 2-4 prefetched the Lambertian kernel's whole record: thirteen
     // registers.  Without them the kernel allocates 91 VGPRs - five waves per SIMD instead of four - and three render lanes gain 6 %:
     // C2 4 310 -> 4 560 Msamples/s on the same box.)
-    constexpr bool PFP = TEX == 0;
+    constexpr bool PFP = TEX == 0 && !CAM;                    // (a camera-fed row knows its primitive when it has traced its ray: nothing to request ahead)
     static_assert(APT_FLAT_MAX_PRIMS < (int)TR_NO_PRIM, "the packed record keeps the hit primitive in 8 bits");
     const float4* trA = (A_->q).tr[cur][0]; const float4* trB = (A_->q).tr[cur][1]; const float4* trC = (A_->q).tr[cur][2]; const float4* trD = (A_->q).tr[cur][3];
-    fix_prologue((A_->sc), (A_->p), (A_->q), cnt, cur, sl.q, bounce);       // before the queue's length is read: the prologue may append to it
-    const uint32_t n = __hip_atomic_load(&cnt->n_tr[bounce % 3][0][sl.q * CNT_PAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t n, cam_total = 0;
+    if constexpr (CAM) {
+        // rows of this sub-queue: 64 per id-space wave w with w % nq == q
+        cam_total = (uint32_t)(A_->p).npix * (uint32_t)(A_->p).spp_batch;
+        const uint32_t n_waves = (cam_total + 63u) / 64u, nq_ = (uint32_t)(A_->p).nq;
+        n = n_waves > (uint32_t)sl.q ? ((n_waves - (uint32_t)sl.q + nq_ - 1u) / nq_) * 64u : 0u;
+    } else {
+        fix_prologue((A_->sc), (A_->p), (A_->q), cnt, cur, sl.q, bounce);       // before the queue's length is read: the prologue may append to it
+        n = __hip_atomic_load(&cnt->n_tr[bounce % 3][0][sl.q * CNT_PAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     uint32_t pf_pm = 0;                                        // (the packed word: primitive, draw index, specular flag)
     auto prefetch_prim = [&](uint32_t b) { pf_pm = ldq(reinterpret_cast<const uint32_t*>(trB), ((qbase + min(b + threadIdx.x, n - 1u)) << 4) + 12u); };      // (lanes past the end re-read the last entry: never used)
     if (PFP && n > 0) prefetch_prim(sl.first);
@@ -341,10 +359,54 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
         Vertex vx; vertex_reset(vx);
         Philox rng; rng_init(rng, 0u, 0u, 0u, 0u);
         f3 Lc = splat3(0.f);                                   // the radiance the path has gathered so far (camera rays carry none: nothing is read at bounce 0)
-        const bool entry = alive;
+        bool entry = alive;
         float ray_pdf = 1.f;
-        if (alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & 2) ray_pdf = dd.w; }
-        if (alive) {
+        if constexpr (CAM) {
+            // ---- the camera vertex: the ray is made, swept against its strip's records and, where that settles it, shaded right here
+            const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)sl.q;
+            const uint32_t id_ = w * 64u + lane_id();
+            const bool valid = alive && id_ < cam_total;
+            f3 dir = mk3(0.f, 0.f, 1.f);
+            uint32_t draws = 0;
+            if (valid) {
+                const uint32_t lp = id_ % (uint32_t)(A_->p).npix, s = id_ / (uint32_t)(A_->p).npix;
+                int i, j; local_to_global((A_->p), lp, i, j);
+                for (int pl = 0; pl < (A_->p).l_planes; pl++) stL((A_->q).L, (A_->p).cap, (id_ << 2) | (uint32_t)pl, splat3(0.f));
+                dir = camera_ray_dir((A_->p), i, j, s, draws);
+                vx.id = (s << (A_->p).pix_bits) | lp;
+            }
+            if (draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
+            const f3 cam_o = mk3((A_->p).cam_t[0], (A_->p).cam_t[1], (A_->p).cam_t[2]);
+            float c_t = 0.f; int c_run = -1, c_idx = -1;
+            if (__any(valid)) c_idx = flat_closest1<true>((A_->sc).flat, cam_o, dir, 1e7f, c_t, c_run, camera_strip_mask((A_->p), strips, w));
+            const bool c_defer = valid && (c_run >= 0 || flat_needs_cull((A_->sc).flat, dir));
+            HitRec hr; hr.t = 1e7f; hr.prim = -1; hr.u = hr.v = 0.f;
+            int hit_cls = 0;
+            if (valid && !c_defer && c_idx >= 0) flat_resolve((A_->sc).flat, c_idx, c_t, cam_o, dir, hr, hit_cls);
+            { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
+            if (__any(c_defer)) {                             // left to the reference-order code: staged for the bounce-0 launch behind this one, as k_generate_trace stages it
+                const int ncls = (A_->q).tr_ncls;
+                const uint32_t dpos = wave_append(c_defer, &cnt->n_tr[0][ncls][sl.q * CNT_PAD]);
+                if (c_defer) {
+                    const uint32_t slot = (A_->q).tr_stage_top ? qbase + (A_->p).subcap - 1u - dpos : (uint32_t)ncls * (A_->p).cap + qbase + dpos, so = slot << 4;
+                    stq((A_->q).tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, hr.t));
+                    stq((A_->q).tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(hr.prim, draws, false))));
+                    stq((A_->q).tr[0][2], so, make_float4(1.f, 1.f, 1.f, __uint_as_float(vx.id)));
+                    stq((A_->q).tr[0][3], so, make_float4(0.f, 0.f, 0.f, 1.f));
+                    if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = hr.u; uv_.y = hr.v; stq((A_->q).tr_uv[0], slot << 3, uv_); }
+                }
+            }
+            entry = valid && !c_defer;
+            alive = entry && hr.prim >= 0;                    // nothing hit: the path ends where it began, nothing gathered
+            if (alive) {
+                vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
+                f3 rec_kd; float2 uv; uv.x = hr.u; uv.y = hr.v;
+                build_hit((A_->sc), hr.prim, hr.t, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+                alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0);
+            }
+        }
+        if (!CAM && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & 2) ray_pdf = dd.w; }
+        if (!CAM && alive) {
             const float4 a = ldq(trA, idx << 4), b_ = ldq(trB, idx << 4), c = ldq(trC, idx << 4);
             vx.o = mk3(a.x, a.y, a.z); vx.d = mk3(b_.x, b_.y, b_.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = __float_as_uint(c.w);
             const uint32_t pm = PFP ? cu_pm : __float_as_uint(b_.w);
@@ -448,6 +510,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur, int bounce) {
     }
     flush_uniform(t_traced, &cnt->stats[sl.q][ST_SHADOW_TRACED]); flush_uniform(t_lit, &cnt->stats[sl.q][ST_LIT]);
     flush_uniform(t_extend, &cnt->stats[sl.q][ST_EXTEND]);
+    if (CAM) flush_uniform(t_samples, &cnt->stats[sl.q][ST_SAMPLES]);
     tally_flush(tl, s_draws, cnt, sl.q);
 #ifdef APT_NEAR_STATS
     flush_uniform(t_near, &cnt->stats[sl.q][14]);
@@ -611,6 +674,18 @@ __global__ void __launch_bounds__(BLOCK) k_shade_traced(DevScene sc, Params p, Q
 template <int BM, int SM>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_WAVES, APT_TRACED_WAVES))) k_shade_traced_lean(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) {
     shade_traced<BM, SM, 0>(kernel_args3(), cnt, cur, bounce);
+}
+// ... and their camera-fed twins (shade_traced, CAM): bounce 0 of a steady full-film batch, in place of k_generate_trace + the first launch above
+template <int BM, int SM, int TEX = 0>
+__global__ void __launch_bounds__(BLOCK) k_shade_traced_cam(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) {
+    shade_traced<BM, SM, TEX, true>(kernel_args3(), cnt, 0, 0, strips);
+}
+#ifndef APT_TRACED_CAM_WAVES
+#define APT_TRACED_CAM_WAVES 7
+#endif
+template <int BM, int SM>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_CAM_WAVES, APT_TRACED_CAM_WAVES))) k_shade_traced_lean_cam(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) {
+    shade_traced<BM, SM, 0, true>(kernel_args3(), cnt, 0, 0, strips);
 }
 #endif
 

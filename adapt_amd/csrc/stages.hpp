@@ -395,6 +395,39 @@ APT_D SubLoop sub_loop(int nq, int nt = BLOCK) {
 #endif
 #define TRACE_NT(MODE) ((MODE) == 2 ? APT_TILE_NT : BLOCK)
 
+// The camera ray of sample `s` of the batch through global pixel (i, j): the jitter comes from the pixel's own stream (`draws` numbers of
+// it), the direction leaves in world space.  One function for k_generate* and the camera-fed shade kernels (shade_stage.hpp), so that the
+// two cannot drift.
+APT_D f3 camera_ray_dir(const Params& p, int i, int j, uint32_t s, uint32_t& draws) {
+    int sample_cnt = p.cnt_base + (int)s + 1;        // cnt is incremented before the pixel loop
+    Philox rng; rng_init(rng, (uint32_t)(i * p.H + j), p.seed, (uint32_t)sample_cnt, 0u);
+    float vx = 0.5f, vy = 0.5f;
+    if (p.anti_alias) {
+        if (p.stratified) {
+            int mod_val = pymod(sample_cnt, 16);
+            vx = (float)(mod_val % 4) * 0.25f + rng_float(rng) * 0.25f;
+            vy = (float)(mod_val / 4) * 0.25f + rng_float(rng) * 0.25f;
+        } else {
+            const float eps = 1e-4f, inv_eps = (float)(1 - 1e-4 * 2.);
+            vx = rng_float(rng) * inv_eps + eps;
+            vy = rng_float(rng) * inv_eps + eps;
+        }
+    }
+    f3 cd = mk3((p.half_w + vx - (float)i) * p.inv_focal, ((float)j - p.half_h - vy) * p.inv_focal, 1.f);
+    m33 R;
+    for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) R.m[a][b] = p.cam_r[3 * a + b];
+    draws = rng.draw;
+    return normalize(mul(R, cd));
+}
+// The record pairs the camera rays of id-space wave `w` (ids 64 w .. 64 w + 63: consecutive local pixels modulo npix) can hit: the union of
+// the strip lists of the block of the first pixel, the block of the last before the film's end and - where the wave wraps into the next
+// sample - block 0 (`strips` below).  Wave-uniform: scalar loads.
+APT_D unsigned long long camera_strip_mask(const Params& p, const unsigned long long* strips, uint32_t w) {
+    typedef const __attribute__((address_space(4))) unsigned long long* strip_ptr;
+    const uint32_t lp0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((w * 64u) % (uint32_t)p.npix)), lp1 = lp0 + 63u, last = (uint32_t)p.npix - 1u;
+    return ((strip_ptr)strips)[lp0 >> 6] | ((strip_ptr)strips)[(lp1 < last ? lp1 : last) >> 6] | ((strip_ptr)strips)[lp1 > last ? 0u : (lp0 >> 6)];
+}
+
 // ----------------------------------------------------------------- generate
 // wave w of the id space feeds sub-queue w % nq at position (w / nq) * 64 + lane: dense and
 // atomic-free unless a crop window makes some lanes inactive.
@@ -424,25 +457,7 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
             alive = !p.do_crop || (i >= p.sx && i < p.ex && j >= p.sy && j < p.ey);
             if (ADAPTIVE) alive = alive && active[lp] != 0;
             if (alive) {
-                int sample_cnt = p.cnt_base + (int)s + 1;        // cnt is incremented before the pixel loop
-                Philox rng; rng_init(rng, (uint32_t)(i * p.H + j), p.seed, (uint32_t)sample_cnt, 0u);
-                float vx = 0.5f, vy = 0.5f;
-                if (p.anti_alias) {
-                    if (p.stratified) {
-                        int mod_val = pymod(sample_cnt, 16);
-                        vx = (float)(mod_val % 4) * 0.25f + rng_float(rng) * 0.25f;
-                        vy = (float)(mod_val / 4) * 0.25f + rng_float(rng) * 0.25f;
-                    } else {
-                        const float eps = 1e-4f, inv_eps = (float)(1 - 1e-4 * 2.);
-                        vx = rng_float(rng) * inv_eps + eps;
-                        vy = rng_float(rng) * inv_eps + eps;
-                    }
-                }
-                f3 cd = mk3((p.half_w + vx - (float)i) * p.inv_focal, ((float)j - p.half_h - vy) * p.inv_focal, 1.f);
-                m33 R;
-                for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) R.m[a][b] = p.cam_r[3 * a + b];
-                dir = normalize(mul(R, cd));
-                draws = rng.draw;
+                dir = camera_ray_dir(p, i, j, s, draws);
             }
         }
         uint32_t pos;
@@ -459,9 +474,7 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
             const f3 cam_o = mk3(p.cam_t[0], p.cam_t[1], p.cam_t[2]);
             float tr_t = 0.f; int tr_run = -1, tr_idx = -1;
             if (__any(alive)) {
-                typedef const __attribute__((address_space(4))) unsigned long long* strip_ptr;      // wave-uniform: scalar loads
-                const uint32_t lp0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((w * 64u) % (uint32_t)p.npix)), lp1 = lp0 + 63u, last = (uint32_t)p.npix - 1u;
-                const unsigned long long mask = ((strip_ptr)strips)[lp0 >> 6] | ((strip_ptr)strips)[(lp1 < last ? lp1 : last) >> 6] | ((strip_ptr)strips)[lp1 > last ? 0u : (lp0 >> 6)];
+                const unsigned long long mask = camera_strip_mask(p, strips, w);
                 tr_idx = flat_closest1<true>(sc->flat, cam_o, dir, 1e7f, tr_t, tr_run, mask);
             }
             const bool defer = alive && (tr_run >= 0 || flat_needs_cull(sc->flat, dir));

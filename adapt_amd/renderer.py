@@ -490,6 +490,13 @@ class Renderer:
                 "traversal": {0: "bvh", 1: "sweep", 2: "tile", 3: "flat"}.get(tm.value, str(tm.value)), "arithmetic": self.arithmetic,
                 "sampling": "adaptive" if self.adaptive else "uniform", **({"adaptive": dict(self.adaptive)} if self.adaptive else {})}
 
+    def camera_fused(self) -> bool:
+        """apt_renderer_camera_fused: the camera vertex is shaded by the kernel that traces the camera ray (rays traced in place, steady
+        full-film renders; APT_CAMERA_FUSE=0 at creation switches it off)."""
+        f = C.c_int32(0)
+        _lib.check(self.lib.apt_renderer_camera_fused(self.handle, C.byref(f)), "apt_renderer_camera_fused", self.lib)
+        return bool(f.value)
+
     # ------------------------------------------------------------ checkpoint
     def get_check_point(self) -> dict:
         """Same keys as the reference's pickle (path_tracer.py:181-193)."""

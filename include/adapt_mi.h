@@ -259,6 +259,9 @@ int apt_transient_bin_probe(int32_t device, int32_t n, const float* t, float min
 /* trace_mode: 0 = BVH traversal, 1 = wave-uniform sweep (scenes of <= 96 primitives; env APT_TRAVERSAL=bvh|sweep overrides) */
 int apt_renderer_info(const apt_renderer*, int32_t* spp_batch, int32_t* n_subqueues, int64_t* queue_bytes,
                       int32_t* lds_bytes, const char** shade_variant, int32_t* trace_mode);
+/* Rays traced in place: *fused = 1 when the renderer shades the camera vertex in the kernel that traces the camera ray (steady full-film
+ * renders with max_bounce >= 1; env APT_CAMERA_FUSE=0, read at apt_renderer_create, selects generate + a queue-fed bounce 0), else 0. */
+int apt_renderer_camera_fused(const apt_renderer*, int32_t* fused);
 
 /* Shader clock (MHz) with every CU busy: cycle counter against the 100 MHz wall clock over a full-grid FMA chain (~1 ms).
  * bench.py prices the VALU roofline of the trace kernels with it.  (No reference counterpart.) */
