@@ -9,6 +9,7 @@
 #pragma once
 #include "vec.hpp"
 #include <stdint.h>
+#include <type_traits>
 
 struct Philox {
     uint32_t key0, key1, ctr0;
@@ -58,6 +59,8 @@ APT_HD uint32_t rng_u32(Philox& r) {
 // and the lanes of an unsorted queue sit at unrelated offsets of their streams: 3.4 passes per shade on the Cornell box where two
 // serve every lane (k_shade, point lights, one light sample: 3.03 -> 2.83 ms per 64 spp).  Stages that draw more keep the lazy
 // per-site generation: there the second buffer only costs registers (measured: C3 13.2 -> 14.7 ms with it).
+// Used by the class kernels without area lights (k_shade_group, emitter set point + spot) and, with APT_DRAW_WINDOW=0, by the traced
+// kernels without area lights; those draw from a DrawWindow (below) otherwise, which generates the second block only when it is read.
 APT_HD void rng_open(Philox& r) {
     const uint32_t b = r.draw >> 2;
     philox4x32_10(r.ctr0, b, 0u, 0u, r.key0, r.key1, r.c); r.blk = b;
@@ -65,5 +68,60 @@ APT_HD void rng_open(Philox& r) {
 }
 APT_HD float rng_float(Philox& r) { return (float)(rng_u32(r) >> 8) * (1.0f / 16777216.0f); }
 APT_HD int32_t rng_int(Philox& r) { return (int32_t)rng_u32(r); }
+
+// The draw window: the same stream for a vertex whose draws are all decided when it is opened - the traced kernels without area lights
+// (shade_stage.hpp shade_traced): [roulette] emitter index [emitter index again, on a surface that carries an emitter] direction u1, u2.
+// Three to five words from draw index d0 on, so they lie in block d0 / 4 and, for some offsets only, in the next one.  window_open
+// generates the first block, tests the roulette on its word, generates the second block only if a surviving lane's LAST word lies in it
+// (`any`: the wave's vote - one scalar branch around the pass; on the Cornell box no lane of any wave needs it at bounces 1 and 2), and
+// then rotates the words into the three registers the draw sites read by name: `e` for the emitter index (the index that counts - a
+// second index draw replaces the first, so both sites read the same register), `u[]` for the direction.  The roulette and the second
+// index draw shift the window, not the sites.  After window_open only `draw` is generator state: no key, no counter, no cached block
+// and no generation code behind any draw site (Philox's rng_u32 keeps a lazy ten-round pass at every site, which rng_open's callers never
+// take and the compiler cannot remove).
+#ifndef APT_DRAW_WINDOW
+#define APT_DRAW_WINDOW 1
+#endif
+#ifndef APT_DRAW_WINDOW_CARRY
+#define APT_DRAW_WINDOW_CARRY 1      // the camera-fed kernel keeps the jitter block's last two words for bounce 0 (shade_stage.hpp)
+#endif
+struct DrawWindow {
+    uint32_t draw;       // the path's draw index, advanced by every site as Philox advances it
+    uint32_t e, u[2];
+    uint32_t rr;         // the roulette's word (read inside window_open only; kept for the host test)
+};
+APT_HD void rng_init(DrawWindow& w, uint32_t, uint32_t, uint32_t, uint32_t draw) { w.draw = draw; w.e = w.u[0] = w.u[1] = w.rr = 0u; }
+APT_HD float window_unit(uint32_t w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }
+// The words a surviving vertex consumes run up to index s + 2 of the two blocks (s: the emitter index's position, below).
+APT_HD bool window_spans(uint32_t s) { return s + 2u >= 4u; }
+// roulette: the vertex draws it, and dies when the draw exceeds `mx`;  relight: the emitter index is drawn twice;  c[]: the first block
+// (generated here unless `have_first`: the camera-fed kernel hands over the words the jitter's pass left, only c[d0 & 3 ..] are read).
+// false: the roulette ended the path (one word consumed).
+template <typename Any>
+APT_HD bool window_open(DrawWindow& w, uint32_t key0, uint32_t key1, uint32_t ctr0, uint32_t d0, bool roulette, float mx, bool relight,
+                        uint32_t c[4], bool have_first, Any&& any) {
+    const uint32_t b = d0 >> 2, off = d0 & 3u;
+    if (!have_first) philox4x32_10(ctr0, b, 0u, 0u, key0, key1, c);
+    const uint32_t c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
+    w.draw = d0; w.rr = 0u;
+    bool live = true;
+    if (roulette) {
+        w.rr = (off & 2u) ? ((off & 1u) ? c3 : c2) : ((off & 1u) ? c1 : c0);
+        w.draw = d0 + 1u;
+        live = !(window_unit(w.rr) > mx);
+    }
+    const uint32_t s = off + (roulette ? 1u : 0u) + (relight ? 1u : 0u);      // 0 .. 5
+    uint32_t n[4] = {0u, 0u, 0u, 0u};
+    if (any(live && window_spans(s))) philox4x32_10(ctr0, b + 1u, 0u, 0u, key0, key1, n);
+    // two blocks, eight words W[0 .. 7]; e = W[s], u = W[s + 1], W[s + 2]: a select per bit of s
+    const bool hi = (s & 4u) != 0u, b1 = (s & 2u) != 0u, b0 = (s & 1u) != 0u;
+    const uint32_t x0 = hi ? n[0] : c0, x1 = hi ? n[1] : c1, x2 = hi ? n[2] : c2, x3 = hi ? n[3] : c3;      // (s >= 4: s & 3 <= 1, nothing past x3 is read)
+    const uint32_t y0 = b1 ? x2 : x0, y1 = b1 ? x3 : x1, y2 = b1 ? n[0] : x2, y3 = b1 ? n[1] : x3;
+    w.e = b0 ? y1 : y0; w.u[0] = b0 ? y2 : y1; w.u[1] = b0 ? y3 : y2;
+    return live;
+}
+// the draw sites: the emitter index (either draw of it), then the direction's two floats in order
+APT_HD int32_t rng_int(DrawWindow& w) { w.draw++; return (int32_t)w.e; }
+APT_HD float rng_float(DrawWindow& w) { const uint32_t v = w.u[0]; w.u[0] = w.u[1]; w.draw++; return window_unit(v); }
 // Python-style modulo: the reference's `ti.random(int) % n` is non-negative
 APT_HD int pymod(int a, int n) { int m = a % n; return (m < 0) ? m + n : m; }

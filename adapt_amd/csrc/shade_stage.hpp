@@ -190,8 +190,10 @@ APT_D void vertex_reset(Vertex& vx) {
 // Step 1, after the hit has been built (vx.it, vx.hit_light; rec_kd: the colour in the primitive's record): material and textures, the
 // path's radiance slot and random stream, the emission MIS weight of this hit (the tail of the previous iteration, vanilla_renderer.py:
 // 111-117) and the roulette (vanilla_renderer.py:50-57).  false: the path ends here.
-template <int BM, int SM, int TEX>
-APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, Philox& rng, int prim, f3 rec_kd, uint32_t meta, float ray_pdf, float2 uv, int bounce) {
+// RNG: the vertex's generator (rng.hpp).  A DrawWindow is filled here, once, with every word the vertex will draw (jitter_tail: the camera-fed
+// kernel's words 2 and 3 of block 0, left by the jitter's pass - camera_ray_dir - so that the block is not generated again; else null).
+template <int BM, int SM, int TEX, typename RNG>
+APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, RNG& rng, int prim, f3 rec_kd, uint32_t meta, float ray_pdf, float2 uv, int bounce, const uint32_t* jitter_tail = nullptr) {
     const bool was_spec = (meta >> 24) & 1u;
     if (BM == 0x002) vx.bx.k_d = rec_kd;               // Lambertian-only scenes: type 1, not delta, not a BSDF (vertex_reset), colour from the record
     else vx.bx = ld_bxdf_lane((A_->sc).bxdf + vx.it.obj_id);
@@ -208,21 +210,36 @@ APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, Philox& rng, int prim, 
     const uint32_t lp = vx.id & ((1u << (A_->p).pix_bits) - 1u), s = vx.id >> (A_->p).pix_bits;
     vx.l_off = (s * (uint32_t)(A_->p).npix + lp) << 2;
     vx.draw0 = meta & 0xffffu;
-    rng_init(rng, ((A_->p).world == 1) ? lp : ldq((A_->p).pix_key, lp << 2), (A_->p).seed, (uint32_t)((A_->p).cnt_base + (int)s + 1), vx.draw0);
+    const uint32_t key0 = ((A_->p).world == 1) ? lp : ldq((A_->p).pix_key, lp << 2), ctr0 = (uint32_t)((A_->p).cnt_base + (int)s + 1);
+    rng_init(rng, key0, (A_->p).seed, ctr0, vx.draw0);
     if (bounce > 0 && (A_->p).use_mis) {
         float e_pdf = 0.0f;
         if (vx.hit_light >= 0 && vx.bx.is_delta == 0 && !was_spec) e_pdf = emitter_solid_angle_pdf((A_->sc).src[vx.hit_light], vx.it, vx.d);
         vx.emission_weight = balance(ray_pdf, e_pdf);
     }
-    if (!(SM & 2)) rng_open(rng);                   // no area lights: a shade with one light sample draws at most five numbers (rng.hpp)
-    if ((A_->p).use_rr) {
-        float mx = max3(vx.thr);
-        if (mx < (A_->p).rr_threshold && bounce >= (A_->p).rr_bounce_th) {
-            if (rng_float(rng) > mx) return false;
-            vx.thr = vx.thr * srcp(mx + 1e-7f);
-        }
-    } else if (max3(vx.thr) < 1e-4f) return false;
-    return true;
+    if constexpr (std::is_same<RNG, DrawWindow>::value) {
+        // every draw of this vertex is decided: the roulette by its throughput, a second emitter index by the surface it is on (sample_light)
+        static_assert(BM == 0x002 && !(SM & 2), "a draw window serves [roulette] index [index] u1 u2: Lambertian surfaces, emitters that draw nothing");
+        bool roulette = false; float mx = 0.f;
+        if ((A_->p).use_rr) { mx = max3(vx.thr); roulette = mx < (A_->p).rr_threshold && bounce >= (A_->p).rr_bounce_th; }
+        else if (max3(vx.thr) < 1e-4f) return false;
+        const bool relight = vx.hit_light >= 0 && (A_->sc).n_sources > 1;
+        const bool have_first = jitter_tail != nullptr && (A_->p).anti_alias != 0;      // (wave-uniform; the jitter drew two numbers: this vertex starts at word 2)
+        uint32_t c[4] = {0u, 0u, have_first ? jitter_tail[0] : 0u, have_first ? jitter_tail[1] : 0u};
+        if (!window_open(rng, key0, (A_->p).seed, ctr0, vx.draw0, roulette, mx, relight, c, have_first, [](bool v) { return __any(v) != 0; })) return false;
+        if (roulette) vx.thr = vx.thr * srcp(mx + 1e-7f);
+        return true;
+    } else {
+        if (!(SM & 2)) rng_open(rng);               // no area lights: a shade with one light sample draws at most five numbers (rng.hpp)
+        if ((A_->p).use_rr) {
+            float mx = max3(vx.thr);
+            if (mx < (A_->p).rr_threshold && bounce >= (A_->p).rr_bounce_th) {
+                if (rng_float(rng) > mx) return false;
+                vx.thr = vx.thr * srcp(mx + 1e-7f);
+            }
+        } else if (max3(vx.thr) < 1e-4f) return false;
+        return true;
+    }
 }
 // Step 2, once per light sample (sample_light, path_tracer.py:537-554; vanilla_renderer.py:68-95): `want` - the sample is worth a shadow
 // ray of direction `dir`, length `dist`, carrying `contrib`; `poisoned` - its MIS weight `mis_w` is NaN (the caller stores it: upstream
@@ -230,8 +247,8 @@ APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, Philox& rng, int prim, 
 // at the end - reproduced without tracing).  LANE_SRC: whole-record emitter loads (the class kernels only: in C2's traced kernel their
 // sixteen registers cost the fourth wave, 127 -> 132 VGPRs).
 struct LightSample { bool want, sampled, poisoned; f3 dir, contrib; float dist, mis_w; int src; };      // src: the emitter sampled
-template <int BM, int SM, bool LANE_SRC>
-APT_D LightSample sample_light(const ShadeArgs3* A_, Vertex& vx, Philox& rng, const EmitterGeom& geom, const DevSrc src_only, bool active, bool& break_flag) {
+template <int BM, int SM, bool LANE_SRC, typename R>
+APT_D LightSample sample_light(const ShadeArgs3* A_, Vertex& vx, R& rng, const EmitterGeom& geom, const DevSrc src_only, bool active, bool& break_flag) {
     LightSample ls; ls.want = ls.sampled = ls.poisoned = false; ls.dir = ls.contrib = splat3(0.f); ls.dist = 0.f; ls.mis_w = 1.0f; ls.src = 0;
     if (!active || break_flag) return ls;
     const int ns = (A_->sc).n_sources;                    // wave-uniform: one light needs no modulo
@@ -270,8 +287,8 @@ APT_D LightSample sample_light(const ShadeArgs3* A_, Vertex& vx, Philox& rng, co
 // un-normalised interpolated vertex normal, i.e. of the barycentrics, which the product build's intersectors return to 1e-6 and not
 // to the bit: DESIGN.md section 5 "non-finite pixels".  Re-sampling such a vertex here with the reference's own triangle test was
 // measured: it costs the Lambertian kernel its fourth wave per SIMD, 122 -> 130 / 158 VGPRs inline / as a loop.)
-template <int BM, int SM, typename Gather>
-APT_D f3 emit_and_scatter(const ShadeArgs3* A_, Vertex& vx, Philox& rng, float& new_pdf, bool& is_spec, Gather&& gather) {
+template <int BM, int SM, typename R, typename Gather>
+APT_D f3 emit_and_scatter(const ShadeArgs3* A_, Vertex& vx, R& rng, float& new_pdf, bool& is_spec, Gather&& gather) {
     if ((SM & 2) && vx.hit_light >= 0) {
         const f3 emit_int = emitter_eval_le((A_->sc).src[vx.hit_light], vx.hit_point - vx.o, vx.it.n_s);
         if (!(emit_int.x == 0.f && emit_int.y == 0.f && emit_int.z == 0.f)) gather((emit_int * vx.emission_weight) * vx.thr);
@@ -333,6 +350,9 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
     // with its queue record instead of a round trip after it.  (Rounds 2-4 prefetched the Lambertian kernel's whole record: thirteen
     // registers.  Without them the kernel allocates 91 VGPRs - five waves per SIMD instead of four - and three render lanes gain 6 %:
     // C2 4 310 -> 4 560 Msamples/s on the same box.)
+    // the generator: without area lights a Lambertian vertex's draws are all decided when it is opened, and it reads them from a draw window (rng.hpp)
+    constexpr bool WINDOW = APT_DRAW_WINDOW != 0 && BM == 0x002 && !(SM & 2);
+    typedef typename std::conditional<WINDOW, DrawWindow, Philox>::type Rng;
     constexpr bool PFP = TEX == 0 && !CAM;                    // (a camera-fed row knows its primitive when it has traced its ray: nothing to request ahead)
     static_assert(APT_FLAT_MAX_PRIMS < (int)TR_NO_PRIM, "the packed record keeps the hit primitive in 8 bits");
     const float4* trA = (A_->q).tr[cur][0]; const float4* trB = (A_->q).tr[cur][1]; const float4* trC = (A_->q).tr[cur][2]; const float4* trD = (A_->q).tr[cur][3];
@@ -357,7 +377,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         float4 cu_ra = make_float4(0.f, 0.f, 0.f, 0.f), cu_rb = cu_ra;
         if (PFP) { const int rp = max(tr_prim(cu_pm), 0); cu_ra = (A_->sc).prim_shade[2 * rp]; cu_rb = (A_->sc).prim_shade[2 * rp + 1]; prefetch_prim(base + sl.stride); }
         Vertex vx; vertex_reset(vx);
-        Philox rng; rng_init(rng, 0u, 0u, 0u, 0u);
+        Rng rng; rng_init(rng, 0u, 0u, 0u, 0u);
         f3 Lc = splat3(0.f);                                   // the radiance the path has gathered so far (camera rays carry none: nothing is read at bounce 0)
         bool entry = alive;
         float ray_pdf = 1.f;
@@ -368,11 +388,12 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
             const bool valid = alive && id_ < cam_total;
             f3 dir = mk3(0.f, 0.f, 1.f);
             uint32_t draws = 0;
+            uint32_t jitter_tail[2] = {0u, 0u};
             if (valid) {
                 const uint32_t lp = id_ % (uint32_t)(A_->p).npix, s = id_ / (uint32_t)(A_->p).npix;
                 int i, j; local_to_global((A_->p), lp, i, j);
                 for (int pl = 0; pl < (A_->p).l_planes; pl++) stL((A_->q).L, (A_->p).cap, (id_ << 2) | (uint32_t)pl, splat3(0.f));
-                dir = camera_ray_dir((A_->p), i, j, s, draws);
+                dir = camera_ray_dir((A_->p), i, j, s, draws, (WINDOW && APT_DRAW_WINDOW_CARRY) ? jitter_tail : nullptr);
                 vx.id = (s << (A_->p).pix_bits) | lp;
             }
             if (draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
@@ -392,7 +413,9 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
                     stq((A_->q).tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, hr.t));
                     stq((A_->q).tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(hr.prim, draws, false))));
                     stq((A_->q).tr[0][2], so, make_float4(1.f, 1.f, 1.f, __uint_as_float(vx.id)));
-                    stq((A_->q).tr[0][3], so, make_float4(0.f, 0.f, 0.f, 1.f));
+                    float one = 1.f;
+                    if (WINDOW) asm volatile("" : "+v"(one));      // (made here, in the rare branch: as a constant, (0, 0, 0, 1) is hoisted in front of the row loop, where the draw-window kernel has no four registers for it - 72 VGPRs and a 16-byte spill)
+                    stq((A_->q).tr[0][3], so, make_float4(0.f, 0.f, 0.f, one));
                     if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = hr.u; uv_.y = hr.v; stq((A_->q).tr_uv[0], slot << 3, uv_); }
                 }
             }
@@ -402,7 +425,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
                 vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
                 f3 rec_kd; float2 uv; uv.x = hr.u; uv.y = hr.v;
                 build_hit((A_->sc), hr.prim, hr.t, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
-                alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0);
+                alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0, (WINDOW && APT_DRAW_WINDOW_CARRY) ? jitter_tail : nullptr);
             }
         }
         if (!CAM && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & 2) ray_pdf = dd.w; }

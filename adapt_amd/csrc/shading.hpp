@@ -106,7 +106,8 @@ APT_D f3 polar_dir(float cos_t, float sin_t, float phi) {
     float s, c; apt_sincos(phi, &s, &c);
     return mk3(c * sin_t, cos_t, s * sin_t);
 }
-APT_D f3 sample_cosine_hemisphere(Philox& r, float& pdf) {
+template <typename R>
+APT_D f3 sample_cosine_hemisphere(R& r, float& pdf) {
     float eps = rng_float(r);
     float cos_t = ssqrt(eps), sin_t = ssqrt(1.f - eps);
     float phi = APT_2PI * rng_float(r);
@@ -154,7 +155,8 @@ APT_D f3 lambert_eval(const DevBxdf& b, f3 normal, f3 out) {
     float c = fmaxf(0.f, dot(normal, out));
     return (b.k_d * APT_INV_PI) * c;
 }
-APT_D f3 lambert_sample(const DevBxdf& b, f3 normal, Philox& r, f3& spec, float& pdf) {
+template <typename R>
+APT_D f3 lambert_sample(const DevBxdf& b, f3 normal, R& r, f3& spec, float& pdf) {
     f3 local = sample_cosine_hemisphere(r, pdf);
     f3 out = delocalize(normal, local);
     spec = lambert_eval(b, normal, out);
@@ -456,22 +458,24 @@ APT_D f3 brdf_eval(const DevBxdf& b, const Hit& it, f3 incid, f3 out) {
     }
     return ret;
 }
-template <int BM>
-APT_D f3 brdf_sample(const DevBxdf& b, const Hit& it, f3 incid, Philox& r, f3& spec, float& pdf, bool& is_specular) {
+// R: the generator (rng.hpp: Philox, or the DrawWindow of a kernel whose masks leave only models that draw the direction's two numbers - the
+// branches of absent models are discarded, not compiled, so they need not accept it)
+template <int BM, typename R>
+APT_D f3 brdf_sample(const DevBxdf& b, const Hit& it, f3 incid, R& r, f3& spec, float& pdf, bool& is_specular) {
     f3 dir = mk3(0.f, 1.f, 0.f);
     spec = splat3(1.f); pdf = 1.0f; is_specular = false;
     switch (b.type) {
-        case 0: if (BXHAS(BM, 0)) {
+        case 0: if constexpr (BXHAS(BM, 0)) {
             f3 local = sample_cosine_hemisphere(r, pdf);
             dir = delocalize(it.n_s, local);
             spec = blinn_phong_eval<BM>(b, it, incid, dir);
         } break;
-        case 1: case 6: if (BXHAS(BM, 1) || BXHAS(BM, 6)) dir = lambert_sample(b, it.n_s, r, spec, pdf); break;
-        case 2: if (BXHAS(BM, 2)) { dir = reflect_in(incid, it.n_s); spec = b.k_d; pdf = 1.0f; } break;
-        case 7: if (BXHAS(BM, 7)) dir = thin_coat_sample(b, it, incid, r, spec, pdf, is_specular); break;
-        case 4: if (BXHAS(BM, 4)) dir = mod_phong_sample(b, it, incid, r, spec, pdf); break;
-        case 5: if (BXHAS(BM, 5)) dir = fresnel_blend_sample(b, it, incid, r, spec, pdf); break;
-        case 3: if (BXHAS(BM, 3)) dir = microfacet_sample(b, it, incid, r, spec, pdf); break;
+        case 1: case 6: if constexpr (BXHAS(BM, 1) || BXHAS(BM, 6)) dir = lambert_sample(b, it.n_s, r, spec, pdf); break;
+        case 2: if constexpr (BXHAS(BM, 2)) { dir = reflect_in(incid, it.n_s); spec = b.k_d; pdf = 1.0f; } break;
+        case 7: if constexpr (BXHAS(BM, 7)) dir = thin_coat_sample(b, it, incid, r, spec, pdf, is_specular); break;
+        case 4: if constexpr (BXHAS(BM, 4)) dir = mod_phong_sample(b, it, incid, r, spec, pdf); break;
+        case 5: if constexpr (BXHAS(BM, 5)) dir = fresnel_blend_sample(b, it, incid, r, spec, pdf); break;
+        case 3: if constexpr (BXHAS(BM, 3)) dir = microfacet_sample(b, it, incid, r, spec, pdf); break;
         default: break;
     }
     if (!(dot(dir, it.n_g) > 0.f)) spec = splat3(0.f);
@@ -628,12 +632,14 @@ APT_D float bsdf_pdf(const DevBxdf& b, const Hit& it, f3 outdir, f3 incid, float
 APT_D void flip_if_two_sided(Hit& it, f3 incid, int two_sides) {
     if (two_sides && dot(incid, it.n_s) > 0.f) { it.n_s = -it.n_s; it.n_g = -it.n_g; }
 }
-template <int BM>
-APT_D f3 surface_sample(const DevBxdf& b, Hit& it, f3 incid, float world_ior, int two_sides, Philox& r, f3& spec, float& pdf, bool& is_specular) {
+template <int BM, typename R>
+APT_D f3 surface_sample(const DevBxdf& b, Hit& it, f3 incid, float world_ior, int two_sides, R& r, f3& spec, float& pdf, bool& is_specular) {
     if (!(BM & 0x700) || !b.is_bsdf) { flip_if_two_sided(it, incid, two_sides); return brdf_sample<BM>(b, it, incid, r, spec, pdf, is_specular); }
-    spec = splat3(0.f); pdf = 0.f; is_specular = false;
-    if (BXHAS(BM, 8) && b.type == 0) return glass_sample(b, it, incid, world_ior, r, spec, pdf);
-    if (BXHAS(BM, 9) && b.type == 1) return lambert_trans_sample(b, it, incid, world_ior, r, spec, pdf, is_specular);
+    if constexpr ((BM & 0x700) != 0) {
+        spec = splat3(0.f); pdf = 0.f; is_specular = false;
+        if (BXHAS(BM, 8) && b.type == 0) return glass_sample(b, it, incid, world_ior, r, spec, pdf);
+        if (BXHAS(BM, 9) && b.type == 1) return lambert_trans_sample(b, it, incid, world_ior, r, spec, pdf, is_specular);
+    }
     return splat3(0.f);
 }
 template <int BM>
@@ -659,15 +665,15 @@ APT_D f3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
 
 // NEE sample: returns the point on the emitter; `inten` is already divided by the
 // area->solid-angle pdf for area emitters (abtract_source.py:129-132)
-template <int SM>
-APT_D f3 emitter_sample_hit(const DevSrc& s, const EmitterGeom& g, f3 hit_pos, Philox& r, f3& inten, float& pdf) {
+template <int SM, typename R>
+APT_D f3 emitter_sample_hit(const DevSrc& s, const EmitterGeom& g, f3 hit_pos, R& r, f3& inten, float& pdf) {
     inten = s.intensity;
     f3 pos = s.pos;
     pdf = 1.0f;
     if (BXHAS(SM, 0) && s.type == 0) {
         f3 x = hit_pos - pos;
         inten = inten * fminf(srcp(fmaxf(norm2(x), 1e-5f)), 1.0f);
-    } else if (BXHAS(SM, 1) && s.type == 1) {
+    } else if (BXHAS(SM, 1) && s.type == 1) { if constexpr (BXHAS(SM, 1)) {      // (the only emitter that draws)
         pdf = s.inv_area;
         f3 normal;
         if (s.prim_count < 0) {
@@ -693,7 +699,7 @@ APT_D f3 emitter_sample_hit(const DevSrc& s, const EmitterGeom& g, f3 hit_pos, P
             pdf *= sdiv(norm2(diff), dl);
             inten = (pdf > 0.0f) ? fdiv3(inten, pdf) : splat3(0.f);
         }
-    } else if (BXHAS(SM, 2) && s.type == 2) {
+    } } else if (BXHAS(SM, 2) && s.type == 2) {
         f3 to_hit = hit_pos - pos;
         float depth = fmaxf(fnorm(to_hit), 1e-5f);
         to_hit = fdiv3(to_hit, depth);

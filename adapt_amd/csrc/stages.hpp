@@ -397,8 +397,9 @@ APT_D SubLoop sub_loop(int nq, int nt = BLOCK) {
 
 // The camera ray of sample `s` of the batch through global pixel (i, j): the jitter comes from the pixel's own stream (`draws` numbers of
 // it), the direction leaves in world space.  One function for k_generate* and the camera-fed shade kernels (shade_stage.hpp), so that the
-// two cannot drift.
-APT_D f3 camera_ray_dir(const Params& p, int i, int j, uint32_t s, uint32_t& draws) {
+// two cannot drift.  tail (camera-fed kernels with a draw window): words 2 and 3 of the block the jitter was drawn from - where bounce 0's
+// draws begin - so that the block is not generated a second time; meaningful with anti-aliasing only (no jitter, no pass).
+APT_D f3 camera_ray_dir(const Params& p, int i, int j, uint32_t s, uint32_t& draws, uint32_t* tail = nullptr) {
     int sample_cnt = p.cnt_base + (int)s + 1;        // cnt is incremented before the pixel loop
     Philox rng; rng_init(rng, (uint32_t)(i * p.H + j), p.seed, (uint32_t)sample_cnt, 0u);
     float vx = 0.5f, vy = 0.5f;
@@ -417,6 +418,7 @@ APT_D f3 camera_ray_dir(const Params& p, int i, int j, uint32_t s, uint32_t& dra
     m33 R;
     for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) R.m[a][b] = p.cam_r[3 * a + b];
     draws = rng.draw;
+    if (tail) { tail[0] = rng.c[2]; tail[1] = rng.c[3]; }
     return normalize(mul(R, cd));
 }
 // The record pairs the camera rays of id-space wave `w` (ids 64 w .. 64 w + 63: consecutive local pixels modulo npix) can hit: the union of
