@@ -2,7 +2,10 @@
 """The committed fixtures are what the committed generator produces (needs the reference tree, see refenv.py).
 
     python tests/golden/gen/check_freshness.py [section ...]        (default: func, which includes media and volfunc; `textured` adds the
-                                                                     whole-kernel section, ~30 s)
+                                                                     whole-kernel section, ~30 s; `settings` the sensor-settings
+                                                                     matrix, tests/golden/settings_matrix.npz: 66 whole-kernel runs
+                                                                     of the reference, measured 560 s on 8 cores - optional, never
+                                                                     part of the default)
 
 `gen_goldens.py --only <section>` draws every fixture's random inputs from a stream seeded by the fixture's file name, so a section
 re-run must reproduce the committed arrays bit for bit.  Arrays are compared, not file bytes: the zip container stores timestamps.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz from the reference's own source (authoring container only).
 
-    python tests/golden/gen/gen_goldens.py [--only parse|func|media|volfunc|image|features|textured|refscenes|vpt|volgrid|bvh|microfacet]
+    python tests/golden/gen/gen_goldens.py [--only parse|func|media|volfunc|image|features|textured|refscenes|vpt|volgrid|bvh|microfacet|settings]
 
 Every fixture is produced by calling UNMODIFIED reference code (/root/reference) under the
 float32 stand-in `taichi` package in shim/ (third-party taichi==1.6.0 is not installable
@@ -11,6 +11,9 @@ here).  Fixtures are plain input/output arrays; no reference source text is stor
 `__ENABLE_MICROFACET__` of bxdf/brdf.py:8, which upstream tells its users to flip by hand (brdf.py:63), is True for that
 section (refenv.py flips it at import, in memory).  It is never part of `all`: the switch is process-wide, so the section
 runs in a process of its own (`ADAPT_REF_MICROFACET=1`, set by this script when it re-executes itself).
+
+`--only settings` (tests/settings_cases.py: every sensor setting flipped on five scenes, one whole-kernel run each) takes minutes and
+is not part of `all` either.
 """
 import argparse
 import os
@@ -514,6 +517,54 @@ def gen_scene(scene_dir, xml, tag, w, h, spp, overrides, seed=0, n_rays=192):
           f"mean draws {draws.mean():.2f}, mean radiance {out['pixels'].mean():.4f}")
 
 
+def _whole_kernel(rdr, w, h, spp, seed):
+    """`spp` calls of the reference's render kernel on the shared Philox stream (key = pixel, seed, sample number): the accumulated
+    image and every sample's draw count"""
+    draws = np.zeros((spp, w, h), np.int32)
+    state = {"prev": None}
+
+    def hook(i, j):
+        if state["prev"] is not None:
+            pi, pj = state["prev"]; draws[state["s"], pi, pj] = ti.RNG.draw
+        ti.RNG.set_philox(i * h + j, seed, rdr.cnt[None])
+        state["prev"] = (i, j)
+
+    ti.PIXEL_HOOK[0] = hook
+    for s_ in range(spp):
+        state["s"], state["prev"] = s_, None
+        rdr.render(0, 0, 0, 0, 0, 0)
+        pi, pj = state["prev"]; draws[s_, pi, pj] = ti.RNG.draw
+    ti.PIXEL_HOOK[0] = None
+    return rdr.color.to_numpy(), draws
+
+
+def gen_settings():
+    """The sensor-settings matrix (tests/settings_cases.py): Renderer.render / VolumeRenderer.render of the reference with each case's
+    overrides written into the sensor dict its parser returned.  One file, per case `<name>:accum`, `<name>:draws` and the nine settings
+    the reference's renderer was created with (`<name>:<key>`); no random inputs."""
+    sys.path.insert(0, os.path.join(refenv.REPO, "tests"))
+    import settings_cases as SC
+    os.chdir(refenv.REPO)                               # asset paths in this repo's scene files are relative to the repository root
+    w, h, spp, seed = SC.FIXTURE_W, SC.FIXTURE_H, SC.FIXTURE_SPP, SC.FIXTURE_SEED
+    out = {"names": np.array([c.name for c in SC.CASES]), "width": np.int32(w), "height": np.int32(h), "spp": np.int32(spp), "seed": np.int32(seed)}
+    t_all = time.time()
+    for case in SC.CASES:
+        sdir, fname, ref, vol = SC.SCENES[case.scene]
+        scene_dir, xml = ref if ref is not None else (os.path.join(refenv.REPO, "scenes", sdir), fname)
+        t0 = time.time()
+        rdr, (_, _, _, cfg) = refenv.make_renderer(scene_dir, xml, dict(case.overrides, width=w, height=h), volumetric=vol)
+        assert SC.within_queue_limit(int(cfg["num_shadow_ray"]), int(cfg["max_bounce"])), case.name
+        accum, draws = _whole_kernel(rdr, w, h, spp, seed)
+        out[f"{case.name}:accum"], out[f"{case.name}:draws"] = accum, draws
+        eff = {"rr_bounce_th": 4, "rr_threshold": 0.1, "brdf_two_sides": False}
+        eff.update({k: cfg[k] for k in SC.SETTING_KEYS if k in cfg})
+        for k in SC.SETTING_KEYS:
+            out[f"{case.name}:{k}"] = np.float64(eff[k]) if k == "rr_threshold" else np.int32(eff[k])
+        print(f"settings {case.name}: {time.time() - t0:.1f}s, mean draws {draws.mean():.2f}, mean radiance {np.nanmean(accum) / spp:.4f}", flush=True)
+    np.savez_compressed(os.path.join(OUT, "settings_matrix.npz"), **out)
+    print(f"settings_matrix: {len(SC.CASES)} cases at {w}x{h}x{spp}spp in {time.time() - t_all:.0f}s")
+
+
 # ------------------------------------------------------------------ sweep over the reference's own bundled scenes
 def gen_refscene(scene_dir, xml, tag, w, h, spp, seed=0, volumetric=False, overrides=None):
     """Whole-kernel run of one of the reference's bundled scene files (its own parser, its own kernel) plus the parsed
@@ -779,6 +830,9 @@ if __name__ == "__main__":
         gen_microfacet_functions()
         gen_scene(os.path.join(refenv.REPO, "scenes", "test"), "microfacet.xml", "microfacet", 40, 30, 4, {}, n_rays=48)
         gen_vptrun(os.path.join(refenv.REPO, "scenes", "test"), "microfacet.xml", "microfacet", 40, 30, 2)       # the same BRDFs in the volumetric loop
+        sys.exit(0)
+    if a.only == "settings":
+        gen_settings()
         sys.exit(0)
     if a.only in ("all", "parse"):
         dump_parse("cbox", "cbox.xml", "cbox")
