@@ -21,6 +21,7 @@ u32p = C.POINTER(C.c_uint32)
 u8p = C.POINTER(C.c_uint8)
 f64p = C.POINTER(C.c_double)
 APT_N_KERNELS = 5
+# the stages of apt_stats.launches[] / kernel_ms[], in the order of APT_K_GENERATE .. APT_K_FINALIZE (include/adapt_mi.h)
 KERNEL_NAMES = ("generate", "extend", "shade", "shadow", "finalize")
 
 

@@ -82,9 +82,6 @@ APT_HD int32_t rng_int(Philox& r) { return (int32_t)rng_u32(r); }
 #ifndef APT_DRAW_WINDOW
 #define APT_DRAW_WINDOW 1
 #endif
-#ifndef APT_DRAW_WINDOW_CARRY
-#define APT_DRAW_WINDOW_CARRY 1      // the camera-fed kernel keeps the jitter block's last two words for bounce 0 (shade_stage.hpp)
-#endif
 struct DrawWindow {
     uint32_t draw;       // the path's draw index, advanced by every site as Philox advances it
     uint32_t e, u[2];

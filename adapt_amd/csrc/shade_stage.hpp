@@ -67,7 +67,7 @@ APT_D void build_hit(const DevScene& sc, int prim, float t, float u, float v, f3
 }
 
 #if APT_FAST
-// ---- rays traced in place (Params::fused == 2; product build, flat sweep, unsorted, one light sample per vertex)
+// ---- rays traced in place (Params::traced; product build, flat sweep, unsorted, one light sample per vertex)
 // The shade kernel sweeps its continuation ray against the scene's records itself (flat_closest1: one ray against two records per packed
 // instruction), as it already does with its light sample, and k_generate does the same for the camera rays: a bounce is ONE launch
 // instead of extend + fix-up + shade, the ray is never read back (24 + 8 bytes per segment), and a ray that hits nothing never enters a
@@ -160,23 +160,14 @@ APT_D void fix_prologue(const DevScene& sc, const Params& p, const Queues& q, Co
 // the pointer is made opaque at the head of every phase of a row (an empty asm: APT_ARGS_PHASE): a field's load can then not be hoisted
 // above the phase that uses it, it becomes an s_load (scalar memory, not a VALU issue slot; the segment stays in the scalar cache) next
 // to its use, and its register is free again after the phase.
-#ifndef APT_ARGS_RELOAD
-#define APT_ARGS_RELOAD 1
-#endif
 struct ShadeArgs3 { DevScene sc; Params p; Queues q; };          // the leading arguments of every shade kernel, laid out as the segment lays them out
 typedef const __attribute__((address_space(4))) ShadeArgs3* args3_ptr;
 APT_D args3_ptr kernel_args3() { return (args3_ptr)__builtin_amdgcn_kernarg_segment_ptr(); }
 APT_D const ShadeArgs3* args_fresh(args3_ptr a) {
-#if APT_ARGS_RELOAD
     asm volatile("" : "+s"(a));
-#endif
     return (const ShadeArgs3*)a;
 }
-#if APT_ARGS_RELOAD
 #define APT_ARGS_PHASE() (A_ = args_fresh(A0))
-#else
-#define APT_ARGS_PHASE() ((void)0)
-#endif
 // ---- a vertex while it is shaded, and the three steps both shade kernels take with it (vanilla_renderer.py:36-120)
 struct Vertex {
     f3 o, d, thr, hit_point; uint32_t id, l_off, draw0; float emission_weight;      // l_off: byte offset of the path's radiance slot; draw0: the path's draw index on entry
@@ -310,7 +301,7 @@ APT_D void tally_flush(const ShadeTally& t, const uint32_t* s_draws, Counters* c
     flush_uniform(t.poison, &cnt->stats[sq][ST_POISON]);
 }
 #if APT_FAST
-// ---- the shade kernel that traces its own rays (Params::fused == 2: "rays traced in place" above).  Input and output are the packed
+// ---- the shade kernel that traces its own rays (Params::traced: "rays traced in place" above).  Input and output are the packed
 // records of Queues::tr; the path's radiance travels with it (Lc) and reaches its slot of L once, when the path ends.
 // For a scene of a few dozen records the any-hit sweep of a shadow ray costs fewer issue slots than the round trip of its 44-byte queue
 // entry through HBM plus the scattered read-modify-write of the path's radiance slot behind it: the vertex's light sample is swept right
@@ -393,7 +384,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
                 const uint32_t lp = id_ % (uint32_t)(A_->p).npix, s = id_ / (uint32_t)(A_->p).npix;
                 int i, j; local_to_global((A_->p), lp, i, j);
                 for (int pl = 0; pl < (A_->p).l_planes; pl++) stL((A_->q).L, (A_->p).cap, (id_ << 2) | (uint32_t)pl, splat3(0.f));
-                dir = camera_ray_dir((A_->p), i, j, s, draws, (WINDOW && APT_DRAW_WINDOW_CARRY) ? jitter_tail : nullptr);
+                dir = camera_ray_dir((A_->p), i, j, s, draws, WINDOW ? jitter_tail : nullptr);
                 vx.id = (s << (A_->p).pix_bits) | lp;
             }
             if (draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
@@ -425,7 +416,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
                 vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
                 f3 rec_kd; float2 uv; uv.x = hr.u; uv.y = hr.v;
                 build_hit((A_->sc), hr.prim, hr.t, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
-                alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0, (WINDOW && APT_DRAW_WINDOW_CARRY) ? jitter_tail : nullptr);
+                alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0, WINDOW ? jitter_tail : nullptr);
             }
         }
         if (!CAM && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & 2) ray_pdf = dd.w; }
@@ -454,7 +445,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         bool break_flag = false;
         DevSrc src_only;                                      // the scene's only light, read once through the scalar path
         if ((A_->sc).n_sources == 1) src_only = ld_src_uniform((A_->sc).src);
-        const LightSample f = sample_light<BM, SM, false>(A_, vx, rng, geom, src_only, alive, break_flag);      // (one light sample per vertex: api.hip, Params::fused)
+        const LightSample f = sample_light<BM, SM, false>(A_, vx, rng, geom, src_only, alive, break_flag);      // (one light sample per vertex: api.hip pick_shading, PIPE_TRACED)
         if (f.poisoned) Lc = splat3(f.mis_w);
         tl.shadow += wave_count(f.sampled); tl.poison += wave_count(f.poisoned);
         // the records the row's light samples are swept against (traverse.hpp flat_occ_list): the occluder list of the emitter that every

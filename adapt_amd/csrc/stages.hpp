@@ -99,8 +99,8 @@ struct Params {
     int volumetric_flat;      // 1: volumetric render (the flat shadow kernels never run: the fix-up launch has no shadow list)
     int nee_vm;               // 1: light samples are queued BY VERTEX (one slot per vertex and sub-queue, sample s in plane s of the sub-queue's region, unwanted samples marked tmax < 0), so that the flat shadow kernel adds a vertex's samples with ONE read-modify-write and the shade kernel moves the queue tail once per tile row (flat sweep, S > 1)
     int l_planes;             // radiance planes of L: light sample s of a vertex adds into plane s (2 <= S <= 4), so that no two entries of a shadow launch share a slot; 1 otherwise
-    int fused;                // 2: the shade kernel traces its own light sample and continuation ray, k_generate its camera rays (flat sweep, one sample per vertex, unsorted: shade_stage.hpp "rays traced in place"):
-                              //    no extend, shadow or fix-up launch per bounce, no shadow queue, radiance travels with the path's record, rays that hit nothing never enter a queue; 0: staged
+    int traced;               // 1: the shade kernel traces its own light sample and continuation ray, k_generate its camera rays (flat sweep, one sample per vertex, unsorted: shade_stage.hpp "rays traced in place"):
+                              //    no extend, shadow or fix-up launch per bounce, no shadow queue, radiance travels with the path's record, rays that hit nothing never enter a queue (api.hip PIPE_TRACED); 0: every other pipeline
     float w_min[3], w_max[3]; // world box = (objects U camera) +- 0.1 (path_tracer.py:130-138); volumetric tracer only
 };
 
@@ -108,7 +108,7 @@ struct Params {
 struct Queues {
     float* ray_o[2]; float* ray_d[2];           // 3 components each
     float* hit_t; int* hit_prim; float* hit_u; float* hit_v;
-    // rays traced in place (Params::fused == 2): the path record as four 16-byte planes per queue parity - A = (ray origin, hit distance),
+    // rays traced in place (Params::traced): the path record as four 16-byte planes per queue parity - A = (ray origin, hit distance),
     // B = (ray direction, pm), C = (throughput, path id), D = (radiance so far, pdf of the ray) - and, where somebody reads them, the hit's
     // barycentrics; pm = hit primitive (8 bits, TR_NO_PRIM: nothing hit) | draw index << 8 | specular bit << 24.  Still SoA - a wave's 64
     // entries of a plane are 1 KiB in a row - but a record is 4 loads and 4 stores instead of 16 and 18, and 8 base pointers instead of 30:
@@ -326,11 +326,7 @@ APT_D DevSrc ld_src_uniform(const DevSrc* p) {
 // An emitter record picked per lane (scenes with several lights): the 64-byte record as FOUR 16-byte loads.  Left to the compiler the struct
 // copy dissolves into one 4-byte load per field at its use site - up to nine scattered loads per light sample, most of the scattered
 // accesses a vertex of the mesh scenes makes (C4: 18 of 25 with two light samples) - and the vector-memory pipe pays per lane address.
-#ifndef APT_SRC_VEC
-#define APT_SRC_VEC 1
-#endif
 APT_D DevSrc ld_src_lane(const DevSrc* p) {
-#if APT_SRC_VEC
     static_assert(sizeof(DevSrc) == 64, "DevSrc is read as four float4");
     const float4* q4 = reinterpret_cast<const float4*>(p);
     float4 a = q4[0], b = q4[1], c = q4[2], d = q4[3];
@@ -341,17 +337,10 @@ APT_D DevSrc ld_src_lane(const DevSrc* p) {
     s.intensity = mk3(b.x, b.y, b.z); s.dir = mk3(b.w, c.x, c.y); s.pos = mk3(c.z, c.w, d.x);
     s.inv_area = d.y; s.r = d.z; s.prim_count = __float_as_int(d.w);
     return s;
-#else
-    return *p;
-#endif
 }
 
 // ... and an object's surface-model record (80 bytes) as five
-#ifndef APT_BXDF_VEC
-#define APT_BXDF_VEC 1
-#endif
 APT_D DevBxdf ld_bxdf_lane(const DevBxdf* p) {
-#if APT_BXDF_VEC
     static_assert(sizeof(DevBxdf) == 80, "DevBxdf is read as five float4");
     const float4* q4 = reinterpret_cast<const float4*>(p);
     float4 a = q4[0], b = q4[1], c = q4[2], d = q4[3], e = q4[4];
@@ -362,9 +351,6 @@ APT_D DevBxdf ld_bxdf_lane(const DevBxdf* p) {
     x.k_d = mk3(b.x, b.y, b.z); x.k_s = mk3(b.w, c.x, c.y); x.k_g = mk3(c.z, c.w, d.x); x.mean = mk3(d.y, d.z, d.w);
     x.ior = e.x; x._pad2[0] = x._pad2[1] = x._pad2[2] = 0.f;
     return x;
-#else
-    return *p;
-#endif
 }
 
 // local pixel -> (global column, row)
@@ -384,7 +370,10 @@ APT_D SubLoop sub_loop(int nq, int nt = BLOCK) {
     s.stride = (gridDim.x / (uint32_t)nq) * (uint32_t)nt;
     return s;
 }
-// trace kernels: MODE 0 BVH walk, 1 wave/workgroup sweep, 2 tiled sweep (its own, larger workgroup), 3 flat sweep (fast build only)
+// trace kernels: MODE = BVH walk, wave/workgroup sweep, tiled sweep (its own, larger workgroup), flat sweep (fast build only: kernels of its own,
+// k_extend_flat ...); TRACE_VFLAT is a mode of the volumetric transmittance walk alone (volumetric.hpp k_vshadow_flat).  The kernels' MODE
+// template parameters stay int.
+enum { TRACE_BVH = 0, TRACE_SWEEP = 1, TRACE_TILE = 2, TRACE_FLAT = 3, TRACE_VFLAT = 4 };
 #ifndef APT_TILE_NT
 #define APT_TILE_NT 512
 #endif
@@ -393,7 +382,7 @@ APT_D SubLoop sub_loop(int nq, int nt = BLOCK) {
 #ifndef APT_TILE_WAVES
 #define APT_TILE_WAVES 6
 #endif
-#define TRACE_NT(MODE) ((MODE) == 2 ? APT_TILE_NT : BLOCK)
+#define TRACE_NT(MODE) ((MODE) == TRACE_TILE ? APT_TILE_NT : BLOCK)
 
 // The camera ray of sample `s` of the batch through global pixel (i, j): the jitter comes from the pixel's own stream (`draws` numbers of
 // it), the direction leaves in world space.  One function for k_generate* and the camera-fed shade kernels (shade_stage.hpp), so that the
@@ -433,7 +422,7 @@ APT_D unsigned long long camera_strip_mask(const Params& p, const unsigned long 
 // ----------------------------------------------------------------- generate
 // wave w of the id space feeds sub-queue w % nq at position (w / nq) * 64 + lane: dense and
 // atomic-free unless a crop window makes some lanes inactive.
-// TRACE (rays traced in place, Params::fused == 2): the camera ray meets the scene's records here and the entry carries its hit record
+// TRACE (rays traced in place, Params::traced): the camera ray meets the scene's records here and the entry carries its hit record
 // (Queues::tr, parity 0, the queue of the hit primitive's class; counted in n_tr[0]); a ray that hits nothing is not queued at all.
 // ADAPTIVE (adaptive sampling): a pixel that has stopped sampling (active[lp] == 0) is one more slot that is not alive;
 // the queue is compacted as for a crop window.
@@ -526,10 +515,10 @@ __global__ void __launch_bounds__(BLOCK) k_generate_trace_ad(DevScene sc, Params
 // closest hit for ray queue `cur`.  Also recycles the counters nobody reads any more: the
 // next-ray queue of this bounce (it was the current queue of the previous bounce) and the
 // shadow queue.  `n_src` = per-sub-queue counts (normally cnt->n_active[cur]).
-// MODE 0: BVH traversal (LDS-staged nodes + per-lane LDS stack); MODE 1: wave-uniform sweep (small scenes)
+// TRACE_BVH: BVH traversal (LDS-staged nodes + per-lane LDS stack); TRACE_SWEEP: wave-uniform sweep (small scenes); TRACE_TILE: tiled sweep
 template <int MODE, int SORTED>
-__global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == 2 ? APT_TILE_WAVES : 1)) k_extend(DevScene sc, Params p, Queues q, Counters* cnt, int cur, const uint32_t* n_src, LdsPlan plan) {
-    __shared__ float s_sweep[MODE == 1 ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
+__global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == TRACE_TILE ? APT_TILE_WAVES : 1)) k_extend(DevScene sc, Params p, Queues q, Counters* cnt, int cur, const uint32_t* n_src, LdsPlan plan) {
+    __shared__ float s_sweep[MODE == TRACE_SWEEP ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
     const SubLoop sl = sub_loop(p.nq, TRACE_NT(MODE));
     const uint32_t n = n_src[sl.q * CNT_PAD];
     if (cnt && sl.first == 0 && threadIdx.x == 0) {
@@ -547,8 +536,8 @@ __global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == 2 ? APT_TILE_WAVES : 
         const f3 o = ld3q(ro, p.cap, io);
         const f3 d = ld3q(rd, p.cap, io);
         HitRec rec; rec.t = 1e7f; rec.prim = -1; rec.u = 0.f; rec.v = 0.f;
-        if (MODE == 0) traverse<false>(sc.bvh, make_stack(plan), o, d, rec);
-        else if (MODE == 1) sweep_wg<false, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep);
+        if (MODE == TRACE_BVH) traverse<false>(sc.bvh, make_stack(plan), o, d, rec);
+        else if (MODE == TRACE_SWEEP) sweep_wg<false, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep);
         else sweep_tile<false, APT_TILE_NT>(sc.sweep, o, d, rec, valid, reinterpret_cast<float*>(s_dyn));
         if (!SORTED) {
             if (valid) { stq(q.hit_t, io, rec.t); stq(q.hit_prim, io, rec.prim); stq(q.hit_u, io, rec.u); stq(q.hit_v, io, rec.v); }
@@ -723,8 +712,8 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_extend_dyn(DevScene sc,
 
 // ------------------------------------------------------------------- shadow
 template <int MODE>
-__global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == 2 ? APT_TILE_WAVES : 1)) k_shadow(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan) {
-    __shared__ float s_sweep[MODE == 1 ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
+__global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == TRACE_TILE ? APT_TILE_WAVES : 1)) k_shadow(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan) {
+    __shared__ float s_sweep[MODE == TRACE_SWEEP ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
     const SubLoop sl = sub_loop(p.nq, TRACE_NT(MODE));
     const uint32_t n = min(cnt->n_shadow[sl.q * CNT_PAD], q.sh_subcap);
     if (sl.first == 0 && threadIdx.x == 0) {
@@ -742,8 +731,8 @@ __global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == 2 ? APT_TILE_WAVES : 
         const f3 d = ld3q(q.sh_d, sc_, io);
         const float dist = ldq(q.sh_tmax, io);
         HitRec rec; rec.t = (dist > 0.0f) ? dist - 1e-4f : 1e7f; rec.prim = -1; rec.u = rec.v = 0.f;
-        const bool occluded = (MODE == 0) ? traverse<true>(sc.bvh, make_stack(plan), o, d, rec)
-                            : (MODE == 1) ? sweep_wg<true, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep)
+        const bool occluded = (MODE == TRACE_BVH) ? traverse<true>(sc.bvh, make_stack(plan), o, d, rec)
+                            : (MODE == TRACE_SWEEP) ? sweep_wg<true, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep)
                                           : sweep_tile<true, APT_TILE_NT>(sc.sweep, o, d, rec, valid, reinterpret_cast<float*>(s_dyn));
         if (valid) {
             f3 c = ld3q(q.sh_c, sc_, io);
@@ -1026,11 +1015,6 @@ APT_D void shadow_flat_body(const DevScene& sc, const Params& p, const Queues& q
         v2f cx = ld2q<v2f>(q.sh_c, io), cy = ld2q<v2f>(q.sh_c, io + cs), cz = ld2q<v2f>(q.sh_c, io + 2u * cs);
         if (VAR >= 2 && odd) { cx = mk2(cx.y, cx.x); cy = mk2(cy.y, cy.x); cz = mk2(cz.y, cz.x); }
         const bool excl = APT_EXCLUSIVE_L(p);
-#ifdef APT_PROBE_NO_L      // measurement only (tools/build_variant.sh nol -DAPT_PROBE_NO_L=1): how much of the stage is the radiance read-modify-write
-        if (cx.x == 123.456f) stL(q.L, p.cap, slot.x, ldL(q.L, p.cap, slot.x));
-        t_lit += (v0 && !occ0 ? 1u : 0u) + (v1 && !occ1 ? 1u : 0u);
-        continue;
-#endif
         // no two entries of the launch share a slot (excl): plain read-modify-writes of one 16-byte slot each; the radiance of both entries is
         // requested together with the contributions (whether it will be written is only known once they arrive)
         f3 a0 = splat3(0.f), a1 = splat3(0.f);
@@ -1062,7 +1046,7 @@ __global__ void __launch_bounds__(BLOCK) k_shadow_flat(DevScene sc, Params p, Qu
 template <int SORTED>
 __global__ void __launch_bounds__(BLOCK) k_fix_flat(DevScene sc, Params p, Queues q, Counters* cnt, int cur, const uint32_t* n_src, LdsPlan plan) {
     extend_flat_body<SORTED, 2>(sc, p, q, cnt, cur, n_src);
-    if (p.S > 0 && !p.volumetric_flat) { if (p.fused) shadow_flat_body<3>(sc, p, q, cnt, cur ^ 1); else shadow_flat_body<2>(sc, p, q, cnt, cur ^ 1); }
+    if (p.S > 0 && !p.volumetric_flat) { if (p.traced) shadow_flat_body<3>(sc, p, q, cnt, cur ^ 1); else shadow_flat_body<2>(sc, p, q, cnt, cur ^ 1); }
 }
 
 __global__ void __launch_bounds__(BLOCK) k_occluded_flat(DevScene sc, uint32_t n, const float* o_, const float* d_, const float* tmax, int* occ, LdsPlan plan) {

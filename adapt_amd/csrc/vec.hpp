@@ -99,9 +99,6 @@ APT_D float apt_sin(float x) { return (float)sin((double)x); }
 // one occupancy step); for |x| < 8 two fused steps against a two-word pi/2 and the fdlibm kernels on [-pi/4, pi/4]
 // (error < 1 ulp in double, i.e. invisible after the rounding to float except on ~1e-8 of arguments) are enough.
 APT_D void apt_sincos(float xf, float* s, float* c) {
-#ifdef APT_SINCOS_OCML
-    { double ds, dc; sincos((double)xf, &ds, &dc); *s = (float)ds; *c = (float)dc; return; }
-#endif
     const double x = (double)xf;
     const double k = __builtin_rint(x * 6.36619772367581382433e-01);                 // nearest multiple of pi/2
     double r = __builtin_fma(-k, 1.57079632679489655800e+00, x);

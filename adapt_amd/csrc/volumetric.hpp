@@ -17,7 +17,7 @@
 #ifndef APT_VSHADOW_NT
 #define APT_VSHADOW_NT 256
 #endif
-#define VSHADOW_NT(MODE) ((MODE) == 2 ? APT_VSHADOW_NT : BLOCK)
+#define VSHADOW_NT(MODE) ((MODE) == TRACE_TILE ? APT_VSHADOW_NT : BLOCK)
 
 APT_D float med_random_rgb(Philox& r, f3 v) {                      // general_sampling.py:17-27
     const int idx = pymod(rng_int(r), 3);
@@ -504,8 +504,8 @@ __global__ void __launch_bounds__(BLOCK, WAVES) k_vshade_ev_group(DevScene sc, P
 // remaining distance shortened, transmittance folded into the contribution - and its slot is appended to the list the next pass
 // reads.  The reference walks at most seven segments; the host launches pass p + 1 only where null surfaces exist.
 template <int MODE>
-__global__ void __launch_bounds__(VSHADOW_NT(MODE), (MODE == 2 ? APT_VSHADOW_WAVES : 1)) k_vshadow(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan, int pass) {
-    __shared__ float s_sweep[MODE == 1 ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
+__global__ void __launch_bounds__(VSHADOW_NT(MODE), (MODE == TRACE_TILE ? APT_VSHADOW_WAVES : 1)) k_vshadow(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan, int pass) {
+    __shared__ float s_sweep[MODE == TRACE_SWEEP ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
     const SubLoop sl = sub_loop(p.nq, VSHADOW_NT(MODE));
     const uint32_t n = min(pass == 0 ? cnt->n_shadow[sl.q * CNT_PAD] : cnt->n_walk[pass][sl.q * CNT_PAD], q.sh_subcap);
     if (pass == 0 && sl.first == 0 && threadIdx.x == 0) {
@@ -529,8 +529,8 @@ __global__ void __launch_bounds__(VSHADOW_NT(MODE), (MODE == 2 ? APT_VSHADOW_WAV
         const f3 d = ld3q(q.sh_d, sc_, io);
         float depth = ldq(q.sh_tmax, io);
         HitRec rec; rec.t = (depth > 0.0f) ? depth - 1e-4f : 1e7f; rec.prim = -1; rec.u = rec.v = 0.f;
-        if (MODE == 0) traverse<false>(sc.bvh, make_stack(plan), o, d, rec);
-        else if (MODE == 1) sweep_wg<false, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep);
+        if (MODE == TRACE_BVH) traverse<false>(sc.bvh, make_stack(plan), o, d, rec);
+        else if (MODE == TRACE_SWEEP) sweep_wg<false, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep);
         else sweep_tile<false, APT_VSHADOW_NT>(sc.sweep, o, d, rec, valid, reinterpret_cast<float*>(s_dyn));
         bool arrived = false, walk_on = false;
         f3 c = splat3(0.f);

@@ -45,6 +45,8 @@ from .tiles import TilePlan
 __all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error"]
 
 ADAPTIVE_DEFAULTS = {"min_spp": 64, "step": 32}
+# apt_renderer_info's trace_mode -> name: TRACE_BVH, TRACE_SWEEP, TRACE_TILE, TRACE_FLAT (csrc/stages.hpp), the words of csrc/api.hip kTraversalName in its order
+TRAVERSAL_NAMES = dict(enumerate(("bvh", "sweep", "tile", "flat")))
 
 
 def adaptive_config(adaptive) -> Optional[dict]:
@@ -487,7 +489,7 @@ class Renderer:
         _lib.check(self.lib.apt_renderer_info(self.handle, C.byref(b), C.byref(nq), C.byref(qb), C.byref(lds), C.byref(name), C.byref(tm)), "apt_renderer_info", self.lib)
         return {"spp_per_batch": b.value, "n_subqueues": nq.value, "queue_bytes": qb.value, "lds_bytes": lds.value,
                 "shade_variant": name.value.decode() if name.value else "",
-                "traversal": {0: "bvh", 1: "sweep", 2: "tile", 3: "flat"}.get(tm.value, str(tm.value)), "arithmetic": self.arithmetic,
+                "traversal": TRAVERSAL_NAMES.get(tm.value, str(tm.value)), "arithmetic": self.arithmetic,
                 "sampling": "adaptive" if self.adaptive else "uniform", **({"adaptive": dict(self.adaptive)} if self.adaptive else {})}
 
     def camera_fused(self) -> bool:

@@ -122,7 +122,9 @@ typedef struct apt_render_cfg {
     float   transient_interval;                   /* ... in bin int((t - min_time) / interval); must be > 0 */
 } apt_render_cfg;
 
-#define APT_N_KERNELS 5   /* generate, extend, shade, shadow, finalize */
+/* The stages a launch is filed under: index of apt_stats.launches[] / kernel_ms[] (adapt_amd/_lib.py KERNEL_NAMES lists them in this order) */
+enum { APT_K_GENERATE = 0, APT_K_EXTEND = 1, APT_K_SHADE = 2, APT_K_SHADOW = 3, APT_K_FINALIZE = 4 };
+#define APT_N_KERNELS 5
 typedef struct apt_stats {
     int64_t n_samples;        /* pixel-samples generated */
     int64_t n_extend;         /* closest-hit rays traced */
@@ -256,7 +258,9 @@ int apt_emitter_probe(const apt_scene*, int32_t n, const float* in11, uint32_t s
 /* Transient binning probe: out[k] = the time bin the transient renderer puts a contribution at time t[k] into (-1: outside the window),
  * for the window of n_bins bins of width interval from min_time, set up as apt_renderer_create sets it up. */
 int apt_transient_bin_probe(int32_t device, int32_t n, const float* t, float min_time, float interval, int32_t n_bins, int32_t* out);
-/* trace_mode: 0 = BVH traversal, 1 = wave-uniform sweep (scenes of <= 96 primitives; env APT_TRAVERSAL=bvh|sweep overrides) */
+/* trace_mode: 0 = BVH traversal, 1 = wave-uniform sweep (scenes of <= 96 primitives with object boxes), 2 = tiled sweep (of those, the
+ * scenes with an object large enough to be worth skipping per ray), 3 = flat sweep (product build: every scene small enough to have flat
+ * records).  env APT_TRAVERSAL=bvh|sweep|tile|flat, read at apt_renderer_create, overrides where the scene allows the mode asked for. */
 int apt_renderer_info(const apt_renderer*, int32_t* spp_batch, int32_t* n_subqueues, int64_t* queue_bytes,
                       int32_t* lds_bytes, const char** shade_variant, int32_t* trace_mode);
 /* Rays traced in place: *fused = 1 when the renderer shades the camera vertex in the kernel that traces the camera ray (steady full-film
