@@ -39,70 +39,96 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 // ------------------------------------------------- shade kernel specialisations
 // (material mask, emitter mask) -> instantiation; the host picks the first one that covers the scene
 typedef void (*shade_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int);
-#if APT_FAST
-#define APT_TRACED_FN(...) __VA_ARGS__
-#else
-#define APT_TRACED_FN(...) nullptr         // rays traced by the shade kernel: a product-build path (it rides on the flat sweep's records)
-#endif
 typedef void (*shade_traced_fn)(DevScene, Params, Queues, Counters*, int, int);
 typedef void (*shade_cam_fn)(DevScene, Params, Queues, Counters*, const unsigned long long*);
 typedef void (*shade_tr_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int, TransQ);
-struct ShadeVariant { int bm, sm; shade_fn fn; const char* name; shade_traced_fn traced; shade_tr_fn transient; shade_cam_fn traced_cam; };      // traced_cam: traced's camera-fed twin (k_shade_traced_cam: bounce 0 of a steady full-film batch, no k_generate_trace in front of it); traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced: flat sweep, one light sample per vertex); transient: fn's time-resolved twin (k_shade_tr)
-static const ShadeVariant kShadeVariants[] = {
-    {0x002, 0x01, k_shade<0x002, 0x01>, "lambertian/point", APT_TRACED_FN(k_shade_traced_lean<0x002, 0x01>), k_shade_tr<0x002, 0x01>, APT_TRACED_FN(k_shade_traced_lean_cam<0x002, 0x01>)},
-    {0x003, 0x03, k_shade<0x003, 0x03>, "phong+lambertian/point+area", APT_TRACED_FN(k_shade_traced<0x003, 0x03>), k_shade_tr<0x003, 0x03>, APT_TRACED_FN(k_shade_traced_cam<0x003, 0x03>)},
-    {0x107, 0x03, k_shade<0x107, 0x03>, "phong+lambertian+mirror+glass/point+area", APT_TRACED_FN(k_shade_traced<0x107, 0x03>), k_shade_tr<0x107, 0x03>, APT_TRACED_FN(k_shade_traced_cam<0x107, 0x03>)},
-    {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL>, "all models", APT_TRACED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL>, APT_TRACED_FN(k_shade_traced_cam<APT_BX_ALL, APT_SRC_ALL>)},
-};
-static const ShadeVariant kTexturedShade = {APT_BX_ALL, APT_SRC_ALL, k_shade<APT_BX_ALL, APT_SRC_ALL, 1>, "all models + image textures", APT_TRACED_FN(k_shade_traced<APT_BX_ALL, APT_SRC_ALL, 1>), k_shade_tr<APT_BX_ALL, APT_SRC_ALL, 1>, APT_TRACED_FN(k_shade_traced_cam<APT_BX_ALL, APT_SRC_ALL, 1>)};
-// Material classes for sorted shading: (class mask) x (emitter mask: point+area | all)
-// A kernel's register allocation is the maximum over the models it contains, so the classes are as fine as the models'
-// footprints differ: Lambertian alone runs at 4 waves per SIMD, together with Blinn-Phong (three double pows) at 2-3.
-#define APT_N_CLASS_DEFS 10
-static const int kClassMask[APT_N_CLASS_DEFS] = {
-    0x002,      // Lambertian
-    0x001,      // Blinn-Phong
-    0x040,      // Oren-Nayar
-    0x504,      // delta: mirror BRDF, det-refraction BSDF, null BSDF
-    0x010,      // modified Phong
-    0x020,      // Fresnel blend
-    0x080,      // thin coat
-    0x200,      // Lambertian transmission
-    0x008,      // Trowbridge-Reitz microfacet (upstream's opt-in model: type 3 reaches the device only with the switch on)
-    0x801,      // Blinn-Phong objects without a specular lobe (k_s = 0, finite k_g >= 0: shading.hpp mask bit 11): no double-precision pow
-};
-static const char* kClassName[APT_N_CLASS_DEFS] = {"lambertian", "blinn-phong", "oren-nayar", "delta", "mod-phong", "fresnel-blend", "thin-coat", "lambert-trans", "microfacet", "blinn-phong(no lobe)"};
-// Class kernels in groups (shade_stage.hpp k_shade_group): one launch per GROUP and bounce instead of one per class.  Groups follow the register
-// footprints - a kernel allocates for its largest member: 0 = the lean classes, up to 96 VGPRs (five waves per SIMD), 1 = the rest, up to 128 (four).
-typedef void (*group_fn)(DevScene, Params, Queues, Counters*, GroupIn, int, int);
-#define APT_N_GROUPS 2
-static const int kClassGroup[APT_N_CLASS_DEFS] = {0, 1, 1, 0, 1, 1, 1, 0, 1, 0};      // class definition -> group
-static const int kClassSlot[APT_N_CLASS_DEFS] = {0, 0, 1, 1, 4, 5, 2, 2, 3, 3};       // ... and its member slot there (the B0..B5 order below)
-#ifndef APT_GROUP0_WAVES
-#define APT_GROUP0_WAVES 5
-#endif
-#define APT_GROUP_ROW(SM) {k_shade_group<SM, APT_GROUP0_WAVES, 0x002, 0x504, 0x200, 0x801>, k_shade_group<SM, 4, 0x001, 0x040, 0x080, 0x008, 0x010, 0x020>}
-// (group 0 at five waves: 93 VGPRs with point + spot lights, 96 and one 8-byte scratch slot with area lights; at four it took 99)
-static const group_fn kGroupShade[3][APT_N_GROUPS] = {APT_GROUP_ROW(0x03), APT_GROUP_ROW(APT_SRC_ALL), APT_GROUP_ROW(0x05)};      // [emitter set: point + area | all | point + spot (no area light: no emission code, no pdf in the record, both Philox blocks up front)][group]
-typedef void (*group_tr_fn)(DevScene, Params, Queues, Counters*, GroupIn, int, int, TransQ);
-#define APT_GROUP_TR_ROW(SM) {k_shade_group_tr<SM, 0x002, 0x504, 0x200, 0x801>, k_shade_group_tr<SM, 0x001, 0x040, 0x080, 0x008, 0x010, 0x020>}
-static const group_tr_fn kGroupShadeTr[3][APT_N_GROUPS] = {APT_GROUP_TR_ROW(0x03), APT_GROUP_TR_ROW(APT_SRC_ALL), APT_GROUP_TR_ROW(0x05)};      // the same, transient renders
-#define APT_CLASS_PHONG 1
-#define APT_CLASS_PHONG_NO_LOBE 9
-static int class_of(int is_bsdf, int type, bool no_lobe) {
-    const int bit = is_bsdf ? (type == 0 ? 8 : (type == 1 ? 9 : 10)) : (type & 7);
-    if (!is_bsdf && (type & 7) == 0 && no_lobe) return APT_CLASS_PHONG_NO_LOBE;
-    for (int c = 0; c < APT_N_CLASS_DEFS - 1; c++) if ((kClassMask[c] >> bit) & 1) return c;
-    return 0;
-}
-typedef void (*extend_fn)(DevScene, Params, Queues, Counters*, int, const uint32_t*, LdsPlan);
-typedef void (*shadow_fn)(DevScene, Params, Queues, Counters*, LdsPlan);
-typedef void (*occluded_fn)(DevScene, uint32_t, const float*, const float*, const float*, int*, LdsPlan);
+// transient: fn's time-resolved twin (k_shade_tr); traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced:
+// flat sweep, one light sample per vertex); traced_cam: traced's camera-fed twin (k_shade_traced_cam: bounce 0 of a steady full-film batch, no k_generate_trace in front of it)
+struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; shade_traced_fn traced; shade_cam_fn traced_cam; };
 #if APT_FAST
 #define APT_FLAT_FN(...) __VA_ARGS__
 #else
-#define APT_FLAT_FN(...) nullptr          // the flat sweep exists in the fast build only (traverse.hpp)
+#define APT_FLAT_FN(...) nullptr          // the flat sweep exists in the fast build only (traverse.hpp), and with it the shade kernels that trace their rays on its records
 #endif
+#define APT_TRACED_PAIR(STEM, ...) APT_FLAT_FN(STEM<__VA_ARGS__>), APT_FLAT_FN(STEM##_cam<__VA_ARGS__>)
+#define APT_TRACED_PLAIN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced, BM, SM, TEX)
+#define APT_TRACED_LEAN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced_lean, BM, SM)
+#define APT_SHADE_VARIANT(BM, SM, TEX, NAME, TRACED) {BM, SM, NAME, k_shade<BM, SM, TEX>, k_shade_tr<BM, SM, TEX>, APT_TRACED_##TRACED(BM, SM, TEX)}
+static const ShadeVariant kShadeVariants[] = {
+    APT_SHADE_VARIANT(APT_BX_LAMBERTIAN, APT_SRC_POINT, 0, "lambertian/point", LEAN),
+    APT_SHADE_VARIANT(APT_BX_BLINN_PHONG | APT_BX_LAMBERTIAN, APT_SRC_POINT_AREA, 0, "phong+lambertian/point+area", PLAIN),
+    APT_SHADE_VARIANT(APT_BX_BLINN_PHONG | APT_BX_LAMBERTIAN | APT_BX_MIRROR | APT_BX_GLASS, APT_SRC_POINT_AREA, 0, "phong+lambertian+mirror+glass/point+area", PLAIN),
+    APT_SHADE_VARIANT(APT_BX_ALL, APT_SRC_ALL, 0, "all models", PLAIN),
+};
+static const ShadeVariant kTexturedShade = APT_SHADE_VARIANT(APT_BX_ALL, APT_SRC_ALL, 1, "all models + image textures", PLAIN);
+// Material classes for sorted shading.  A kernel's register allocation is the maximum over the models it contains, so the classes are as fine as the
+// models' footprints differ: Lambertian alone runs at 4 waves per SIMD, together with Blinn-Phong (three double pows) at 2-3.  The class kernels are
+// launched in groups (shade_stage.hpp k_shade_group), one launch per GROUP and bounce, that follow the footprints too - a kernel allocates for its
+// largest member: 0 = the lean classes, up to 96 VGPRs (five waves per SIMD), 1 = the rest, up to 128 (four).  Volumetric shading sorted by EVENT
+// (volumetric.hpp k_vevent) has a queue per class and one for the medium, and groups of its own (k_vshade_ev_group; the medium is member 0 of group 1).
+struct ClassDef { int mask; const char* name; int group, slot, vgroup, vslot; };      // member slot of the surface group kernels | of the volumetric ones
+constexpr int APT_N_GROUPS = 2, APT_N_VGROUPS = 3, APT_VGROUP_SLOTS = 4;      // (APT_GROUP_SLOTS: shade_stage.hpp GroupIn)
+static constexpr ClassDef kClass[] = {
+    {APT_BX_LAMBERTIAN, "lambertian", 0, 0, 0, 0},
+    {APT_BX_BLINN_PHONG, "blinn-phong", 1, 0, 2, 0},
+    {APT_BX_OREN_NAYAR, "oren-nayar", 1, 1, 0, 1},
+    {APT_BX_MIRROR | APT_BX_GLASS | APT_BX_NULL, "delta", 0, 1, 0, 2},
+    {APT_BX_MOD_PHONG, "mod-phong", 1, 4, 2, 1},
+    {APT_BX_FRESNEL_BLEND, "fresnel-blend", 1, 5, 2, 2},
+    {APT_BX_THIN_COAT, "thin-coat", 1, 2, 1, 1},
+    {APT_BX_LAMBERT_TRANS, "lambert-trans", 0, 2, 0, 3},
+    {APT_BX_MICROFACET, "microfacet", 1, 3, 1, 2},       // Trowbridge-Reitz (upstream's opt-in model: type 3 reaches the device only with the switch on)
+    {APT_BX_BLINN_PHONG | APT_BX_NO_LOBE, "blinn-phong(no lobe)", 0, 3, 2, 3},       // Blinn-Phong objects without a specular lobe (k_s = 0, finite k_g >= 0: shading.hpp APT_BX_NO_LOBE): no double-precision pow
+};
+constexpr int APT_N_CLASS_DEFS = sizeof(kClass) / sizeof(kClass[0]), APT_CLASS_PHONG = 1, APT_CLASS_PHONG_NO_LOBE = APT_N_CLASS_DEFS - 1;
+// mask of the member at (group, slot) of the surface / volumetric group kernels, 0 where there is none: the group rows below take their template arguments from it
+static constexpr int group_mask(int g, int s) { for (const ClassDef& c : kClass) if (c.group == g && c.slot == s) return c.mask; return 0; }
+static constexpr int vgroup_mask(int g, int s) {       // (without the no-lobe bit: the volumetric tracer does not split Blinn-Phong by lobe)
+    for (const ClassDef& c : kClass) if (c.vgroup == g && c.vslot == s) return c.mask & ~APT_BX_NO_LOBE;
+    return (g == 1 && s == 0) ? APT_VEV_MEDIUM_CODE : 0;
+}
+static constexpr bool class_masks_partition_all() {
+    int all = 0;
+    for (int c = 0; c < APT_N_CLASS_DEFS - 1; c++) { if (all & kClass[c].mask) return false; all |= kClass[c].mask; }
+    return all == APT_BX_ALL;
+}
+static constexpr bool class_slots_ok() {
+    for (int a = 0; a < APT_N_CLASS_DEFS; a++) {
+        const ClassDef& c = kClass[a];
+        if ((unsigned)c.group >= APT_N_GROUPS || (unsigned)c.slot >= APT_GROUP_SLOTS || (unsigned)c.vgroup >= APT_N_VGROUPS || (unsigned)c.vslot >= APT_VGROUP_SLOTS) return false;
+        if (c.vgroup == 1 && c.vslot == 0) return false;       // the medium's
+        for (int b = 0; b < a; b++)
+            if ((kClass[b].group == c.group && kClass[b].slot == c.slot) || (kClass[b].vgroup == c.vgroup && kClass[b].vslot == c.vslot)) return false;
+    }
+    return true;
+}
+static_assert(class_masks_partition_all(), "every surface model belongs to exactly one of the classes in front of the lobe-free one");
+static_assert(class_slots_ok(), "every class needs a member slot of its own, inside APT_GROUP_SLOTS / APT_VGROUP_SLOTS, in a surface and in a volumetric group");
+static_assert(kClass[APT_CLASS_PHONG].mask == APT_BX_BLINN_PHONG && kClass[APT_CLASS_PHONG_NO_LOBE].mask == (APT_BX_BLINN_PHONG | APT_BX_NO_LOBE), "APT_CLASS_PHONG / APT_CLASS_PHONG_NO_LOBE name these entries");
+static int class_of(int is_bsdf, int type, bool no_lobe) {
+    const int bit = bx_bit(is_bsdf, type);
+    if (bit == APT_BX_BLINN_PHONG && no_lobe) return APT_CLASS_PHONG_NO_LOBE;
+    for (int c = 0; c < APT_N_CLASS_DEFS - 1; c++) if (kClass[c].mask & bit) return c;
+    return 0;
+}
+// The emitter set a scene's kernels are compiled for, as the index of the tables below
+static int group_emitter_set(int src_mask) { return (src_mask & ~APT_SRC_POINT_AREA) == 0 ? 0 : ((src_mask & ~APT_SRC_POINT_SPOT) == 0 ? 2 : 1); }      // point + area | all | point + spot (no area light: no emission code, no pdf in the record, both Philox blocks up front)
+static int vgroup_emitter_set(int src_mask) { return (src_mask & ~APT_SRC_POINT_AREA) == 0 ? 0 : 1; }                                                       // point + area | all
+typedef void (*group_fn)(DevScene, Params, Queues, Counters*, GroupIn, int, int);
+#ifndef APT_GROUP0_WAVES
+#define APT_GROUP0_WAVES 5
+#endif
+#define APT_GROUP_MASKS(G) group_mask(G, 0), group_mask(G, 1), group_mask(G, 2), group_mask(G, 3), group_mask(G, 4), group_mask(G, 5)
+static_assert(APT_GROUP_SLOTS == 6 && APT_VGROUP_SLOTS == 4, "APT_GROUP_MASKS and APT_VGROUP_ROW spell out every member slot");
+#define APT_GROUP_ROW(SM) {k_shade_group<SM, APT_GROUP0_WAVES, APT_GROUP_MASKS(0)>, k_shade_group<SM, 4, APT_GROUP_MASKS(1)>}
+// (group 0 at five waves: 93 VGPRs with point + spot lights, 96 and one 8-byte scratch slot with area lights; at four it took 99)
+static const group_fn kGroupShade[3][APT_N_GROUPS] = {APT_GROUP_ROW(APT_SRC_POINT_AREA), APT_GROUP_ROW(APT_SRC_ALL), APT_GROUP_ROW(APT_SRC_POINT_SPOT)};      // [group_emitter_set][group]
+typedef void (*group_tr_fn)(DevScene, Params, Queues, Counters*, GroupIn, int, int, TransQ);
+#define APT_GROUP_TR_ROW(SM) {k_shade_group_tr<SM, APT_GROUP_MASKS(0)>, k_shade_group_tr<SM, APT_GROUP_MASKS(1)>}
+static const group_tr_fn kGroupShadeTr[3][APT_N_GROUPS] = {APT_GROUP_TR_ROW(APT_SRC_POINT_AREA), APT_GROUP_TR_ROW(APT_SRC_ALL), APT_GROUP_TR_ROW(APT_SRC_POINT_SPOT)};      // the same, transient renders
+typedef void (*extend_fn)(DevScene, Params, Queues, Counters*, int, const uint32_t*, LdsPlan);
+typedef void (*shadow_fn)(DevScene, Params, Queues, Counters*, LdsPlan);
+typedef void (*occluded_fn)(DevScene, uint32_t, const float*, const float*, const float*, int*, LdsPlan);
 static_assert(TRACE_BVH == 0 && TRACE_SWEEP == 1 && TRACE_TILE == 2 && TRACE_FLAT == 3 && TRACE_VFLAT == 4, "the kernel tables below are indexed by traversal mode");
 static const char* const kTraversalName[4] = {"bvh", "sweep", "tile", "flat"};      // [mode]: the words of APT_TRAVERSAL (adapt_amd/renderer.py TRAVERSAL_NAMES repeats them for info())
 static const extend_fn kExtend[4][2] = {{k_extend<TRACE_BVH, 0>, k_extend<TRACE_BVH, 1>}, {k_extend<TRACE_SWEEP, 0>, k_extend<TRACE_SWEEP, 1>}, {k_extend<TRACE_TILE, 0>, k_extend<TRACE_TILE, 1>},
@@ -113,20 +139,16 @@ static const extend_fn kFixFlat[2] = {APT_FLAT_FN(k_fix_flat<0>), APT_FLAT_FN(k_
 static const extend_fn kExtendDyn[2] = {k_extend_dyn<0>, k_extend_dyn<1>};      // BVH walk with dynamic ray fetch [sorted]
 static const shadow_fn kShadow[4] = {k_shadow<TRACE_BVH>, k_shadow<TRACE_SWEEP>, k_shadow<TRACE_TILE>, /* TRACE_FLAT */ APT_FLAT_FN(k_shadow_flat<1>)};      // (flat: the hot variant; its list is served by the next kFixFlat launch)
 static const occluded_fn kOccluded[4] = {k_occluded<TRACE_BVH>, k_occluded<TRACE_SWEEP>, k_occluded<TRACE_TILE>, /* TRACE_FLAT */ APT_FLAT_FN(k_occluded_flat)};
-// Volumetric shading sorted by EVENT (volumetric.hpp k_vevent / k_vshade_ev): one queue per surface class (kClassMask order; the volumetric
-// tracer does not split Blinn-Phong by lobe) and one for the medium, shaded by the group kernels below; textured scenes, or scenes with
-// more classes than queues, keep ONE surface queue, shaded by the all-models kernel: [emitter set: point + area | all][without / with a grid volume]
+// Volumetric shading sorted by EVENT: the class queues are shaded by the group kernels below; textured scenes, or scenes with more classes than
+// queues, keep ONE surface queue, shaded by the all-models kernel: [vgroup_emitter_set][without / with a grid volume]
 typedef void (*vevent_fn)(DevScene, Params, Queues, Counters*, int, int);
 typedef void (*vev_shade_fn)(DevScene, Params, Queues, Counters*, int, int);
 static const vevent_fn kVEvent[2] = {k_vevent<0>, k_vevent<1>};
-static const vev_shade_fn kVEventAll[2][2] = {{k_vshade_ev<APT_BX_ALL, 0x03, 0, 0>, k_vshade_ev<APT_BX_ALL, 0x03, 1, 0>}, {k_vshade_ev<APT_BX_ALL, APT_SRC_ALL, 0, 0>, k_vshade_ev<APT_BX_ALL, APT_SRC_ALL, 1, 0>}};
-// ... launched in register-footprint groups (volumetric.hpp k_vshade_ev_group): class definition -> (group, member slot); the medium is member 0 of group 1
+static const vev_shade_fn kVEventAll[2][2] = {{k_vshade_ev<APT_BX_ALL, APT_SRC_POINT_AREA, 0, 0>, k_vshade_ev<APT_BX_ALL, APT_SRC_POINT_AREA, 1, 0>}, {k_vshade_ev<APT_BX_ALL, APT_SRC_ALL, 0, 0>, k_vshade_ev<APT_BX_ALL, APT_SRC_ALL, 1, 0>}};
 typedef void (*vev_group_fn)(DevScene, Params, Queues, Counters*, VGroupIn, int);
-#define APT_N_VGROUPS 3
-static const int kVClassGroup[APT_N_CLASS_DEFS] = {0, 2, 0, 0, 2, 2, 1, 0, 1, 2};
-static const int kVClassSlot[APT_N_CLASS_DEFS] = {0, 0, 1, 2, 1, 2, 1, 3, 2, 3};
-#define APT_VGROUP_ROW(SM, VOL) {k_vshade_ev_group<SM, VOL, 4, 0x002, 0x040, 0x504, 0x200>, k_vshade_ev_group<SM, VOL, 3, APT_VEV_MEDIUM_CODE, 0x080, 0x008, 0>, k_vshade_ev_group<SM, VOL, 1, 0x001, 0x010, 0x020, 0x001>}
-static const vev_group_fn kVGroup[2][2][APT_N_VGROUPS] = {{APT_VGROUP_ROW(0x03, 0), APT_VGROUP_ROW(0x03, 1)}, {APT_VGROUP_ROW(APT_SRC_ALL, 0), APT_VGROUP_ROW(APT_SRC_ALL, 1)}};      // [emitter set][grid volume][group]
+#define APT_VGROUP_MASKS(G) vgroup_mask(G, 0), vgroup_mask(G, 1), vgroup_mask(G, 2), vgroup_mask(G, 3)
+#define APT_VGROUP_ROW(SM, VOL) {k_vshade_ev_group<SM, VOL, 4, APT_VGROUP_MASKS(0)>, k_vshade_ev_group<SM, VOL, 3, APT_VGROUP_MASKS(1)>, k_vshade_ev_group<SM, VOL, 1, APT_VGROUP_MASKS(2)>}
+static const vev_group_fn kVGroup[2][2][APT_N_VGROUPS] = {{APT_VGROUP_ROW(APT_SRC_POINT_AREA, 0), APT_VGROUP_ROW(APT_SRC_POINT_AREA, 1)}, {APT_VGROUP_ROW(APT_SRC_ALL, 0), APT_VGROUP_ROW(APT_SRC_ALL, 1)}};      // [vgroup_emitter_set][grid volume][group]
 typedef void (*vshadow_fn)(DevScene, Params, Queues, Counters*, LdsPlan, int);
 static const vshadow_fn kVShadow[5] = {k_vshadow<TRACE_BVH>, k_vshadow<TRACE_SWEEP>, k_vshadow<TRACE_TILE>, /* TRACE_FLAT: never the walk's mode (plan_lds_and_grids) */ nullptr,
                                        /* TRACE_VFLAT */ APT_FLAT_FN(k_vshadow_flat)};     // volumetric: transmittance walk (one closest-hit query per pass; TRACE_VFLAT: the flat sweep, two samples per lane, every segment in one launch)
@@ -228,7 +250,7 @@ struct apt_renderer {
     vev_shade_fn vev_all = nullptr;
     bool vev_live[APT_MAX_CLASSES] = {};      // an event queue that can receive entries at all (a class of null surfaces only is never shaded)
     vev_group_fn vgroup_fn[APT_N_VGROUPS] = {};           // ... the event kernels in groups
-    int vgroup_cls[APT_N_VGROUPS][4] = {};                // ... event queue of each member slot (-1: none)
+    int vgroup_cls[APT_N_VGROUPS][APT_VGROUP_SLOTS] = {};                // ... event queue of each member slot (-1: none)
     group_fn group_fn_[APT_N_GROUPS] = {};                // ... the group kernels for this scene's emitter set
     int group_cls[APT_N_GROUPS][APT_GROUP_SLOTS] = {};    // ... compact class id of each member slot (-1: the scene has no such class)
     std::string shade_name;
@@ -412,6 +434,12 @@ static int build_tree(const apt_scene_desc* d, int device, apt::WideBvhData& wid
     timer.tick("8-wide collapse");
     return APT_OK;
 }
+// One packed material row (bxdf_i[4], bxdf_f[13]) -> DevBxdf: the scene's table and apt_bxdf_probe's
+static void fill_bxdf(DevBxdf& b, const int32_t* bi, const float* bf) {
+    memset(&b, 0, sizeof(b));
+    b.type = bi[0]; b.is_delta = bi[1]; b.is_bsdf = bi[2];
+    b.k_d = mk3(bf[0], bf[1], bf[2]); b.k_s = mk3(bf[3], bf[4], bf[5]); b.k_g = mk3(bf[6], bf[7], bf[8]); b.mean = mk3(bf[9], bf[10], bf[11]); b.ior = bf[12];
+}
 // Materials (DevBxdf, bx_mask) and the classes present in this scene -> compact ids, per object and per primitive (the sorting extend).
 // Blinn-Phong objects without a specular lobe (the diffuse walls of most scenes) get a class of their own, whose kernel carries no double-precision
 // pow - unless that would need more class queues than there are (APT_MAX_CLASSES), then they stay with the other Blinn-Phong objects.
@@ -420,11 +448,10 @@ static int pack_materials(const apt_scene_desc* d, apt_scene* s, const std::vect
     std::vector<DevBxdf> bx((size_t)O);
     std::vector<uint8_t> no_lobe((size_t)O, 0);
     for (int o = 0; o < O; o++) {
-        const int32_t* bi = d->bxdf_i + 4 * o; const float* bf = d->bxdf_f + 13 * o;
-        DevBxdf& b = bx[(size_t)o]; memset(&b, 0, sizeof(b));
-        b.type = bi[0]; b.is_delta = bi[1]; b.is_bsdf = bi[2];
-        s->bx_mask |= b.is_bsdf ? (b.type == 0 ? 0x100 : (b.type == 1 ? 0x200 : 0x400)) : (1 << (b.type & 7));
-        b.k_d = mk3(bf[0], bf[1], bf[2]); b.k_s = mk3(bf[3], bf[4], bf[5]); b.k_g = mk3(bf[6], bf[7], bf[8]); b.mean = mk3(bf[9], bf[10], bf[11]); b.ior = bf[12];
+        const float* bf = d->bxdf_f + 13 * o;
+        DevBxdf& b = bx[(size_t)o];
+        fill_bxdf(b, d->bxdf_i + 4 * o, bf);
+        s->bx_mask |= bx_bit(b.is_bsdf, b.type);
         bool lean = !b.is_bsdf && b.type == 0;      // Blinn-Phong without a specular lobe: k_s = +0, finite k_g >= 0
         for (int a = 0; a < 3; a++) lean = lean && bf[3 + a] == 0.f && !std::signbit(bf[3 + a]) && bf[6 + a] >= 0.f && std::isfinite(bf[6 + a]);
         no_lobe[(size_t)o] = lean ? 1 : 0;
@@ -593,19 +620,23 @@ static int pack_textures(const apt_scene_desc* d, apt_scene* s) {
     }
     return APT_OK;
 }
+// One packed medium row (med_i[1], med_f[16]) -> DevMedium: the scene's table and apt_medium_probe's
+static void fill_medium(DevMedium& m, int32_t type, const float* f) {
+    memset(&m, 0, sizeof(m));
+    m.type = type; m.ior = f[0];
+    m.u_s = mk3(f[1], f[2], f[3]); m.u_a = mk3(f[4], f[5], f[6]); m.u_e = mk3(f[7], f[8], f[9]);
+    m.par = mk3(f[10], f[11], f[12]); m.pdf = mk3(f[13], f[14], f[15]);
+}
 // Participating media, n_objects + 1 rows (transparent unless the description carries the tables); the union of the object boxes (path_tracer.py:130-134).
 static int pack_media(const apt_scene_desc* d, apt_scene* s) {
     const int O = s->n_objects;
     std::vector<DevMedium> md((size_t)O + 1);
     for (int o = 0; o <= O; o++) {
-        DevMedium& m = md[(size_t)o]; memset(&m, 0, sizeof(m));
+        DevMedium& m = md[(size_t)o];
         if (d->med_i && d->med_f) {
-            const float* f = d->med_f + 16 * (size_t)o;
-            m.type = d->med_i[o]; m.ior = f[0];
-            m.u_s = mk3(f[1], f[2], f[3]); m.u_a = mk3(f[4], f[5], f[6]); m.u_e = mk3(f[7], f[8], f[9]);
-            m.par = mk3(f[10], f[11], f[12]); m.pdf = mk3(f[13], f[14], f[15]);
+            fill_medium(m, d->med_i[o], d->med_f + 16 * (size_t)o);
             if (m.type < -1 || m.type > 3) return fail(APT_E_INVALID, "apt_scene_create: unknown medium type");
-        } else { m.type = -1; m.ior = (o < O) ? d->bxdf_f[13 * o + 12] : d->world_ior; m.pdf = mk3(1.f, 0.f, 0.f); }
+        } else { memset(&m, 0, sizeof(m)); m.type = -1; m.ior = (o < O) ? d->bxdf_f[13 * o + 12] : d->world_ior; m.pdf = mk3(1.f, 0.f, 0.f); }
     }
     if (!put("med", s->med, md)) return APT_E_HIP;
     s->dev.med = s->med.as<DevMedium>();
@@ -803,29 +834,29 @@ static int pick_shading(apt_renderer* r) {
         r->vev_single = (textured || sc->n_classes + 1 > APT_MAX_CLASSES) ? 1 : 0;
         const int n_surf = r->vev_single ? 1 : sc->n_classes;
         r->n_cq = n_surf + 1;
-        const int smi = ((sc->src_mask & ~0x03) == 0) ? 0 : 1, vi = sc->has_volume ? 1 : 0;
+        const int smi = vgroup_emitter_set(sc->src_mask), vi = sc->has_volume ? 1 : 0;
         r->vev_all = kVEventAll[smi][vi];
         for (size_t o = 0; o < sc->obj_class.size(); o++)           // which surface queues can receive a hit at all
             if (!sc->obj_null[o]) r->vev_live[r->vev_single ? 0 : sc->obj_class[o]] = true;
         r->vev_live[n_surf] = true;
-        for (int g = 0; g < APT_N_VGROUPS; g++) { r->vgroup_fn[g] = kVGroup[smi][vi][g]; for (int k = 0; k < 4; k++) r->vgroup_cls[g][k] = -1; }
-        if (!r->vev_single) for (int c = 0; c < n_surf; c++) if (r->vev_live[c]) r->vgroup_cls[kVClassGroup[sc->class_def[c]]][kVClassSlot[sc->class_def[c]]] = c;
+        for (int g = 0; g < APT_N_VGROUPS; g++) { r->vgroup_fn[g] = kVGroup[smi][vi][g]; for (int k = 0; k < APT_VGROUP_SLOTS; k++) r->vgroup_cls[g][k] = -1; }
+        if (!r->vev_single) for (int c = 0; c < n_surf; c++) if (r->vev_live[c]) r->vgroup_cls[kClass[sc->class_def[c]].vgroup][kClass[sc->class_def[c]].vslot] = c;
         r->vgroup_cls[1][0] = n_surf;                         // the medium's queue is the last one
         for (int a = 0; a < 3; a++) {                         // path_tracer.py:136-138
             p.w_min[a] = std::min(c.cam_t[a], sc->box_min[a]) - 0.1f; p.w_max[a] = std::max(c.cam_t[a], sc->box_max[a]) + 0.1f;
         }
         r->shade_name = std::string(sc->has_volume ? "volumetric + grid volume, sorted by event: medium | " : "volumetric, sorted by event: medium | ");
         if (r->vev_single) r->shade_name += "all surface models";
-        else for (int c = 0; c < sc->n_classes; c++) r->shade_name += std::string(c ? "+" : "") + kClassName[sc->class_def[c]];
+        else for (int c = 0; c < sc->n_classes; c++) r->shade_name += std::string(c ? "+" : "") + kClass[sc->class_def[c]].name;
     } else if (r->pipeline == PIPE_SORTED) {
         r->n_cq = sc->n_classes;
-        const int smi = ((sc->src_mask & ~0x03) == 0) ? 0 : (((sc->src_mask & ~0x05) == 0) ? 2 : 1);
+        const int smi = group_emitter_set(sc->src_mask);
         for (int g = 0; g < APT_N_GROUPS; g++) { r->group_fn_[g] = kGroupShade[smi][g]; for (int k = 0; k < APT_GROUP_SLOTS; k++) r->group_cls[g][k] = -1; }
         r->shade_name = "sorted, launched in register-footprint groups:";
         for (int g = 0; g < APT_N_GROUPS; g++) r->group_tr_[g] = kGroupShadeTr[smi][g];
         for (int c = 0; c < sc->n_classes; c++) {
-            r->group_cls[kClassGroup[sc->class_def[c]]][kClassSlot[sc->class_def[c]]] = c;
-            r->shade_name += std::string(c ? "+" : "") + kClassName[sc->class_def[c]];
+            r->group_cls[kClass[sc->class_def[c]].group][kClass[sc->class_def[c]].slot] = c;
+            r->shade_name += std::string(c ? "+" : "") + kClass[sc->class_def[c]].name;
         }
     } else {
         r->shade_name = r->shade->name;
@@ -1689,81 +1720,60 @@ APT_EXPORT int apt_occluded(apt_renderer* r, int32_t n, const float* o, const fl
     HIP_TRY(hipMemcpy(occ_out, bocc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return APT_OK;
 }
-APT_EXPORT int apt_rng_stream(int32_t device, uint32_t pixel, uint32_t seed, uint32_t sample, int32_t n, uint32_t* out) {
-    if (n <= 0 || !out) return fail(APT_E_INVALID, "apt_rng_stream: bad argument");
+// The probes below run device code on explicit inputs, for the parity tests.  Each one checks its arguments, decodes what is packed, and hands the rest to a Probe: the
+// device, inputs uploaded straight from the caller's arrays, a zero-filled output, and - after the entry point's one launch on the null stream - the error check, the wait and the copy back.
+static int use_device(const char* who, int device) {
     int ndev = 0;
     if (int rc = count_device(&ndev)) return rc;
+    if (device < 0 || device >= ndev) return fail(APT_E_INVALID, std::string(who) + ": device ordinal out of range");
     HIP_TRY(hipSetDevice(device));
-    DevBuf b; HIP_TRY(b.alloc((size_t)n * 4));
-    hipLaunchKernelGGL(k_rng_stream, dim3(1), dim3(64), 0, 0, pixel, seed, sample, n, b.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, b.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return APT_OK;
 }
-
-// BxDF / emitter probes: run the device shading code on explicit inputs (parity tests vs the golden vectors)
-static void fill_bxdf(DevBxdf& b, const int32_t* bi, const float* bf) {
-    memset(&b, 0, sizeof(b));
-    b.type = bi[0]; b.is_delta = bi[1]; b.is_bsdf = bi[2];
-    b.k_d = mk3(bf[0], bf[1], bf[2]); b.k_s = mk3(bf[3], bf[4], bf[5]); b.k_g = mk3(bf[6], bf[7], bf[8]); b.mean = mk3(bf[9], bf[10], bf[11]); b.ior = bf[12];
+struct Probe {
+    DevBuf in[3], out;
+    int begin(const char* who, int device, size_t out_bytes) {
+        if (int rc = use_device(who, device)) return rc;
+        HIP_TRY(out.alloc(out_bytes)); HIP_TRY(hipMemset(out.p, 0, out_bytes));
+        return APT_OK;
+    }
+    int finish(void* host_out) {
+        HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipMemcpy(host_out, out.p, out.bytes, hipMemcpyDeviceToHost));
+        return APT_OK;
+    }
+};
+APT_EXPORT int apt_rng_stream(int32_t device, uint32_t pixel, uint32_t seed, uint32_t sample, int32_t n, uint32_t* out) {
+    if (n <= 0 || !out) return fail(APT_E_INVALID, "apt_rng_stream: bad argument");
+    Probe pr; if (int rc = pr.begin("apt_rng_stream", device, (size_t)n * 4)) return rc;
+    hipLaunchKernelGGL(k_rng_stream, dim3(1), dim3(64), 0, 0, pixel, seed, sample, n, pr.out.as<uint32_t>());
+    return pr.finish(out);
 }
 APT_EXPORT int apt_bxdf_probe(int32_t device, int32_t n, const int32_t* bxdf_i, const float* bxdf_f, const float* dirs12, float world_ior,
                               int32_t do_sample, uint32_t seed, float* out) {
     if (n <= 0 || !bxdf_i || !bxdf_f || !dirs12 || !out) return fail(APT_E_INVALID, "apt_bxdf_probe: bad argument");
-    int ndev = 0;
-    if (int rc = count_device(&ndev)) return rc;
-    HIP_TRY(hipSetDevice(device));
     std::vector<DevBxdf> bx((size_t)n);
     for (int k = 0; k < n; k++) fill_bxdf(bx[(size_t)k], bxdf_i + 4 * k, bxdf_f + 13 * k);
-    std::vector<float> in(dirs12, dirs12 + (size_t)n * 12);
-    DevBuf dbx, din, dout;
-    HIP_TRY(upload(dbx, bx)); HIP_TRY(upload(din, in));
-    const size_t per = do_sample ? 9 : 4;
-    HIP_TRY(dout.alloc((size_t)n * per * 4));
-    if (do_sample) hipLaunchKernelGGL(k_bxdf_sample, dim3((n + 63) / 64), dim3(64), 0, 0, n, dbx.as<DevBxdf>(), din.as<float>(), world_ior, seed, dout.as<float>());
-    else hipLaunchKernelGGL(k_bxdf_eval, dim3((n + 63) / 64), dim3(64), 0, 0, n, dbx.as<DevBxdf>(), din.as<float>(), world_ior, dout.as<float>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * per * 4, hipMemcpyDeviceToHost));
-    return APT_OK;
+    Probe pr; if (int rc = pr.begin("apt_bxdf_probe", device, (size_t)n * (do_sample ? 9 : 4) * 4)) return rc;
+    HIP_TRY(upload(pr.in[0], bx.data(), bx.size())); HIP_TRY(upload(pr.in[1], dirs12, (size_t)n * 12));
+    if (do_sample) hipLaunchKernelGGL(k_bxdf_sample, dim3((n + 63) / 64), dim3(64), 0, 0, n, pr.in[0].as<DevBxdf>(), pr.in[1].as<float>(), world_ior, seed, pr.out.as<float>());
+    else hipLaunchKernelGGL(k_bxdf_eval, dim3((n + 63) / 64), dim3(64), 0, 0, n, pr.in[0].as<DevBxdf>(), pr.in[1].as<float>(), world_ior, pr.out.as<float>());
+    return pr.finish(out);
 }
 APT_EXPORT int apt_transient_bin_probe(int32_t device, int32_t n, const float* t, float min_time, float interval, int32_t n_bins, int32_t* out) {
     if (n <= 0 || !t || !out || n_bins <= 0) return fail(APT_E_INVALID, "apt_transient_bin_probe: bad argument");
-    int ndev = 0;
-    if (int rc = count_device(&ndev)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    TransQ tq{};
-    transient_window(tq, n_bins, min_time, interval);
-    std::vector<float> in(t, t + (size_t)n);
-    DevBuf din, dout;
-    HIP_TRY(upload(din, in)); HIP_TRY(dout.alloc((size_t)n * 4));
-    hipLaunchKernelGGL(k_transient_bin_probe, dim3((n + 63) / 64), dim3(64), 0, 0, tq, n, din.as<float>(), dout.as<int>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return APT_OK;
+    TransQ tq{}; transient_window(tq, n_bins, min_time, interval);
+    Probe pr; if (int rc = pr.begin("apt_transient_bin_probe", device, (size_t)n * 4)) return rc;
+    HIP_TRY(upload(pr.in[0], t, (size_t)n));
+    hipLaunchKernelGGL(k_transient_bin_probe, dim3((n + 63) / 64), dim3(64), 0, 0, tq, n, pr.in[0].as<float>(), pr.out.as<int>());
+    return pr.finish(out);
 }
 APT_EXPORT int apt_medium_probe(int32_t device, int32_t n, const int32_t* med_i, const float* med_f, int32_t mode, const float* in7, uint32_t seed, float* out8) {
     if (n <= 0 || !med_i || !med_f || !in7 || !out8 || mode < 0 || mode > 2) return fail(APT_E_INVALID, "apt_medium_probe: bad argument");
-    int ndev = 0;
-    if (int rc = count_device(&ndev)) return rc;
-    HIP_TRY(hipSetDevice(device));
     std::vector<DevMedium> md((size_t)n);
-    for (int k = 0; k < n; k++) {
-        const float* f = med_f + 16 * (size_t)k; DevMedium& m = md[(size_t)k]; memset(&m, 0, sizeof(m));
-        m.type = med_i[k]; m.ior = f[0]; m.u_s = mk3(f[1], f[2], f[3]); m.u_a = mk3(f[4], f[5], f[6]); m.u_e = mk3(f[7], f[8], f[9]);
-        m.par = mk3(f[10], f[11], f[12]); m.pdf = mk3(f[13], f[14], f[15]);
-    }
-    std::vector<float> in(in7, in7 + (size_t)n * 7);
-    DevBuf dmed, din, dout;
-    HIP_TRY(upload(dmed, md)); HIP_TRY(upload(din, in)); HIP_TRY(dout.alloc((size_t)n * 32));
-    HIP_TRY(hipMemset(dout.p, 0, (size_t)n * 32));
-    hipLaunchKernelGGL(k_medium_probe, dim3((n + 63) / 64), dim3(64), 0, 0, n, dmed.as<DevMedium>(), mode, din.as<float>(), seed, dout.as<float>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out8, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-    return APT_OK;
+    for (int k = 0; k < n; k++) fill_medium(md[(size_t)k], med_i[k], med_f + 16 * (size_t)k);
+    Probe pr; if (int rc = pr.begin("apt_medium_probe", device, (size_t)n * 32)) return rc;
+    HIP_TRY(upload(pr.in[0], md.data(), md.size())); HIP_TRY(upload(pr.in[1], in7, (size_t)n * 7));
+    hipLaunchKernelGGL(k_medium_probe, dim3((n + 63) / 64), dim3(64), 0, 0, n, pr.in[0].as<DevMedium>(), mode, pr.in[1].as<float>(), seed, pr.out.as<float>());
+    return pr.finish(out8);
 }
 APT_EXPORT int apt_volume_probe(int32_t device, int32_t n, const int32_t* vol_i, const float* vol_f, const float* vol_grid, int32_t mode,
                                 const float* in10, uint32_t seed, float* out8) {
@@ -1774,32 +1784,20 @@ APT_EXPORT int apt_volume_probe(int32_t device, int32_t n, const int32_t* vol_i,
         const float ch = in10[10 * (size_t)k + 6];
         if (!(ch == 0.f || ch == 1.f || ch == 2.f)) return fail(APT_E_INVALID, "apt_volume_probe: channel must be 0, 1 or 2");
     }
-    int ndev = 0;
-    if (int rc = count_device(&ndev)) return rc;
-    if (device < 0 || device >= ndev) return fail(APT_E_INVALID, "apt_volume_probe: device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-    std::vector<float> grid(vol_grid, vol_grid + (size_t)vo.xres * (size_t)vo.yres * (size_t)vo.zres * 3), in(in10, in10 + (size_t)n * 10);
-    DevBuf dgrid, din, dout;
-    HIP_TRY(upload(dgrid, grid)); HIP_TRY(upload(din, in)); HIP_TRY(dout.alloc((size_t)n * 32));
-    HIP_TRY(hipMemset(dout.p, 0, (size_t)n * 32));
-    vo.grid = dgrid.as<float>();
-    hipLaunchKernelGGL(k_volume_probe, dim3((n + 63) / 64), dim3(64), 0, 0, n, vo, mode, din.as<float>(), seed, dout.as<float>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out8, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-    return APT_OK;
+    Probe pr; if (int rc = pr.begin("apt_volume_probe", device, (size_t)n * 32)) return rc;
+    HIP_TRY(upload(pr.in[0], vol_grid, (size_t)vo.xres * (size_t)vo.yres * (size_t)vo.zres * 3)); HIP_TRY(upload(pr.in[1], in10, (size_t)n * 10));
+    vo.grid = pr.in[0].as<float>();
+    hipLaunchKernelGGL(k_volume_probe, dim3((n + 63) / 64), dim3(64), 0, 0, n, vo, mode, pr.in[1].as<float>(), seed, pr.out.as<float>());
+    return pr.finish(out8);
 }
 APT_EXPORT int apt_emitter_probe(const apt_scene* sc, int32_t n, const float* in11, uint32_t seed, float* out12) {
     if (!sc || n <= 0 || !in11 || !out12) return fail(APT_E_INVALID, "apt_emitter_probe: bad argument");
-    HIP_TRY(hipSetDevice(sc->device));
-    std::vector<float> in(in11, in11 + (size_t)n * 11);
-    DevBuf din, dout;
-    HIP_TRY(upload(din, in)); HIP_TRY(dout.alloc((size_t)n * 48));
-    hipLaunchKernelGGL(k_emitter_probe, dim3((n + 63) / 64), dim3(64), 0, 0, sc->dev, n, din.as<float>(), seed, dout.as<float>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out12, dout.p, (size_t)n * 48, hipMemcpyDeviceToHost));
-    return APT_OK;
+    for (int k = 0; k < n; k++)            // the kernel indexes the scene's emitter table with it
+        if (const float e = in11[11 * (size_t)k]; !(e >= 0.f && e < (float)sc->n_sources && e == std::floor(e))) return fail(APT_E_INVALID, "apt_emitter_probe: no such emitter");
+    Probe pr; if (int rc = pr.begin("apt_emitter_probe", sc->device, (size_t)n * 48)) return rc;
+    HIP_TRY(upload(pr.in[0], in11, (size_t)n * 11));
+    hipLaunchKernelGGL(k_emitter_probe, dim3((n + 63) / 64), dim3(64), 0, 0, sc->dev, n, pr.in[0].as<float>(), seed, pr.out.as<float>());
+    return pr.finish(out12);
 }
 APT_EXPORT int apt_texture_probe(const apt_scene* sc, int32_t n, const int32_t* map_obj, const float* uv, float* out3) {
     if (!sc || n <= 0 || !map_obj || !uv || !out3) return fail(APT_E_INVALID, "apt_texture_probe: bad argument");
@@ -1808,24 +1806,16 @@ APT_EXPORT int apt_texture_probe(const apt_scene* sc, int32_t n, const int32_t* 
         const int m = map_obj[2 * k], o = map_obj[2 * k + 1];
         if (m < 0 || m > 2 || o < 0 || o >= sc->n_objects || !sc->dev.atlas[m]) return fail(APT_E_INVALID, "apt_texture_probe: no such texture");
     }
-    HIP_TRY(hipSetDevice(sc->device));
-    DevBuf dmo, duv, dout;
-    std::vector<int> mo(map_obj, map_obj + 2 * (size_t)n); std::vector<float> vuv(uv, uv + 2 * (size_t)n);
-    HIP_TRY(upload(dmo, mo)); HIP_TRY(upload(duv, vuv)); HIP_TRY(dout.alloc((size_t)n * 12));
-    hipLaunchKernelGGL(k_texture_probe, dim3((n + 63) / 64), dim3(64), 0, 0, sc->dev, n, dmo.as<int>(), duv.as<float>(), dout.as<float>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out3, dout.p, (size_t)n * 12, hipMemcpyDeviceToHost));
-    return APT_OK;
+    Probe pr; if (int rc = pr.begin("apt_texture_probe", sc->device, (size_t)n * 12)) return rc;
+    HIP_TRY(upload(pr.in[0], map_obj, 2 * (size_t)n)); HIP_TRY(upload(pr.in[1], uv, 2 * (size_t)n));
+    hipLaunchKernelGGL(k_texture_probe, dim3((n + 63) / 64), dim3(64), 0, 0, sc->dev, n, pr.in[0].as<int>(), pr.in[1].as<float>(), pr.out.as<float>());
+    return pr.finish(out3);
 }
 // Shader clock while the whole chip is busy (bench.py prices its VALU roofline with it): median over the waves of a full grid of
 // cycle-counter ticks per 100 MHz wall-clock tick.
 APT_EXPORT int apt_measure_sclk_mhz(int32_t device, float* mhz) {
     if (!mhz) return fail(APT_E_INVALID, "apt_measure_sclk_mhz: bad argument");
-    int ndev = 0;
-    if (int rc = count_device(&ndev)) return rc;
-    if (device < 0 || device >= ndev) return fail(APT_E_INVALID, "apt_measure_sclk_mhz: device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = use_device("apt_measure_sclk_mhz", device)) return rc;
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     const int grid = std::max(1, prop.multiProcessorCount) * 8, n_waves = grid * (BLOCK / 64);

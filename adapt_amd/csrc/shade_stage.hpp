@@ -186,7 +186,7 @@ APT_D void vertex_reset(Vertex& vx) {
 template <int BM, int SM, int TEX, typename RNG>
 APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, RNG& rng, int prim, f3 rec_kd, uint32_t meta, float ray_pdf, float2 uv, int bounce, const uint32_t* jitter_tail = nullptr) {
     const bool was_spec = (meta >> 24) & 1u;
-    if (BM == 0x002) vx.bx.k_d = rec_kd;               // Lambertian-only scenes: type 1, not delta, not a BSDF (vertex_reset), colour from the record
+    if (BM == APT_BX_LAMBERTIAN) vx.bx.k_d = rec_kd;               // Lambertian-only scenes: type 1, not delta, not a BSDF (vertex_reset), colour from the record
     else vx.bx = ld_bxdf_lane((A_->sc).bxdf + vx.it.obj_id);
     if (TEX && (A_->sc).tex_i != nullptr) {                // the scene declares image textures (TEX kernels only)
         f3 tx;
@@ -210,7 +210,7 @@ APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, RNG& rng, int prim, f3 
     }
     if constexpr (std::is_same<RNG, DrawWindow>::value) {
         // every draw of this vertex is decided: the roulette by its throughput, a second emitter index by the surface it is on (sample_light)
-        static_assert(BM == 0x002 && !(SM & 2), "a draw window serves [roulette] index [index] u1 u2: Lambertian surfaces, emitters that draw nothing");
+        static_assert(BM == APT_BX_LAMBERTIAN && !(SM & APT_SRC_AREA), "a draw window serves [roulette] index [index] u1 u2: Lambertian surfaces, emitters that draw nothing");
         bool roulette = false; float mx = 0.f;
         if ((A_->p).use_rr) { mx = max3(vx.thr); roulette = mx < (A_->p).rr_threshold && bounce >= (A_->p).rr_bounce_th; }
         else if (max3(vx.thr) < 1e-4f) return false;
@@ -221,7 +221,7 @@ APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, RNG& rng, int prim, f3 
         if (roulette) vx.thr = vx.thr * srcp(mx + 1e-7f);
         return true;
     } else {
-        if (!(SM & 2)) rng_open(rng);               // no area lights: a shade with one light sample draws at most five numbers (rng.hpp)
+        if (!(SM & APT_SRC_AREA)) rng_open(rng);               // no area lights: a shade with one light sample draws at most five numbers (rng.hpp)
         if ((A_->p).use_rr) {
             float mx = max3(vx.thr);
             if (mx < (A_->p).rr_threshold && bounce >= (A_->p).rr_bounce_th) {
@@ -280,7 +280,7 @@ APT_D LightSample sample_light(const ShadeArgs3* A_, Vertex& vx, R& rng, const E
 // measured: it costs the Lambertian kernel its fourth wave per SIMD, 122 -> 130 / 158 VGPRs inline / as a loop.)
 template <int BM, int SM, typename R, typename Gather>
 APT_D f3 emit_and_scatter(const ShadeArgs3* A_, Vertex& vx, R& rng, float& new_pdf, bool& is_spec, Gather&& gather) {
-    if ((SM & 2) && vx.hit_light >= 0) {
+    if ((SM & APT_SRC_AREA) && vx.hit_light >= 0) {
         const f3 emit_int = emitter_eval_le((A_->sc).src[vx.hit_light], vx.hit_point - vx.o, vx.it.n_s);
         if (!(emit_int.x == 0.f && emit_int.y == 0.f && emit_int.z == 0.f)) gather((emit_int * vx.emission_weight) * vx.thr);
     }
@@ -342,7 +342,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
     // registers.  Without them the kernel allocates 91 VGPRs - five waves per SIMD instead of four - and three render lanes gain 6 %:
     // C2 4 310 -> 4 560 Msamples/s on the same box.)
     // the generator: without area lights a Lambertian vertex's draws are all decided when it is opened, and it reads them from a draw window (rng.hpp)
-    constexpr bool WINDOW = APT_DRAW_WINDOW != 0 && BM == 0x002 && !(SM & 2);
+    constexpr bool WINDOW = APT_DRAW_WINDOW != 0 && BM == APT_BX_LAMBERTIAN && !(SM & APT_SRC_AREA);
     typedef typename std::conditional<WINDOW, DrawWindow, Philox>::type Rng;
     constexpr bool PFP = TEX == 0 && !CAM;                    // (a camera-fed row knows its primitive when it has traced its ray: nothing to request ahead)
     static_assert(APT_FLAT_MAX_PRIMS < (int)TR_NO_PRIM, "the packed record keeps the hit primitive in 8 bits");
@@ -419,7 +419,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
                 alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0, WINDOW ? jitter_tail : nullptr);
             }
         }
-        if (!CAM && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & 2) ray_pdf = dd.w; }
+        if (!CAM && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & APT_SRC_AREA) ray_pdf = dd.w; }
         if (!CAM && alive) {
             const float4 a = ldq(trA, idx << 4), b_ = ldq(trB, idx << 4), c = ldq(trC, idx << 4);
             vx.o = mk3(a.x, a.y, a.z); vx.d = mk3(b_.x, b_.y, b_.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = __float_as_uint(c.w);
@@ -583,11 +583,11 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
                 if (CQ) {
                     const float4 a = ldq(cqA, idx << 4), b_ = ldq(cqB, idx << 4), c = ldq(cqC, idx << 4), dd = ldq(cqD, idx << 4);
                     vx.o = mk3(a.x, a.y, a.z); t_in = a.w; vx.d = mk3(b_.x, b_.y, b_.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = __float_as_uint(c.w);
-                    meta = __float_as_uint(dd.x); if (SM & 2) ray_pdf = dd.y; uv.x = dd.z; uv.y = dd.w;
+                    meta = __float_as_uint(dd.x); if (SM & APT_SRC_AREA) ray_pdf = dd.y; uv.x = dd.z; uv.y = dd.w;
                 } else {
                     vx.o = ld3q(in.ray_o, (A_->p).cap, io); vx.d = ld3q(in.ray_d, (A_->p).cap, io); vx.thr = ld3q(in.thr, (A_->p).cap, io);
                     vx.id = ldq(in.id, io); meta = ldq(in.meta, io); t_in = ldq(in.t, io);
-                    if (SM & 2) ray_pdf = ldq(in.pdf, io);          // (its only reader is the emission MIS weight: scenes without area lights never look at it)
+                    if (SM & APT_SRC_AREA) ray_pdf = ldq(in.pdf, io);          // (its only reader is the emission MIS weight: scenes without area lights never look at it)
                     if ((A_->sc).has_vn || (TEX && (A_->sc).tex_i != nullptr)) { uv.x = ldq(in.u, io); uv.y = ldq(in.v, io); }      // otherwise nobody reads the barycentrics (and the flat extend kernel does not write them)
                 }
                 f3 rec_kd;
@@ -659,7 +659,7 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
             st3q((A_->q).thr[nxt], (A_->p).cap, so, vx.thr);
             stq((A_->q).id[nxt], so, vx.id);
             stq((A_->q).meta[nxt], so, pack_meta(rng.draw, (uint32_t)(bounce + 1), is_spec));
-            if (SM & 2) stq((A_->q).pdf[nxt], so, new_pdf);
+            if (SM & APT_SRC_AREA) stq((A_->q).pdf[nxt], so, new_pdf);
         }
     }
     tally_flush(tl, s_draws, cnt, sl.q);
@@ -709,7 +709,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_
 // The classes of a bounce are independent, so a group kernel walks the class queues of its members one after the other - every workgroup
 // its sub-queue of class A, then of class B, ... with no barrier in between: a workgroup that runs out of A entries starts on B while
 // others still shade A - and the launch boundary between them is gone.  A kernel's register allocation is the maximum over its members',
-// so the groups follow the footprints (api.hip kClassGroup).  Round 5 had three - up to 128 VGPRs / four waves per SIMD, up to 168 / three,
+// so the groups follow the footprints (api.hip kClass).  Round 5 had three - up to 128 VGPRs / four waves per SIMD, up to 168 / three,
 // beyond / two (modified Phong and Fresnel blend with their double-precision pow: 201-217).  With the product build's float transcendentals
 // and 1-ulp divisions (round 6) no class kernel allocates more than 125, so there are TWO: the lean classes - Lambertian, delta, lobe-free
 // Blinn-Phong, Lambertian transmission: 93-96 VGPRs, held to FIVE waves per SIMD - and everything else (Blinn-Phong, Oren-Nayar, thin coat,

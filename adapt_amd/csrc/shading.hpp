@@ -162,13 +162,27 @@ APT_D f3 lambert_sample(const DevBxdf& b, f3 normal, R& r, f3& spec, float& pdf)
     spec = lambert_eval(b, normal, out);
     return out;
 }
+// Material-set and emitter-set masks.  The dispatchers take the scene's mask as a template argument so that a shade kernel specialised for,
+// say, {Lambertian} x {point} carries none of the other models' registers or code.  Bit t (0..7) = BRDF type t (the `case` labels of
+// brdf_eval / brdf_sample below), bits 8..10 = the BSDFs (surface_*) ...
+#define BXHAS(M, bits) (((M) & (bits)) != 0)
+constexpr int APT_BX_BLINN_PHONG = 1 << 0, APT_BX_LAMBERTIAN = 1 << 1, APT_BX_MIRROR = 1 << 2, APT_BX_MICROFACET = 1 << 3, APT_BX_MOD_PHONG = 1 << 4,
+              APT_BX_FRESNEL_BLEND = 1 << 5, APT_BX_OREN_NAYAR = 1 << 6, APT_BX_THIN_COAT = 1 << 7,
+              APT_BX_GLASS = 1 << 8, APT_BX_LAMBERT_TRANS = 1 << 9, APT_BX_NULL = 1 << 10,       // the BSDFs: det-refraction (type 0), Lambertian transmission (1), null (any other)
+              APT_BX_NO_LOBE = 1 << 11,                                                           // Blinn-Phong without a specular lobe (blinn_phong_eval); not a model, not part of APT_BX_ALL
+              APT_BX_BSDFS = APT_BX_GLASS | APT_BX_LAMBERT_TRANS | APT_BX_NULL, APT_BX_ALL = APT_BX_NO_LOBE - 1;         // (ALL: every bit below the flag, 0x7ff)
+// ... and bit = emitter type (the ids of adapt_amd/emitters.py); the emitter sets the kernel tables are compiled for
+constexpr int APT_SRC_POINT = 1 << 0, APT_SRC_AREA = 1 << 1, APT_SRC_SPOT = 1 << 2, APT_SRC_COLLIMATED = 1 << 4,
+              APT_SRC_POINT_AREA = APT_SRC_POINT | APT_SRC_AREA, APT_SRC_POINT_SPOT = APT_SRC_POINT | APT_SRC_SPOT, APT_SRC_ALL = APT_SRC_POINT_AREA | APT_SRC_SPOT | APT_SRC_COLLIMATED;
+constexpr int bx_bit(int is_bsdf, int type) { return is_bsdf ? (type == 0 ? APT_BX_GLASS : (type == 1 ? APT_BX_LAMBERT_TRANS : APT_BX_NULL)) : (1 << (type & 7)); }      // mask bit of a material row (DevBxdf::is_bsdf, ::type)
+
 // Mask bit 11 ("no specular lobe"): every Blinn-Phong material of the scene has k_s = (0, 0, 0) and finite k_g >= 0, e.g. the
 // "phong" walls of BASELINE C3.  The lobe is then k_s * (finite) = +0 and k_d + 0 = k_d exactly, so it is left out together with
 // its pow - which is what costs the class kernel a third of its registers (187 -> 4 waves per SIMD without it).
 template <int BM>
 APT_D f3 blinn_phong_eval(const DevBxdf& b, const Hit& it, f3 in, f3 out) {
     float c = fmaxf(0.f, dot(it.n_s, out));
-    if ((BM >> 11) & 1) return (b.k_d * APT_INV_PI) * c;
+    if (BXHAS(BM, APT_BX_NO_LOBE)) return (b.k_d * APT_INV_PI) * c;
     f3 h = out - in;
     if (max3(abs3(h)) > BRDF_EPS) h = normalize(h); else h = splat3(0.f);
     float dc = fmaxf(0.f, dot(h, it.n_s));
@@ -432,27 +446,19 @@ APT_D f3 microfacet_sample(const DevBxdf& b, const Hit& it, f3 incid, Philox& r,
     return out_d;
 }
 
-// Material-set masks: bit t (0..7) = BRDF type t present, bit 8 = det-refraction BSDF, bit 9 = Lambertian
-// transmission BSDF, bit 10 = null BSDF.  Emitter mask: bit = emitter type (0 point, 1 area, 2 spot, 4 collimated).
-// The dispatchers take the scene's mask as a template argument so that a shade kernel specialised for,
-// say, {Lambertian} x {point} carries none of the other models' registers or code.
-#define APT_BX_ALL 0x7ff
-#define APT_SRC_ALL 0x17
-#define BXHAS(M, bit) (((M) >> (bit)) & 1)
-
 // BRDF.eval: f * cos, zero unless incid/out are on opposite sides of the GEOMETRIC normal
 template <int BM>
 APT_D f3 brdf_eval(const DevBxdf& b, const Hit& it, f3 incid, f3 out) {
     f3 ret = splat3(0.f);
     if (dot(incid, it.n_g) * dot(out, it.n_g) < 0.f) {
         switch (b.type) {
-            case 0: if (BXHAS(BM, 0)) ret = blinn_phong_eval<BM>(b, it, incid, out); break;
-            case 1: if (BXHAS(BM, 1)) ret = lambert_eval(b, it.n_s, out); break;
-            case 4: if (BXHAS(BM, 4)) ret = mod_phong_eval(b, it, incid, out); break;
-            case 5: if (BXHAS(BM, 5)) { m33 R; rotation_between(mk3(0.f, 1.f, 0.f), it.n_s, R); ret = fresnel_blend_eval(b, it, incid, out, R); } break;
-            case 6: if (BXHAS(BM, 6)) ret = oren_nayar_eval(b, it, incid, out); break;
-            case 7: if (BXHAS(BM, 7)) ret = thin_coat_eval(b, it, incid, out); break;
-            case 3: if (BXHAS(BM, 3)) ret = microfacet_eval(b, it, incid, out); break;
+            case 0: if (BXHAS(BM, APT_BX_BLINN_PHONG)) ret = blinn_phong_eval<BM>(b, it, incid, out); break;
+            case 1: if (BXHAS(BM, APT_BX_LAMBERTIAN)) ret = lambert_eval(b, it.n_s, out); break;
+            case 4: if (BXHAS(BM, APT_BX_MOD_PHONG)) ret = mod_phong_eval(b, it, incid, out); break;
+            case 5: if (BXHAS(BM, APT_BX_FRESNEL_BLEND)) { m33 R; rotation_between(mk3(0.f, 1.f, 0.f), it.n_s, R); ret = fresnel_blend_eval(b, it, incid, out, R); } break;
+            case 6: if (BXHAS(BM, APT_BX_OREN_NAYAR)) ret = oren_nayar_eval(b, it, incid, out); break;
+            case 7: if (BXHAS(BM, APT_BX_THIN_COAT)) ret = thin_coat_eval(b, it, incid, out); break;
+            case 3: if (BXHAS(BM, APT_BX_MICROFACET)) ret = microfacet_eval(b, it, incid, out); break;
             default: break;
         }
     }
@@ -465,17 +471,17 @@ APT_D f3 brdf_sample(const DevBxdf& b, const Hit& it, f3 incid, R& r, f3& spec, 
     f3 dir = mk3(0.f, 1.f, 0.f);
     spec = splat3(1.f); pdf = 1.0f; is_specular = false;
     switch (b.type) {
-        case 0: if constexpr (BXHAS(BM, 0)) {
+        case 0: if constexpr (BXHAS(BM, APT_BX_BLINN_PHONG)) {
             f3 local = sample_cosine_hemisphere(r, pdf);
             dir = delocalize(it.n_s, local);
             spec = blinn_phong_eval<BM>(b, it, incid, dir);
         } break;
-        case 1: case 6: if constexpr (BXHAS(BM, 1) || BXHAS(BM, 6)) dir = lambert_sample(b, it.n_s, r, spec, pdf); break;
-        case 2: if constexpr (BXHAS(BM, 2)) { dir = reflect_in(incid, it.n_s); spec = b.k_d; pdf = 1.0f; } break;
-        case 7: if constexpr (BXHAS(BM, 7)) dir = thin_coat_sample(b, it, incid, r, spec, pdf, is_specular); break;
-        case 4: if constexpr (BXHAS(BM, 4)) dir = mod_phong_sample(b, it, incid, r, spec, pdf); break;
-        case 5: if constexpr (BXHAS(BM, 5)) dir = fresnel_blend_sample(b, it, incid, r, spec, pdf); break;
-        case 3: if constexpr (BXHAS(BM, 3)) dir = microfacet_sample(b, it, incid, r, spec, pdf); break;
+        case 1: case 6: if constexpr (BXHAS(BM, APT_BX_LAMBERTIAN) || BXHAS(BM, APT_BX_OREN_NAYAR)) dir = lambert_sample(b, it.n_s, r, spec, pdf); break;
+        case 2: if constexpr (BXHAS(BM, APT_BX_MIRROR)) { dir = reflect_in(incid, it.n_s); spec = b.k_d; pdf = 1.0f; } break;
+        case 7: if constexpr (BXHAS(BM, APT_BX_THIN_COAT)) dir = thin_coat_sample(b, it, incid, r, spec, pdf, is_specular); break;
+        case 4: if constexpr (BXHAS(BM, APT_BX_MOD_PHONG)) dir = mod_phong_sample(b, it, incid, r, spec, pdf); break;
+        case 5: if constexpr (BXHAS(BM, APT_BX_FRESNEL_BLEND)) dir = fresnel_blend_sample(b, it, incid, r, spec, pdf); break;
+        case 3: if constexpr (BXHAS(BM, APT_BX_MICROFACET)) dir = microfacet_sample(b, it, incid, r, spec, pdf); break;
         default: break;
     }
     if (!(dot(dir, it.n_g) > 0.f)) spec = splat3(0.f);
@@ -489,7 +495,7 @@ APT_D float brdf_pdf(const DevBxdf& b, const Hit& it, f3 outdir, f3 incid) {
     if (d_out * d_in < 0.f) {
         switch (b.type) {
             case 0: case 1: case 6: pdf = d_out * APT_INV_PI; break;
-            case 4: if (BXHAS(BM, 4)) {
+            case 4: if (BXHAS(BM, APT_BX_MOD_PHONG)) {
                 float g = b.mean.z;
                 f3 rv = reflect_in(incid, it.n_s);
                 float dro = fmaxf(0.f, dot(rv, outdir));
@@ -497,12 +503,12 @@ APT_D float brdf_pdf(const DevBxdf& b, const Hit& it, f3 outdir, f3 incid) {
                 float spdf = 0.5f * (g + 1.f) * APT_INV_PI * apt_pow(dro, g);
                 pdf = max3(b.k_d) * dpdf + max3(b.k_s) * spdf;
             } break;
-            case 7: if (BXHAS(BM, 7)) {
+            case 7: if (BXHAS(BM, APT_BX_THIN_COAT)) {
                 f3 refl = reflect_in(incid, it.n_s);
                 float F = thin_coat_fresnel(b, it, incid);
                 pdf = (fabsf(dot(outdir, refl)) > (1.f - 1e-3f)) ? F : (1.f - F) * d_out * APT_INV_PI;
             } break;
-            case 5: if (BXHAS(BM, 5)) {
+            case 5: if (BXHAS(BM, APT_BX_FRESNEL_BLEND)) {
                 f3 h = normalize(outdir - incid);
                 float d_half = dot(h, it.n_s);
                 m33 R; rotation_between(mk3(0.f, 1.f, 0.f), it.n_s, R);
@@ -510,7 +516,7 @@ APT_D float brdf_pdf(const DevBxdf& b, const Hit& it, f3 outdir, f3 incid) {
                 pdf = b.k_g.z * apt_pow(d_half, b.k_g.x * c2 + b.k_g.y * s2) / fabsf(dot(incid, h));
                 pdf = 0.5f * (pdf + d_out * APT_INV_PI);
             } break;
-            case 3: if (BXHAS(BM, 3)) {
+            case 3: if (BXHAS(BM, APT_BX_MICROFACET)) {
                 const f3 wh = normalize(outdir - incid);
                 pdf = trow_reitz_pdf(-incid, wh, b.k_g, it.n_s) / (-4.f * dot(wh, incid));
             } break;
@@ -634,24 +640,24 @@ APT_D void flip_if_two_sided(Hit& it, f3 incid, int two_sides) {
 }
 template <int BM, typename R>
 APT_D f3 surface_sample(const DevBxdf& b, Hit& it, f3 incid, float world_ior, int two_sides, R& r, f3& spec, float& pdf, bool& is_specular) {
-    if (!(BM & 0x700) || !b.is_bsdf) { flip_if_two_sided(it, incid, two_sides); return brdf_sample<BM>(b, it, incid, r, spec, pdf, is_specular); }
-    if constexpr ((BM & 0x700) != 0) {
+    if (!(BM & APT_BX_BSDFS) || !b.is_bsdf) { flip_if_two_sided(it, incid, two_sides); return brdf_sample<BM>(b, it, incid, r, spec, pdf, is_specular); }
+    if constexpr ((BM & APT_BX_BSDFS) != 0) {
         spec = splat3(0.f); pdf = 0.f; is_specular = false;
-        if (BXHAS(BM, 8) && b.type == 0) return glass_sample(b, it, incid, world_ior, r, spec, pdf);
-        if (BXHAS(BM, 9) && b.type == 1) return lambert_trans_sample(b, it, incid, world_ior, r, spec, pdf, is_specular);
+        if (BXHAS(BM, APT_BX_GLASS) && b.type == 0) return glass_sample(b, it, incid, world_ior, r, spec, pdf);
+        if (BXHAS(BM, APT_BX_LAMBERT_TRANS) && b.type == 1) return lambert_trans_sample(b, it, incid, world_ior, r, spec, pdf, is_specular);
     }
     return splat3(0.f);
 }
 template <int BM>
 APT_D f3 surface_eval(const DevBxdf& b, Hit& it, f3 incid, f3 out, float world_ior, int two_sides) {
-    if (!(BM & 0x700) || !b.is_bsdf) { flip_if_two_sided(it, incid, two_sides); return brdf_eval<BM>(b, it, incid, out); }
-    if (BXHAS(BM, 8) && b.type == 0) return glass_eval(b, it, incid, out, world_ior);
-    if (BXHAS(BM, 9) && b.type == 1) return lambert_trans_eval(b, it, incid, out, world_ior);
+    if (!(BM & APT_BX_BSDFS) || !b.is_bsdf) { flip_if_two_sided(it, incid, two_sides); return brdf_eval<BM>(b, it, incid, out); }
+    if (BXHAS(BM, APT_BX_GLASS) && b.type == 0) return glass_eval(b, it, incid, out, world_ior);
+    if (BXHAS(BM, APT_BX_LAMBERT_TRANS) && b.type == 1) return lambert_trans_eval(b, it, incid, out, world_ior);
     return splat3(0.f);
 }
 template <int BM>
 APT_D float surface_pdf(const DevBxdf& b, Hit& it, f3 outdir, f3 incid, float world_ior, int two_sides) {
-    if (!(BM & 0x700) || !b.is_bsdf) { flip_if_two_sided(it, incid, two_sides); return brdf_pdf<BM>(b, it, outdir, incid); }
+    if (!(BM & APT_BX_BSDFS) || !b.is_bsdf) { flip_if_two_sided(it, incid, two_sides); return brdf_pdf<BM>(b, it, outdir, incid); }
     return bsdf_pdf(b, it, outdir, incid, world_ior);
 }
 
@@ -670,10 +676,10 @@ APT_D f3 emitter_sample_hit(const DevSrc& s, const EmitterGeom& g, f3 hit_pos, R
     inten = s.intensity;
     f3 pos = s.pos;
     pdf = 1.0f;
-    if (BXHAS(SM, 0) && s.type == 0) {
+    if (BXHAS(SM, APT_SRC_POINT) && s.type == 0) {
         f3 x = hit_pos - pos;
         inten = inten * fminf(srcp(fmaxf(norm2(x), 1e-5f)), 1.0f);
-    } else if (BXHAS(SM, 1) && s.type == 1) { if constexpr (BXHAS(SM, 1)) {      // (the only emitter that draws)
+    } else if (BXHAS(SM, APT_SRC_AREA) && s.type == 1) { if constexpr (BXHAS(SM, APT_SRC_AREA)) {      // (the only emitter that draws)
         pdf = s.inv_area;
         f3 normal;
         if (s.prim_count < 0) {
@@ -699,13 +705,13 @@ APT_D f3 emitter_sample_hit(const DevSrc& s, const EmitterGeom& g, f3 hit_pos, R
             pdf *= sdiv(norm2(diff), dl);
             inten = (pdf > 0.0f) ? fdiv3(inten, pdf) : splat3(0.f);
         }
-    } } else if (BXHAS(SM, 2) && s.type == 2) {
+    } } else if (BXHAS(SM, APT_SRC_SPOT) && s.type == 2) {
         f3 to_hit = hit_pos - pos;
         float depth = fmaxf(fnorm(to_hit), 1e-5f);
         to_hit = fdiv3(to_hit, depth);
         if (dot(to_hit, s.dir) > s.r) inten = fdiv3(inten, depth * depth);
         else inten = splat3(0.f);
-    } else if (BXHAS(SM, 4) && s.type == 4) {
+    } else if (BXHAS(SM, APT_SRC_COLLIMATED) && s.type == 4) {
         pdf = 0.f;
         if (s.r > 0.f) {
             f3 to_hit = hit_pos - s.pos;

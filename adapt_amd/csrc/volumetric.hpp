@@ -416,7 +416,7 @@ APT_D void vshade_ev_body(const DevScene& sc, const Params& p, const Queues& q, 
         f3 new_d = d;
         bool is_spec = false, cont = false;
         if (shade) {
-            if (!MI && (SM & 2) && hit_light >= 0) {
+            if (!MI && (SM & APT_SRC_AREA) && hit_light >= 0) {
                 const f3 emit_int = emitter_eval_le(sc.src[hit_light], hit_point - o, it.n_g);      // geometric normal here (vpt.py:233)
                 if (!(emit_int.x == 0.f && emit_int.y == 0.f && emit_int.z == 0.f)) {
                     const f3 add = (emit_int * emission_weight) * thr;

@@ -226,7 +226,10 @@ int apt_get_stats(apt_renderer*, apt_stats* out);
 int apt_device_ptr(apt_renderer*, void** accum_dev, int32_t* cnt); /* device float[n_cols*height*3] accumulation buffer */
 int apt_stream(apt_renderer*, void** hip_stream);         /* the hipStream_t every kernel of this renderer runs on */
 
-/* ---- unit entry points used by the parity tests (same device code paths as apt_render) */
+/* ---- unit entry points used by the parity tests (same device code paths as apt_render)
+ * The ones from apt_rng_stream on check their arguments before they look for a device, so a bad call is APT_E_INVALID with or without
+ * one; a device ordinal outside 0..count-1 is APT_E_INVALID, "<name>: device ordinal out of range"; apt_emitter_probe refuses a row whose
+ * source index is not an integer in 0..n_sources-1 (NaN included) with APT_E_INVALID, "apt_emitter_probe: no such emitter". */
 int apt_intersect(apt_renderer*, int32_t n, const float* o, const float* d,
                   int32_t* prim_out, float* t_out, float* uv_out);
 int apt_occluded(apt_renderer*, int32_t n, const float* o, const float* d, const float* tmax, int32_t* occ_out);

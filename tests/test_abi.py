@@ -170,6 +170,74 @@ def test_volume_probe_checks_its_arguments_before_the_device():
         assert call() == -2 and b"no HIP device" in lib.apt_last_error()
 
 
+ORDINAL_ENTRY_POINTS = ["apt_rng_stream", "apt_bxdf_probe", "apt_transient_bin_probe", "apt_medium_probe", "apt_measure_sclk_mhz"]
+SCENE_ENTRY_POINTS = ["apt_emitter_probe", "apt_texture_probe"]
+EMITTER_ROW = np.float32([0, 0.1, 0.2, 0.3, 0, 1, 0, 0, -1, 0, 1])       # emitter 0, hit_pos, normal, ray_d, min_depth
+
+
+def _unit_calls(lib):
+    """name -> call(device, n=1): a well-formed one-row call of a unit entry point.  n = 0 makes it a bad argument (apt_measure_sclk_mhz
+    has no n: a null result pointer); the two entry points that take a scene get a null scene, which is a bad argument as well."""
+    fp, ip = (lambda a: a.ctypes.data_as(_lib.f32p)), (lambda a: a.ctypes.data_as(_lib.i32p))
+    u32, i1, f1, out = np.zeros(1, np.uint32), np.zeros(2, np.int32), np.float32([1.0, 0.5]), np.zeros(12, np.float32)
+    bi, bf, dirs = np.int32([1, 0, 0, 0]), np.float32([0.5] * 12 + [1.0]), np.float32([0, 0, 1, 0, 0, 1, 0, 0, -1, 0, 0, 1])
+    mi, mf, in7 = np.int32([-1]), np.zeros(16, np.float32), np.float32([0, 0, 1, 0, 0, 1, 1])
+    vi, vf, vg, in10 = np.int32([2, 2, 2, 2, 0]), np.zeros(33, np.float32), np.zeros(2 * 2 * 2 * 3, np.float32), np.zeros(10, np.float32)
+    vf[21:24] = 1
+    in10[3:6] = (0, 0, 1)
+    return {
+        "apt_rng_stream": lambda dev, n=1: lib.apt_rng_stream(dev, 0, 0, 0, n, u32.ctypes.data_as(_lib.u32p)),
+        "apt_bxdf_probe": lambda dev, n=1: lib.apt_bxdf_probe(dev, n, ip(bi), fp(bf), fp(dirs), 1.0, 0, 0, fp(out)),
+        "apt_transient_bin_probe": lambda dev, n=1: lib.apt_transient_bin_probe(dev, n, fp(f1), 0.0, 1.0, 4, ip(i1)),
+        "apt_medium_probe": lambda dev, n=1: lib.apt_medium_probe(dev, n, ip(mi), fp(mf), 0, fp(in7), 0, fp(out)),
+        "apt_volume_probe": lambda dev, n=1: lib.apt_volume_probe(dev, n, ip(vi), fp(vf), fp(vg), 0, fp(in10), 0, fp(out)),
+        "apt_measure_sclk_mhz": lambda dev, n=1: lib.apt_measure_sclk_mhz(dev, fp(f1) if n else None),
+        "apt_emitter_probe": lambda dev, n=1: lib.apt_emitter_probe(None, n, fp(EMITTER_ROW), 0, fp(out)),
+        "apt_texture_probe": lambda dev, n=1: lib.apt_texture_probe(None, n, ip(i1), fp(f1), fp(out)),
+    }
+
+
+@pytest.mark.parametrize("name", ORDINAL_ENTRY_POINTS + SCENE_ENTRY_POINTS)
+def test_unit_entry_point_checks_its_arguments_before_the_device(name):
+    """Every unit entry point refuses a bad argument with APT_E_INVALID and its own name before it looks for a device; where there is
+    none, a well-formed call of one that takes a device ordinal gets as far as the device check."""
+    lib = _lib.load()
+    call = _unit_calls(lib)[name]
+    assert call(0, 0) == -1 and name.encode() + b": bad argument" in lib.apt_last_error(), lib.apt_last_error()
+    if name in ORDINAL_ENTRY_POINTS and not has_gpu():
+        assert call(0) == -2 and b"no HIP device" in lib.apt_last_error(), lib.apt_last_error()
+
+
+@pytest.mark.gpu
+def test_unit_entry_points_refuse_a_device_ordinal_out_of_range():
+    """One answer from every entry point that takes a device ordinal: APT_E_INVALID, "<name>: device ordinal out of range", from the host."""
+    import torch
+    lib = _lib.load()
+    calls = _unit_calls(lib)
+    for name in ORDINAL_ENTRY_POINTS + ["apt_volume_probe"]:
+        for device in (torch.cuda.device_count(), -1):
+            assert calls[name](device) == -1 and name.encode() + b": device ordinal out of range" in lib.apt_last_error(), (name, device, lib.apt_last_error())
+
+
+@pytest.mark.gpu
+def test_emitter_probe_refuses_a_row_without_an_emitter(flat):
+    """The emitter index of a row must be an integer in 0..n_sources-1 (the kernel indexes the scene's emitter table with it): anything
+    else, NaN included, is refused on the host, and a valid row right after it runs."""
+    lib = _lib.load()
+    fs = flat("cbox")
+    desc, keep = _scene_desc(fs)
+    h = C.c_void_p()
+    _lib.check(lib.apt_scene_create(C.byref(desc), 0, C.byref(h)), "apt_scene_create")
+    fp, out = (lambda a: a.ctypes.data_as(_lib.f32p)), np.zeros(12, np.float32)
+    try:
+        for index in (fs.n_sources, -1, 0.5, np.nan):
+            row = EMITTER_ROW.copy(); row[0] = index
+            assert lib.apt_emitter_probe(h, 1, fp(row), 0, fp(out)) == -1 and b"apt_emitter_probe: no such emitter" in lib.apt_last_error(), (index, lib.apt_last_error())
+            _lib.check(lib.apt_emitter_probe(h, 1, fp(EMITTER_ROW), 0, fp(out)), "apt_emitter_probe")
+    finally:
+        lib.apt_scene_destroy(h)
+
+
 def build_bvh(fs):
     lib = _lib.load()
     prims, info = np.ascontiguousarray(fs.prims), np.ascontiguousarray(fs.obj_info)
