@@ -109,6 +109,7 @@ SYMBOLS = {
     "apt_volume_probe": (C.c_int, [C.c_int32, C.c_int32, i32p, f32p, f32p, C.c_int32, f32p, C.c_uint32, f32p]),
     "apt_emitter_probe": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_uint32, f32p]),
     "apt_texture_probe": (C.c_int, [C.c_void_p, C.c_int32, i32p, f32p, f32p]),
+    "apt_surface_maps_probe": (C.c_int, [C.c_void_p, C.c_int32, i32p, f32p, f32p]),
     "apt_transient_bin_probe": (C.c_int, [C.c_int32, C.c_int32, f32p, C.c_float, C.c_float, C.c_int32, i32p]),
     "apt_renderer_info": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_int64), i32p, C.POINTER(C.c_char_p), i32p]),
     "apt_renderer_camera_fused": (C.c_int, [C.c_void_p, i32p]),

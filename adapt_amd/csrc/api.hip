@@ -184,6 +184,7 @@ struct apt_scene {
     std::vector<float> h_prims, h_flat_recs, h_flat_tab; int h_flat_counts[7] = {0, 0, 0, 0, 0, 0, 0};      // ... and what a renderer builds its camera strip lists from (flat_build.cpp camera_strips)
     bool has_flat = false;
     DevBuf uvs, tex_i, tex_f, atlas[3];      // image textures (empty when the scene has none)
+    std::vector<int32_t> tex_type;       // ... per object and map, the texture's type (-255: none; apt_texture_probe refuses a lookup in one that is not there)
     DevBuf prim_shade;                   // per-primitive shading records (stages.hpp DevScene::prim_shade)
     DevBuf med;                          // participating media, n_objects + 1 rows (volumetric path tracer)
     DevBuf vol_grid;                     // grid volume densities
@@ -614,6 +615,8 @@ static int pack_textures(const apt_scene_desc* d, apt_scene* s) {
     }
     if (!put("uvs", s->uvs, d->uvs, (size_t)s->n_prims * 6) || !put("tex_i", s->tex_i, d->tex_i, (size_t)O * 15) || !put("tex_f", s->tex_f, d->tex_f, (size_t)O * 6)) return APT_E_HIP;
     s->dev.uvs = s->uvs.as<float>(); s->dev.tex_i = s->tex_i.as<int>(); s->dev.tex_f = s->tex_f.as<float>();
+    s->tex_type.resize((size_t)O * 3);
+    for (int k = 0; k < O * 3; k++) s->tex_type[(size_t)k] = d->tex_i[5 * (size_t)k];
     for (int m = 0; m < 3; m++) if (d->atlas[m]) {
         if (!put("atlas[m]", s->atlas[m], d->atlas[m], (size_t)d->atlas_w[m] * (size_t)d->atlas_h[m] * 3)) return APT_E_HIP;
         s->dev.atlas[m] = s->atlas[m].as<float>(); s->dev.atlas_w[m] = d->atlas_w[m];
@@ -1804,12 +1807,22 @@ APT_EXPORT int apt_texture_probe(const apt_scene* sc, int32_t n, const int32_t* 
     if (!sc->dev.tex_i) return fail(APT_E_INVALID, "apt_texture_probe: the scene has no textures");
     for (int k = 0; k < n; k++) {
         const int m = map_obj[2 * k], o = map_obj[2 * k + 1];
-        if (m < 0 || m > 2 || o < 0 || o >= sc->n_objects || !sc->dev.atlas[m]) return fail(APT_E_INVALID, "apt_texture_probe: no such texture");
+        if (m < 0 || m > 2 || o < 0 || o >= sc->n_objects || !sc->dev.atlas[m] || !(sc->tex_type[3 * (size_t)o + m] > -255)) return fail(APT_E_INVALID, "apt_texture_probe: no such texture");
     }
     Probe pr; if (int rc = pr.begin("apt_texture_probe", sc->device, (size_t)n * 12)) return rc;
     HIP_TRY(upload(pr.in[0], map_obj, 2 * (size_t)n)); HIP_TRY(upload(pr.in[1], uv, 2 * (size_t)n));
     hipLaunchKernelGGL(k_texture_probe, dim3((n + 63) / 64), dim3(64), 0, 0, sc->dev, n, pr.in[0].as<int>(), pr.in[1].as<float>(), pr.out.as<float>());
     return pr.finish(out3);
+}
+APT_EXPORT int apt_surface_maps_probe(const apt_scene* sc, int32_t n, const int32_t* prim_first, const float* bary, float* out7) {
+    if (!sc || n <= 0 || !prim_first || !bary || !out7) return fail(APT_E_INVALID, "apt_surface_maps_probe: bad argument");
+    if (!sc->dev.tex_i) return fail(APT_E_INVALID, "apt_surface_maps_probe: the scene has no textures");
+    for (int k = 0; k < n; k++)            // the kernel indexes the scene's primitive tables with it
+        if (const int p = prim_first[2 * (size_t)k]; p < 0 || p >= sc->n_prims) return fail(APT_E_INVALID, "apt_surface_maps_probe: no such primitive");
+    Probe pr; if (int rc = pr.begin("apt_surface_maps_probe", sc->device, (size_t)n * 28)) return rc;
+    HIP_TRY(upload(pr.in[0], prim_first, 2 * (size_t)n)); HIP_TRY(upload(pr.in[1], bary, 2 * (size_t)n));
+    hipLaunchKernelGGL(k_surface_maps_probe, dim3((n + 63) / 64), dim3(64), 0, 0, sc->dev, n, pr.in[0].as<int>(), pr.in[1].as<float>(), pr.out.as<float>());
+    return pr.finish(out7);
 }
 // Shader clock while the whole chip is busy (bench.py prices its VALU roofline with it): median over the waves of a full grid of
 // cycle-counter ticks per 100 MHz wall-clock tick.

@@ -14,18 +14,28 @@
 // Taichi's float `a % b` is a - b * floor(a / b) (python/taichi/lang/ops.py, mod)
 APT_D float ti_fmod(float a, float b) { float q = floorf(a / b); return a - b * q; }
 APT_D f3 mix3(f3 a, f3 b, float t) { return a * (1.0f - t) + b * t; }          // taichi.math.mix: x * (1 - a) + y * a
-// Texture.query, bxdf/texture.py:111-139: bilinear lookup inside the texture's rectangle of the atlas
+// Texture.query, bxdf/texture.py:111-139: bilinear lookup inside the texture's rectangle of the atlas.
+// Contract (the coordinates come straight from a scene file: OBJ `vt`, XML scale_u / scale_v):
+//   * the wrapped coordinate lies in [0, w-1) and floor + 1 <= w-1: the reference's arithmetic, bit for bit - the clamps below are the identity;
+//   * the float remainder comes out as w-1 itself (a tiny negative coordinate: a - b * floor(a / b) rounds to b): the last texel itself,
+//     what the reference's formula gives when the neighbour it reads at weight 0 is finite;
+//   * any other coordinate (the remainder of a large tile count leaves [0, w-1); an overflowing product or a non-finite coordinate gives
+//     NaN): upstream reads an unchecked field there, nothing to be faithful to.  Here no texel outside the rectangle is ever read: the
+//     floor is clamped to [0, w-1] in float before the cast, a NaN goes to 0 (fmaxf returns its other operand), the ceil texel is
+//     min(floor + 1, w-1).  The ratios stay as computed (always in [0, 1] when they are numbers); a NaN ratio counts as 0.  So every
+//     lookup is a convex combination of the rectangle's own texels: finite when they are.
 APT_D f3 texture_query(const DevScene& sc, int map, int obj, float u, float v) {
     const int* ti_ = sc.tex_i + 15 * obj + 5 * map; const float* tf = sc.tex_f + 6 * obj + 2 * map;
     const float w = (float)ti_[3], h = (float)ti_[4];
     const float scaled_u = ti_fmod((u * tf[0]) * w, w - 1.f), scaled_v = ti_fmod((v * tf[1]) * h, h - 1.f);
     float floor_u = floorf(scaled_u), floor_v = floorf(scaled_v);
-    const float ratio_u = scaled_u - floor_u, ratio_v = scaled_v - floor_v;
-    floor_u = floor_u + (float)ti_[1]; floor_v = floor_v + (float)ti_[2];
-    const int fu = (int)floor_u, fv = (int)floor_v;
+    const float ratio_u = fmaxf(scaled_u - floor_u, 0.f), ratio_v = fmaxf(scaled_v - floor_v, 0.f);
+    floor_u = fminf(fmaxf(floor_u, 0.f), w - 1.f); floor_v = fminf(fmaxf(floor_v, 0.f), h - 1.f);
+    const float ceil_u = fminf(floor_u + 1.f, w - 1.f), ceil_v = fminf(floor_v + 1.f, h - 1.f);
+    const int fu = (int)(floor_u + (float)ti_[1]), fv = (int)(floor_v + (float)ti_[2]), cu = (int)(ceil_u + (float)ti_[1]), cv = (int)(ceil_v + (float)ti_[2]);
     const float* img = sc.atlas[map]; const int W = sc.atlas_w[map];
-    const float* r0 = img + ((size_t)fv * W + fu) * 3; const float* r1 = r0 + (size_t)W * 3;
-    const f3 q_ff = mk3(r0[0], r0[1], r0[2]), q_cf = mk3(r0[3], r0[4], r0[5]), q_fc = mk3(r1[0], r1[1], r1[2]), q_cc = mk3(r1[3], r1[4], r1[5]);
+    const float* r0 = img + (size_t)fv * W * 3; const float* r1 = img + (size_t)cv * W * 3;
+    const f3 q_ff = ld3(r0 + 3 * fu), q_cf = ld3(r0 + 3 * cu), q_fc = ld3(r1 + 3 * fu), q_cc = ld3(r1 + 3 * cu);
     return mix3(mix3(q_ff, q_cf, ratio_u), mix3(q_fc, q_cc, ratio_u), ratio_v);
 }
 // PathTracer.get_uv_item, path_tracer.py:276-289 (meshes only: textured spheres are refused at scene creation)
@@ -36,6 +46,19 @@ APT_D bool get_uv_item(const DevScene& sc, int map, int obj, int prim, float bu,
     const float gu = (uv[2] * bu + uv[4] * bv) + uv[0] * w0, gv = (uv[3] * bu + uv[5] * bv) + uv[1] * w0;
     out = texture_query(sc, map, obj, gu, gv);
     return true;
+}
+// The maps of a vertex on object it.obj_id, primitive `prim`, at barycentrics (bu, bv); returns which applied (1 albedo, 2 normal, 4 bump).
+// What open_vertex does with the scene's textures, and what apt_surface_maps_probe runs on explicit inputs.
+APT_D int surface_maps(const DevScene& sc, Hit& it, int prim, float bu, float bv, bool first_hit, f3& k_d) {
+    int applied = 0; f3 tx;
+    if (first_hit) {                                 // PathTracer.process_ns, applied to the camera ray's hit only (vanilla_renderer.py:42)
+        if (get_uv_item(sc, 1, it.obj_id, prim, bu, bv, tx)) { m33 R; rotation_between(mk3(0.f, 1.f, 0.f), it.n_g, R); it.n_s = mul(R, tx); applied |= 2; }
+        if (get_uv_item(sc, 2, it.obj_id, prim, bu, bv, tx)) { it.n_s = delocalize(it.n_s, tx); applied |= 4; }
+    }
+    // it.tex (vanilla_renderer.py:66): every surface model reads its diffuse colour as select(tex invalid, k_d, tex)
+    // and nothing else reads k_d on the device, so a valid lookup simply replaces this path's copy of k_d
+    if (get_uv_item(sc, 0, it.obj_id, prim, bu, bv, tx)) { k_d = tx; applied |= 1; }
+    return applied;
 }
 
 // -------------------------------------------------------------------- shade
@@ -188,16 +211,7 @@ APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, RNG& rng, int prim, f3 
     const bool was_spec = (meta >> 24) & 1u;
     if (BM == APT_BX_LAMBERTIAN) vx.bx.k_d = rec_kd;               // Lambertian-only scenes: type 1, not delta, not a BSDF (vertex_reset), colour from the record
     else vx.bx = ld_bxdf_lane((A_->sc).bxdf + vx.it.obj_id);
-    if (TEX && (A_->sc).tex_i != nullptr) {                // the scene declares image textures (TEX kernels only)
-        f3 tx;
-        if (bounce == 0) {                           // PathTracer.process_ns, applied to the camera ray's hit only (vanilla_renderer.py:42)
-            if (get_uv_item((A_->sc), 1, vx.it.obj_id, prim, uv.x, uv.y, tx)) { m33 R; rotation_between(mk3(0.f, 1.f, 0.f), vx.it.n_g, R); vx.it.n_s = mul(R, tx); }
-            if (get_uv_item((A_->sc), 2, vx.it.obj_id, prim, uv.x, uv.y, tx)) vx.it.n_s = delocalize(vx.it.n_s, tx);
-        }
-        // it.tex (vanilla_renderer.py:66): every surface model reads its diffuse colour as select(tex invalid, k_d, tex)
-        // and nothing else reads k_d on the device, so a valid lookup simply replaces this path's copy of k_d
-        if (get_uv_item((A_->sc), 0, vx.it.obj_id, prim, uv.x, uv.y, tx)) vx.bx.k_d = tx;
-    }
+    if (TEX && (A_->sc).tex_i != nullptr) surface_maps((A_->sc), vx.it, prim, uv.x, uv.y, bounce == 0, vx.bx.k_d);      // the scene declares image textures (TEX kernels only)
     const uint32_t lp = vx.id & ((1u << (A_->p).pix_bits) - 1u), s = vx.id >> (A_->p).pix_bits;
     vx.l_off = (s * (uint32_t)(A_->p).npix + lp) << 2;
     vx.draw0 = meta & 0xffffu;

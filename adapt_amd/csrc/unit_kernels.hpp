@@ -1,5 +1,5 @@
 // unit_kernels.hpp - the entry kernels behind the C-ABI's unit functions (apt_occluded, apt_rng_stream, apt_bxdf_*, apt_texture_query,
-// apt_emitter_probe, apt_clock_probe): single device functions run on explicit inputs, for the parity tests and the bench's clock check.
+// apt_surface_maps_probe, apt_emitter_probe, apt_clock_probe): single device functions run on explicit inputs, for the parity tests and the bench's clock check.
 #pragma once
 #include "shade_stage.hpp"
 
@@ -69,6 +69,19 @@ __global__ void k_texture_probe(DevScene sc, int n, const int* map_obj, const fl
     if (k >= n) return;
     f3 r = texture_query(sc, map_obj[2 * k], map_obj[2 * k + 1], uv[2 * k], uv[2 * k + 1]);
     out3[3 * k] = r.x; out3[3 * k + 1] = r.y; out3[3 * k + 2] = r.z;
+}
+// shade_stage.hpp surface_maps (the normal, bump and albedo maps of a vertex, as open_vertex applies them) on explicit inputs: row k is
+// primitive prim_first[2k] at barycentrics bary[2k..], prim_first[2k + 1] != 0 for a camera ray's hit.  The vertex starts as build_hit
+// leaves it (the record's colour, the interpolated shading normal); out7[7k..] = k_d, n_s, the maps that applied (1 albedo | 2 normal | 4 bump)
+__global__ void k_surface_maps_probe(DevScene sc, int n, const int* prim_first, const float* bary, float* out7) {
+    int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int prim = prim_first[2 * k]; const float bu = bary[2 * k], bv = bary[2 * k + 1];
+    Hit it; int light; f3 kd;
+    build_hit(sc, prim, 1.f, bu, bv, splat3(0.f), mk3(0.f, 0.f, 1.f), it, light, kd);
+    const int applied = surface_maps(sc, it, prim, bu, bv, prim_first[2 * k + 1] != 0, kd);
+    float* o = out7 + 7 * k;
+    o[0] = kd.x; o[1] = kd.y; o[2] = kd.z; o[3] = it.n_s.x; o[4] = it.n_s.y; o[5] = it.n_s.z; o[6] = (float)applied;
 }
 // stages.hpp transient_bin on explicit times (the window as make_transient sets it up)
 __global__ void k_transient_bin_probe(TransQ tq, int n, const float* t, int* out) {

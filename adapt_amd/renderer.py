@@ -196,6 +196,17 @@ class DeviceScene:
         _lib.check(self.lib.apt_texture_probe(self.handle, uv.shape[0], _ip(mo), _fp(uv), _fp(out)), "apt_texture_probe", self.lib)
         return out
 
+    def surface_maps(self, prims, bary, first_hit=True):
+        """The normal, bump and albedo maps of a vertex on the device (parity probe of shade_stage.hpp surface_maps): primitives, (n,2)
+        barycentrics, first-hit flag(s) -> k_d (n,3), n_s (n,3), the maps that applied (n,) as 1 albedo | 2 normal | 4 bump"""
+        bary = np.ascontiguousarray(bary, np.float32).reshape(-1, 2)
+        pf = np.ascontiguousarray(np.stack(np.broadcast_arrays(np.int32(prims), np.int32(first_hit)), -1).reshape(-1, 2), np.int32)
+        if pf.shape[0] != bary.shape[0]:
+            raise ValueError("surface_maps: one primitive per row of barycentrics")
+        out = np.zeros((bary.shape[0], 7), np.float32)
+        _lib.check(self.lib.apt_surface_maps_probe(self.handle, bary.shape[0], _ip(pf), _fp(bary), _fp(out)), "apt_surface_maps_probe", self.lib)
+        return out[:, 0:3].copy(), out[:, 3:6].copy(), out[:, 6].astype(np.int32)
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.apt_scene_destroy(self.handle)

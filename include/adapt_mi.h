@@ -239,8 +239,14 @@ int apt_rng_stream(int32_t device, uint32_t pixel, uint32_t seed, uint32_t sampl
  * do_sample = 1: out[9k..] = dir xyz, f*cos rgb, pdf, is_specular, draws; RNG = Philox(key=(k, seed), sample 1). */
 int apt_bxdf_probe(int32_t device, int32_t n, const int32_t* bxdf_i, const float* bxdf_f, const float* dirs12,
                    float world_ior, int32_t do_sample, uint32_t seed, float* out);
-/* Texture probe: map_obj[2k..] = map (0 albedo, 1 normal, 2 bump), object; uv[2k..]; out3[3k..] = Texture.query. */
+/* Texture probe: map_obj[2k..] = map (0 albedo, 1 normal, 2 bump), object; uv[2k..]; out3[3k..] = Texture.query.  Any coordinate may be
+ * asked for: no texel outside the texture's rectangle is read (the contract is stated at texture_query, csrc/shade_stage.hpp). */
 int apt_texture_probe(const apt_scene*, int32_t n, const int32_t* map_obj, const float* uv, float* out3);
+/* Surface-maps probe: the normal, bump and albedo maps of a vertex as the shade kernels apply them.  Row k: primitive prim_first[2k],
+ * prim_first[2k+1] != 0 for a camera ray's hit (the only one whose shading normal the maps touch), barycentrics bary[2k..].
+ * out7[7k..] = k_d, n_s, the maps that applied (1 albedo | 2 normal | 4 bump).  A primitive outside 0..n_prims-1 is APT_E_INVALID,
+ * "apt_surface_maps_probe: no such primitive". */
+int apt_surface_maps_probe(const apt_scene*, int32_t n, const int32_t* prim_first, const float* bary, float* out7);
 /* Medium probe (volumetric tracer; bxdf/medium.py:84-125, bxdf/phase.py): test k uses medium (med_i[k], med_f[16k..]) and in7[7k..].
  * mode 0: Medium.sample_mfp, in = max_depth            -> out8[8k..] = is_mi, t, beta rgb, draws
  * mode 1: Medium.sample_new_rays, in = incid xyz       -> dir xyz, phase value x3, pdf, draws

@@ -68,6 +68,7 @@ def lib():
         _lib.orc_scene_create.argtypes = [C.POINTER(SceneDesc), f32p, C.c_int]
         _lib.orc_scene_destroy.argtypes = [C.c_void_p]
         _lib.orc_texture_query.argtypes = [C.c_void_p, C.c_int, i32p, f32p, f32p]
+        _lib.orc_surface_maps.argtypes = [C.c_void_p, C.c_int, i32p, f32p, f32p]
         _lib.orc_render.argtypes = [C.c_void_p, C.POINTER(Cfg), f32p, i32p, C.c_int, C.c_int, C.POINTER(Stats)]
         _lib.orc_render_contributions.restype = C.c_longlong
         _lib.orc_render_contributions.argtypes = [C.c_void_p, C.POINTER(Cfg), C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, f32p, C.POINTER(Stats)]
@@ -156,6 +157,16 @@ class OracleScene:
         if lib().orc_texture_query(self.handle, uv.shape[0], _ip(mo), _fp(uv), _fp(out)) != 0:
             raise ValueError("texture_query: no such texture")
         return out
+
+    def surface_maps(self, prims, bary, first_hit=True):
+        """process_ns and the albedo lookup on explicit inputs (what DeviceScene.surface_maps runs on the device): mesh primitives, (n,2)
+        barycentrics, first-hit flag(s) -> k_d (n,3), n_s (n,3), the maps that applied (n,) as 1 albedo | 2 normal | 4 bump"""
+        bary = np.ascontiguousarray(bary, np.float32).reshape(-1, 2)
+        pf = np.ascontiguousarray(np.stack(np.broadcast_arrays(np.int32(prims), np.int32(first_hit)), -1).reshape(-1, 2), np.int32)
+        out = np.zeros((bary.shape[0], 7), np.float32)
+        if pf.shape[0] != bary.shape[0] or lib().orc_surface_maps(self.handle, bary.shape[0], _ip(pf), _fp(bary), _fp(out)) != 0:
+            raise ValueError("surface_maps: one mesh primitive per row of barycentrics")
+        return out[:, 0:3].copy(), out[:, 3:6].copy(), out[:, 6].astype(np.int32)
 
     # ---- whole-image render (Renderer.render x n_spp)
     def render(self, rc, n_spp: int, accum=None, cnt: int = 0, threads: int = 0):

@@ -1568,16 +1568,22 @@ typedef struct {
 /* Taichi's float `a % b` is a - b * floor(a / b) (python/taichi/lang/ops.py, mod) */
 static inline float ti_fmod(float a, float b) { float q = floorf(a / b); return a - b * q; }
 static inline v3 vmix(v3 a, v3 b, float t) { return vadd(vscale(a, 1.0f - t), vscale(b, t)); }       /* taichi.math.mix: x * (1 - a) + y * a */
-/* Texture.query, bxdf/texture.py:111-139: bilinear lookup inside the texture's rectangle of the atlas */
+/* Texture.query, bxdf/texture.py:111-139: bilinear lookup inside the texture's rectangle of the atlas.
+ * Contract (the same text as adapt_amd/csrc/shade_stage.hpp texture_query): where the wrapped coordinate lies in [0, w-1) and
+ * floor + 1 <= w-1 this is the reference's arithmetic bit for bit (the clamps are the identity); where the float remainder comes
+ * out as w-1 itself (a tiny negative coordinate) the result is the last texel itself; for every other coordinate - the reference reads
+ * an unchecked field there - no texel outside the rectangle is read: the floor is clamped to [0, w-1] in float before the cast, a NaN
+ * goes to 0, the ceil texel is min(floor + 1, w-1), the ratios stay as computed and a NaN ratio counts as 0. */
 static v3 texture_query(const scene_t* sc, int map, int obj, float u, float v) {
     const int* ti_ = sc->tex_i[obj][map]; const float* tf = sc->tex_f[obj][map];
     float w = (float)ti_[3], h = (float)ti_[4];
     float scaled_u = ti_fmod((u * tf[0]) * w, w - 1.f);
     float scaled_v = ti_fmod((v * tf[1]) * h, h - 1.f);
     float floor_u = floorf(scaled_u), floor_v = floorf(scaled_v);
-    float ratio_u = scaled_u - floor_u, ratio_v = scaled_v - floor_v;
-    floor_u = floor_u + (float)ti_[1]; floor_v = floor_v + (float)ti_[2];
-    int fu = (int)floor_u, fv = (int)floor_v, cu = fu + 1, cv = fv + 1;
+    float ratio_u = fmaxf(scaled_u - floor_u, 0.f), ratio_v = fmaxf(scaled_v - floor_v, 0.f);
+    floor_u = fminf(fmaxf(floor_u, 0.f), w - 1.f); floor_v = fminf(fmaxf(floor_v, 0.f), h - 1.f);
+    float ceil_u = fminf(floor_u + 1.f, w - 1.f), ceil_v = fminf(floor_v + 1.f, h - 1.f);
+    int fu = (int)(floor_u + (float)ti_[1]), fv = (int)(floor_v + (float)ti_[2]), cu = (int)(ceil_u + (float)ti_[1]), cv = (int)(ceil_v + (float)ti_[2]);
     const float* img = sc->atlas[map]; int W = sc->atlas_w[map];
 #define TEXEL(y, x) V(img[((size_t)(y) * W + (x)) * 3], img[((size_t)(y) * W + (x)) * 3 + 1], img[((size_t)(y) * W + (x)) * 3 + 2])
     v3 q_ff = TEXEL(fv, fu), q_cf = TEXEL(fv, cu), q_fc = TEXEL(cv, fu), q_cc = TEXEL(cv, cu);
@@ -1604,6 +1610,30 @@ static void process_ns(const scene_t* sc, isect_t* it) {
     v3 t;
     if (get_uv_item(sc, 1, it, &t)) { m3 R; rotation_between(V(0.f, 1.f, 0.f), it->n_g, &R); it->n_s = m3mulv(&R, t); }
     if (get_uv_item(sc, 2, it, &t)) { m3 R; it->n_s = delocalize_rotate(it->n_s, t, &R); }
+}
+/* The maps of a vertex on explicit inputs - process_ns, then the albedo lookup of vanilla_renderer.py:66 - for apt_surface_maps_probe:
+ * row k is mesh primitive prim_first[2k] at barycentrics bary[2k..], prim_first[2k+1] != 0 for a camera ray's hit.
+ * out7[7k..] = k_d (the texture's where the albedo map applies, else the material's), n_s, the maps that applied (1 albedo | 2 normal | 4 bump) */
+ORC_API int orc_surface_maps(const scene_t* sc, int n, const int* prim_first, const float* bary, float* out7) {
+    for (int k = 0; k < n; k++) {
+        int prim = prim_first[2 * k], obj = -1;
+        for (int o = 0; o < sc->n_objects; o++) if (prim >= sc->obj_info[o][0] && prim < sc->obj_info[o][0] + sc->obj_info[o][1]) obj = o;
+        if (obj < 0 || sc->obj_info[obj][2] != 0) return -1;
+        isect_t it; memset(&it, 0, sizeof(it));
+        it.obj_id = obj; it.prim_id = prim; it.u = bary[2 * k]; it.v = bary[2 * k + 1]; it.min_depth = 1.f;
+        finish_isect(sc, &it, 0, V(0.f, 0.f, 1.f), ZERO3);
+        int applied = 0; v3 t;
+        if (prim_first[2 * k + 1]) {
+            applied |= get_uv_item(sc, 1, &it, &t) ? 2 : 0;
+            applied |= get_uv_item(sc, 2, &it, &t) ? 4 : 0;
+            process_ns(sc, &it);
+        }
+        v3 kd = sc->bxdf[obj].k_d;
+        if (get_uv_item(sc, 0, &it, &it.tex)) { kd = it.tex; applied |= 1; }
+        float* o7 = out7 + 7 * k;
+        o7[0] = kd.x; o7[1] = kd.y; o7[2] = kd.z; o7[3] = it.n_s.x; o7[4] = it.n_s.y; o7[5] = it.n_s.z; o7[6] = (float)applied;
+    }
+    return 0;
 }
 
 /* Per-contribution log of one pixel-sample (orc_render_contributions: the transient renderer's binning).  One record

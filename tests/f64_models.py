@@ -136,6 +136,18 @@ def delocalize(anchor, d, mg=None):
     return mat_mul(rotation_between(Y, anchor, mg), d)
 
 
+def surface_maps_ns(applied, n_g, n_s, t_normal, t_bump):
+    """(n_s, margin) after shade_stage.hpp surface_maps: the normal-map texel taken from the +y frame onto n_g (applied & 2), then the
+    bump-map texel delocalized around that shading normal (applied & 4).  n_s: the shading normal the vertex arrives with."""
+    mg = Margin()
+    n = v(n_s)
+    if int(applied) & 2:
+        n = mat_mul(rotation_between(Y, v(n_g), mg), v(t_normal))
+    if int(applied) & 4:
+        n = delocalize(n, v(t_bump), mg)
+    return np.array(n), mg
+
+
 def raw_of_local(l, mg=None):
     """(cos_t, sin_t, cos_p, sin_p) of a local direction (+y = normal); the azimuth is (1, 0) while sin_t <= 1e-5 (knife edge)"""
     cos_t = l[1]

@@ -171,13 +171,13 @@ def test_volume_probe_checks_its_arguments_before_the_device():
 
 
 ORDINAL_ENTRY_POINTS = ["apt_rng_stream", "apt_bxdf_probe", "apt_transient_bin_probe", "apt_medium_probe", "apt_measure_sclk_mhz"]
-SCENE_ENTRY_POINTS = ["apt_emitter_probe", "apt_texture_probe"]
+SCENE_ENTRY_POINTS = ["apt_emitter_probe", "apt_texture_probe", "apt_surface_maps_probe"]
 EMITTER_ROW = np.float32([0, 0.1, 0.2, 0.3, 0, 1, 0, 0, -1, 0, 1])       # emitter 0, hit_pos, normal, ray_d, min_depth
 
 
 def _unit_calls(lib):
     """name -> call(device, n=1): a well-formed one-row call of a unit entry point.  n = 0 makes it a bad argument (apt_measure_sclk_mhz
-    has no n: a null result pointer); the two entry points that take a scene get a null scene, which is a bad argument as well."""
+    has no n: a null result pointer); the entry points that take a scene get a null scene, which is a bad argument as well."""
     fp, ip = (lambda a: a.ctypes.data_as(_lib.f32p)), (lambda a: a.ctypes.data_as(_lib.i32p))
     u32, i1, f1, out = np.zeros(1, np.uint32), np.zeros(2, np.int32), np.float32([1.0, 0.5]), np.zeros(12, np.float32)
     bi, bf, dirs = np.int32([1, 0, 0, 0]), np.float32([0.5] * 12 + [1.0]), np.float32([0, 0, 1, 0, 0, 1, 0, 0, -1, 0, 0, 1])
@@ -194,6 +194,7 @@ def _unit_calls(lib):
         "apt_measure_sclk_mhz": lambda dev, n=1: lib.apt_measure_sclk_mhz(dev, fp(f1) if n else None),
         "apt_emitter_probe": lambda dev, n=1: lib.apt_emitter_probe(None, n, fp(EMITTER_ROW), 0, fp(out)),
         "apt_texture_probe": lambda dev, n=1: lib.apt_texture_probe(None, n, ip(i1), fp(f1), fp(out)),
+        "apt_surface_maps_probe": lambda dev, n=1: lib.apt_surface_maps_probe(None, n, ip(i1), fp(f1), fp(out)),
     }
 
 
@@ -236,6 +237,38 @@ def test_emitter_probe_refuses_a_row_without_an_emitter(flat):
             _lib.check(lib.apt_emitter_probe(h, 1, fp(EMITTER_ROW), 0, fp(out)), "apt_emitter_probe")
     finally:
         lib.apt_scene_destroy(h)
+
+
+@pytest.mark.gpu
+def test_texture_probes_refuse_what_the_scene_does_not_have(flat):
+    """apt_texture_probe looks up only a texture the scene declares (map 0..2 with an atlas, an object in range whose record is not the
+    "none" type: such a record has no rectangle), apt_surface_maps_probe only a primitive in 0..n_prims-1; both refuse a scene without
+    textures.  Refused on the host, and a valid row right after runs."""
+    lib = _lib.load()
+    from adapt_amd.renderer import DeviceScene
+    fs = flat("textured")
+    fp, ip = (lambda a: a.ctypes.data_as(_lib.f32p)), (lambda a: a.ctypes.data_as(_lib.i32p))
+    uv, out = np.float32([0.25, 0.5]), np.zeros(7, np.float32)
+    have = np.asarray(fs.tex_i).reshape(fs.n_objects, 3, 5)[:, :, 0] > -255
+    good = np.int32([0, int(np.nonzero(have[:, 0])[0][0])])
+    missing = np.int32([0, int(np.nonzero(~have[:, 0])[0][0])])
+    sc = DeviceScene(fs)
+    try:
+        for row in (missing, np.int32([3, good[1]]), np.int32([-1, good[1]]), np.int32([0, fs.n_objects]), np.int32([0, -1])):
+            assert lib.apt_texture_probe(sc.handle, 1, ip(row), fp(uv), fp(out)) == -1 and b"apt_texture_probe: no such texture" in lib.apt_last_error(), row
+            _lib.check(lib.apt_texture_probe(sc.handle, 1, ip(good), fp(uv), fp(out)), "apt_texture_probe")
+        for prim in (fs.n_prims, -1):
+            row = np.int32([prim, 1])
+            assert lib.apt_surface_maps_probe(sc.handle, 1, ip(row), fp(uv), fp(out)) == -1 and b"apt_surface_maps_probe: no such primitive" in lib.apt_last_error(), prim
+            _lib.check(lib.apt_surface_maps_probe(sc.handle, 1, ip(np.int32([0, 1])), fp(uv), fp(out)), "apt_surface_maps_probe")
+    finally:
+        sc.close()
+    plain = DeviceScene(flat("cbox"))
+    try:
+        assert lib.apt_texture_probe(plain.handle, 1, ip(good), fp(uv), fp(out)) == -1 and b"apt_texture_probe: the scene has no textures" in lib.apt_last_error()
+        assert lib.apt_surface_maps_probe(plain.handle, 1, ip(np.int32([0, 1])), fp(uv), fp(out)) == -1 and b"apt_surface_maps_probe: the scene has no textures" in lib.apt_last_error()
+    finally:
+        plain.close()
 
 
 def build_bvh(fs):

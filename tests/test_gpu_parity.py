@@ -700,7 +700,7 @@ def test_texture_lookup_vs_reference_vectors_and_oracle(parsed, flat, oracle_sce
         tin, tout = g["texq_in"], g["texq_out"]
         got = sc.texture_query(tin[:, 0], tin[:, 1], tin[:, 2:4])
         bad = (got.view(np.uint32) != tout.view(np.uint32)).any(axis=1)
-        assert bad.mean() <= 0.01, int(bad.sum())                      # wrap-seam rounding of the stand-in's float remainder, see the CPU test
+        assert int(bad.sum()) == 0                                     # as on the CPU (test_oracle_golden.test_texture_query_bit_exact: no recorded lookup differs, wrap seams included)
         rs = np.random.RandomState(3)
         fs = flat("textured")
         maps, objs = np.nonzero(fs.tex_i[:, :, 0].T > -255)

@@ -40,6 +40,15 @@ FAMILIES = {
     # solid-angle pdf: one sdiv = v_rcp (1 ulp) AND a multiplication whose rounding the IEEE quotient does not have; the budget of
     # "1 per v_rcp" leaves that rounding out (measured 1.07 against a budget of 1), so it is counted here: 1 + 1
     "emitter_pdf":   2,
+    # shade_stage.hpp surface_maps (tests/test_gpu_texture_chain.py): a frame is R = c I + k n n^T + [axis]x with n = fnormalize(axis), and
+    # fnormalize is axis * v_rsq in the product build.  The one v_rsq (1 ulp = up to 2 u relative) scales n, n enters every entry twice
+    # (k n_i n_j: 4 u), and k = 1 - c reaches 2 where the target is next to -Y, where c + k n_i^2 = -1 + 2 is a result of the size of the
+    # output: 2 x 2 x 2 = 8 u S per frame in the worst case (a float32 restatement with the reciprocal square root moved by one ulp gives
+    # exactly 8.0 on such a row, one the oracle gets exactly; 4 where the target is at right angles to Y), on top of the roundings every
+    # build makes, which the floor of 1 stands for: 9 per frame.  One frame for a normal map or a bump map, two for a bump map on a
+    # normal-mapped vertex; the lookups substitute nothing.
+    "maps_one_frame":  9,
+    "maps_two_frames": 18,
 }
 AGG = 2.0
 
