@@ -160,7 +160,7 @@ APT_D void fix_prologue(const DevScene& sc, const Params& p, const Queues& q, Co
         const f3 o = ld3q(q.sh_o, q.sh_cap, io), d = ld3q(q.sh_d, q.sh_cap, io), c = ld3q(q.sh_c, q.sh_cap, io);
         const float dist = ldq(q.sh_tmax, io); const uint32_t slot = ldq(q.sh_id, io);
         bool occ, occ_b;
-        const float lim = (dist > 0.0f) ? dist - 1e-4f : 1e7f;
+        const float lim = shadow_limit(dist);
         flat_any2(sc.flat, sc.sweep, o, d, o, d, lim, lim, occ, occ_b);
         // (several samples of one vertex may be listed - S > 1 - and share its slot: one entry at a time within the wave's 64)
         const bool weird = !(isfinite(c.x) && isfinite(c.y) && isfinite(c.z));
@@ -506,7 +506,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
             bool occ = false;
             if (__any(f.want && !defer)) {
                 const FlatList ls = (occ_e >= 0) ? flat_occ_list((A_->sc).flat, occ_e) : flat_full_list((A_->sc).flat);
-                occ = flat_any1(ls, vx.hit_point, f.dir, (f.dist > 0.0f) ? f.dist - 1e-4f : 1e7f);
+                occ = flat_any1(ls, vx.hit_point, f.dir, shadow_limit(f.dist));
             }
             if (__any(defer)) {
                 const uint32_t spos = wave_append(defer, &cnt->n_fix_sh[cur][sl.q * CNT_PAD]);

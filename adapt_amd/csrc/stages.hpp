@@ -238,6 +238,15 @@ APT_D void add_radiance(float* L, uint32_t cap, uint32_t code, f3 c, bool exclus
     if (exclusive) { const f3 a = ldL(L, cap, code); stL(L, cap, code, mk3(a.x + c.x, a.y + c.y, a.z + c.z)); }
     else { float* p_ = L_slot(L, cap, code); atomicAdd(p_, c.x); atomicAdd(p_ + 1, c.y); atomicAdd(p_ + 2, c.z); }
 }
+// The search limit of a light sample's ray: just short of the light (distance - 1e-4), or the whole scene where the sample carries no
+// distance (dist <= 0).  A caller that wants a finished sample to accept nothing passes -1 instead.
+APT_D float shadow_limit(float dist) { return (dist > 0.0f) ? dist - 1e-4f : 1e7f; }
+// Upstream an occluded light sample still enters the sum as 0 * throughput; with a non-finite throughput (pdf == 0 upstream, quirk A.3 #11)
+// that is NaN, so the sample component is zeroed at the end.  A contribution c carries the throughput factor: c * 0 reproduces exactly
+// that, and is 0 for finite c - so only a non-finite contribution has to be added when its sample is occluded.
+// (k_shadow and k_shadow_dyn spell the test out: called there, the three comparisons are merged differently and k_shadow's BVH
+// instantiation takes one more VGPR in the exact build.)
+APT_D bool non_finite(f3 c) { return !(isfinite(c.x) && isfinite(c.y) && isfinite(c.z)); }
 // number of set bits of a ballot mask below this lane (v_mbcnt: no lane-mask registers to keep alive)
 APT_D uint32_t rank_in(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
 // append `flag` lanes of the wave to the queue counted by *counter; returns this lane's position
@@ -269,8 +278,8 @@ APT_D uint32_t wave_append_n(bool flag, uint32_t* counter, uint32_t k) {
 }
 
 // Append to one of several queues at once (rays traced in place: material classes + the staging queue, `nq_` of them; which = this lane's
-// queue, -1: none): the tails of all queues move with ONE atomic instruction (lane c carries queue c's count), as in k_extend's class
-// appends.  tr_append_issue sends it on its way, tr_append_pos waits for it.  `counters` = the first queue's tail of this sub-queue, queue c's
+// queue, -1: none): the tails of all queues move with ONE atomic instruction (lane c carries queue c's count), as in class_append's
+// class appends.  tr_append_issue sends it on its way, tr_append_pos waits for it.  `counters` = the first queue's tail of this sub-queue, queue c's
 // is `stride` words further per c.
 struct TrAppend { uint32_t raw, rank; };
 APT_D TrAppend tr_append_issue(int which, int nq_, uint32_t* counters, uint32_t stride) {
@@ -293,6 +302,40 @@ APT_D void cq_store(const Queues& q, uint32_t slot, f3 o, f3 d, f3 thr, uint32_t
     *reinterpret_cast<float4*>(reinterpret_cast<char*>(q.cq[1]) + so) = make_float4(d.x, d.y, d.z, __int_as_float(prim));
     *reinterpret_cast<float4*>(reinterpret_cast<char*>(q.cq[2]) + so) = make_float4(thr.x, thr.y, thr.z, __uint_as_float(id));
     *reinterpret_cast<float4*>(reinterpret_cast<char*>(q.cq[3]) + so) = make_float4(__uint_as_float(meta), pdf, u, v);
+}
+
+// Class-sort append of one finished ray per lane (cls: the hit primitive's material class, -1: a miss or an idle lane - misses vanish
+// here): every hit path's record goes to the dense queue of its class.  The queue tails of ALL classes move with one atomic instruction
+// (lane c carries class c's count), so a wave pays one memory round trip for its appends instead of one per class present, and the class
+// is part of the lane's slot.  All lanes of the wave take part.  Callers request the rest of the path's record before the class lookup,
+// so that its round trip overlaps the lookup's and the tail atomic's.
+APT_D void class_append(const Queues& q, const Params& p, Counters* cnt, int sq, uint32_t qbase, int cls, f3 o, f3 d, f3 thr, uint32_t id, uint32_t meta, float pdf, const HitRec& rec) {
+    uint32_t my_rank = 0, cnt_vec = 0;
+    for (int c = 0; c < q.n_classes; c++) {
+        const unsigned long long m = __ballot(cls == c);
+        if (cls == c) my_rank = rank_in(m);
+        if ((int)lane_id() == c) cnt_vec = (uint32_t)__popcll(m);
+    }
+    uint32_t tail = 0;
+    if ((int)lane_id() < q.n_classes && cnt_vec) tail = atomicAdd(&cnt->n_cls[lane_id()][sq * CNT_PAD], cnt_vec);
+    const uint32_t cpos = (uint32_t)__shfl((int)tail, cls < 0 ? 0 : cls) + my_rank;
+    if (cls >= 0) cq_store(q, (uint32_t)cls * p.cap + qbase + cpos, o, d, thr, id, meta, pdf, rec.t, rec.prim, rec.u, rec.v);
+}
+
+// What the first thread of a sub-queue's first workgroup does for everybody at the head of an extend launch: recycle the counters nobody
+// reads any more - the shadow queue, the next-ray queue of this bounce (it was the current queue of the previous bounce), the volumetric
+// walk lists - and count the launch's rays.
+APT_D void begin_extend(Counters* cnt, int sq, int cur, uint32_t n) {
+    cnt->n_shadow[sq * CNT_PAD] = 0; cnt->n_active[cur ^ 1][sq * CNT_PAD] = 0;
+    for (int w = 0; w < 8; w++) cnt->n_walk[w][sq * CNT_PAD] = 0;
+    cnt->stats[sq][ST_EXTEND] += n;
+}
+// ... and of a shadow launch: the light samples it reads (a sub-queue's entries beyond sh_subcap were never stored), counted as traced
+// (tally: unless the kernel counts them sample by sample), and the class queues' tails zeroed - every shade of this bounce is done.
+APT_D uint32_t shadow_count(const uint32_t* n_src, int sq, const Queues& q) { return min(n_src[sq * CNT_PAD], q.sh_subcap); }
+APT_D void begin_shadow(Counters* cnt, const Queues& q, int sq, uint32_t n, bool tally = true) {
+    if (tally) cnt->stats[sq][ST_SHADOW_TRACED] += n;
+    for (int c = 0; c < q.n_classes; c++) cnt->n_cls[c][sq * CNT_PAD] = 0;
 }
 
 // Queue addressing.  Every queue array is indexed by a 32-bit slot whose BYTE offset also fits 32 bits (the host
@@ -521,11 +564,7 @@ __global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == TRACE_TILE ? APT_TILE
     __shared__ float s_sweep[MODE == TRACE_SWEEP ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
     const SubLoop sl = sub_loop(p.nq, TRACE_NT(MODE));
     const uint32_t n = n_src[sl.q * CNT_PAD];
-    if (cnt && sl.first == 0 && threadIdx.x == 0) {
-        cnt->n_shadow[sl.q * CNT_PAD] = 0; cnt->n_active[cur ^ 1][sl.q * CNT_PAD] = 0;
-        for (int w = 0; w < 8; w++) cnt->n_walk[w][sl.q * CNT_PAD] = 0;
-        cnt->stats[sl.q][ST_EXTEND] += n;
-    }
+    if (cnt && sl.first == 0 && threadIdx.x == 0) begin_extend(cnt, sl.q, cur, n);
     const float* ro = q.ray_o[cur]; const float* rd = q.ray_d[cur];
     const uint32_t qbase = (uint32_t)sl.q * p.subcap;
     for (uint32_t base = sl.first; base < n; base += sl.stride) {
@@ -542,22 +581,10 @@ __global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == TRACE_TILE ? APT_TILE
         if (!SORTED) {
             if (valid) { stq(q.hit_t, io, rec.t); stq(q.hit_prim, io, rec.prim); stq(q.hit_u, io, rec.u); stq(q.hit_v, io, rec.v); }
         } else {
-            // sort by material class: misses vanish here, every hit path's record goes to the dense queue of its class.  The queue tails
-            // of ALL classes move with one atomic instruction (lane c carries class c's count), so a tile pays one memory round trip for
-            // its appends instead of one per class present; the record stores then run class by class with scalar queue pointers.
-            // the rest of the path's record travels with the hit: requested before the class lookup and the tail atomic, so that all three round trips overlap
+            // sort by material class; the rest of the path's record travels with the hit
             const f3 st_thr = ld3q(q.thr[cur], p.cap, io); const uint32_t st_id = ldq(q.id[cur], io), st_meta = ldq(q.meta[cur], io); const float st_pdf = ldq(q.pdf[cur], io);
             const int cls = (valid && rec.prim >= 0) ? sc.prim_class[rec.prim] : -1;
-            uint32_t my_rank = 0, cnt_vec = 0;
-            for (int c = 0; c < q.n_classes; c++) {
-                const unsigned long long m = __ballot(cls == c);
-                if (cls == c) my_rank = rank_in(m);
-                if ((int)lane_id() == c) cnt_vec = (uint32_t)__popcll(m);
-            }
-            uint32_t tail = 0;
-            if ((int)lane_id() < q.n_classes && cnt_vec) tail = atomicAdd(&cnt->n_cls[lane_id()][sl.q * CNT_PAD], cnt_vec);
-            const uint32_t cpos = (uint32_t)__shfl((int)tail, cls < 0 ? 0 : cls) + my_rank;
-            if (cls >= 0) cq_store(q, (uint32_t)cls * p.cap + qbase + cpos, o, d, st_thr, st_id, st_meta, st_pdf, rec.t, rec.prim, rec.u, rec.v);
+            class_append(q, p, cnt, sl.q, qbase, cls, o, d, st_thr, st_id, st_meta, st_pdf, rec);
         }
     }
 }
@@ -595,6 +622,42 @@ APT_D void walk_settle(const TravStack& ts, int& sp, grp_t& ng, const grp_t& tg,
         if (sp == 0) state = 2; else ng = tpop(ts, sp);
     }
 }
+// Walk scheduling statistics (-DAPT_WALK_STATS, Counters::wdbg): nothing in a shipped build.
+struct WalkDbg {
+#ifdef APT_WALK_STATS
+    uint32_t wd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+};
+// Dynamic ray fetch, the claim: the wave's idle lanes (`need`) take the next queue positions from the sub-queue's work counter with one
+// atomic; a lane has a ray when its position is below n.  exhausted (wave-uniform): the counter has run past the queue.
+APT_D uint32_t claim_rays(uint32_t* work, uint32_t n, bool need, bool& exhausted, WalkDbg& dbg) {
+    const unsigned long long m = __ballot(need);
+    uint32_t base = 0;
+    if (lane_id() == 0 && m) base = atomicAdd(work, (uint32_t)__popcll(m));
+    base = (uint32_t)__builtin_amdgcn_readlane((int)base, 0);      // v_readlane: lane 0's value as a scalar (a shuffle would go through the LDS crossbar)
+    const uint32_t pos = base + rank_in(m);
+    if (base + (uint32_t)__popcll(m) >= n) exhausted = true;
+#ifdef APT_WALK_STATS
+    dbg.wd[5]++; dbg.wd[6] += (uint32_t)__popcll(__ballot(need && pos < n));
+#endif
+    return pos;
+}
+// Dynamic ray fetch, the walk: rounds of one action for the whole wave, chosen by vote (above) - a node step for the lanes without pending
+// primitives, or one primitive test for the lanes with some - until fewer than min_active lanes still hold a ray.  Per ray nothing
+// changes against traverse<ANY>: same nodes, same primitives, same order.  ANY: the first occluder ends the lane's walk.
+template <bool ANY, int WEIGHT>
+APT_D void walk_rounds(const DevBvh& bvh, const TravStack& ts, uint32_t min_active, int& sp, grp_t& ng, grp_t& tg, int& state, const WalkRay& r, HitRec& rec, WalkStats& ws, bool& occluded, WalkDbg& dbg) {
+    do {
+        const bool want_t = state == 1 && tg.y != 0u, want_n = state == 1 && tg.y == 0u;
+#ifdef APT_WALK_STATS
+        { const uint32_t a_ = (uint32_t)__popcll(__ballot(want_t)), b_ = (uint32_t)__popcll(__ballot(want_n)); dbg.wd[4] += a_ + b_; if (a_ * WEIGHT >= b_) { dbg.wd[2]++; dbg.wd[3] += a_; } else { dbg.wd[0]++; dbg.wd[1] += b_; } }
+#endif
+        if (__popcll(__ballot(want_t)) * WEIGHT >= __popcll(__ballot(want_n))) {
+            if (want_t && tri_one<ANY>(bvh, tg, r, rec, ws) && ANY) { occluded = true; sp = 0; ng.y = 0u; tg.y = 0u; }
+        } else if (want_n) group_step(bvh, ts, sp, ng, tg, r, rec.t, ws);
+        walk_settle(ts, sp, ng, tg, state);
+    } while ((uint32_t)__popcll(__ballot(state == 1)) >= min_active);
+}
 // Register budget of the walk kernels: left alone the allocator takes 86 VGPRs for the class-sorting closest-hit walk (five waves per SIMD);
 // asked for seven waves it finds 70 without a spill (eight: 64 and a 20-byte spill).  Measured (product build, one lane, ms per 64 / 32 spp
 // of C4 / C5): extend 18.73 -> 17.79 / 13.35 -> 13.04 at seven, 17.83 / 13.41 at eight, 18.03 / 13.23 at six.
@@ -612,9 +675,7 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_extend_dyn(DevScene sc,
     const int sq = (int)(blockIdx.x % (uint32_t)p.nq);
     const uint32_t n = n_src[sq * CNT_PAD];
     if (blockIdx.x / (uint32_t)p.nq == 0 && threadIdx.x == 0) {
-        cnt->n_shadow[sq * CNT_PAD] = 0; cnt->n_active[cur_q ^ 1][sq * CNT_PAD] = 0;
-        for (int w = 0; w < 8; w++) cnt->n_walk[w][sq * CNT_PAD] = 0;
-        cnt->stats[sq][ST_EXTEND] += n;
+        begin_extend(cnt, sq, cur_q, n);
         cnt->n_work[1][sq * CNT_PAD] = 0;                                          // this bounce's any-hit walk (k_shadow_dyn) starts at the head of its queue
     }
     uint32_t* work = &cnt->n_work[0][sq * CNT_PAD];
@@ -629,10 +690,8 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_extend_dyn(DevScene sc,
     WalkStats ws; ws.nodes = ws.prims = 0;
     int sp = 0;
     grp_t ng = mk_grp(0u, 0u), tg = mk_grp(0u, 0u);       // node group / triangle group of the ray being walked (traverse.hpp)
-    bool exhausted = false;                     // wave-uniform: the work counter has run past the queue
-#ifdef APT_WALK_STATS
-    uint32_t wd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+    bool exhausted = false, occluded = false;   // (occluded: the any-hit walk's)
+    WalkDbg dbg;
     for (;;) {
         // ---- hand in finished rays (all lanes take part: the class appends are ballot-compacted)
         const bool fin = state == 2;
@@ -643,7 +702,6 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_extend_dyn(DevScene sc,
         if (!SORTED) {
             if (fin) { stq(q.hit_t, io, rec.t); stq(q.hit_prim, io, rec.prim); stq(q.hit_u, io, rec.u); stq(q.hit_v, io, rec.v); }
         } else if (__any(fin)) {
-            // (as in k_extend: the rest of the record is requested first, the queue tails of all classes move with ONE atomic instruction)
             // (the rest of the path's record was fetched WITH the ray - six coalesced loads at the claim - and has waited in LDS behind the stack:
             // fetched here, by the finished lanes' scattered queue positions, it was six of the ~42 scattered accesses a ray makes)
             f3 st_thr = splat3(0.f); uint32_t st_id = 0, st_meta = 0; float st_pdf = 0.f;
@@ -653,26 +711,13 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_extend_dyn(DevScene sc,
 #else
             const int cls = (fin && rec.prim >= 0) ? sc.prim_class[rec.prim] : -1;
 #endif
-            uint32_t my_rank = 0, cnt_vec = 0;
-            for (int c = 0; c < q.n_classes; c++) {
-                const unsigned long long m = __ballot(cls == c);
-                if (cls == c) my_rank = rank_in(m);
-                if ((int)lane_id() == c) cnt_vec = (uint32_t)__popcll(m);
-            }
-            uint32_t tail = 0;
-            if ((int)lane_id() < q.n_classes && cnt_vec) tail = atomicAdd(&cnt->n_cls[lane_id()][sq * CNT_PAD], cnt_vec);
-            const uint32_t cpos = (uint32_t)__shfl((int)tail, cls < 0 ? 0 : cls) + my_rank;
-            if (cls >= 0) cq_store(q, (uint32_t)cls * p.cap + qbase + cpos, r.o, r.d, st_thr, st_id, st_meta, st_pdf, rec.t, rec.prim, rec.u, rec.v);
+            class_append(q, p, cnt, sq, qbase, cls, r.o, r.d, st_thr, st_id, st_meta, st_pdf, rec);
         }
         if (fin) state = 0;
         // ---- claim fresh rays for the idle lanes
         if (!exhausted) {
             const bool need = state == 0;
-            const unsigned long long m = __ballot(need);
-            uint32_t base = 0;
-            if (lane_id() == 0 && m) base = atomicAdd(work, (uint32_t)__popcll(m));
-            base = (uint32_t)__builtin_amdgcn_readlane((int)base, 0);      // v_readlane: lane 0's value as a scalar (a shuffle would go through the LDS crossbar)
-            const uint32_t pos = base + rank_in(m);
+            const uint32_t pos = claim_rays(work, n, need, exhausted, dbg);
             if (need && pos < n) {
                 io = (qbase + pos) << 2;
                 r = make_walk_ray(sc.bvh, ld3q(ro, p.cap, io), ld3q(rd, p.cap, io));
@@ -684,29 +729,14 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_extend_dyn(DevScene sc,
                 rec.t = 1e7f; rec.prim = -1; rec.u = 0.f; rec.v = 0.f;
                 sp = 0; ng = APT_ROOT_GROUP; state = 1;
             }
-            if (base + (uint32_t)__popcll(m) >= n) exhausted = true;
-#ifdef APT_WALK_STATS
-            wd[5]++; wd[6] += (uint32_t)__popcll(__ballot(need && pos < n));
-#endif
         }
         if (!__any(state == 1)) break;
-        // ---- walk: the while-while loop of traverse<false>, left as soon as too few lanes still hold a ray
-        const uint32_t min_active = exhausted ? 1u : (uint32_t)APT_DYN_MIN_ACTIVE;
-        // One action per iteration for the whole wave, chosen by vote (see walk_settle): a node step for the lanes without pending primitives,
-        // or one primitive test for the lanes with some.  Per ray nothing changes - same nodes, same primitives, same order.
-        do {
-            const bool want_t = state == 1 && tg.y != 0u, want_n = state == 1 && tg.y == 0u;
-#ifdef APT_WALK_STATS
-            { const uint32_t a_ = (uint32_t)__popcll(__ballot(want_t)), b_ = (uint32_t)__popcll(__ballot(want_n)); wd[4] += a_ + b_; if (a_ * APT_VOTE_TRI_WEIGHT >= b_) { wd[2]++; wd[3] += a_; } else { wd[0]++; wd[1] += b_; } }
-#endif
-            if (__popcll(__ballot(want_t)) * APT_VOTE_TRI_WEIGHT >= __popcll(__ballot(want_n))) { if (want_t) tri_one<false>(sc.bvh, tg, r, rec, ws); }
-            else if (want_n) group_step(sc.bvh, ts, sp, ng, tg, r, rec.t, ws);
-            walk_settle(ts, sp, ng, tg, state);
-        } while ((uint32_t)__popcll(__ballot(state == 1)) >= min_active);
+        // ---- walk: left as soon as too few lanes still hold a ray
+        walk_rounds<false, APT_VOTE_TRI_WEIGHT>(sc.bvh, ts, exhausted ? 1u : (uint32_t)APT_DYN_MIN_ACTIVE, sp, ng, tg, state, r, rec, ws, occluded, dbg);
     }
 #ifdef APT_WALK_STATS
     flush_stat(ws.nodes, &cnt->stats[sq][10]); flush_stat(ws.prims, &cnt->stats[sq][11]);
-    if (lane_id() == 0) for (int k = 0; k < 7; k++) atomicAdd(&cnt->wdbg[0][k], (unsigned long long)wd[k]);
+    if (lane_id() == 0) for (int k = 0; k < 7; k++) atomicAdd(&cnt->wdbg[0][k], (unsigned long long)dbg.wd[k]);
 #endif
 }
 
@@ -715,11 +745,8 @@ template <int MODE>
 __global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == TRACE_TILE ? APT_TILE_WAVES : 1)) k_shadow(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan) {
     __shared__ float s_sweep[MODE == TRACE_SWEEP ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
     const SubLoop sl = sub_loop(p.nq, TRACE_NT(MODE));
-    const uint32_t n = min(cnt->n_shadow[sl.q * CNT_PAD], q.sh_subcap);
-    if (sl.first == 0 && threadIdx.x == 0) {
-        cnt->stats[sl.q][ST_SHADOW_TRACED] += n;
-        for (int c = 0; c < q.n_classes; c++) cnt->n_cls[c][sl.q * CNT_PAD] = 0;      // every shade of this bounce is done
-    }
+    const uint32_t n = shadow_count(cnt->n_shadow, sl.q, q);
+    if (sl.first == 0 && threadIdx.x == 0) begin_shadow(cnt, q, sl.q, n);
     const uint32_t qbase = (uint32_t)sl.q * q.sh_subcap, sc_ = q.sh_cap;
     uint32_t t_lit = 0;
     for (uint32_t base = sl.first; base < n; base += sl.stride) {
@@ -730,16 +757,13 @@ __global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == TRACE_TILE ? APT_TILE
         const f3 o = ld3q(q.sh_o, sc_, io);
         const f3 d = ld3q(q.sh_d, sc_, io);
         const float dist = ldq(q.sh_tmax, io);
-        HitRec rec; rec.t = (dist > 0.0f) ? dist - 1e-4f : 1e7f; rec.prim = -1; rec.u = rec.v = 0.f;
+        HitRec rec; rec.t = shadow_limit(dist); rec.prim = -1; rec.u = rec.v = 0.f;
         const bool occluded = (MODE == TRACE_BVH) ? traverse<true>(sc.bvh, make_stack(plan), o, d, rec)
                             : (MODE == TRACE_SWEEP) ? sweep_wg<true, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep)
                                           : sweep_tile<true, APT_TILE_NT>(sc.sweep, o, d, rec, valid, reinterpret_cast<float*>(s_dyn));
         if (valid) {
             f3 c = ld3q(q.sh_c, sc_, io);
-            // Upstream an occluded light sample still enters the sum as 0 * throughput; with a non-finite
-            // throughput (pdf == 0 upstream, quirk A.3 #11) that is NaN, so the sample component is zeroed at
-            // the end.  c carries the throughput factor: c * 0 reproduces exactly that, and is 0 for finite c.
-            const bool weird = !(isfinite(c.x) && isfinite(c.y) && isfinite(c.z));
+            const bool weird = !(isfinite(c.x) && isfinite(c.y) && isfinite(c.z));      // non_finite(c) spelled out: the rule, and why it is not called here, are at non_finite
             if (occluded && weird) c = c * 0.f;
             if (!occluded || weird) {
                 add_radiance(q.L, p.cap, ldq(q.sh_id, io), c, APT_EXCLUSIVE_L(p));      // sh_id: byte offset of the path's radiance slot
@@ -751,15 +775,14 @@ __global__ void __launch_bounds__(TRACE_NT(MODE), (MODE == TRACE_TILE ? APT_TILE
 }
 
 // ------------------------------------------------------- shadow, BVH walk with dynamic ray fetch
-// Any-hit twin of k_extend_dyn: a lane leaves the walk at its first occluder or when its stack runs empty, adds its contribution if
+// The any-hit walk: a lane leaves the walk at its first occluder or when its stack runs empty, adds its contribution if
 // unoccluded, and claims the next shadow ray as soon as the wave runs low on walking lanes.
 __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_shadow_dyn(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan) {
     const TravStack ts = make_walk_stack(plan);
     const int sq = (int)(blockIdx.x % (uint32_t)p.nq);
-    const uint32_t n = min(cnt->n_shadow[sq * CNT_PAD], q.sh_subcap);
+    const uint32_t n = shadow_count(cnt->n_shadow, sq, q);
     if (blockIdx.x / (uint32_t)p.nq == 0 && threadIdx.x == 0) {
-        cnt->stats[sq][ST_SHADOW_TRACED] += n;
-        for (int c = 0; c < q.n_classes; c++) cnt->n_cls[c][sq * CNT_PAD] = 0;      // every shade of this bounce is done
+        begin_shadow(cnt, q, sq, n);
         cnt->n_work[0][sq * CNT_PAD] = 0;                                          // the next bounce's closest-hit walk starts at the head of its queue (a host-side fill per bounce was a launch of its own: 15 us)
     }
     uint32_t* work = &cnt->n_work[1][sq * CNT_PAD];
@@ -769,19 +792,17 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_shadow_dyn(DevScene sc,
     bool occluded = false;
     uint32_t io = 0;
     WalkRay r = make_walk_ray(sc.bvh, splat3(0.f), mk3(0.f, 0.f, 1.f));
-    HitRec rec; rec.t = 0.f; rec.prim = -1; rec.u = rec.v = 0.f;      // rec.t = the search limit (distance to the light - 1e-4)
+    HitRec rec; rec.t = 0.f; rec.prim = -1; rec.u = rec.v = 0.f;      // rec.t = the search limit (shadow_limit)
     WalkStats ws; ws.nodes = ws.prims = 0;
     int sp = 0;
     grp_t ng = mk_grp(0u, 0u), tg = mk_grp(0u, 0u);
     bool exhausted = false;
     uint32_t t_lit = 0;
-#ifdef APT_WALK_STATS
-    uint32_t wd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+    WalkDbg dbg;
     for (;;) {
-        if (state == 2) {
-            f3 c = mk3(park[0], park[BLOCK], park[2 * BLOCK]);      // (contribution and slot were fetched with the ray - coalesced - and have waited in LDS: k_extend_dyn)
-            const bool weird = !(isfinite(c.x) && isfinite(c.y) && isfinite(c.z));       // see k_shadow
+        if (state == 2) {      // (contribution and slot were fetched with the ray - coalesced - and have waited in LDS, like the closest-hit walk's path record)
+            f3 c = mk3(park[0], park[BLOCK], park[2 * BLOCK]);
+            const bool weird = !(isfinite(c.x) && isfinite(c.y) && isfinite(c.z));      // non_finite(c), spelled out as in k_shadow
             if (occluded && weird) c = c * 0.f;
             if (!occluded || weird) {
                 add_radiance(q.L, p.cap, __float_as_uint(park[3 * BLOCK]), c, APT_EXCLUSIVE_L(p));
@@ -791,41 +812,23 @@ __global__ void __launch_bounds__(BLOCK) APT_WALK_ATTR k_shadow_dyn(DevScene sc,
         }
         if (!exhausted) {
             const bool need = state == 0;
-            const unsigned long long m = __ballot(need);
-            uint32_t base = 0;
-            if (lane_id() == 0 && m) base = atomicAdd(work, (uint32_t)__popcll(m));
-            base = (uint32_t)__builtin_amdgcn_readlane((int)base, 0);      // v_readlane: lane 0's value as a scalar (a shuffle would go through the LDS crossbar)
-            const uint32_t pos = base + rank_in(m);
+            const uint32_t pos = claim_rays(work, n, need, exhausted, dbg);
             if (need && pos < n) {
                 io = (qbase + pos) << 2;
                 r = make_walk_ray(sc.bvh, ld3q(q.sh_o, sc_, io), ld3q(q.sh_d, sc_, io));
                 const float dist = ldq(q.sh_tmax, io);
                 { const f3 c_ = ld3q(q.sh_c, sc_, io); park[0] = c_.x; park[BLOCK] = c_.y; park[2 * BLOCK] = c_.z; park[3 * BLOCK] = __uint_as_float(ldq(q.sh_id, io)); }
-                rec.t = (dist > 0.0f) ? dist - 1e-4f : 1e7f;
+                rec.t = shadow_limit(dist);
                 occluded = false; sp = 0; ng = APT_ROOT_GROUP; state = 1;
             }
-            if (base + (uint32_t)__popcll(m) >= n) exhausted = true;
-#ifdef APT_WALK_STATS
-            wd[5]++; wd[6] += (uint32_t)__popcll(__ballot(need && pos < n));
-#endif
         }
         if (!__any(state == 1)) break;
-        const uint32_t min_active = exhausted ? 1u : (uint32_t)APT_DYN_MIN_ACTIVE_SH;
-        do {
-            const bool want_t = state == 1 && tg.y != 0u, want_n = state == 1 && tg.y == 0u;
-#ifdef APT_WALK_STATS
-            { const uint32_t a_ = (uint32_t)__popcll(__ballot(want_t)), b_ = (uint32_t)__popcll(__ballot(want_n)); wd[4] += a_ + b_; if (a_ * APT_VOTE_TRI_WEIGHT_SH >= b_) { wd[2]++; wd[3] += a_; } else { wd[0]++; wd[1] += b_; } }
-#endif
-            if (__popcll(__ballot(want_t)) * APT_VOTE_TRI_WEIGHT_SH >= __popcll(__ballot(want_n))) {
-                if (want_t && tri_one<true>(sc.bvh, tg, r, rec, ws)) { occluded = true; sp = 0; ng.y = 0u; tg.y = 0u; }      // first occluder ends the walk
-            } else if (want_n) group_step(sc.bvh, ts, sp, ng, tg, r, rec.t, ws);
-            walk_settle(ts, sp, ng, tg, state);
-        } while ((uint32_t)__popcll(__ballot(state == 1)) >= min_active);
+        walk_rounds<true, APT_VOTE_TRI_WEIGHT_SH>(sc.bvh, ts, exhausted ? 1u : (uint32_t)APT_DYN_MIN_ACTIVE_SH, sp, ng, tg, state, r, rec, ws, occluded, dbg);
     }
     flush_stat(t_lit, &cnt->stats[sq][ST_LIT]);
 #ifdef APT_WALK_STATS
     flush_stat(ws.nodes, &cnt->stats[sq][12]); flush_stat(ws.prims, &cnt->stats[sq][13]);
-    if (lane_id() == 0) for (int k = 0; k < 7; k++) atomicAdd(&cnt->wdbg[1][k], (unsigned long long)wd[k]);
+    if (lane_id() == 0) for (int k = 0; k < 7; k++) atomicAdd(&cnt->wdbg[1][k], (unsigned long long)dbg.wd[k]);
 #endif
 }
 
@@ -854,34 +857,45 @@ APT_D void fix_append(bool f0, bool f1, uint32_t pos, uint32_t* counter, uint32_
     if (f0) stq(list, at, pos);
     if (f1) stq(list, at + (f0 ? 4u : 0u), pos + 1u);
 }
+// Which pair of queue entries a lane of a flat stage kernel works on.  Hot lanes (LISTED false) own entries pos and pos + 1 of a
+// 512-entry tile (v0, v1: which of them exist; idle lanes re-read the last pair, never written back).  Listed lanes (the fix-up variants)
+// own ONE entry, as "entry 0" of its pair - position `pos` taken from the fix-up list, or the lane's own index where there is no list (the
+// queue holds nothing but deferred entries): they load the aligned pair that contains it (io) and, for an odd position, swap the halves
+// of everything they loaded (swap_if).  io0: byte offset of entry 0's own slot.
+struct FlatLane { uint32_t pos, io, io0; bool v0, v1, odd; };
+template <bool LISTED>
+APT_D FlatLane flat_lane(uint32_t base, uint32_t n, uint32_t qbase, const uint32_t* list) {
+    FlatLane l;
+    if (LISTED) {
+        const uint32_t li = base + threadIdx.x;
+        l.v0 = li < n; l.v1 = false;
+        l.pos = list ? ldq(list, (qbase + (l.v0 ? li : n - 1u)) << 2) : (l.v0 ? li : n - 1u);
+        l.odd = (l.pos & 1u) != 0u; l.io = (qbase + (l.pos & ~1u)) << 2; l.io0 = (qbase + l.pos) << 2;
+    } else {
+        l.pos = base + 2u * threadIdx.x;
+        l.v0 = l.pos < n; l.v1 = l.pos + 1u < n; l.odd = false;
+        l.io = l.io0 = (qbase + (l.v0 ? l.pos : ((n - 1u) & ~1u))) << 2;
+    }
+    return l;
+}
+template <typename T2> APT_D void swap_if(bool odd, T2& v) { if (odd) { T2 t_; t_.x = v.y; t_.y = v.x; v = t_; } }
+
 template <int SORTED, int VAR>
 APT_D void extend_flat_body(const DevScene& sc, const Params& p, const Queues& q, Counters* cnt, int cur, const uint32_t* n_src) {
     const SubLoop sl = sub_loop(p.nq, VAR == 2 ? BLOCK : FLAT_NT);
     const uint32_t n = (VAR == 2) ? cnt->n_fix_ext[cur][sl.q * CNT_PAD] : n_src[sl.q * CNT_PAD];
     if (VAR != 2 && cnt && sl.first == 0 && threadIdx.x == 0) {
-        cnt->n_shadow[sl.q * CNT_PAD] = 0; cnt->n_active[cur ^ 1][sl.q * CNT_PAD] = 0;
-        for (int w = 0; w < 8; w++) cnt->n_walk[w][sl.q * CNT_PAD] = 0;
+        begin_extend(cnt, sl.q, cur, n);
         cnt->n_fix_ext[cur ^ 1][sl.q * CNT_PAD] = 0; cnt->n_fix_sh[cur][sl.q * CNT_PAD] = 0;   // (both lists were consumed by fix-up launches that have finished)
-        cnt->stats[sl.q][ST_EXTEND] += n;
     }
     const float* ro = q.ray_o[cur]; const float* rd = q.ray_d[cur];
     const uint32_t qbase = (uint32_t)sl.q * p.subcap, cs = p.cap * 4u;             // component stride in bytes
     for (uint32_t base = sl.first; base < n; base += sl.stride) {
-        uint32_t pos; bool v0, v1; uint32_t io; bool odd = false;
-        if (VAR == 2) {                                                            // one listed entry per lane, as "entry 0" of its pair
-            const uint32_t li = base + threadIdx.x;
-            v0 = li < n; v1 = false;
-            pos = ldq(q.fix_ext, (qbase + (v0 ? li : n - 1u)) << 2);
-            odd = (pos & 1u) != 0u; io = (qbase + (pos & ~1u)) << 2;
-        } else {
-            pos = base + 2u * threadIdx.x;
-            v0 = pos < n; v1 = pos + 1u < n;
-            io = (qbase + (v0 ? pos : ((n - 1u) & ~1u))) << 2;                      // idle lanes re-read the last pair (never written back)
-        }
+        const FlatLane ln = flat_lane<VAR == 2>(base, n, qbase, q.fix_ext);
+        const uint32_t pos = ln.pos, io = ln.io, io0 = ln.io0; const bool v0 = ln.v0, v1 = ln.v1, odd = ln.odd;
         v2f ox = ld2q<v2f>(ro, io), oy = ld2q<v2f>(ro, io + cs), oz = ld2q<v2f>(ro, io + 2u * cs);
         v2f dx = ld2q<v2f>(rd, io), dy = ld2q<v2f>(rd, io + cs), dz = ld2q<v2f>(rd, io + 2u * cs);
-        if (VAR == 2 && odd) { ox = mk2(ox.y, ox.x); oy = mk2(oy.y, oy.x); oz = mk2(oz.y, oz.x); dx = mk2(dx.y, dx.x); dy = mk2(dy.y, dy.x); dz = mk2(dz.y, dz.x); }
-        const uint32_t io0 = (VAR == 2) ? (qbase + pos) << 2 : io;                  // byte offset of entry 0's own slot
+        swap_if(odd, ox); swap_if(odd, oy); swap_if(odd, oz); swap_if(odd, dx); swap_if(odd, dy); swap_if(odd, dz);
         const f3 o0 = mk3(ox.x, oy.x, oz.x), d0 = mk3(dx.x, dy.x, dz.x), o1 = mk3(ox.y, oy.y, oz.y), d1 = mk3(dx.y, dy.y, dz.y);
         HitRec r0, r1; r0.t = r1.t = 1e7f; r0.prim = r1.prim = -1; r0.u = r0.v = r1.u = r1.v = 0.f;
         int c0, c1; bool sp0, sp1;
@@ -896,10 +910,10 @@ APT_D void extend_flat_body(const DevScene& sc, const Params& p, const Queues& q
             } else if (v0) { stq(q.hit_t, io0, r0.t); stq(q.hit_prim, io0, r0.prim); if (need_uv) { stq(q.hit_u, io0, r0.u); stq(q.hit_v, io0, r0.v); } }
             // (VAR 1 writes a provisional record for a deferred entry; the fix-up launch overwrites it before anybody reads it)
         } else {
-            // sort by material class (see k_extend): the tails of all class queues move with ONE atomic instruction per tile row
+            // sort by material class: class_append's rule for the lane's TWO entries - one tail atomic per tile row, and another rank rule
             v2f tx = ld2q<v2f>(q.thr[cur], io), ty = ld2q<v2f>(q.thr[cur], io + cs), tz = ld2q<v2f>(q.thr[cur], io + 2u * cs);
             v2u pid = ld2q<v2u>(q.id[cur], io), pmeta = ld2q<v2u>(q.meta[cur], io); v2f ppdf = ld2q<v2f>(q.pdf[cur], io);
-            if (VAR == 2 && odd) { tx = mk2(tx.y, tx.x); ty = mk2(ty.y, ty.x); tz = mk2(tz.y, tz.x); ppdf = mk2(ppdf.y, ppdf.x); v2u t_; t_.x = pid.y; t_.y = pid.x; pid = t_; t_.x = pmeta.y; t_.y = pmeta.x; pmeta = t_; }
+            swap_if(odd, tx); swap_if(odd, ty); swap_if(odd, tz); swap_if(odd, ppdf); swap_if(odd, pid); swap_if(odd, pmeta);
             // (a deferred entry joins its class queue in the fix-up launch)
             const int cls0 = (v0 && !sp0 && r0.prim >= 0) ? c0 : -1, cls1 = (v1 && !sp1 && r1.prim >= 0) ? c1 : -1;
             uint32_t rank0 = 0, rank1 = 0, cnt_vec = 0;
@@ -935,11 +949,8 @@ APT_D void shadow_flat_body(const DevScene& sc, const Params& p, const Queues& q
     // VAR 3: the fix-up pass of a render whose shade kernel traces its rays itself (shade_stage.hpp k_shade_traced): the shadow queue then holds
     // nothing but the deferred entries, n_fix_sh[par] of them, and every one is done in full, one per lane, like VAR 2's.
     const SubLoop sl = sub_loop(p.nq, VAR >= 2 ? BLOCK : FLAT_NT);
-    const uint32_t n = (VAR == 2) ? cnt->n_fix_sh[par][sl.q * CNT_PAD] : ((VAR == 3) ? min(cnt->n_fix_sh[par][sl.q * CNT_PAD], q.sh_subcap) : min(cnt->n_shadow[sl.q * CNT_PAD], q.sh_subcap));
-    if (VAR < 2 && sl.first == 0 && threadIdx.x == 0) {
-        if (!p.nee_vm) cnt->stats[sl.q][ST_SHADOW_TRACED] += n;
-        for (int c = 0; c < q.n_classes; c++) cnt->n_cls[c][sl.q * CNT_PAD] = 0;      // every shade of this bounce is done
-    }
+    const uint32_t n = (VAR == 2) ? cnt->n_fix_sh[par][sl.q * CNT_PAD] : ((VAR == 3) ? min(cnt->n_fix_sh[par][sl.q * CNT_PAD], q.sh_subcap) : shadow_count(cnt->n_shadow, sl.q, q));
+    if (VAR < 2 && sl.first == 0 && threadIdx.x == 0) begin_shadow(cnt, q, sl.q, n, !p.nee_vm);      // (by vertex: the samples are counted as they are traced)
     const uint32_t qbase = (uint32_t)sl.q * q.sh_subcap, cs = q.sh_cap * 4u;
     uint32_t* fix_counter = &cnt->n_fix_sh[par][sl.q * CNT_PAD];
     uint32_t t_lit = 0, t_traced = 0;
@@ -947,7 +958,7 @@ APT_D void shadow_flat_body(const DevScene& sc, const Params& p, const Queues& q
         // Light samples by vertex (S > 1; `n` counts VERTICES): a lane owns one vertex and walks its sample planes two at a time - the two
         // rays of a packed test then share their origin.  The samples are summed in sample order, as upstream sums direct_int, and the
         // vertex's radiance slot takes ONE read-modify-write, which no other lane of the launch touches.  (tmax < 0: a sample the shade
-        // kernel found not worth tracing.)  An occluded sample still enters the sum as 0 * contribution - NaN for a non-finite one (see k_shadow).
+        // kernel found not worth tracing.)  An occluded sample still enters the sum as 0 * contribution - NaN for a non-finite one (non_finite).
         const SubLoop sv = sub_loop(p.nq, BLOCK);
         for (uint32_t base = sv.first; base < n; base += sv.stride) {
             const uint32_t li = base + threadIdx.x;
@@ -965,10 +976,10 @@ APT_D void shadow_flat_body(const DevScene& sc, const Params& p, const Queues& q
                 const bool la = valid && !(ta < 0.0f), lb = valid && two && !(tb < 0.0f);
                 const f3 da = ld3q(q.sh_d, q.sh_cap, ia), db = ld3q(q.sh_d, q.sh_cap, ib);
                 bool oa, ob, spa, spb;
-                flat_any2<VAR == 1>(sc.flat, sc.sweep, o, da, o, db, la ? ((ta > 0.0f) ? ta - 1e-4f : 1e7f) : -1.0f, lb ? ((tb > 0.0f) ? tb - 1e-4f : 1e7f) : -1.0f, oa, ob, spa, spb);
+                flat_any2<VAR == 1>(sc.flat, sc.sweep, o, da, o, db, la ? shadow_limit(ta) : -1.0f, lb ? shadow_limit(tb) : -1.0f, oa, ob, spa, spb);
                 if (VAR == 1) defer = defer || (la && spa) || (lb && spb);
                 f3 ca = ld3q(q.sh_c, q.sh_cap, ia), cb = ld3q(q.sh_c, q.sh_cap, ib);
-                const bool wa = !(isfinite(ca.x) && isfinite(ca.y) && isfinite(ca.z)), wb = !(isfinite(cb.x) && isfinite(cb.y) && isfinite(cb.z));
+                const bool wa = non_finite(ca), wb = non_finite(cb);
                 if (la && (!oa || wa)) { if (oa) ca = ca * 0.f; sum = any ? sum + ca : ca; any = true; }
                 if (lb && (!ob || wb)) { if (ob) cb = cb * 0.f; sum = any ? sum + cb : cb; any = true; }
                 v_traced += (la ? 1u : 0u) + (lb ? 1u : 0u); v_lit += (la && !oa ? 1u : 0u) + (lb && !ob ? 1u : 0u);
@@ -984,45 +995,33 @@ APT_D void shadow_flat_body(const DevScene& sc, const Params& p, const Queues& q
         return;
     }
     for (uint32_t base = sl.first; base < n; base += sl.stride) {
-        uint32_t pos; bool v0, v1; uint32_t io; bool odd = false;
-        if (VAR >= 2) {
-            const uint32_t li = base + threadIdx.x;
-            v0 = li < n; v1 = false;
-            pos = (VAR == 2) ? ldq(q.fix_sh, (qbase + (v0 ? li : n - 1u)) << 2) : (v0 ? li : n - 1u);
-            odd = (pos & 1u) != 0u; io = (qbase + (pos & ~1u)) << 2;
-        } else {
-            pos = base + 2u * threadIdx.x;
-            v0 = pos < n; v1 = pos + 1u < n;
-            io = (qbase + (v0 ? pos : ((n - 1u) & ~1u))) << 2;
-        }
+        const FlatLane ln = flat_lane<VAR >= 2>(base, n, qbase, VAR == 2 ? q.fix_sh : nullptr);
+        const uint32_t pos = ln.pos, io = ln.io; bool v0 = ln.v0, v1 = ln.v1; const bool odd = ln.odd;
         v2f ox = ld2q<v2f>(q.sh_o, io), oy = ld2q<v2f>(q.sh_o, io + cs), oz = ld2q<v2f>(q.sh_o, io + 2u * cs);
         v2f dx = ld2q<v2f>(q.sh_d, io), dy = ld2q<v2f>(q.sh_d, io + cs), dz = ld2q<v2f>(q.sh_d, io + 2u * cs);
         v2f dist = ld2q<v2f>(q.sh_tmax, io);
         // the radiance slots are requested with the rays, so that after the sweep ONE round trip fetches contribution and radiance of both entries
         v2u slot = ld2q<v2u>(q.sh_id, io);
-        if (VAR >= 2 && odd) {
-            ox = mk2(ox.y, ox.x); oy = mk2(oy.y, oy.x); oz = mk2(oz.y, oz.x); dx = mk2(dx.y, dx.x); dy = mk2(dy.y, dy.x); dz = mk2(dz.y, dz.x);
-            dist = mk2(dist.y, dist.x); v2u t_; t_.x = slot.y; t_.y = slot.x; slot = t_;
-        }
+        swap_if(odd, ox); swap_if(odd, oy); swap_if(odd, oz); swap_if(odd, dx); swap_if(odd, dy); swap_if(odd, dz); swap_if(odd, dist); swap_if(odd, slot);
         bool occ0, occ1, sp0, sp1;
         flat_any2<VAR == 1>(sc.flat, sc.sweep, mk3(ox.x, oy.x, oz.x), mk3(dx.x, dy.x, dz.x), mk3(ox.y, oy.y, oz.y), mk3(dx.y, dy.y, dz.y),
-                            (dist.x > 0.0f) ? dist.x - 1e-4f : 1e7f, (dist.y > 0.0f) ? dist.y - 1e-4f : 1e7f, occ0, occ1, sp0, sp1);
+                            shadow_limit(dist.x), shadow_limit(dist.y), occ0, occ1, sp0, sp1);
         if (VAR == 1) {
             sp0 = sp0 && v0; sp1 = sp1 && v1;
             fix_append(sp0, sp1, pos, fix_counter, q.fix_sh, qbase);
             v0 = v0 && !sp0; v1 = v1 && !sp1;                                    // a listed entry is left alone here
         }
         v2f cx = ld2q<v2f>(q.sh_c, io), cy = ld2q<v2f>(q.sh_c, io + cs), cz = ld2q<v2f>(q.sh_c, io + 2u * cs);
-        if (VAR >= 2 && odd) { cx = mk2(cx.y, cx.x); cy = mk2(cy.y, cy.x); cz = mk2(cz.y, cz.x); }
+        swap_if(odd, cx); swap_if(odd, cy); swap_if(odd, cz);
         const bool excl = APT_EXCLUSIVE_L(p);
         // no two entries of the launch share a slot (excl): plain read-modify-writes of one 16-byte slot each; the radiance of both entries is
         // requested together with the contributions (whether it will be written is only known once they arrive)
         f3 a0 = splat3(0.f), a1 = splat3(0.f);
         if (excl && v0 && !occ0) a0 = ldL(q.L, p.cap, slot.x);
         if (excl && v1 && !occ1) a1 = ldL(q.L, p.cap, slot.y);
-        // see k_shadow: an occluded sample still enters the sum as 0 * contribution, which is NaN for a non-finite contribution
+        // an occluded sample still enters the sum as 0 * contribution, which is NaN for a non-finite contribution (non_finite)
         f3 c0 = mk3(cx.x, cy.x, cz.x), c1 = mk3(cx.y, cy.y, cz.y);
-        const bool weird0 = !(isfinite(c0.x) && isfinite(c0.y) && isfinite(c0.z)), weird1 = !(isfinite(c1.x) && isfinite(c1.y) && isfinite(c1.z));
+        const bool weird0 = non_finite(c0), weird1 = non_finite(c1);
         if (excl) {
             if (v0 && !occ0) stL(q.L, p.cap, slot.x, mk3(a0.x + c0.x, a0.y + c0.y, a0.z + c0.z));
             else if (v0 && weird0) add_radiance(q.L, p.cap, slot.x, c0 * 0.f, true);          // rare: poisons the slot
@@ -1057,7 +1056,7 @@ __global__ void __launch_bounds__(BLOCK) k_occluded_flat(DevScene sc, uint32_t n
         const f3 o0 = mk3(o_[i0], o_[n + i0], o_[2 * n + i0]), d0 = mk3(d_[i0], d_[n + i0], d_[2 * n + i0]);
         const f3 o1 = mk3(o_[i1], o_[n + i1], o_[2 * n + i1]), d1 = mk3(d_[i1], d_[n + i1], d_[2 * n + i1]);
         bool a, b;
-        flat_any2(sc.flat, sc.sweep, o0, d0, o1, d1, (tmax[i0] > 0.0f) ? tmax[i0] - 1e-4f : 1e7f, (tmax[i1] > 0.0f) ? tmax[i1] - 1e-4f : 1e7f, a, b);
+        flat_any2(sc.flat, sc.sweep, o0, d0, o1, d1, shadow_limit(tmax[i0]), shadow_limit(tmax[i1]), a, b);
         if (v0) occ[i0] = a ? 1 : 0;
         if (v1) occ[i1] = b ? 1 : 0;
     }

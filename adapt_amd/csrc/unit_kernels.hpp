@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(TRACE_NT(MODE)) k_occluded(DevScene sc, uint32
         const bool valid = pos < n;
         const uint32_t idx = valid ? pos : n - 1;
         f3 o = mk3(o_[idx], o_[n + idx], o_[2 * n + idx]), d = mk3(d_[idx], d_[n + idx], d_[2 * n + idx]);
-        HitRec rec; rec.t = (tmax[idx] > 0.0f) ? tmax[idx] - 1e-4f : 1e7f; rec.prim = -1; rec.u = rec.v = 0.f;
+        HitRec rec; rec.t = shadow_limit(tmax[idx]); rec.prim = -1; rec.u = rec.v = 0.f;
         const bool hit = (MODE == TRACE_BVH) ? traverse<true>(sc.bvh, make_stack(plan), o, d, rec)
                        : (MODE == TRACE_SWEEP) ? sweep_any(sc.sweep, o, d, rec)
                                      : sweep_tile<true, APT_TILE_NT>(sc.sweep, o, d, rec, valid, reinterpret_cast<float*>(s_dyn));

@@ -503,15 +503,48 @@ __global__ void __launch_bounds__(BLOCK, WAVES) k_vshade_ev_group(DevScene sc, P
 // that crossed a null surface (or a stretch of scattering world) is written back in place - origin moved to the crossing point,
 // remaining distance shortened, transmittance folded into the contribution - and its slot is appended to the list the next pass
 // reads.  The reference walks at most seven segments; the host launches pass p + 1 only where null surfaces exist.
+// One segment of one light sample, given its closest hit `rec` below the remaining distance `depth`: blocked by a non-null surface (the
+// contribution becomes c * 0 - NaN for a non-finite c, exactly as upstream's 0 * x), arrived (nothing in the way, at the light, or the
+// seventh segment, seg_no 6), or across a null surface or a stretch of scattering world: transmittance folded into c, origin moved to
+// the crossing point, distance shortened.  A sample that ends here adds its contribution to its path's radiance (excl: add_radiance's
+// exclusive flag).  Returns true when the sample has to walk on.
+APT_D bool track_segment(const DevScene& sc, const Params& p, const Queues& q, const f3& world_ue, bool world_scat, bool valid, f3& o, const f3& d, float& depth, f3& c,
+                         const HitRec& rec, uint32_t io, int seg_no, bool excl, uint32_t& t_lit, uint32_t& t_track) {
+    if (!valid) return false;
+    t_track++;
+    int obj = -1; bool in_free = true, blocked = false, arrived = false, walk_on = false; float seg = depth;
+    if (rec.prim < 0) { if (!world_scat) arrived = true; }                 // nothing in the way and nothing to attenuate: done
+    else {
+        obj = sc.prim_obj[rec.prim];
+        if (vpt_non_null(sc, obj)) blocked = true;
+        else {
+            Hit it; build_hit(sc, rec.prim, rec.t, rec.u, rec.v, o, d, it);
+            in_free = dot(it.n_g, d) < 0.f;
+            seg = rec.t;
+        }
+    }
+    if (blocked) c = c * 0.f;
+    else if (!arrived) {
+        // get_transmittance, vpt.py:52-62
+        if (in_free && world_scat) c = c * exp_neg(world_ue, seg);
+        else if (!in_free && vpt_is_scattering(sc, obj)) c = c * exp_neg(sc.med[obj].u_e, seg);
+        o = o + d * seg;
+        depth -= seg;
+        if (depth <= 5e-5f || seg_no >= 6) arrived = true;                  // at the light, or the seventh segment (vpt.py:113)
+        else walk_on = true;
+    }
+    if (arrived || blocked) {
+        if (!(c.x == 0.f && c.y == 0.f && c.z == 0.f)) add_radiance(q.L, p.cap, ldq(q.sh_id, io), c, excl);      // (one radiance plane per light sample of a vertex, or one sample: no two entries of a launch share a slot)
+        if (arrived) t_lit++;
+    }
+    return walk_on;
+}
 template <int MODE>
 __global__ void __launch_bounds__(VSHADOW_NT(MODE), (MODE == TRACE_TILE ? APT_VSHADOW_WAVES : 1)) k_vshadow(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan, int pass) {
     __shared__ float s_sweep[MODE == TRACE_SWEEP ? APT_SWEEP_LDS_FLOATS(BLOCK) : 1];
     const SubLoop sl = sub_loop(p.nq, VSHADOW_NT(MODE));
-    const uint32_t n = min(pass == 0 ? cnt->n_shadow[sl.q * CNT_PAD] : cnt->n_walk[pass][sl.q * CNT_PAD], q.sh_subcap);
-    if (pass == 0 && sl.first == 0 && threadIdx.x == 0) {
-        cnt->stats[sl.q][ST_SHADOW_TRACED] += n;
-        for (int c = 0; c < q.n_classes; c++) cnt->n_cls[c][sl.q * CNT_PAD] = 0;      // every shade of this iteration is done
-    }
+    const uint32_t n = shadow_count(pass == 0 ? cnt->n_shadow : cnt->n_walk[pass], sl.q, q);
+    if (pass == 0 && sl.first == 0 && threadIdx.x == 0) begin_shadow(cnt, q, sl.q, n);
     const uint32_t qbase = (uint32_t)sl.q * q.sh_subcap, sc_ = q.sh_cap;
     const uint32_t* list_in = q.sh_walk[pass & 1];
     uint32_t* list_out = q.sh_walk[(pass + 1) & 1];
@@ -528,43 +561,13 @@ __global__ void __launch_bounds__(VSHADOW_NT(MODE), (MODE == TRACE_TILE ? APT_VS
         f3 o = ld3q(q.sh_o, sc_, io);
         const f3 d = ld3q(q.sh_d, sc_, io);
         float depth = ldq(q.sh_tmax, io);
-        HitRec rec; rec.t = (depth > 0.0f) ? depth - 1e-4f : 1e7f; rec.prim = -1; rec.u = rec.v = 0.f;
+        HitRec rec; rec.t = shadow_limit(depth); rec.prim = -1; rec.u = rec.v = 0.f;
         if (MODE == TRACE_BVH) traverse<false>(sc.bvh, make_stack(plan), o, d, rec);
         else if (MODE == TRACE_SWEEP) sweep_wg<false, BLOCK>(sc.sweep, o, d, rec, valid, s_sweep);
         else sweep_tile<false, APT_VSHADOW_NT>(sc.sweep, o, d, rec, valid, reinterpret_cast<float*>(s_dyn));
-        bool arrived = false, walk_on = false;
         f3 c = splat3(0.f);
-        if (valid) {
-            t_track++;
-            c = ld3q(q.sh_c, sc_, io);
-            int obj = -1; bool in_free = true, blocked = false; float seg = depth;
-            if (rec.prim < 0) { if (!world_scat) arrived = true; }         // nothing in the way and nothing to attenuate: done
-            else {
-                obj = sc.prim_obj[rec.prim];
-                if (vpt_non_null(sc, obj)) blocked = true;
-                else {
-                    Hit it; build_hit(sc, rec.prim, rec.t, rec.u, rec.v, o, d, it);
-                    in_free = dot(it.n_g, d) < 0.f;
-                    seg = rec.t;
-                }
-            }
-            if (blocked) c = c * 0.f;                                       // NaN for a non-finite c, exactly as upstream's 0 * x
-            else if (!arrived) {
-                // get_transmittance, vpt.py:52-62
-                if (in_free && world_scat) c = c * exp_neg(world_ue, seg);
-                else if (!in_free && vpt_is_scattering(sc, obj)) c = c * exp_neg(sc.med[obj].u_e, seg);
-                o = o + d * seg;
-                depth -= seg;
-                if (depth <= 5e-5f || pass >= 6) arrived = true;            // at the light, or the seventh segment (vpt.py:113)
-                else walk_on = true;
-            }
-            if (arrived || blocked) {
-                if (!(c.x == 0.f && c.y == 0.f && c.z == 0.f)) {
-                    add_radiance(q.L, p.cap, ldq(q.sh_id, io), c, APT_EXCLUSIVE_L(p));      // (one radiance plane per light sample of a vertex, or one sample: no two entries of a launch share a slot)
-                }
-                if (arrived) t_lit++;
-            }
-        }
+        if (valid) c = ld3q(q.sh_c, sc_, io);
+        const bool walk_on = track_segment(sc, p, q, world_ue, world_scat, valid, o, d, depth, c, rec, io, pass, APT_EXCLUSIVE_L(p), t_lit, t_track);
         if (list_out != nullptr) {
             const uint32_t wpos = wave_append(walk_on, next_counter);
             if (walk_on && wpos < q.sh_subcap) {
@@ -586,16 +589,13 @@ __global__ void __launch_bounds__(VSHADOW_NT(MODE), (MODE == TRACE_TILE ? APT_VS
 // arithmetic through workgroup lists in LDS; this kernel keeps its pass structure (pass 0 reads the queue, pass p the slot list of the
 // samples that crossed a null surface in pass p - 1: a sweep is wave-uniform over the records, so the survivors have to be packed densely
 // again or later segments cost what the first one did - measured with all segments in one launch: V1 walk 38.5 -> 33.0 ms only) and
-// replaces the intersector.  Per sample the arithmetic after the hit is k_vshadow's; the hit itself is the flat sweep's (t
+// replaces the intersector.  Per sample the arithmetic after the hit is track_segment, as in k_vshadow; the hit itself is the flat sweep's (t
 // within 1e-5 relative, same primitive unless tied; coplanar near-ties and zero-component directions settled by the reference-order code
 // inside flat_closest2).
 __global__ void __launch_bounds__(BLOCK) k_vshadow_flat(DevScene sc, Params p, Queues q, Counters* cnt, LdsPlan plan, int pass) {
     const SubLoop sl = sub_loop(p.nq, FLAT_NT);
-    const uint32_t n = min(pass == 0 ? cnt->n_shadow[sl.q * CNT_PAD] : cnt->n_walk[pass][sl.q * CNT_PAD], q.sh_subcap);
-    if (pass == 0 && sl.first == 0 && threadIdx.x == 0) {
-        cnt->stats[sl.q][ST_SHADOW_TRACED] += n;
-        for (int c = 0; c < q.n_classes; c++) cnt->n_cls[c][sl.q * CNT_PAD] = 0;      // every shade of this iteration is done
-    }
+    const uint32_t n = shadow_count(pass == 0 ? cnt->n_shadow : cnt->n_walk[pass], sl.q, q);
+    if (pass == 0 && sl.first == 0 && threadIdx.x == 0) begin_shadow(cnt, q, sl.q, n);
     const uint32_t qbase = (uint32_t)sl.q * q.sh_subcap, sc_ = q.sh_cap;
     const uint32_t* list_in = q.sh_walk[pass & 1];
     uint32_t* list_out = q.sh_walk[(pass + 1) & 1];
@@ -604,37 +604,6 @@ __global__ void __launch_bounds__(BLOCK) k_vshadow_flat(DevScene sc, Params p, Q
     const bool world_scat = sc.med[sc.n_objects].type >= 0;
     const bool excl = APT_EXCLUSIVE_L(p);
     uint32_t t_lit = 0, t_track = 0;
-    // one segment of one sample, given its closest hit (k_vshadow's per-sample block); returns true when the sample has to walk on
-    auto segment = [&](bool valid, f3& o, const f3& d, float& depth, f3& c, const HitRec& rec, uint32_t io, int seg_no) -> bool {
-        if (!valid) return false;
-        t_track++;
-        int obj = -1; bool in_free = true, blocked = false, arrived = false, walk_on = false; float seg = depth;
-        if (rec.prim < 0) { if (!world_scat) arrived = true; }             // nothing in the way and nothing to attenuate: done
-        else {
-            obj = sc.prim_obj[rec.prim];
-            if (vpt_non_null(sc, obj)) blocked = true;
-            else {
-                Hit it; build_hit(sc, rec.prim, rec.t, rec.u, rec.v, o, d, it);
-                in_free = dot(it.n_g, d) < 0.f;
-                seg = rec.t;
-            }
-        }
-        if (blocked) c = c * 0.f;                                           // NaN for a non-finite c, exactly as upstream's 0 * x
-        else if (!arrived) {
-            // get_transmittance, vpt.py:52-62
-            if (in_free && world_scat) c = c * exp_neg(world_ue, seg);
-            else if (!in_free && vpt_is_scattering(sc, obj)) c = c * exp_neg(sc.med[obj].u_e, seg);
-            o = o + d * seg;
-            depth -= seg;
-            if (depth <= 5e-5f || seg_no >= 6) arrived = true;              // at the light, or the seventh segment (vpt.py:113)
-            else walk_on = true;
-        }
-        if (arrived || blocked) {
-            if (!(c.x == 0.f && c.y == 0.f && c.z == 0.f)) add_radiance(q.L, p.cap, ldq(q.sh_id, io), c, excl);
-            if (arrived) t_lit++;
-        }
-        return walk_on;
-    };
     for (uint32_t base = sl.first; base < n; base += sl.stride) {
         const uint32_t pos = base + 2u * threadIdx.x;
         const bool v0 = pos < n, v1 = pos + 1u < n;
@@ -648,11 +617,11 @@ __global__ void __launch_bounds__(BLOCK) k_vshadow_flat(DevScene sc, Params p, Q
         bool on0 = v0, on1 = v1;
         for (int seg = pass; ; seg++) {
             HitRec r0, r1; int k0, k1;
-            r0.t = !on0 ? -1.0f : ((depth0 > 0.0f) ? depth0 - 1e-4f : 1e7f); r0.prim = -1; r0.u = r0.v = 0.f;      // (a finished sample searches below a negative limit: nothing is accepted)
-            r1.t = !on1 ? -1.0f : ((depth1 > 0.0f) ? depth1 - 1e-4f : 1e7f); r1.prim = -1; r1.u = r1.v = 0.f;
+            r0.t = !on0 ? -1.0f : shadow_limit(depth0); r0.prim = -1; r0.u = r0.v = 0.f;      // (a finished sample searches below a negative limit: nothing is accepted)
+            r1.t = !on1 ? -1.0f : shadow_limit(depth1); r1.prim = -1; r1.u = r1.v = 0.f;
             flat_closest2(sc.flat, sc.sweep, sc.prim_class, o0, d0, o1, d1, r0, r1, k0, k1);
-            on0 = segment(on0, o0, d0, depth0, c0, r0, io0, seg);
-            on1 = segment(on1, o1, d1, depth1, c1, r1, io1, seg);
+            on0 = track_segment(sc, p, q, world_ue, world_scat, on0, o0, d0, depth0, c0, r0, io0, seg, excl, t_lit, t_track);
+            on1 = track_segment(sc, p, q, world_ue, world_scat, on1, o1, d1, depth1, c1, r1, io1, seg, excl, t_lit, t_track);
             // the last launch of an iteration (pass APT_VSHADOW_FLAT_PASSES - 1) walks what is left of its samples' segments itself: by then a
             // handful of samples are still going (V1: a tenth after two segments), and four more launches over near-empty lists cost more than a thin wave
             if (pass < APT_VSHADOW_FLAT_PASSES - 1 || seg >= 6 || !__any(on0 || on1)) break;
