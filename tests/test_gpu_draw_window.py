@@ -18,7 +18,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COUNTERS = ("n_samples", "n_extend", "n_shade", "n_shadow", "n_shadow_traced", "n_lit", "n_draws", "n_poisoned")
 
 CHILD = r"""
 import json, os, sys
@@ -26,9 +25,9 @@ import numpy as np
 root, out = sys.argv[1], sys.argv[2]
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
 import conftest
+import gpu_ab
 from adapt_amd import materials
 from adapt_amd.parsers import scene_parsing
-from adapt_amd.renderer import Renderer
 
 def parse(tag):
     d, f, _ = conftest.SCENES[tag]
@@ -36,29 +35,15 @@ def parse(tag):
     try: return scene_parsing(d, f)
     finally: materials.ENABLE_MICROFACET = False
 
-def render(tup, w, h, spp, max_bounce=None, cfg=None, env=None, lights=1):
+results, accums = {}, {}
+def case(key, tup, w, h, spp, max_bounce=None, cfg=None, env=None, lights=1):
     emitters, arrays, objects, prop = tup
-    if cfg: prop = dict(prop); prop.update(cfg)
-    env = env or {}
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)                              # read at scene / renderer creation
-    try: r = Renderer(list(emitters) * lights, arrays, objects, prop, width=w, height=h, exact=False, max_bounce=max_bounce)
-    finally:
-        for k, v in old.items():
-            if v is None: os.environ.pop(k)
-            else: os.environ[k] = v
-    try:
-        name = r.info()["shade_variant"]
-        if not ("lambertian/point" in name and "[rays traced in place]" in name): return name, None, None, None
-        r.render(n_spp=spp)
-        return name, r.tile_accum().copy(), r.stats(), bool(r.camera_fused())
-    finally: r.close()
-
-results, arrays = {}, {}
-def case(key, *a, **kw):
-    name, acc, st, fused = render(*a, **kw)
-    results[key] = {"variant": name, "fused": fused, "counters": None if st is None else {k: int(st[k]) for k in %(counters)r}}
-    if acc is not None: arrays[key] = acc.view(np.uint32)
+    if cfg: prop = dict(prop, **cfg)
+    with gpu_ab.open_renderer((list(emitters) * lights, arrays, objects, prop), w, h, env=env, max_bounce=max_bounce) as r:
+        name = r.info()["shade_variant"]                # only the lean traced variant is rendered
+        run = gpu_ab.run_of(r, spp) if "lambertian/point" in name and gpu_ab.TRACED in name else None
+    results[key] = {"variant": name, "fused": run and bool(run.fused), "counters": run and {k: int(run.stats[k]) for k in gpu_ab.COUNTERS}}
+    if run: accums[key] = run.accum.view(np.uint32)
 
 for tag in conftest.ALL_TAGS: case("scene_" + tag, parse(tag), 64, 64, 8)
 cbox = parse("cbox")
@@ -73,9 +58,9 @@ case("rr_from_bounce_0_no_anti_alias", cbox, 64, 64, 32, cfg={"rr_bounce_th": 0,
 case("rr_at_every_vertex", cbox, 64, 64, 32, cfg={"rr_bounce_th": 0, "rr_threshold": 2.0})
 case("rr_at_every_vertex_no_anti_alias", cbox, 64, 64, 32, cfg={"rr_bounce_th": 0, "rr_threshold": 2.0, "anti_alias": False})
 case("two_lights", cbox, 64, 64, 16, lights=2)
-np.savez(out + ".npz", **arrays)
+np.savez(out + ".npz", **accums)
 json.dump(results, open(out + ".json", "w"))
-""" % {"counters": COUNTERS}
+"""
 
 
 def _build_variant(dst, flag):

@@ -21,8 +21,7 @@ with S = 1 (traced, non-lean) and S = 5 (one shared plane) for that.
 
 All measured figures go through record_metric; the log of record is profiles/r06_settings_matrix_metrics.log.
 """
-import contextlib
-import os
+from collections import namedtuple
 
 import numpy as np
 import pytest
@@ -30,6 +29,7 @@ import pytest
 import settings_cases as SC
 import test_gpu_fast as product_tests          # the product build's rows, counter tolerance and other-seed criterion: imported, not copied
 from conftest import golden, image_metrics, record_metric
+from gpu_ab import COUNTERS, Run, differences, open_renderer
 from adapt_amd.scene_pack import make_config, pack_scene
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +44,6 @@ FILM_ODD = (50, 30, 20)                         # 1500 pixels: no multiple of 64
 ODD_AXES = ("rr_off", "shadow_5")               # the two cases per scene that also run on the odd film (both axes exist on all five scenes)
 FILM_D = (64, 48, 16)                           # test_rays_traced_in_place_render_the_staged_pipeline_s_image's film
 FILM_TRAVERSAL = (64, 48, 8)                    # test_every_traversal_mode_gives_the_same_hits_and_image's film
-COUNTERS = ("n_samples", "n_extend", "n_shade", "n_shadow", "n_shadow_traced", "n_lit", "n_draws", "n_poisoned")      # test_gpu_camera_fuse.COUNTERS
 
 # Same-stream figures of the product build on the cases that miss their scene's row in test_gpu_fast.IMAGE_CASES although the exact build
 # holds 8(d) on them in (a), the product build's counters stay inside their tolerance and the other-seed criterion holds (all three asserted,
@@ -86,19 +85,7 @@ PIPELINES = ("lean traced, camera-fused", "traced, non-lean", "class-sorted grou
              "nee_vm", "volumetric event-sorted", "BVH walk")
 RAN = {p: set() for p in PIPELINES}             # pipeline -> axis labels that ran on it (filled by every render of this module)
 MULTI_CLASS = {"cbox": False, "balls_mono": True, "glass_box": True, "features_a": True, "media_a": True}
-
-
-@contextlib.contextmanager
-def _env(env):
-    """environment switches are read when the scene / the renderer is created"""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None: os.environ.pop(k)
-            else: os.environ[k] = v
+Took = namedtuple("Took", "variant traversal fused")             # the pipeline a renderer took, as _enter asserts it
 
 
 def expected_pipeline(scene, build, S, max_bounce, env):
@@ -114,7 +101,7 @@ def expected_pipeline(scene, build, S, max_bounce, env):
 
 
 def _enter(r, case, build, env, axis=None):
-    """assert the pipeline this renderer took and enter it into RAN; -> (shade variant, traversal, camera fused)"""
+    """assert the pipeline this renderer took and enter it into RAN; -> Took"""
     st = SC.settings(case)
     S, mb = r.num_shadow_ray, r.max_bounce
     info, fused = r.info(), r.camera_fused()
@@ -143,14 +130,12 @@ def _enter(r, case, build, env, axis=None):
     if trav == "bvh": took.append("BVH walk")
     for p in took:
         RAN[p].add(axis or case.axis)
-    return name, trav, fused
+    return Took(name, trav, fused)
 
 
 def _open(case, build, w, h, env=None, extra=None, **kw):
-    from adapt_amd.renderer import Renderer, VolumeRenderer
     tup = SC.with_overrides(SC.parse(case.scene), dict(case.overrides, **(extra or {})))
-    with _env(env or {}):
-        return (VolumeRenderer if case.volumetric else Renderer)(*tup, width=w, height=h, exact=(build == "exact"), **kw)
+    return open_renderer(tup, w, h, env=env, exact=(build == "exact"), volumetric=case.volumetric, **kw)
 
 
 _oracle_scenes, _oracle_images = {}, {}
@@ -173,14 +158,11 @@ def _oracle(case, w, h, spp, seed=0, extra=None):
 
 
 def _render(case, build, w, h, spp, env=None, extra=None, axis=None, **kw):
-    """-> (accumulation, counters, (shade variant, traversal, camera fused)); the renderer is closed before the next one opens"""
-    r = _open(case, build, w, h, env, extra, **kw)
-    try:
+    """-> (accumulation, counters, Took); the renderer is closed before the next one opens"""
+    with _open(case, build, w, h, env, extra, **kw) as r:
         took = _enter(r, case, build, env or {}, axis)
         r.render(n_spp=spp)
         return r.color.to_numpy(), r.stats(), took
-    finally:
-        r.close()
 
 
 def _against_oracle(label, case, acc, st, w, h, spp, extra=None):
@@ -317,12 +299,11 @@ def _traced_vs_staged(a, b, what):
 
 
 def _bit_identical(a, b):
-    """tests/test_gpu_camera_fuse.py's bit identity: accumulation as uint32, every counter, and no generate launch in the fused form"""
-    (img1, st1), (img0, st0) = a, b
-    bad = []
-    if not np.array_equal(img0.view(np.uint32), img1.view(np.uint32)): bad.append(("accumulation", float(np.nanmax(np.abs(img0 - img1)))))
-    bad += [(k, st0[k], st1[k]) for k in COUNTERS if st0[k] != st1[k]]
-    if not (st1["launches"]["generate"] == 0 and st0["launches"]["generate"] > 0): bad.append(("generate launches", st1["launches"], st0["launches"]))
+    """tests/gpu_ab.py's bit identity, and no generate launch in the fused form; a, b: what _render returns, fused and two-launch"""
+    run = lambda img, st, took: Run(took.variant, took.traversal, img, st, None, took.fused)
+    bad = differences(run(*b), run(*a))
+    l1, l0 = a[1]["launches"], b[1]["launches"]
+    if not (l1["generate"] == 0 and l0["generate"] > 0): bad.append(("generate launches", l1, l0))
     return bad
 
 
@@ -347,24 +328,21 @@ def test_pipeline_switches_render_the_same_image_under_every_setting(scene, buil
         if expected_pipeline(scene, build, S_f, 1, base)[1] == "traced":
             on, st_on, took = run(base, one)
             off, st_off, took0 = run(dict(base, APT_FUSED="0"), one)
-            assert "[rays traced in place]" in took[0] and "[rays traced in place]" not in took0[0] and took[1] == took0[1] == "flat"
+            assert "[rays traced in place]" in took.variant and "[rays traced in place]" not in took0.variant and took.traversal == took0.traversal == "flat"
             bad += [("APT_FUSED=0",) + b for b in _traced_vs_staged((on, st_on), (off, st_off), f"APT_FUSED {build} {case.name}")]
             # APT_CAMERA_FUSE: the camera-fed launch against k_generate_trace + the queue-fed bounce 0
             off, st_off, took0 = run(dict(base, APT_CAMERA_FUSE="0"), one)
-            assert took[2] is True and took0[2] is False and took0[0] == took[0]
-            bad += [("APT_CAMERA_FUSE=0",) + b for b in _bit_identical((on, st_on), (off, st_off))]
+            assert took.fused is True and took0.fused is False and took0.variant == took.variant
+            bad += [("APT_CAMERA_FUSE=0",) + b for b in _bit_identical((on, st_on, took), (off, st_off, took0))]
         else:                                   # nothing to trace in place, nothing to fuse: the switches leave the pipeline as it is
             for env in ({"APT_FUSED": "0"}, {"APT_CAMERA_FUSE": "0"}):
-                r = _open(case, build, w, h, env)
-                try:
-                    assert _enter(r, case, build, env)[2] is False
-                finally:
-                    r.close()
+                with _open(case, build, w, h, env) as r:
+                    assert _enter(r, case, build, env).fused is False
         # APT_SORTED: one all-models kernel against the class kernels (a scene of one class is not sorted in the first place)
         if MULTI_CLASS[scene]:
             srt, st_s, took_s = run({})
             uns, st_u, took_u = run({"APT_SORTED": "0"})
-            assert took_s[0].startswith("sorted") and not took_u[0].startswith("sorted") and took_s[1] == took_u[1]
+            assert took_s.variant.startswith("sorted") and not took_u.variant.startswith("sorted") and took_s.traversal == took_u.traversal
             bad += [("APT_SORTED=0",) + b for b in _traced_vs_staged((uns, st_u), (srt, st_s), f"APT_SORTED {build} {case.name}")]
         # APT_TRAVERSAL: the BVH walk and the tiled sweep against the oracle (test_every_traversal_mode_gives_the_same_hits_and_image's image
         # criterion, 8(d)); the flag cases of balls_mono once more with five light samples - one shared radiance plane
@@ -372,7 +350,7 @@ def test_pipeline_switches_render_the_same_image_under_every_setting(scene, buil
             routes = [(None, None)] + ([({"num_shadow_ray": 5}, case.axis)] if (scene == "balls_mono" and free_S and mode == "tile") else [])
             for extra, axis in routes:
                 acc, st, took = run({"APT_TRAVERSAL": mode}, extra, FILM_TRAVERSAL, axis)
-                assert took[1] == mode
+                assert took.traversal == mode
                 label = f"APT_TRAVERSAL={mode} {build} {case.name}{' S=5' if extra else ''}"
                 own = TRAVERSAL_OWN_BOUNDS.get((mode, case.name)) if (build == "fast" and not extra) else None
                 if own is None:
@@ -402,15 +380,12 @@ def test_split_calls_and_batch_sizes_leave_the_accumulation_bit_identical(axis, 
     w, h = 64, 48
     out = {}
     for key, calls, kw in (("one call", (20,), {}), ("7 + 13", (7, 13), {}), ("batches of 3", (20,), {"spp_per_batch": 3})):
-        r = _open(case, build, w, h, **kw)
-        try:
+        with _open(case, build, w, h, **kw) as r:
             _enter(r, case, build, {})
             for n in calls:
                 r.render(n_spp=n)
             assert r.cnt[None] == 20 and (key != "batches of 3" or r.info()["spp_per_batch"] == 3)
             out[key] = (r.color.to_numpy().view(np.uint32).copy(), {k: r.stats()[k] for k in COUNTERS})
-        finally:
-            r.close()
     assert out["one call"][0].any()
     for key in ("7 + 13", "batches of 3"):
         assert np.array_equal(out[key][0], out["one call"][0]), (axis, build, key, int((out[key][0] != out["one call"][0]).sum()))

@@ -1,55 +1,23 @@
 """Occluder lists of the light samples (csrc/flat_build.cpp flat_occluders) on the device: every bundled scene that the
 product build renders with the traced shade kernel (shade_stage.hpp k_shade_traced) gives the same accumulation and the same counters,
 bit for bit, with the lists (APT_SHADOW_CULL=1, the default) and with the full stream for every emitter (APT_SHADOW_CULL=0)."""
-import os
-
-import numpy as np
 import pytest
 
-from conftest import ALL_TAGS
+from gpu_ab import assert_same_run, render_run, traced_pairs
 
 pytestmark = pytest.mark.gpu
 
-COUNTERS = ("n_samples", "n_extend", "n_shade", "n_shadow", "n_shadow_traced", "n_lit", "n_draws", "n_poisoned")
-
-
-def _render(tup, cull, w, h, spp, max_bounce=None, unsorted=False):
-    """unsorted: APT_SORTED=0 and one light sample per vertex - the scenes of several material classes then take the traced kernel too"""
-    from adapt_amd.renderer import Renderer
-    env = {"APT_SHADOW_CULL": str(cull)}                # read once, at scene creation
-    if unsorted: env["APT_SORTED"] = "0"                # read at renderer creation
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        r = Renderer(*tup, width=w, height=h, exact=False, max_bounce=max_bounce, num_shadow_ray=1 if unsorted else None)
-    finally:
-        for k, v in old.items():
-            if v is None: os.environ.pop(k)
-            else: os.environ[k] = v
-    try:
-        r.render(n_spp=spp)
-        return r.info()["shade_variant"], r.color.to_numpy().copy(), r.stats()
-    finally:
-        r.close()
+ON, OFF = {"APT_SHADOW_CULL": "1"}, {"APT_SHADOW_CULL": "0"}
 
 
 @pytest.mark.parametrize("unsorted", [False, True])
-def test_occluder_lists_leave_every_traced_scene_bit_identical(parsed, unsorted):
-    traced = {}
-    for tag in ALL_TAGS:
-        tup = parsed(tag)
-        name, acc1, st1 = _render(tup, 1, 64, 64, 8, unsorted=unsorted)
-        if "[rays traced in place]" not in name:
-            continue
-        _, acc0, st0 = _render(tup, 0, 64, 64, 8, unsorted=unsorted)
-        assert np.array_equal(acc0.view(np.uint32), acc1.view(np.uint32)), (tag, float(np.nanmax(np.abs(acc0 - acc1))))
-        for k in COUNTERS:
-            assert st0[k] == st1[k], (tag, k, st0[k], st1[k])
-        assert st1["n_shadow_traced"] > 0 and st1["n_lit"] > 0, tag
-        traced[tag] = st1["n_shadow_traced"]
-    assert "cbox" in traced, traced
+def test_occluder_lists_leave_every_traced_scene_bit_identical(parsed, flat, unsorted):
+    traced = []
+    for tag, on, _ in traced_pairs(parsed, unsorted, ON, OFF):
+        assert on.stats["n_shadow_traced"] > 0 and on.stats["n_lit"] > 0, tag
+        traced.append(tag)
     if not unsorted: return                             # (by default only the Cornell box takes the traced kernel)
-    fs = {tag: _pack(parsed, tag) for tag in traced}
+    fs = {tag: flat(tag) for tag in traced}
     assert any((f.src_i[:, 0] == 1).any() for f in fs.values()), f"no area-light scene took the traced kernel: {sorted(traced)}"
     assert any(f.src_i.shape[0] > 1 for f in fs.values()), f"no multi-emitter scene took the traced kernel: {sorted(traced)}"
 
@@ -57,13 +25,6 @@ def test_occluder_lists_leave_every_traced_scene_bit_identical(parsed, unsorted)
 def test_occluder_lists_leave_c1_bit_identical(parsed):
     """C1: the Cornell box at 256 x 256, 4 bounces (bench.py's c1), with more samples per pixel"""
     tup = parsed("cbox")
-    name, acc1, st1 = _render(tup, 1, 256, 256, 16, max_bounce=4)
-    assert "[rays traced in place]" in name
-    _, acc0, st0 = _render(tup, 0, 256, 256, 16, max_bounce=4)
-    assert np.array_equal(acc0.view(np.uint32), acc1.view(np.uint32))
-    assert {k: st0[k] for k in COUNTERS} == {k: st1[k] for k in COUNTERS}
-
-
-def _pack(parsed, tag):
-    from adapt_amd.scene_pack import pack_scene
-    return pack_scene(*parsed(tag))
+    on = render_run(tup, 256, 256, 16, env=ON, max_bounce=4)
+    assert on.traced
+    assert_same_run(on, render_run(tup, 256, 256, 16, env=OFF, max_bounce=4), "c1")
