@@ -66,6 +66,11 @@ class Stats(C.Structure):
         return d
 
 
+class DenoiseCfg(C.Structure):
+    _fields_ = [("firefly_threshold", C.c_float), ("firefly_only", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_n", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("sigma_c", C.c_float), ("demodulate", C.c_int32)]
+
+
 # every symbol include/adapt_mi.h declares: (restype, argtypes)
 SYMBOLS = {
     "apt_bvh_build": (C.c_int, [f32p, C.c_int32, i32p, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -98,6 +103,11 @@ SYMBOLS = {
     "apt_read_sample_counts": (C.c_int, [C.c_void_p, i32p, u8p]),
     "apt_read_moments": (C.c_int, [C.c_void_p, f64p]),
     "apt_set_adaptive_state": (C.c_int, [C.c_void_p, i32p, f64p, u8p]),
+    "apt_render_aov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "apt_read_aov": (C.c_int, [C.c_void_p, f32p]),
+    "apt_set_aov": (C.c_int, [C.c_void_p, f32p]),
+    "apt_clear_aov": (C.c_int, [C.c_void_p]),
+    "apt_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseCfg), f32p, f32p]),
     "apt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "apt_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), i32p]),
     "apt_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

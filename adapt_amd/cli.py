@@ -17,6 +17,9 @@ written as upstream's `export_transient_profile` writes them (render.py:36-56,16
 `--noise_threshold t` (with `--min_spp`, `--adaptive_step`): adaptive sampling; `--iter_num` is then the most samples
 any pixel gets, and the per-pixel sample counts are written as `<img_name>-<scene file stem>-<type>-spp.npy` (w, h) int32 next to the
 image (cropped like it).  Not with `--transient`.
+`--denoise` (with `--type pt`; `--firefly_threshold t`, `--save_aov`): the frame through the firefly filter (t > 0) and the edge-avoiding
+a-trous filter, written as `<img_name>-<scene file stem>-<type>-denoised.<ext>` next to the image (cropped and normalised
+like it); `--save_aov` writes the feature buffers the filter was guided by as `...-<type>-aov.npz` (albedo, normal, depth, hit_fraction).
 """
 from __future__ import annotations
 
@@ -68,6 +71,9 @@ def get_options(argv=None):
     p.add_argument("--noise_threshold", default=0., type=float, help="adaptive sampling: a pixel stops once the relative standard error of its mean is <= this (0: off)")
     p.add_argument("--min_spp", default=64, type=int, help="adaptive sampling: no pixel stops before this many samples")
     p.add_argument("--adaptive_step", default=32, type=int, help="adaptive sampling: pixels are retired at sample numbers that are multiples of this")
+    p.add_argument("--denoise", default=False, action="store_true", help="also write the frame through the edge-avoiding denoiser (pt only), as ...-denoised.<ext>")
+    p.add_argument("--firefly_threshold", default=0., type=float, help="--denoise: run the firefly filter first, with this rgb distance threshold (0: off; upstream's value is 0.4)")
+    p.add_argument("--save_aov", default=False, action="store_true", help="--denoise: also write the feature buffers (albedo, normal, depth, hit_fraction) as ...-aov.npz")
     argv = list(sys.argv[1:] if argv is None else argv)
     pre, _ = p.parse_known_args(argv)
     if pre.config:
@@ -143,6 +149,12 @@ def main(argv=None) -> int:
         return 2
     if opts.transient and opts.type != "pt":
         print(f"--transient: time-resolved output exists for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
+        return 2
+    if (opts.denoise or opts.save_aov) and opts.type != "pt":
+        print(f"--denoise / --save_aov: feature buffers and the denoiser exist for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
+        return 2
+    if opts.firefly_threshold < 0:
+        print("--firefly_threshold must be >= 0 (0: no firefly filter)", file=sys.stderr)
         return 2
     adaptive = None
     if opts.noise_threshold > 0:
@@ -230,6 +242,20 @@ def main(argv=None) -> int:
             out_spp = os.path.join(opts.output_path, f"{opts.img_name}-{stem}-{opts.type}-spp.npy")
             np.save(out_spp, spp_map)
             print(f"[adapt_amd] wrote {out_spp}")
+    if (opts.denoise or opts.save_aov) and not opts.no_save_fig:
+        base = os.path.join(opts.output_path, f"{opts.img_name}-{stem}-{opts.type}")
+
+        def window(a):
+            return a[rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y] if rdr.do_crop else a
+        if opts.denoise:
+            den = window(rdr.denoised(firefly_threshold=opts.firefly_threshold))
+            if opts.normalize > 0.9:
+                den = den / np.quantile(den, opts.normalize)
+            write_image(den, f"{base}-denoised.{opts.img_ext}")
+            print(f"[adapt_amd] wrote {base}-denoised.{opts.img_ext}")
+        if opts.save_aov:
+            np.savez(f"{base}-aov.npz", **{k: window(v) for k, v in rdr.aov().items()})
+            print(f"[adapt_amd] wrote {base}-aov.npz")
     if opts.transient:
         export_transient(rdr, opts.output_path, stem, opts.img_ext, opts.normalize)      # render.py:166: folder named after the scene file
     rdr.close()

@@ -22,6 +22,7 @@
 #include "bvh_build.hpp"
 #include "shade_stage.hpp"
 #include "unit_kernels.hpp"
+#include "aov.hpp"
 #include "volumetric.hpp"
 
 #define APT_EXPORT extern "C" __attribute__((visibility("default")))
@@ -284,6 +285,10 @@ struct apt_renderer {
     hipEvent_t ad_ev = nullptr;           // ... valid once this event has passed
     bool ad_pending = false;
     uint32_t n_live = 0;                  // active pixels of the coming round
+    // feature buffers and denoiser (aov.hpp): allocated on first use, freed with the renderer
+    DevBuf aov_rec, aov_sum;              // the AOV pass's per-slot records (aov_batch samples in flight) and per-pixel sums
+    int aov_batch = 0;
+    DevBuf dn_rgb, dn_planes;             // the denoiser's packed colour in / out (3 floats per pixel) and its four float4 planes (colour x 2, guides x 2)
 };
 
 static int count_device(int* n) {
@@ -1579,6 +1584,7 @@ APT_EXPORT int apt_reset(apt_renderer* r) {
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
     if (r->transient) HIP_TRY(hipMemsetAsync(r->tr_bins.p, 0, r->tr_bins.bytes, r->stream()));
+    if (r->aov_sum.p) HIP_TRY(hipMemsetAsync(r->aov_sum.p, 0, r->aov_sum.bytes, r->stream()));
     for (Lane& ln : r->lanes) HIP_TRY(hipMemsetAsync(ln.counters.p, 0, sizeof(Counters), r->stream()));      // lanes are idle between render calls
     r->cnt = 0;
     if (int rc = resolve_events(r)) return rc;
@@ -1673,6 +1679,118 @@ APT_EXPORT int apt_stream(apt_renderer* r, void** hip_stream) {
     if (!r || !hip_stream) return fail(APT_E_INVALID, "apt_stream: bad argument");
     *hip_stream = (void*)r->stream();
     return APT_OK;
+}
+
+// ---- feature buffers (AOV pass) and denoiser: aov.hpp, DESIGN.md 4.7
+// Both describe the camera ray's first SURFACE hit of one rank's whole film: the volumetric tracer's first event through null surfaces and
+// fog is another question, and a rank owns bands of the film, not the neighbourhoods a filter reads.
+static int aov_refuse(const apt_renderer* r, const char* who) {
+    if (r->cfg.volumetric) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser belong to the surface renderer (volumetric = 0)");
+    if (r->cfg.world_size > 1) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser run on one rank (world_size = 1)");
+    return APT_OK;
+}
+typedef void (*aov_fn)(DevScene, Params, AovQ, LdsPlan);
+static const aov_fn kAovTrace[4] = {k_aov_trace<TRACE_BVH>, k_aov_trace<TRACE_SWEEP>, k_aov_trace<TRACE_TILE>, /* TRACE_FLAT */ APT_FLAT_FN(k_aov_trace_flat)};
+constexpr int APT_AOV_MAX_BATCH = 16;               // samples in flight per batch of the pass ...
+constexpr size_t APT_AOV_MAX_SCRATCH = 512u << 20;  // ... fewer where their records (32 bytes per slot) would take more than this
+static int aov_ensure(apt_renderer* r) {
+    if (r->aov_sum.p) return APT_OK;
+    const int fit = (int)std::max<size_t>(1, APT_AOV_MAX_SCRATCH / ((size_t)r->npix * 32));
+    r->aov_batch = std::min(APT_AOV_MAX_BATCH, fit);
+    hipError_t e;
+    if ((e = r->aov_rec.alloc((size_t)r->npix * (size_t)r->aov_batch * 32)) != hipSuccess || (e = r->aov_sum.alloc((size_t)r->npix * 32)) != hipSuccess)
+        return fail(APT_E_NOMEM, std::string("feature buffers: ") + hipGetErrorString(e));      // (aov_sum stays null: the next call tries again)
+    if (r->lds_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kAovTrace[r->trace_mode], hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
+    HIP_TRY(hipMemsetAsync(r->aov_sum.p, 0, r->aov_sum.bytes, r->stream()));
+    return APT_OK;
+}
+APT_EXPORT int apt_render_aov(apt_renderer* r, int32_t first_sample, int32_t n_spp) {
+    if (!r || first_sample < 0 || n_spp < 0) return fail(APT_E_INVALID, "apt_render_aov: bad argument");
+    if (int rc = aov_refuse(r, "apt_render_aov")) return rc;
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (int rc = aov_ensure(r)) return rc;
+    unchain(r, r->stream());
+    AovQ a; a.rec = r->aov_rec.as<float4>(); a.sum = r->aov_sum.as<float4>(); a.stride = (uint32_t)((size_t)r->npix * (size_t)r->aov_batch);
+    for (int done = 0; done < n_spp;) {
+        const int b = std::min(r->aov_batch, n_spp - done);
+        Params p = r->par; p.cnt_base = first_sample + done; p.spp_batch = b;
+        const size_t total = (size_t)r->npix * (size_t)b;
+        hipLaunchKernelGGL(kAovTrace[r->trace_mode], dim3(grid_for(total, r->grid_trace, 1, r->trace_items)), dim3(r->trace_nt), r->lds_bytes, r->stream(), r->scene->dev, p, a, r->lanes[0].plan);
+        hipLaunchKernelGGL(k_aov_sum, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, r->stream(), p, a);
+        HIP_TRY(hipGetLastError());
+        done += b;
+    }
+    return APT_OK;
+}
+APT_EXPORT int apt_read_aov(apt_renderer* r, float* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_read_aov: bad argument");
+    if (int rc = aov_refuse(r, "apt_read_aov")) return rc;
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (int rc = aov_ensure(r)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, r->aov_sum.p, r->aov_sum.bytes, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
+APT_EXPORT int apt_set_aov(apt_renderer* r, const float* in) {
+    if (!r || !in) return fail(APT_E_INVALID, "apt_set_aov: bad argument");
+    if (int rc = aov_refuse(r, "apt_set_aov")) return rc;
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (int rc = aov_ensure(r)) return rc;
+    HIP_TRY(hipMemcpyAsync(r->aov_sum.p, in, r->aov_sum.bytes, hipMemcpyHostToDevice, r->stream()));
+    return resolve_events(r);
+}
+APT_EXPORT int apt_clear_aov(apt_renderer* r) {
+    if (!r) return fail(APT_E_INVALID, "apt_clear_aov: bad argument");
+    if (!r->aov_sum.p) return APT_OK;               // never used (or a renderer the pass refuses): nothing to clear
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemsetAsync(r->aov_sum.p, 0, r->aov_sum.bytes, r->stream()));
+    return resolve_events(r);
+}
+APT_EXPORT int apt_denoise(apt_renderer* r, const apt_denoise_cfg* cfg, const float* colour_in, float* out) {
+    if (!cfg || !out) return fail(APT_E_INVALID, "apt_denoise: bad argument");
+    if (!(cfg->firefly_threshold >= 0.f) || !std::isfinite(cfg->firefly_threshold)) return fail(APT_E_INVALID, "apt_denoise: firefly_threshold must be finite and >= 0 (0 = no firefly stage)");
+    if (cfg->firefly_only && !(cfg->firefly_threshold > 0.f)) return fail(APT_E_INVALID, "apt_denoise: firefly_only needs firefly_threshold > 0");
+    if (!cfg->firefly_only) {
+        if (cfg->iterations < 1 || cfg->iterations > 24) return fail(APT_E_INVALID, "apt_denoise: iterations must be in 1..24");
+        if (!(cfg->sigma_n >= 0.f) || !(cfg->sigma_z > 0.f) || !(cfg->sigma_a > 0.f) || !std::isfinite(cfg->sigma_n) || !std::isfinite(cfg->sigma_z) || !std::isfinite(cfg->sigma_a) || std::isnan(cfg->sigma_c))
+            return fail(APT_E_INVALID, "apt_denoise: sigma_n must be >= 0, sigma_z and sigma_a > 0, all finite (sigma_c <= 0 drops the colour term)");
+    }
+    if (!r) return fail(APT_E_INVALID, "apt_denoise: bad argument");      // (the settings are checked first: a bad one is refused with or without a renderer)
+    if (int rc = aov_refuse(r, "apt_denoise")) return rc;
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    const size_t np = (size_t)r->npix;
+    if (!r->dn_planes.p) {
+        hipError_t e;
+        if ((e = r->dn_rgb.alloc(np * 12)) != hipSuccess || (e = r->dn_planes.alloc(np * 64)) != hipSuccess) { return fail(APT_E_NOMEM, std::string("denoiser planes: ") + hipGetErrorString(e)); }
+    }
+    hipStream_t st = r->stream();
+    unchain(r, st);
+    float* rgb = r->dn_rgb.as<float>();
+    const uint32_t n3 = (uint32_t)np * 3u;
+    if (colour_in) HIP_TRY(hipMemcpyAsync(rgb, colour_in, np * 12, hipMemcpyHostToDevice, st));
+    else if (r->adaptive) hipLaunchKernelGGL(k_divide_ad, dim3((n3 + 255) / 256), dim3(256), 0, st, r->accum.as<float>(), (const int32_t*)r->ad_n.p, rgb, n3);
+    else hipLaunchKernelGGL(k_divide, dim3((n3 + 255) / 256), dim3(256), 0, st, r->accum.as<float>(), rgb, n3, (float)(r->cnt > 0 ? r->cnt : 1));      // (what apt_read_pixels hands out)
+    DenoiseQ q; q.W = r->cfg.width; q.H = r->cfg.height;
+    q.x0 = r->cfg.do_crop ? std::max(0, r->cfg.start_x) : 0; q.x1 = r->cfg.do_crop ? std::min(q.W, r->cfg.end_x) : q.W;
+    q.y0 = r->cfg.do_crop ? std::max(0, r->cfg.start_y) : 0; q.y1 = r->cfg.do_crop ? std::min(q.H, r->cfg.end_y) : q.H;
+    float4* planes = r->dn_planes.as<float4>();
+    q.c[0] = planes; q.c[1] = planes + np; q.g0 = planes + 2 * np; q.g1 = planes + 3 * np;
+    const bool atrous = !cfg->firefly_only, firefly = cfg->firefly_threshold > 0.f, demod = atrous && cfg->demodulate != 0;
+    const dim3 lin((unsigned)((np + 255) / 256)), tile((unsigned)((q.H + 63) / 64), (unsigned)((q.W + DN_BX - 1) / DN_BX)), tile_nt(64, DN_BX);
+    hipLaunchKernelGGL(k_dn_prepare, lin, dim3(256), 0, st, q, (const float*)rgb, (const float4*)r->aov_sum.p, (demod && !firefly) ? 1 : 0);
+    int src = 0;
+    if (firefly) { hipLaunchKernelGGL(k_dn_firefly, tile, tile_nt, 0, st, q, src, cfg->firefly_threshold, demod ? 1 : 0); src ^= 1; }
+    for (int k = 0; atrous && k < cfg->iterations; k++) {
+        AtrousPar ap; ap.step = 1 << k; ap.sigma_n = cfg->sigma_n; ap.inv_z = 1.f / cfg->sigma_z; ap.inv_a2 = 1.f / (cfg->sigma_a * cfg->sigma_a);
+        const float sc_k = cfg->sigma_c > 0.f ? std::ldexp(cfg->sigma_c, -k) : 0.f;
+        ap.inv_c2 = sc_k > 0.f ? 1.f / (sc_k * sc_k) : 0.f;
+        ap.remod = (demod && k == cfg->iterations - 1) ? 1 : 0;
+        hipLaunchKernelGGL(k_dn_atrous, tile, tile_nt, 0, st, q, src, ap);
+        src ^= 1;
+    }
+    hipLaunchKernelGGL(k_dn_unpack, lin, dim3(256), 0, st, q, src, rgb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, rgb, np * 12, hipMemcpyDeviceToHost, st));
+    return resolve_events(r);
 }
 
 // ---- unit entry points

@@ -25,6 +25,13 @@ and >= `min_spp`.  `render(n)` still advances `cnt` by n (the most samples any p
     rdr.relative_error()           # (w, h) float64: e_p, the quantity the threshold is held against
     rdr.active_fraction()          # share of this rank's sampled pixels that still sample
 
+Feature buffers and denoiser, `pt` on one rank: `Renderer(..., aov_spp=32)`.  The camera ray of a pixel-sample is a pure
+function of (pixel, sample number, seed), so a pass of its own restates the rays of samples 1..min(cnt, aov_spp) and records what they hit:
+
+    rdr.aov()                      # {"albedo": (w,h,3), "normal": (w,h,3), "depth": (w,h), "hit_fraction": (w,h)} float32, means over the hits
+    rdr.denoised(**cfg)            # (w, h, 3): `pixels` through the firefly filter (firefly_threshold > 0) and the a-trous filter guided by aov()
+    rdr.firefly_filtered(0.4)      # (w, h, 3): the firefly filter alone (upstream's post_processing.py)
+
 Extensions (keyword-only, all optional): `n_spp=` on render() to queue many samples per
 call (the wavefront batches them), `device/rank/world_size/band_width` for image-tile
 sharding across GPUs, `seed`, `spp_per_batch`, `profile`, and film/bounce overrides so the
@@ -42,9 +49,11 @@ from . import _lib
 from .scene_pack import FlatScene, RenderConfig, make_config, pack_scene
 from .tiles import TilePlan
 
-__all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error"]
+__all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error", "DENOISE_DEFAULTS"]
 
 ADAPTIVE_DEFAULTS = {"min_spp": 64, "step": 32}
+# apt_denoise_cfg's defaults (include/adapt_mi.h; DESIGN.md §4.7 says how they were chosen)
+DENOISE_DEFAULTS = {"firefly_threshold": 0.0, "iterations": 3, "sigma_n": 128.0, "sigma_z": 0.1, "sigma_a": 0.1, "sigma_c": 1.0, "demodulate": True}
 # apt_renderer_info's trace_mode -> name: TRACE_BVH, TRACE_SWEEP, TRACE_TILE, TRACE_FLAT (csrc/stages.hpp), the words of csrc/api.hip kTraversalName in its order
 TRAVERSAL_NAMES = dict(enumerate(("bvh", "sweep", "tile", "flat")))
 
@@ -245,7 +254,7 @@ class Renderer:
                  seed: int = 0, spp_per_batch: int = 0, profile: bool = False,
                  width: Optional[int] = None, height: Optional[int] = None,
                  max_bounce: Optional[int] = None, num_shadow_ray: Optional[int] = None, volumetric: Optional[bool] = None,
-                 exact: Optional[bool] = None, transient=None, adaptive=None):
+                 exact: Optional[bool] = None, transient=None, adaptive=None, aov_spp: int = 32):
         # transient = None / False: steady state; True: time bins from the sensor's sample_count / min_time / interval; a dict overrides them
         # (scene_pack.transient_config).  Surface renderer, at most 4 light samples per vertex, one rank: apt_renderer_create refuses the rest.
         # exact = True: the bit-parity build (the reference's float32 arithmetic operation for operation; debugging and the exact
@@ -275,6 +284,10 @@ class Renderer:
         self.plan = TilePlan(self.w, self.h, band_width if world_size > 1 else self.w, world_size)
         self._cnt = 0
         self._t0 = time.time()
+        # feature buffers: the camera rays of samples 1..min(cnt, aov_spp) are restated on demand (aov()); _aov_n = how many are in
+        self.aov_spp, self._aov_n = int(aov_spp), 0
+        if self.aov_spp < 0:
+            raise ValueError("aov_spp must be >= 0")
 
         self.scene = DeviceScene(self.flat, self.device, self.lib)
         cfg = _lib.RenderCfg()
@@ -317,12 +330,78 @@ class Renderer:
         _lib.check(self.lib.apt_synchronize(self.handle), "apt_synchronize", self.lib)
 
     def reset(self):
-        """No-op, exactly like the reference (`TracerBase.reset` is an empty kernel, tracer_base.py:284-286)."""
+        """Leaves the render alone, exactly like the reference (`TracerBase.reset` is an empty kernel, tracer_base.py:284-286); the
+        feature buffers, which can be restated at any time, start over."""
+        self._clear_aov()
 
     def clear(self):
-        """Zero the accumulation, the sample counter, the statistics and the transient bins."""
+        """Zero the accumulation, the sample counter, the statistics, the transient bins and the feature buffers."""
         _lib.check(self.lib.apt_reset(self.handle), "apt_reset", self.lib)
         self._cnt = 0
+        self._aov_n = 0
+
+    # ------------------------------------------------- feature buffers and denoiser (DESIGN.md §4.7)
+    def _clear_aov(self):
+        if getattr(self, "handle", None) and self._aov_n:
+            _lib.check(self.lib.apt_clear_aov(self.handle), "apt_clear_aov", self.lib)
+        self._aov_n = 0
+
+    def _update_aov(self):
+        """Bring the feature buffers to the camera rays of samples 1..min(cnt, aov_spp): a top-up after more rendering, a fresh start where
+        the sample counter went back."""
+        want = min(self._cnt, self.aov_spp)
+        if want < self._aov_n:
+            self._clear_aov()
+        _lib.check(self.lib.apt_render_aov(self.handle, self._aov_n, want - self._aov_n), "apt_render_aov", self.lib)      # (refuses vpt and ranks even with nothing to add)
+        self._aov_n = want
+
+    def tile_aov(self) -> np.ndarray:
+        """The raw sums, (w, h, 8) float32: albedo rgb, depth, normal xyz, hit count - over the camera rays of samples 1..min(cnt, aov_spp)."""
+        self._update_aov()
+        out = np.empty((self.n_cols, self.h, 8), np.float32)
+        _lib.check(self.lib.apt_read_aov(self.handle, _fp(out)), "apt_read_aov", self.lib)
+        return out
+
+    def aov(self) -> dict:
+        """What the camera rays hit first: albedo (w,h,3) - the diffuse colour the shade stage reads, record or texture -, normal (w,h,3) -
+        the shading normal after the maps, world space, renormalised mean -, depth (w,h) and hit_fraction (w,h).  Means over the rays that
+        hit, 0 where none did; hit_fraction = hits / samples covered (0 outside a crop window)."""
+        raw = self.tile_aov()
+        n = raw[..., 7]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = np.where(n[..., None] > 0, raw[..., :7] / n[..., None], np.float32(0)).astype(np.float32)
+            normal = mean[..., 4:7]
+            length = np.sqrt((normal[..., 0] * normal[..., 0] + normal[..., 1] * normal[..., 1]) + normal[..., 2] * normal[..., 2])
+            normal = np.where(length[..., None] > 0, normal / length[..., None], normal).astype(np.float32)
+        return {"albedo": np.ascontiguousarray(mean[..., 0:3]), "normal": np.ascontiguousarray(normal), "depth": np.ascontiguousarray(mean[..., 3]),
+                "hit_fraction": (n / np.float32(max(1, self._aov_n))).astype(np.float32)}
+
+    def _denoise(self, cfg: dict, colour) -> np.ndarray:
+        unknown = set(cfg) - set(DENOISE_DEFAULTS) - {"firefly_only"}
+        if unknown:
+            raise ValueError(f"denoise: unknown setting(s) {sorted(unknown)}")
+        c = {**DENOISE_DEFAULTS, "firefly_only": False, **cfg}
+        dc = _lib.DenoiseCfg(float(c["firefly_threshold"]), int(bool(c["firefly_only"])), int(c["iterations"]), float(c["sigma_n"]), float(c["sigma_z"]),
+                             float(c["sigma_a"]), float(c["sigma_c"]), int(bool(c["demodulate"])))
+        if not c["firefly_only"]:
+            self._update_aov()                    # the guides: up to date before the filter reads them
+        src = None
+        if colour is not None:
+            src = np.ascontiguousarray(colour, np.float32)
+            if src.shape != (self.w, self.h, 3):
+                raise ValueError(f"denoise: colour must be ({self.w},{self.h},3), got {src.shape}")
+        out = np.empty((self.w, self.h, 3), np.float32)
+        _lib.check(self.lib.apt_denoise(self.handle, C.byref(dc), _fp(src) if src is not None else None, _fp(out)), "apt_denoise", self.lib)
+        return out
+
+    def denoised(self, colour=None, **cfg) -> np.ndarray:
+        """(w, h, 3) float32: `pixels` (or `colour`, a (w,h,3) image of this film) through the firefly filter (firefly_threshold > 0) and K
+        iterations of the a-trous filter guided by aov().  Settings: DENOISE_DEFAULTS."""
+        return self._denoise(cfg, colour)
+
+    def firefly_filtered(self, threshold: float = 0.4, colour=None) -> np.ndarray:
+        """(w, h, 3) float32: upstream's firefly filter alone (post_processing.py; its THRESHOLD is 0.4)."""
+        return self._denoise({"firefly_threshold": threshold, "firefly_only": True}, colour)
 
     # ------------------------------------------------------------- readback
     def tile_accum(self) -> np.ndarray:
@@ -518,6 +597,7 @@ class Renderer:
                 "cam_orient": np.array(self.cam_orient), "src_num": self.src_num, "cam_t": np.array(self.cam_t),
                 "accumulation": self.color.to_numpy(), "counter": self._cnt,
                 **({"transient_bins": self.tile_transient()} if self.n_bins else {}),
+                **({"aov_sums": self.tile_aov(), "aov_samples": self._aov_n} if self._aov_n else {}),
                 **(self._adaptive_check_point() if self.adaptive else {})}
 
     _ADAPTIVE_KEYS = ("adaptive", "sample_counts", "moments", "active")
@@ -533,7 +613,7 @@ class Renderer:
         if not self.adaptive and any(k in check_point for k in self._ADAPTIVE_KEYS):
             raise ValueError("this checkpoint is an adaptive render's: continue it with Renderer(..., adaptive=...)")
         for key, val in check_point.items():
-            if key in ("accumulation", "counter", "transient_bins") + self._ADAPTIVE_KEYS:
+            if key in ("accumulation", "counter", "transient_bins", "aov_sums", "aov_samples") + self._ADAPTIVE_KEYS:
                 continue
             if key in ("cam_t", "cam_orient"):
                 ok = np.abs(np.asarray(val) - np.asarray(getattr(self, key))).max() < 1e-4
@@ -544,6 +624,13 @@ class Renderer:
         self._set_accum(np.asarray(check_point["accumulation"], np.float32), int(check_point["counter"]))
         if self.adaptive:
             self._set_adaptive_state(check_point["sample_counts"], check_point["moments"], check_point["active"])
+        # feature buffers: taken from the checkpoint where it has them for this film; else they start over and aov() restates them
+        self._clear_aov()
+        sums = check_point.get("aov_sums")
+        if sums is not None and np.shape(sums) == (self.n_cols, self.h, 8) and 0 < int(check_point.get("aov_samples", 0)) <= min(self._cnt, self.aov_spp):
+            sums = np.ascontiguousarray(sums, np.float32)
+            _lib.check(self.lib.apt_set_aov(self.handle, _fp(sums)), "apt_set_aov", self.lib)
+            self._aov_n = int(check_point["aov_samples"])
         cube = check_point.get("transient_bins")
         if self.n_bins and cube is not None and np.shape(cube) == (self.n_bins, self.n_cols, self.h, 4):
             self._set_transient(cube)           # (a checkpoint of another bin layout, or of a steady render, leaves the bins as they are)

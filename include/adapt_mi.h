@@ -20,6 +20,8 @@
  *   apt_get_accum / apt_set_accum  tracer/path_tracer.py:181-211  get_check_point / load_check_point
  *   apt_read_transient             renderer/bdpt.py:57-58,164-166  time_bins / time_cnts (TRANSIENT_CAM), for the `pt` renderer
  *   apt_read_sample_counts / apt_read_moments / apt_set_adaptive_state   (none; adaptive sampling)
+ *   apt_render_aov / apt_read_aov / apt_set_aov / apt_clear_aov   (none; per-pixel albedo, normal and depth of the camera rays' first hits)
+ *   apt_denoise                    post_processing.py:15-32 (the firefly filter: stage 1) + an edge-avoiding a-trous filter guided by those buffers (stage 2; none upstream)
  *   apt_get_stats                  (none; the reference only has ti.profiler, render.py:154-160)
  *   apt_device_ptr                 (none; hands the tile framebuffer to RCCL for the multi-GPU gather)
  *
@@ -140,6 +142,24 @@ typedef struct apt_stats {
     int64_t n_track;                    /* volumetric: closest-hit queries made by the transmittance walk of the light samples */
 } apt_stats;
 
+/* Denoiser settings.  Stage 1, the firefly filter, is upstream's rule (post_processing.py:15-32): on the zero-padded film a pixel
+   keeps its value if any of its 8 neighbours lies within Euclidean rgb distance < firefly_threshold of it, else it becomes the float32 sum of the 8
+   (first index outermost) / 8; non-finite input components count as 0.  Stage 2 is the a-trous wavelet filter of Dammertz et al. 2010: iteration
+   k = 0 .. iterations-1 has 5x5 taps 2^k pixels apart with h = (1/16, 1/4, 3/8, 1/4, 1/16) per axis and tap weight h(dx) h(dy) w_n w_z w_a w_c w_hit:
+     w_n = max(0, n_p . n_q)^sigma_n            w_z = exp(-|z_p - z_q| / (sigma_z max(z_p, 1e-6)))
+     w_a = exp(-|a_p - a_q|^2 / sigma_a^2)      w_c = exp(-|c_p - c_q|^2 / (sigma_c 2^-k)^2)   (sigma_c <= 0: no colour term)
+     w_hit = 1 when p and q agree on hit_fraction > 0, else 0; between two pixels that hit nothing w_n = w_z = w_a = 1
+   with n, z, a the feature buffers' means (unit normal, depth, albedo) and c the iteration's input colour.  Taps outside the film or the crop window are
+   skipped, the centre tap always counts with h(0)^2, output = weighted sum / weight sum.  demodulate: where hit_fraction > 0 the filter runs on
+   c / max(a, 1e-3) and the albedo is multiplied back at the end. */
+typedef struct apt_denoise_cfg {
+    float   firefly_threshold;                    /* > 0: stage 1 runs (upstream's THRESHOLD is 0.4); 0: off */
+    int32_t firefly_only;                         /* 1: stage 1 alone (needs firefly_threshold > 0; the fields below are not read) */
+    int32_t iterations;                           /* K, 1..24 (default 3) */
+    float   sigma_n, sigma_z, sigma_a, sigma_c;   /* defaults 128, 0.1, 0.1, 1.0: chosen on a measured grid, DESIGN.md §4.7 */
+    int32_t demodulate;                           /* default 1 */
+} apt_denoise_cfg;
+
 /* ---- BVH build (host, own layout; replaces bvh_cpp.bvh_build) */
 int apt_bvh_build(const float* prims /* n_prims*9 */, int32_t n_prims,
                   const int32_t* obj_info /* n_objects*3 */, int32_t n_objects, apt_bvh** out);
@@ -211,7 +231,7 @@ int apt_tile_shape(const apt_renderer*, int32_t* n_cols, int32_t* height);   /* 
 int apt_read_pixels(apt_renderer*, float* out);           /* owned tile, [local col][y][rgb], color / cnt (adaptive: color / n_p, 0 where n_p = 0) */
 int apt_get_accum(apt_renderer*, float* out, int32_t* cnt);
 int apt_set_accum(apt_renderer*, const float* in, int32_t cnt);
-int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0, transient bins = 0, adaptive state = start */
+int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0, transient bins = 0, adaptive state = start, feature buffers = 0 */
 /* transient renders: the owned tile's bins, [bin][local col][y][rgba] - summed r, g, b (divide by cnt for radiance, as pixels) and the
    number of contributions (a); transient_bins * n_cols * height * 4 floats.  apt_set_transient restores them (checkpoints). */
 int apt_read_transient(apt_renderer*, float* out);
@@ -222,6 +242,19 @@ int apt_set_transient(apt_renderer*, const float* in);
 int apt_read_sample_counts(apt_renderer*, int32_t* counts, uint8_t* active);
 int apt_read_moments(apt_renderer*, double* s2);
 int apt_set_adaptive_state(apt_renderer*, const int32_t* counts, const double* s2, const uint8_t* active);
+/* Feature buffers of the surface renderer on one rank (volumetric = 1 and world_size > 1: APT_E_INVALID).  apt_render_aov adds the camera rays of
+   samples first_sample+1 .. first_sample+n_spp - the rays apt_render traces for those sample numbers, met with the renderer's own traversal - to the
+   per-pixel sums: a ray that hits contributes the albedo the shade stage would read (k_d or the albedo map), the shading normal after the maps
+   (world space, not flipped) and the hit distance; a miss nothing.  The caller keeps track of which samples are in.  apt_read_aov: owned pixels in
+   [local col][y] order, 8 floats each: sum albedo rgb, sum depth, sum normal xyz, hit count (all 0 outside a crop window).  Sums are added in sample
+   order by one thread per pixel: repeated runs and other call splits give the same bits.  apt_set_aov restores them (checkpoints). */
+int apt_render_aov(apt_renderer*, int32_t first_sample, int32_t n_spp);
+int apt_read_aov(apt_renderer*, float* out);
+int apt_set_aov(apt_renderer*, const float* in);
+int apt_clear_aov(apt_renderer*);
+/* Denoise colour_in ([x][y][rgb], width*height*3 floats; NULL: the renderer's current pixels, as apt_read_pixels hands them out) into out, guided by
+   the feature buffers as they stand.  The settings are checked before the handle and the device.  Same refusals as the feature buffers. */
+int apt_denoise(apt_renderer*, const apt_denoise_cfg* cfg, const float* colour_in, float* out);
 int apt_get_stats(apt_renderer*, apt_stats* out);
 int apt_device_ptr(apt_renderer*, void** accum_dev, int32_t* cnt); /* device float[n_cols*height*3] accumulation buffer */
 int apt_stream(apt_renderer*, void** hip_stream);         /* the hipStream_t every kernel of this renderer runs on */
