@@ -877,6 +877,7 @@ if __name__ == "__main__":
         test_dir = os.path.join(refenv.REPO, "scenes", "test")
         gen_refscene(test_dir, "media_a.xml", "media_a", 40, 30, 3, volumetric=True)
         gen_refscene(test_dir, "media_b.xml", "media_b", 40, 30, 3, volumetric=True)
+        gen_refscene(test_dir, "null_panes.xml", "null_panes", 40, 30, 3, volumetric=True)      # four null-surface panes: track_ray to its seven-segment limit
         # surface-only scenes through the volumetric loop (the reference's default renderer type): every BRDF / BSDF / emitter type,
         # and image textures (vpt.py looks up the albedo map only)
         os.chdir(refenv.REPO)                           # texture paths in textured.xml are relative to the repository root

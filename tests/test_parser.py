@@ -270,7 +270,7 @@ def test_reference_parser_objects_are_accepted(d, f, tag, flat):
 
 
 # ---- participating media (volumetric tracer inputs)
-@pytest.mark.parametrize("name", ["media_a", "media_b"])
+@pytest.mark.parametrize("name", ["media_a", "media_b", "null_panes"])
 def test_media_scene_parse_matches_reference_parser_arrays(name):
     """scenes/test/media_*.xml through this repo's front end = the arrays the reference's parser produced for the same file (stored
     in the vptscene fixture): geometry, materials, emitters and the per-object / world medium tables, bit for bit."""
