@@ -123,6 +123,7 @@ SYMBOLS = {
     "apt_transient_bin_probe": (C.c_int, [C.c_int32, C.c_int32, f32p, C.c_float, C.c_float, C.c_int32, i32p]),
     "apt_renderer_info": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_int64), i32p, C.POINTER(C.c_char_p), i32p]),
     "apt_renderer_camera_fused": (C.c_int, [C.c_void_p, i32p]),
+    "apt_renderer_record_staged": (C.c_int, [C.c_void_p, i32p]),
     "apt_measure_sclk_mhz": (C.c_int, [C.c_int32, f32p]),
     "apt_last_error": (C.c_char_p, []),
     "apt_version": (C.c_char_p, []),

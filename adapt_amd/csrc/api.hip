@@ -44,16 +44,17 @@ typedef void (*shade_traced_fn)(DevScene, Params, Queues, Counters*, int, int);
 typedef void (*shade_cam_fn)(DevScene, Params, Queues, Counters*, const unsigned long long*);
 typedef void (*shade_tr_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int, TransQ);
 // transient: fn's time-resolved twin (k_shade_tr); traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced:
-// flat sweep, one light sample per vertex); traced_cam: traced's camera-fed twin (k_shade_traced_cam: bounce 0 of a steady full-film batch, no k_generate_trace in front of it)
-struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; shade_traced_fn traced; shade_cam_fn traced_cam; };
+// flat sweep, one light sample per vertex); traced_cam: traced's camera-fed twin (k_shade_traced_cam: bounce 0 of a steady full-film batch, no k_generate_trace in front of it);
+// traced_staged: traced with its record staged in LDS a row ahead (shade_traced, STAGE; null: the variant has no such form)
+struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; shade_traced_fn traced; shade_cam_fn traced_cam; shade_traced_fn traced_staged; };
 #if APT_FAST
 #define APT_FLAT_FN(...) __VA_ARGS__
 #else
 #define APT_FLAT_FN(...) nullptr          // the flat sweep exists in the fast build only (traverse.hpp), and with it the shade kernels that trace their rays on its records
 #endif
 #define APT_TRACED_PAIR(STEM, ...) APT_FLAT_FN(STEM<__VA_ARGS__>), APT_FLAT_FN(STEM##_cam<__VA_ARGS__>)
-#define APT_TRACED_PLAIN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced, BM, SM, TEX)
-#define APT_TRACED_LEAN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced_lean, BM, SM)
+#define APT_TRACED_PLAIN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced, BM, SM, TEX), nullptr
+#define APT_TRACED_LEAN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced_lean, BM, SM), APT_FLAT_FN(k_shade_traced_lean_staged<BM, SM>)
 #define APT_SHADE_VARIANT(BM, SM, TEX, NAME, TRACED) {BM, SM, NAME, k_shade<BM, SM, TEX>, k_shade_tr<BM, SM, TEX>, APT_TRACED_##TRACED(BM, SM, TEX)}
 static const ShadeVariant kShadeVariants[] = {
     APT_SHADE_VARIANT(APT_BX_LAMBERTIAN, APT_SRC_POINT, 0, "lambertian/point", LEAN),
@@ -235,6 +236,8 @@ struct apt_renderer {
     hipStream_t stream() const { return lanes[0].stream; }
     DevBuf accum, scratch, pix_key;
     DevBuf cam_strips;            // rays traced in place: per 64 local pixels, the record pairs a camera ray can hit (flat_build.cpp camera_strips)
+    int record_stage = 0;         // rays traced in place: 1 = the queue-fed shade kernel stages its record in LDS a row ahead (ShadeVariant::traced_staged; APT_RECORD_STAGE=0 switches it off)
+    shade_traced_fn traced_fn = nullptr;      // the queue-fed kernel of a PIPE_TRACED render: shade->traced_staged or shade->traced
     int camera_fuse = 0;          // rays traced in place: 1 = the camera vertex is shaded by the kernel that traces the camera ray (k_shade_traced_cam; steady full-film renders with max_bounce >= 1, APT_CAMERA_FUSE=0 switches it off)
     Counters host_counters{};
     int grid_small = 0, grid_trace = 0, nq = APT_MAX_NQ;
@@ -830,6 +833,9 @@ static int pick_shading(apt_renderer* r) {
     const bool can_trace = r->trace_mode == TRACE_FLAT && S == 1 && !r->transient && r->shade->traced != nullptr;
     r->pipeline = c.volumetric ? PIPE_VOLUMETRIC : (sorted ? PIPE_SORTED : ((can_trace && want_traced) ? PIPE_TRACED : PIPE_STAGED));
     p.traced = (r->pipeline == PIPE_TRACED) ? 1 : 0;
+    const bool want_stage = !(getenv("APT_RECORD_STAGE") && atoi(getenv("APT_RECORD_STAGE")) == 0);
+    r->record_stage = (p.traced && want_stage && r->shade->traced_staged != nullptr) ? 1 : 0;
+    r->traced_fn = r->record_stage ? r->shade->traced_staged : r->shade->traced;
     // flat sweep with several light samples per vertex: the samples are queued by vertex and the shadow kernel adds a vertex's samples with
     // one read-modify-write (stages.hpp k_shadow_flat); otherwise 2-4 samples per vertex add into one radiance plane each (stages.hpp
     // APT_EXCLUSIVE_L) - a transient render always, its bins want the samples apart
@@ -1396,7 +1402,7 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
                 // the camera vertex in one launch (no k_generate_trace, no record of the camera ray), then the ordinary bounce-0 launch for the
                 // handful of camera rays it staged for the reference-order code: that launch's prologue resolves them, its loop shades them
                 { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->shade->traced_cam, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips); }
-                { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->shade->traced, dim3(r->grid_fix), dim3(BLOCK), 0, st, sc, p, q, cnt, 0, 0); }
+                { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->traced_fn, dim3(r->grid_fix), dim3(BLOCK), 0, st, sc, p, q, cnt, 0, 0); }
                 cur = 1; b0 = 1;
             } else {
                 LaunchTimer t(r, APT_K_GENERATE, st);
@@ -1404,7 +1410,7 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
                 else hipLaunchKernelGGL(k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips);
             }
             for (int b = b0; b < p.max_bounce; b++) {
-                { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->shade->traced, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, b); }      // (the records are Queues::tr[cur]: one queue for the scene)
+                { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->traced_fn, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, b); }      // (the records are Queues::tr[cur]: one queue for the scene)
                 cur ^= 1;
             }
             if (p.max_bounce > 0) { LaunchTimer t(r, APT_K_SHADOW, st, false); hipLaunchKernelGGL(r->fix, dim3(r->grid_fix), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, (const uint32_t*)cnt->n_active[cur], ln.plan); }
@@ -1642,13 +1648,17 @@ APT_EXPORT int apt_get_stats(apt_renderer* r, apt_stats* out) {
     out->n_samples = sum(ST_SAMPLES); out->n_extend = sum(ST_EXTEND); out->n_shade = sum(ST_SHADE);
     out->n_shadow = sum(ST_SHADOW); out->n_shadow_traced = sum(ST_SHADOW_TRACED); out->n_lit = sum(ST_LIT);
     out->n_draws = sum(ST_DRAWS); out->n_poisoned = sum(ST_POISON); out->n_track = sum(ST_TRACK);
-#if defined(APT_WALK_STATS) || defined(APT_NEAR_STATS)
+#if defined(APT_WALK_STATS) || defined(APT_NEAR_STATS) || defined(APT_ROWTOP_STATS)
     const int64_t n_overflow = 0;                // profiling builds keep their counters in stats[8..15], which overlaps ST_OVERFLOW
 #else
     const int64_t n_overflow = sum(ST_OVERFLOW);
 #endif
 #ifdef APT_NEAR_STATS
     fprintf(stderr, "[near stats] shaded vertices %lld, of which within 2e-3 of the vertex before them %lld\n", (long long)out->n_shade, (long long)sum(14));
+#endif
+#ifdef APT_ROWTOP_STATS
+    fprintf(stderr, "[row-top stats] queue-fed traced shade kernel: %lld rows, %.1f ticks per row waiting for the row's record, %.1f ticks per row in all: %.4f of the waves' time in the row loop\n",
+            (long long)sum(14), (double)sum(12) / (double)std::max<int64_t>(1, sum(14)), (double)sum(13) / (double)std::max<int64_t>(1, sum(14)), (double)sum(12) / (double)std::max<int64_t>(1, sum(13)));
 #endif
 #ifdef APT_WALK_STATS
     {
@@ -1969,6 +1979,11 @@ APT_EXPORT int apt_measure_sclk_mhz(int32_t device, float* mhz) {
 APT_EXPORT int apt_renderer_camera_fused(const apt_renderer* r, int32_t* out) {
     if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_camera_fused: null argument");
     *out = r->camera_fuse;
+    return APT_OK;
+}
+APT_EXPORT int apt_renderer_record_staged(const apt_renderer* r, int32_t* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_record_staged: null argument");
+    *out = r->record_stage;
     return APT_OK;
 }
 APT_EXPORT int apt_renderer_info(const apt_renderer* r, int32_t* spp_batch, int32_t* n_subqueues, int64_t* queue_bytes, int32_t* lds_bytes, const char** shade_variant, int32_t* trace_mode) {

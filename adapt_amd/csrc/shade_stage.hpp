@@ -331,8 +331,19 @@ APT_D void tally_flush(const ShadeTally& t, const uint32_t* s_draws, Counters* c
 // strip-mask rule holds as it stands; the row count is a closed form, no counter is read.  Camera rays the sweep cannot settle are staged
 // exactly as k_generate_trace stages them (top of the sub-queue's region of tr[0], n_tr[0][ncls]); the ordinary bounce-0 launch that
 // follows resolves them in its prologue and shades that handful.  This kernel runs no prologue: nothing is listed before it.
-template <int BM, int SM, int TEX, bool CAM = false>
+//
+// STAGE, the staged record (queue-fed form only): a row's record - planes A to D, 64 entries of 16 bytes each: 1 KiB per
+// plane and wave - is requested a row AHEAD, by loads that write LDS directly (global_load_lds_dwordx4: no register holds the data in
+// flight), into 4 KiB that the wave owns; the scene's shading records (at most 96 x 32 bytes) sit in LDS too, one copy per workgroup.
+// A row then opens with LDS reads only - its lane's four words into the registers the direct loads fill, the shading record of the hit
+// primitive, which arrives with plane B (the word requested ahead on its own, PFP, and its register are gone) - and waits on no
+// vector memory: the next row's loads are issued behind the light sample, in front of the two sweeps, and waited for at the end of
+// the row, before its stores (a wait at the next row's top would also wait for those stores to be acknowledged: one in-order counter).
+// Lanes past the queue's end stage its last entry, never used: no address leaves the sub-queue's region; nothing is staged for an empty
+// sub-queue or behind the last row.  STAGE = false is the kernel with the direct loads, instruction for instruction.
+template <int BM, int SM, int TEX, bool CAM = false, bool STAGE = false>
 APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, const unsigned long long* strips = nullptr) {
+    static_assert(!(CAM && STAGE), "a camera-fed row loads no record");
     const ShadeArgs3* A_ = args_fresh(A0);                      // scene, parameters, queues: read through the kernel-argument segment, re-fetched per phase (APT_ARGS_PHASE)
     const int cur = CAM ? 0 : cur_, bounce = CAM ? 0 : bounce_;
     const int nxt = cur ^ 1;
@@ -351,6 +362,9 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
 #ifdef APT_NEAR_STATS
     uint32_t t_near = 0;
 #endif
+#ifdef APT_ROWTOP_STATS      // diagnostic build: per wave, the clock ticks of the row loop and those of them spent waiting for the row's record at its top (stats[12..14])
+    unsigned long long t_rowtop = 0, t_rows = 0, t_loop0 = 0;
+#endif
     // The next row's hit primitive is requested one row ahead (PFP: one register), so that a row's shading record can be requested together
     // with its queue record instead of a round trip after it.  (Rounds 2-4 prefetched the Lambertian kernel's whole record: thirteen
     // registers.  Without them the kernel allocates 91 VGPRs - five waves per SIMD instead of four - and three render lanes gain 6 %:
@@ -358,9 +372,20 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
     // the generator: without area lights a Lambertian vertex's draws are all decided when it is opened, and it reads them from a draw window (rng.hpp)
     constexpr bool WINDOW = APT_DRAW_WINDOW != 0 && BM == APT_BX_LAMBERTIAN && !(SM & APT_SRC_AREA);
     typedef typename std::conditional<WINDOW, DrawWindow, Philox>::type Rng;
-    constexpr bool PFP = TEX == 0 && !CAM;                    // (a camera-fed row knows its primitive when it has traced its ray: nothing to request ahead)
+    constexpr bool PFP = TEX == 0 && !CAM && !STAGE;          // (a camera-fed row knows its primitive when it has traced its ray: nothing to request ahead; a staged row's arrives with its plane B)
     static_assert(APT_FLAT_MAX_PRIMS < (int)TR_NO_PRIM, "the packed record keeps the hit primitive in 8 bits");
     const float4* trA = (A_->q).tr[cur][0]; const float4* trB = (A_->q).tr[cur][1]; const float4* trC = (A_->q).tr[cur][2]; const float4* trD = (A_->q).tr[cur][3];
+    // the staged record: plane k of this wave's row at s_rec[64 * k + lane]; one buffer per wave - a row's loads are issued when the row has read the buffer
+    rec4* s_rec = nullptr; rec4* s_prim = nullptr;             // ... and the scene's shading records (DevScene::prim_shade), one copy per workgroup, filled below
+    if constexpr (STAGE) {
+        __shared__ rec4 s_stage[(BLOCK / 64) * 4 * 64]; __shared__ rec4 s_shade[2 * APT_FLAT_MAX_PRIMS];
+        s_rec = s_stage + (threadIdx.x >> 6) * (4 * 64); s_prim = s_shade;
+    }
+    if constexpr (STAGE) {                                     // (before the prologue: every wave of the workgroup passes here, none has a staged load in flight)
+        static_assert(2 * APT_FLAT_MAX_PRIMS <= BLOCK, "one shading-record word per thread");
+        if ((int)threadIdx.x < 2 * min((A_->sc).n_prims, APT_FLAT_MAX_PRIMS)) { const float4 w_ = (A_->sc).prim_shade[threadIdx.x]; s_prim[threadIdx.x] = rec4{w_.x, w_.y, w_.z, w_.w}; }
+        __syncthreads();
+    }
     uint32_t n, cam_total = 0;
     if constexpr (CAM) {
         // rows of this sub-queue: 64 per id-space wave w with w % nq == q
@@ -374,6 +399,24 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
     uint32_t pf_pm = 0;                                        // (the packed word: primitive, draw index, specular flag)
     auto prefetch_prim = [&](uint32_t b) { pf_pm = ldq(reinterpret_cast<const uint32_t*>(trB), ((qbase + min(b + threadIdx.x, n - 1u)) << 4) + 12u); };      // (lanes past the end re-read the last entry: never used)
     if (PFP && n > 0) prefetch_prim(sl.first);
+    auto stage_row = [&](uint32_t b) {                         // (wave-uniform: b < n)
+        const uint32_t off = (qbase + min(b + threadIdx.x, n - 1u)) << 4;      // (lanes past the end stage the last entry: never used)
+        stage_plane(trA, off, s_rec); stage_plane(trB, off, s_rec + 64); stage_plane(trC, off, s_rec + 128);
+        if (bounce > 0) stage_plane(trD, off, s_rec + 192);
+    };
+    if (STAGE && sl.first < n) {
+        stage_row(sl.first);
+#ifdef APT_ROWTOP_STATS
+        const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
+#endif
+        staged_wait();                                         // (the first row's record: the only one whose round trip the wave sits out)
+#ifdef APT_ROWTOP_STATS
+        t_rowtop += __builtin_amdgcn_s_memtime() - t0_;
+#endif
+    }
+#ifdef APT_ROWTOP_STATS
+    t_loop0 = __builtin_amdgcn_s_memtime();
+#endif
     for (uint32_t base = sl.first; base < n; base += sl.stride) {
         APT_ARGS_PHASE();
         const uint32_t pos = base + threadIdx.x, idx = qbase + pos;                    // (unsorted renders: one queue for the scene)
@@ -433,9 +476,21 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
                 alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0, WINDOW ? jitter_tail : nullptr);
             }
         }
-        if (!CAM && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & APT_SRC_AREA) ray_pdf = dd.w; }
+        rec4 sa = {0.f, 0.f, 0.f, 0.f}, sb = sa, sc_ = sa, sd = sa;      // (STAGE: this lane's words of the row's record)
+        if constexpr (STAGE) {
+            // (the record landed before the row in front of this one stored its own - staged_wait below; nothing at a row's top waits on vector memory)
+            staged_read(s_rec + lane_id(), sa, sb, sc_, sd);    // (plane D's words are read at bounce 0 too, where nothing was staged into them: never used)
+            { const int rp = max(tr_prim(__float_as_uint(sb.w)), 0); rec4 pa, pb; staged_read2(s_prim + 2 * rp, pa, pb); cu_ra = make_float4(pa.x, pa.y, pa.z, pa.w); cu_rb = make_float4(pb.x, pb.y, pb.z, pb.w); }
+            if (alive && bounce > 0) { Lc = mk3(sd.x, sd.y, sd.z); if (SM & APT_SRC_AREA) ray_pdf = sd.w; }
+        }
+        if (!CAM && !STAGE && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & APT_SRC_AREA) ray_pdf = dd.w; }
         if (!CAM && alive) {
-            const float4 a = ldq(trA, idx << 4), b_ = ldq(trB, idx << 4), c = ldq(trC, idx << 4);
+            float4 a, b_, c;
+            if constexpr (STAGE) { a = make_float4(sa.x, sa.y, sa.z, sa.w); b_ = make_float4(sb.x, sb.y, sb.z, sb.w); c = make_float4(sc_.x, sc_.y, sc_.z, sc_.w); }
+            else { a = ldq(trA, idx << 4); b_ = ldq(trB, idx << 4); c = ldq(trC, idx << 4); }
+#ifdef APT_ROWTOP_STATS      // (direct loads: everything the row has requested - record, shading record - is waited for between two stamps; the staged form's wait is stamped where it stands)
+            if constexpr (!STAGE) { const unsigned long long t0_ = __builtin_amdgcn_s_memtime(); staged_wait(); t_rowtop += __builtin_amdgcn_s_memtime() - t0_; t_rows++; }
+#endif
             vx.o = mk3(a.x, a.y, a.z); vx.d = mk3(b_.x, b_.y, b_.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = __float_as_uint(c.w);
             const uint32_t pm = PFP ? cu_pm : __float_as_uint(b_.w);
             const int prim = tr_prim(pm);
@@ -443,7 +498,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
             else {
                 f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
                 if ((A_->sc).has_vn || (TEX && (A_->sc).tex_i != nullptr)) uv = ldq((A_->q).tr_uv[cur], idx << 3);      // otherwise nobody reads the barycentrics (and nobody wrote them)
-                if (PFP) build_hit_rec((A_->sc), cu_ra, cu_rb, prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+                if (PFP || STAGE) build_hit_rec((A_->sc), cu_ra, cu_rb, prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
                 else build_hit((A_->sc), prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
                 alive = open_vertex<BM, SM, TEX>(A_, vx, rng, prim, rec_kd, tr_meta(pm, (uint32_t)bounce), ray_pdf, uv, bounce);
             }
@@ -474,6 +529,10 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
                 if (!__any(f.want && f.src != e0)) occ_e = e0;
             }
         }
+        // The next row's record starts on its way HERE, behind the last load that the row's shading waits for: loads come back in the order
+        // they were issued, so the wait for any load issued behind the staged ones is a wait for them - the round trip this form takes out
+        // of the row.  In front of them lie the continuation's sample and its sweep: time enough to land.
+        if constexpr (STAGE) if (base + sl.stride < n) stage_row(base + sl.stride);
         APT_ARGS_PHASE();
         // ---- emission of the surface we are on, then the continuation
         bool cont = false, is_spec = false;
@@ -483,7 +542,10 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
             new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { Lc = Lc + add; });
             cont = (bounce + 1) < (A_->p).max_bounce;
         }
-        if (rng.draw != vx.draw0) atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);      // also paths that died in the roulette
+        if (rng.draw != vx.draw0) {                            // also paths that died in the roulette
+            if constexpr (STAGE) lds_add_unordered(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
+            else atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
+        }
         APT_ARGS_PHASE();
         // the continuation ray meets the scene's records here.  Only rays that hit something (or whose answer is left to the reference-order
         // code: listed, with a provisional record) enter the next queue; the tail atomic is on its way while the light sample is swept below.
@@ -520,6 +582,17 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
             }
             t_traced += wave_count(f.want); t_lit += wave_count(traced && !occ);
         }
+        if constexpr (STAGE) {
+            // the next row's record has landed - it has had both sweeps - before this row's stores are issued: a wait at the next row's top
+            // would be a wait for these stores to be acknowledged as well (one counter, in order)
+#ifdef APT_ROWTOP_STATS
+            const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
+#endif
+            staged_wait();
+#ifdef APT_ROWTOP_STATS
+            t_rowtop += __builtin_amdgcn_s_memtime() - t0_; t_rows++;
+#endif
+        }
         uint32_t npos = (uint32_t)__builtin_amdgcn_readlane((int)tr_app.raw, 0) + tr_app.rank;
         if (__any(tr_q == 1)) { const uint32_t dpos = wave_append(tr_q == 1, next_counter + APT_MAX_NQ * CNT_PAD); if (tr_q == 1) npos = dpos; }
         if (cont) {
@@ -542,6 +615,11 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
     tally_flush(tl, s_draws, cnt, sl.q);
 #ifdef APT_NEAR_STATS
     flush_uniform(t_near, &cnt->stats[sl.q][14]);
+#endif
+#ifdef APT_ROWTOP_STATS
+    if (!CAM && lane_id() == 0 && t_rows) {
+        atomicAdd(&cnt->stats[sl.q][12], t_rowtop); atomicAdd(&cnt->stats[sl.q][13], (unsigned long long)__builtin_amdgcn_s_memtime() - t_loop0); atomicAdd(&cnt->stats[sl.q][14], t_rows);
+    }
 #endif
 }
 #endif
@@ -702,6 +780,11 @@ __global__ void __launch_bounds__(BLOCK) k_shade_traced(DevScene sc, Params p, Q
 template <int BM, int SM>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_WAVES, APT_TRACED_WAVES))) k_shade_traced_lean(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) {
     shade_traced<BM, SM, 0>(kernel_args3(), cnt, cur, bounce);
+}
+// ... with the record staged in LDS a row ahead (shade_traced, STAGE); APT_RECORD_STAGE=0 selects the kernel above
+template <int BM, int SM>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_WAVES, APT_TRACED_WAVES))) k_shade_traced_lean_staged(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) {
+    shade_traced<BM, SM, 0, false, true>(kernel_args3(), cnt, cur, bounce);
 }
 // ... and their camera-fed twins (shade_traced, CAM): bounce 0 of a steady full-film batch, in place of k_generate_trace + the first launch above
 template <int BM, int SM, int TEX = 0>

@@ -345,6 +345,36 @@ APT_D void begin_shadow(Counters* cnt, const Queues& q, int sq, uint32_t n, bool
 // strides are added on the scalar unit.  With `ptr[index]` each access costs a 64-bit VALU address and a VGPR pair.
 template <typename T> APT_D T ldq(const T* base, uint32_t off) { return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off); }
 template <typename T> APT_D void stq(T* base, uint32_t off, T v) { *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off) = v; }
+// ---- a queue record staged in LDS a row ahead (shade_stage.hpp shade_traced, STAGE).  One plane of a wave's row is 64 entries of 16
+// bytes, 1 KiB in a row: what one global_load_lds_dwordx4 writes - each lane's 16 bytes from its OWN global address to the wave's LDS
+// base + 16 * lane; the data passes through no register.  The load counts on the vector-memory counter like any other load.
+typedef float rec4 __attribute__((ext_vector_type(4)));
+// lane's 16 bytes at byte offset `off` of `plane` -> dst[lane] (dst: wave-uniform, 64 entries owned by this wave)
+APT_D void stage_plane(const float4* plane, uint32_t off, rec4* dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(plane) + off), (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+// every staged load of this wave has landed in LDS
+APT_D void staged_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// LDS reads by statements of their own, complete when the statement ends (from there on the buffer may be staged into again).  In front
+// of an LDS instruction of its own making the compiler waits for every staged load it believes in flight - it cannot tell their LDS
+// destination from the instruction's address - and with them, on the one in-order counter, for every store issued before: at a row's
+// top, the stores of the row before.  The waits that make these reads safe are staged_wait's, placed by hand (shade_traced).
+APT_D uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
+// a lane's words of planes A to D: rec[0], rec[64], rec[128], rec[192]
+APT_D void staged_read(const rec4* rec, rec4& a, rec4& b, rec4& c, rec4& d) {
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(lds_addr(rec)) : "memory");
+}
+// two consecutive 16-byte words
+APT_D void staged_read2(const rec4* p, rec4& a, rec4& b) {
+    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=&v"(a), "=&v"(b) : "v"(lds_addr(p)) : "memory");
+}
+// *word += v in LDS, by a statement of its own: in front of a compiler-made LDS instruction the compiler waits for every staged load in
+// flight (it cannot tell their LDS destination from `word`); this add touches no staged byte and wants no such wait.  Nothing is
+// returned; the wave's later LDS reads see it (LDS instructions of a wave execute in order).
+APT_D void lds_add_unordered(uint32_t* word, uint32_t v) {
+    asm volatile("ds_add_u32 %0, %1" :: "v"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)word), "v"(v) : "memory");
+}
 APT_D f3 ld3q(const float* base, uint32_t stride, uint32_t off) { return mk3(ldq(base, off), ldq(base + stride, off), ldq(base + 2 * stride, off)); }
 APT_D void st3q(float* base, uint32_t stride, uint32_t off, f3 v) { stq(base, off, v.x); stq(base + stride, off, v.y); stq(base + 2 * stride, off, v.z); }
 // wave-uniform tally: how many lanes of the wave have `flag` set (lives in an SGPR)

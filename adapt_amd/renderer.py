@@ -589,6 +589,13 @@ class Renderer:
         _lib.check(self.lib.apt_renderer_camera_fused(self.handle, C.byref(f)), "apt_renderer_camera_fused", self.lib)
         return bool(f.value)
 
+    def record_staged(self) -> bool:
+        """apt_renderer_record_staged: the queue-fed shade kernel stages each row's path record in LDS a row ahead (rays traced in place,
+        Lambertian surfaces under point lights; APT_RECORD_STAGE=0 at creation switches it off)."""
+        f = C.c_int32(0)
+        _lib.check(self.lib.apt_renderer_record_staged(self.handle, C.byref(f)), "apt_renderer_record_staged", self.lib)
+        return bool(f.value)
+
     # ------------------------------------------------------------ checkpoint
     def get_check_point(self) -> dict:
         """Same keys as the reference's pickle (path_tracer.py:181-193)."""

@@ -308,6 +308,9 @@ int apt_renderer_info(const apt_renderer*, int32_t* spp_batch, int32_t* n_subque
 /* Rays traced in place: *fused = 1 when the renderer shades the camera vertex in the kernel that traces the camera ray (steady full-film
  * renders with max_bounce >= 1; env APT_CAMERA_FUSE=0, read at apt_renderer_create, selects generate + a queue-fed bounce 0), else 0. */
 int apt_renderer_camera_fused(const apt_renderer*, int32_t* fused);
+/* Rays traced in place: *staged = 1 when the queue-fed shade kernel stages each row's path record in LDS a row ahead (the Lambertian /
+ * point-light kernel; env APT_RECORD_STAGE=0, read at apt_renderer_create, selects the kernel that loads the record where it is used), else 0. */
+int apt_renderer_record_staged(const apt_renderer*, int32_t* staged);
 
 /* Shader clock (MHz) with every CU busy: cycle counter against the 100 MHz wall clock over a full-grid FMA chain (~1 ms).
  * bench.py prices the VALU roofline of the trace kernels with it.  (No reference counterpart.) */
