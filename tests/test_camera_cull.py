@@ -12,8 +12,7 @@ import pytest
 from adapt_amd import _lib
 from adapt_amd.scene_pack import make_config
 from conftest import ALL_TAGS
-from test_flat_records import flat_records
-from test_shadow_cull import _fma, sections
+from flat_cases import _fma, flat_records, sections
 
 FLAT_MAX_PRIMS = 96                     # traverse.hpp APT_FLAT_MAX_PRIMS: scenes up to here get flat records, and with them the traced kernel
 BENCH_BAND_WIDTH = 4                    # bench.py BAND_WIDTH

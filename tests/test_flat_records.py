@@ -3,23 +3,10 @@ here in numpy - the same formulas the kernels use (traverse.hpp planar_solve / f
 values - and the hits compared with the oracle's brute-force intersector (the reference's loop, tracer_base.py:168-237) on the same rays.
 What it pins without a device: the rows U, V, T of every record, which triangle pairs were merged (and that concave or folded pairs were
 not), the far-edge functions of convex quads, the per-triangle barycentric maps, the coplanar groups."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from adapt_amd import _lib
-
-
-def flat_records(prims, obj_info):
-    lib = _lib.load()
-    prims = np.ascontiguousarray(prims, np.float32).reshape(-1, 9); obj_info = np.ascontiguousarray(obj_info, np.int32).reshape(-1, 3)
-    counts = np.zeros(7, np.int32); ns, nt = C.c_int32(0), C.c_int32(0)
-    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)); ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    _lib.check(lib.apt_flat_records(fp(prims), prims.shape[0], ip(obj_info), obj_info.shape[0], ip(counts), None, 0, None, 0, C.byref(ns), C.byref(nt)), "apt_flat_records", lib)
-    stream, tab = np.zeros(ns.value, np.float32), np.zeros(nt.value, np.float32)
-    _lib.check(lib.apt_flat_records(fp(prims), prims.shape[0], ip(obj_info), obj_info.shape[0], ip(counts), fp(stream), ns.value, fp(tab), nt.value, C.byref(ns), C.byref(nt)), "apt_flat_records", lib)
-    return counts, stream, tab
+from flat_cases import flat_records
 
 
 def sweep_records(counts, stream, tab, o, d):
@@ -108,9 +95,9 @@ def test_flat_records_reproduce_the_brute_force_hits(tag, expect, flat, oracle_s
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_flat_records_merge_convex_pairs_only(seed):
-    """Random quad soups (tests/test_gpu_fast.py _quad_soup): 6 convex quads + 2 pairs of a five-triangle fan -> 8 convex-quad records,
+    """Random quad soups (tests/flat_cases.py _quad_soup): 6 convex quads + 2 pairs of a five-triangle fan -> 8 convex-quad records,
     3 parallelograms, and every concave, folded or edge-less pair left as triangles; hits against a brute force over the triangles."""
-    from test_gpu_fast import _quad_soup
+    from flat_cases import _quad_soup
     from adapt_amd.scene_pack import pack_scene, make_config
     from oracle import binding as ob
     tup = _quad_soup(seed)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, image_metrics, record_metric
-from test_adaptive_host import rule_error
+from adaptive_cases import rule_error
 from adapt_amd.scene_pack import make_config
 
 pytestmark = pytest.mark.gpu

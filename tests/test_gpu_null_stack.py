@@ -7,6 +7,7 @@ import pytest
 import null_stack_cases as ns
 from conftest import image_metrics, record_metric
 from gpu_ab import assert_same_run, open_renderer, run_of
+from gpu_cases import counters_within
 
 pytestmark = pytest.mark.gpu
 
@@ -83,8 +84,7 @@ def test_front_stack_matches_the_oracle(case, walk):
     record_metric(f"null stack front {case} {walk}", dict(m, n_track=st["n_track"], n_track_oracle=ost["n_track"], n_extend=st["n_extend"], n_extend_oracle=ost["n_extend"]))
     print(f"front stack {case} {walk}: {m}, n_track {st['n_track']} of {ost['n_track']}")
     assert m["frac_within"] >= 0.99 and m["relMSE"] <= 1e-3, (case, walk, m)
-    for k in ("n_shade", "n_shadow", "n_draws"):
-        assert abs(st[k] - ost[k]) <= 5e-4 * ost[k], (case, walk, k, st[k], ost[k])
+    counters_within(st, ost, 5e-4, 0, label=(case, walk))
     assert st["n_samples"] == ost["n_samples"] == ns.FRONT_W * ns.FRONT_H * ns.FRONT_SPP
     assert 0 < st["n_track"] <= ost["n_track"] and st["n_lit"] <= ost["n_lit"] * (1 + 5e-4)
 

@@ -18,7 +18,10 @@ import os
 import numpy as np
 import pytest
 
+import gpu_cases as GC
 from conftest import SCENES, golden, image_metrics, scene_from_golden
+from gpu_cases import counters_within, image_within
+from parity_bounds import EXACT, REFERENCE_RUN
 from adapt_amd.scene_pack import make_config
 
 pytestmark = pytest.mark.gpu
@@ -43,17 +46,9 @@ def close(a, b, rel=3e-6, abs_=1e-7):
 
 @pytest.fixture
 def renderer(parsed):
-    """factory; every renderer a test makes is closed when that test ends (a renderer holds several GiB of queues per render lane)"""
-    from adapt_amd.renderer import Renderer
-    made = []
-
-    def make(tag, **kw):
-        r = Renderer(*parsed(tag), **kw)
-        made.append(r)
-        return r
-    yield make
-    for r in made:
-        r.close()
+    """tests/gpu_cases.py renderer_factory: every renderer a test makes is closed when that test ends"""
+    with GC.renderer_factory(parsed) as make:
+        yield make
 
 
 def test_native_library_is_the_one_in_tree():
@@ -181,11 +176,8 @@ def test_every_traversal_mode_gives_the_same_hits_and_image(mode, parsed, oracle
         r.render(n_spp=8)
         rc = make_config(parsed(tag)[3], width=64, height=48)
         ref, _, ost = sc.render(rc, 8)
-        m = image_metrics(r.color.to_numpy() / 8, ref / 8)
-        assert m["frac_within"] >= 0.995 and m["relMSE"] <= 1e-4, m
-        st = r.stats()
-        for k in ("n_shade", "n_shadow", "n_draws"):
-            assert abs(st[k] - ost[k]) <= 2e-4 * ost[k], (k, st[k], ost[k])
+        image_within(r.color.to_numpy(), ref, 8, EXACT.within, EXACT.rel, label=mode)
+        counters_within(r.stats(), ost, EXACT.counters, 0, label=mode)
     finally:
         r.close()
 
@@ -224,54 +216,24 @@ IMAGE_CASES = [
 
 @pytest.mark.parametrize("tag,w,h,spp,ov", IMAGE_CASES)
 def test_image_matches_oracle_same_stream(tag, w, h, spp, ov, renderer, parsed, oracle_scene):
-    r = renderer(tag, width=w, height=h, **ov)
-    r.render(n_spp=spp)
-    acc = r.color.to_numpy()
-    st = r.stats()
-    rc = make_config(parsed(tag)[3], width=w, height=h, **ov)
-    ref, cnt, ost = oracle_scene(tag).render(rc, spp)
-    m = image_metrics(acc / spp, ref / spp)
-    assert m["frac_within"] >= 0.995 and m["relMSE"] <= 1e-4, m
-    # path structure: the same samples were shaded, the same shadow rays cast, (almost) the same randoms drawn
-    assert st["n_samples"] == ost["n_samples"] == w * h * spp
-    for k in ("n_shade", "n_shadow", "n_draws"):
-        assert abs(st[k] - ost[k]) <= 2e-4 * ost[k], (k, st[k], ost[k])
-    assert st["n_lit"] <= ost["n_lit"] and st["n_shadow_traced"] <= st["n_shadow"]
-    assert r.cnt[None] == spp and np.array_equal(r.pixels.to_numpy(), acc / np.float32(spp))
+    """tests/gpu_cases.py image_vs_oracle_same_stream on the exact build: SURVEY 8(d) verbatim, and the exact path structure"""
+    info = GC.image_vs_oracle_same_stream(renderer, parsed, oracle_scene, tag, w, h, spp, ov, *EXACT, exact_structure=True)
+    assert info["arithmetic"] == "exact"
 
 
 @pytest.mark.parametrize("tag", ["cbox", "balls_mono", "glass_box", "features_a", "features_b", "features_c", "textured", "microfacet"])
 def test_image_matches_reference_run(tag, renderer):
-    """Directly against the fixture recorded from the reference's own kernel (same Philox stream)."""
-    g = golden(f"scene_{SCENES[tag][2]}.npz")
-    w, h, spp = int(g["width"]), int(g["height"]), int(g["spp"])
-    r = renderer(tag, width=w, height=h, max_bounce=int(g["max_bounce"]))
-    r.render(n_spp=1)
-    first = r.color.to_numpy()
-    m1 = image_metrics(first, g["first_sample"])
-    r.render(n_spp=spp - 1)
-    m = image_metrics(r.pixels.to_numpy(), g["pixels"])
-    assert m1["frac_within"] >= 0.99 and m["frac_within"] >= 0.99 and m["relMSE"] <= 2e-4, (m1, m)
-    assert abs(r.stats()["n_draws"] - int(g["draws"].sum())) <= 2e-3 * int(g["draws"].sum())
+    """Directly against the fixture recorded from the reference's own kernel (same Philox stream), the first sample alone too."""
+    assert GC.image_vs_reference_run(renderer, tag, *REFERENCE_RUN, first_sample=True)["arithmetic"] == "exact"
 
 
 @pytest.mark.parametrize("tag", ["cbox", "balls_mono"])
 def test_statistical_cross_check_other_seed(tag, renderer, parsed, oracle_scene):
     """the HIP estimator is the same estimator, not merely the same stream -- against a CPU render with ANOTHER seed its
     relMSE stays within 1.5x of the relMSE between two CPU renders with different seeds."""
-    w, h, spp = 48, 48, 64
-    def rel(a, b):
-        return float(np.mean((a - b) ** 2 / (b ** 2 + 1e-2)))
-    cpu = {}
-    for seed in (0, 1, 2):
-        rc = make_config(parsed(tag)[3], width=w, height=h, seed=seed)
-        cpu[seed] = oracle_scene(tag).render(rc, spp)[0].astype(np.float64) / spp
-    r = renderer(tag, width=w, height=h, seed=0)
-    r.render(n_spp=spp)
-    hip = r.pixels.to_numpy().astype(np.float64)
-    noise = rel(cpu[1], cpu[2])
-    assert noise > 0 and rel(hip, cpu[1]) <= 1.5 * noise and rel(hip, cpu[2]) <= 1.5 * noise, (rel(hip, cpu[1]), rel(hip, cpu[2]), noise)
-    assert rel(hip, cpu[0]) <= 1e-4 < noise              # and on the SAME seed it is the same image, far below the noise floor
+    hip, cpu, info = GC.other_seed_images(renderer, parsed, oracle_scene, tag)
+    GC.other_seed_criterion_exact(tag, hip, cpu)
+    assert info["arithmetic"] == "exact"
 
 
 def test_cbox_is_bit_reproducible_and_batch_invariant(renderer):
@@ -383,26 +345,9 @@ FULL_SIZE = os.environ.get("APT_FULL_SIZE_PARITY") == "1"
 def test_full_size_parity_c2_c3(tag, spp, renderer, parsed, oracle_scene, capsys):
     """BASELINE configs[1] and [2] at their FULL size - 512x512, 1024 samples per pixel, 8 / 16 bounces - HIP against the oracle on the
     same Philox stream, every pixel: the per-pixel tolerance of the small cases holds at 268 M samples, and the path statistics agree."""
-    r = renderer(tag)
-    assert (r.w, r.h) == (512, 512) and r.max_bounce == (8 if tag == "cbox" else 16)
-    r.render(n_spp=spp)
-    acc = r.color.to_numpy()
-    st = r.stats()
-    rc = make_config(parsed(tag)[3])
-    ref, cnt, ost = oracle_scene(tag).render(rc, spp, threads=0)
-    fin = np.isfinite(acc).all(axis=2) & np.isfinite(ref).all(axis=2)
-    assert np.array_equal(np.isfinite(acc), np.isfinite(ref))                     # the one inf pixel of C2 (vanilla_renderer.py:119 zeroes NaN only) coincides
-    a, b = np.where(fin[..., None], acc, 0) / spp, np.where(fin[..., None], ref, 0) / spp
-    m = image_metrics(a, b)
-    l2 = np.sqrt(((a - b) ** 2).sum(axis=2))
-    with capsys.disabled():
-        print(f"\n[full size] {tag}: 512x512x{spp} spp  relMSE {m['relMSE']:.3e}  max|diff| {m['max_abs']:.3e}  pixels within 1e-3(1+x) {100 * m['frac_within']:.4f} %  "
-              f"per-pixel L2 mean {l2.mean():.3e} max {l2.max():.3e}  non-finite pixels {int((~fin).sum())}  "
-              f"n_shade {st['n_shade']} / {ost['n_shade']}  n_shadow {st['n_shadow']} / {ost['n_shadow']}  n_draws {st['n_draws']} / {ost['n_draws']}")
-    assert m["frac_within"] >= 0.9999 and m["relMSE"] <= 1e-7, m
-    assert st["n_samples"] == ost["n_samples"] == 512 * 512 * spp
-    for k in ("n_shade", "n_shadow", "n_draws"):
-        assert abs(st[k] - ost[k]) <= 1e-5 * ost[k], (k, st[k], ost[k])
+    # "identical": the one inf pixel of C2 (vanilla_renderer.py:119 zeroes NaN only) coincides
+    info = GC.full_size_parity(renderer, parsed, oracle_scene, capsys, tag, spp, 0.9999, 1e-7, 1e-5, non_finite="identical", print_l2=True)
+    assert info["arithmetic"] == "exact"
 
 
 # ---------------------------------------------------------------- large scenes: BVH traversal path
@@ -411,21 +356,9 @@ def test_full_frame_c2_c3_against_the_oracle_statistics(tag, scene, renderer):
     """BASELINE configs[1] / [2] at their FULL film size (512 x 512, all bounces; 64 of the 1024 spp) against the oracle's render of the
     same samples (tests/golden/fullsize_*.npz, generated by tests/golden/gen/gen_fullsize_stats.py): path statistics, the 8 x 8 grid of
     tile means, the image at 1/8 resolution.  Un-gated twin of test_full_size_parity_c2_c3, which compares every pixel at 1024 spp."""
-    g = golden(f"fullsize_{tag}.npz")
-    w, h, spp = int(g["width"]), int(g["height"]), int(g["spp"])
-    r = renderer(scene, width=w, height=h, max_bounce=int(g["max_bounce"]))
-    r.render(n_spp=spp)
-    st = r.stats()
-    assert st["n_samples"] == int(g["n_samples"]) == w * h * spp
-    for k in ("n_shade", "n_shadow", "n_draws"):
-        assert abs(st[k] - int(g[k])) <= 2e-6 * int(g[k]), (k, st[k], int(g[k]))          # an ulp in a transcendental can flip a branch: 81 of 1.2e9 vertices at 1024 spp
-    img = r.pixels.to_numpy().astype(np.float64)
-    img[~np.isfinite(img).all(axis=2)] = 0.0
-    tiles = img.reshape(w // 64, 64, h // 64, 64, 3).mean(axis=(1, 3))
-    small = img.reshape(w // 8, 8, h // 8, 8, 3).mean(axis=(1, 3))
-    assert np.abs(tiles - g["tiles"]).max() <= 2e-5 * g["tiles"].mean(), float(np.abs(tiles - g["tiles"]).max() / g["tiles"].mean())
-    m = image_metrics(small, g["small"].astype(np.float64))
-    assert m["relMSE"] <= 1e-9 and m["frac_within"] >= 0.9999, m
+    # counters 2e-6: an ulp in a transcendental can flip a branch: 81 of 1.2e9 vertices at 1024 spp
+    info = GC.full_frame_vs_oracle_statistics(renderer, tag, scene, counters=2e-6, tiles=2e-5, within=0.9999, rel=1e-9)
+    assert info["arithmetic"] == "exact"
 
 
 @pytest.fixture(scope="module")
@@ -612,21 +545,7 @@ def test_full_size_properties_c3(renderer):
 
 def test_full_size_c3_crop_matches_oracle(parsed, oracle_scene):
     """C3 at full film size, a 128 x 96 window x 16 spp, all 16 bounces and S = 4: HIP (wave sweep) vs the oracle, same stream."""
-    from adapt_amd.renderer import Renderer
-    em, arr, objs, cfg = parsed("balls_mono")
-    cfg = dict(cfg); cfg["film"] = {"width": 512, "height": 512, "crop_x": 250, "crop_y": 200, "crop_rx": 64, "crop_ry": 48}
-    r = Renderer(em, arr, objs, cfg)
-    r.render(n_spp=16)
-    rc = make_config(cfg)
-    win = (slice(rc.start_x, rc.end_x), slice(rc.start_y, rc.end_y))
-    ref, cnt, ost = oracle_scene("balls_mono").render(rc, 16)
-    m = image_metrics(r.pixels.to_numpy()[win], (ref / np.float32(cnt))[win])
-    st = r.stats()
-    assert st["n_samples"] == ost["n_samples"] == 16 * 128 * 96
-    assert m["frac_within"] >= 0.995 and m["relMSE"] <= 1e-4, m
-    for k in ("n_shade", "n_shadow", "n_draws"):
-        assert abs(st[k] - ost[k]) <= 5e-4 * ost[k], (k, st[k], ost[k])
-    r.close()
+    assert GC.c3_crop_vs_oracle(parsed, oracle_scene, spp=16, within=0.995, rel=1e-4, counters=5e-4)["arithmetic"] == "exact"
 
 
 @pytest.mark.parametrize("tag", ["cbox", "bunnies1", "bunnies3"])
@@ -635,9 +554,8 @@ def test_hip_vs_the_reference_intersectors_on_recorded_rays(tag):
     HIP returns the brute-force answer on every ray: equal to both reference intersectors where those agree, and on the rays of
     the 95 050-triangle scene where the reference's BVH walk loses a hit (DESIGN "the reference's BVH path") HIP has the nearer hit
     its brute force finds."""
-    from test_oracle_golden import bvhref_scene
     from adapt_amd.renderer import Renderer
-    tup, fs, g = bvhref_scene(tag)
+    tup, fs, g = GC.bvhref_scene(tag)
     r = Renderer(*tup, width=64, height=64)
     try:
         O, D, TM = g["ray_o"], g["ray_d"], g["ray_tmax"]
@@ -671,22 +589,12 @@ def test_reference_bundled_scene_hip_vs_reference_run(tag):
     from adapt_amd.scene_pack import make_config, pack_scene
     from oracle import binding as ob
     tup, g = scene_from_golden(tag)
-    w, h, spp = int(g["width"]), int(g["height"]), int(g["spp"])
+    w, h = int(g["width"]), int(g["height"])
     r = Renderer(*tup, width=w, height=h)
     try:
-        r.render(n_spp=spp)
-        acc = r.color.to_numpy()
-        m = image_metrics(acc / spp, g["accum"] / spp)
-        assert m["frac_within"] >= 0.99 and m["relMSE"] <= 1e-3, (tag, m)        # 768 pixels: one flipped branch is 0.13 %
-        assert abs(r.stats()["n_draws"] - int(g["draws"].sum())) <= 2e-3 * int(g["draws"].sum())
-        r.clear(); r.render(n_spp=24)
         rc = make_config(tup[3], width=w, height=h)
-        ref, _, ost = ob.OracleScene(pack_scene(*tup), rc.cam_t).render(rc, 24)
-        m = image_metrics(r.color.to_numpy() / 24, ref / 24)
-        assert m["frac_within"] >= 0.99 and m["relMSE"] <= 1e-3, (tag, m)
-        st = r.stats()
-        for k in ("n_shade", "n_shadow", "n_draws"):
-            assert abs(st[k] - ost[k]) <= 5e-4 * ost[k], (tag, k, st[k], ost[k])
+        # 0.99: 768 pixels, one flipped branch is 0.13 %
+        GC.fixture_then_oracle(r, g, ob.OracleScene(pack_scene(*tup), rc.cam_t), rc, 24, tag, within=0.99, rel=1e-3, draws_tol=2e-3, stat_tol=5e-4)
     finally:
         r.close()
 
@@ -740,11 +648,8 @@ def test_volumetric_every_traversal_mode(mode, monkeypatch):
         r.render(n_spp=spp)
         rc = make_config(tup[3], width=w, height=h, volumetric=True)
         ref, _, ost = ob.OracleScene(pack_scene(*tup), rc.cam_t).render(rc, spp)
-        m = image_metrics(r.color.to_numpy() / spp, ref / spp)
-        assert m["frac_within"] >= 0.99 and m["relMSE"] <= 1e-3, (mode, m)
-        st = r.stats()
-        for k in ("n_shade", "n_shadow", "n_draws"):
-            assert abs(st[k] - ost[k]) <= 1e-3 * ost[k], (mode, k, st[k], ost[k])
+        image_within(r.color.to_numpy(), ref, spp, 0.99, 1e-3, label=mode)
+        counters_within(r.stats(), ost, 1e-3, 0, label=mode)
     finally:
         r.close()
 
@@ -822,11 +727,8 @@ def test_volumetric_tracer_on_scenes_without_media(tag, renderer, parsed, oracle
         r.render(n_spp=spp)
         rc = make_config(tup[3], width=w, height=h, volumetric=True)
         ref, _, ost = oracle_scene(tag).render(rc, spp)
-        m = image_metrics(r.color.to_numpy() / spp, ref / spp)
-        assert m["frac_within"] >= 0.99 and m["relMSE"] <= 1e-3, (tag, m)
-        st = r.stats()
-        for k in ("n_shade", "n_shadow", "n_draws"):
-            assert abs(st[k] - ost[k]) <= 1e-3 * ost[k], (tag, k, st[k], ost[k])
+        image_within(r.color.to_numpy(), ref, spp, 0.99, 1e-3, label=tag)
+        counters_within(r.stats(), ost, 1e-3, 0, label=tag)
     finally:
         r.close()
 
@@ -1105,38 +1007,17 @@ def test_tree_builders_on_degenerate_inputs(builder, monkeypatch):
 
 
 # ---------------------------------------------------------------- what the driver launches on the 8-GPU node: bench.py under torch.distributed.run
-def _run_bench(n, extra, tmp_path, tag):
-    import json
-    import os
-    import socket
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    img = str(tmp_path / f"{tag}.npy")
-    common = ["bench.py", "--gpus", str(n), "--config", "c1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-exclusive-pass", "--dump-image", img] + extra
-    if n > 1:
-        sock = socket.socket(); sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]; sock.close()
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(port)] + common + ["--single-device", "--backend", "gloo"]
-    else:
-        cmd = [sys.executable] + common
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]
-    return json.loads(line), np.load(img)
-
-
 def test_two_and_three_rank_bench_on_one_gpu_equal_the_single_rank_image(tmp_path):
     """bench.py exactly as the driver starts it for N > 1 (torch.distributed.run, one process per rank), except that every rank renders
     on cuda:0 and the tiles travel over gloo: real `Renderer(rank, world_size)` instances in separate processes, the all_gather, the
     tile assembly.  Weak scaling (N x the samples) and strong scaling (same film and samples) both reproduce the single-process
     image BIT FOR BIT, because the Philox key is the global pixel; the JSON line carries the contract's fields and per-rank timings."""
-    one, img1 = _run_bench(1, ["--spp", "6"], tmp_path, "n1")
+    one, img1 = GC.run_bench(1, ["--spp", "6"], tmp_path, "n1")
     assert one["n_gpus"] == 1 and one["scaling"] == "weak" and one["config"]["spp_per_step"] == 6 and img1.shape == (256, 256, 3)
-    weak, img2 = _run_bench(2, ["--spp", "3"], tmp_path, "n2w")                        # 2 ranks x 3 spp = 6 spp per step
+    weak, img2 = GC.run_bench(2, ["--spp", "3"], tmp_path, "n2w")                        # 2 ranks x 3 spp = 6 spp per step
     assert weak["n_gpus"] == 2 and weak["scaling"] == "weak" and weak["config"]["spp_per_step"] == 6
     assert np.array_equal(img2, img1)
-    strong, img3 = _run_bench(3, ["--spp", "6", "--scaling", "strong"], tmp_path, "n3s")
+    strong, img3 = GC.run_bench(3, ["--spp", "6", "--scaling", "strong"], tmp_path, "n3s")
     assert strong["n_gpus"] == 3 and strong["scaling"] == "strong" and strong["config"]["spp_per_step"] == 6
     assert np.array_equal(img3, img1)
     for d in (weak, strong):

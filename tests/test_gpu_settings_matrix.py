@@ -6,8 +6,8 @@ settings from them.  Here each setting is flipped alone (and in a few pairs) on 
   (a) the oracle on the same Philox stream, exact build, 64 x 48 x 20 spp (twenty passes sample 16, where the stratified cell index wraps),
       SURVEY 8(d) as tests/test_gpu_parity.py::test_image_matches_oracle_same_stream holds it; two cases per scene also on a 50 x 30 film;
   (b) the reference's own kernel run with the same overrides (tests/golden/settings_matrix.npz), exact build, without the oracle in between;
-  (c) the oracle on the same stream, product build, at the film and the bound of the scene's row in test_gpu_fast.IMAGE_CASES (media_a: the
-      bounds of the volumetric product test), counters at that module's tolerance;
+  (c) the oracle on the same stream, product build, at the film and the bound of the scene's row in parity_bounds.PRODUCT_IMAGE_CASES
+      (media_a: the bounds of the volumetric product test), counters at the product build's tolerance;
   (d) each other: the alternatives the environment switches select at renderer creation render what the default pipeline renders, by the
       criterion the existing test of that switch uses at the scene's own settings;
   (e) itself: splitting a render call or changing the batch size does not change a bit of the accumulation.
@@ -26,26 +26,25 @@ from collections import namedtuple
 import numpy as np
 import pytest
 
+import parity_bounds as PB                      # the bounds tests/test_gpu_parity.py and tests/test_gpu_fast.py assert: read, not copied
 import settings_cases as SC
-import test_gpu_fast as product_tests          # the product build's rows, counter tolerance and other-seed criterion: imported, not copied
 from conftest import golden, image_metrics, record_metric
 from gpu_ab import COUNTERS, Run, differences, open_renderer
+from gpu_cases import COUNTER_KEYS, OTHER_SEED_FILM, counters_within, other_seed_criterion
 from adapt_amd.scene_pack import make_config, pack_scene
 
 pytestmark = pytest.mark.gpu
 
 BUILDS = ("exact", "fast")
-# SURVEY 8(d), project policy, as tests/test_gpu_parity.py::test_image_matches_oracle_same_stream asserts it on the exact build
-EXACT_WITHIN, EXACT_REL, EXACT_COUNTERS = 0.995, 1e-4, 2e-4
-# tests/test_gpu_parity.py::test_image_matches_reference_run: the exact build against a reference-run fixture
-REFRUN_WITHIN, REFRUN_REL, REFRUN_DRAWS = 0.99, 2e-4, 2e-3
+EXACT_WITHIN, EXACT_REL, EXACT_COUNTERS = PB.EXACT          # SURVEY 8(d), as test_image_matches_oracle_same_stream holds the exact build to it
+REFRUN_WITHIN, REFRUN_REL, REFRUN_DRAWS = PB.REFERENCE_RUN  # test_image_matches_reference_run: the exact build against a reference-run fixture
 FILM_A = (64, 48, 20)
 FILM_ODD = (50, 30, 20)                         # 1500 pixels: no multiple of 64
 ODD_AXES = ("rr_off", "shadow_5")               # the two cases per scene that also run on the odd film (both axes exist on all five scenes)
 FILM_D = (64, 48, 16)                           # test_rays_traced_in_place_render_the_staged_pipeline_s_image's film
 FILM_TRAVERSAL = (64, 48, 8)                    # test_every_traversal_mode_gives_the_same_hits_and_image's film
 
-# Same-stream figures of the product build on the cases that miss their scene's row in test_gpu_fast.IMAGE_CASES although the exact build
+# Same-stream figures of the product build on the cases that miss their scene's row in parity_bounds.PRODUCT_IMAGE_CASES although the exact build
 # holds 8(d) on them in (a), the product build's counters stay inside their tolerance and the other-seed criterion holds (all three asserted,
 # for each of them, by the tests below): case -> measured (frac_within, relMSE) at the row's film, profiles/r06_settings_matrix_metrics.log
 # ("product same-stream <case>").  `_own_bound` makes the bound from them.  What moves them: more light samples per vertex or roulette at every vertex are more
@@ -169,7 +168,7 @@ def _against_oracle(label, case, acc, st, w, h, spp, extra=None):
     """-> (image metrics, largest relative counter deviation, problems with exact sample counts and the shadow stage)"""
     ref, ost = _oracle(case, w, h, spp, extra=extra)
     m = image_metrics(acc / spp, ref / spp)
-    dev = {k: abs(st[k] - ost[k]) / max(1, ost[k]) for k in ("n_shade", "n_shadow", "n_draws")}
+    dev = {k: abs(st[k] - ost[k]) / max(1, ost[k]) for k in COUNTER_KEYS}
     record_metric(label, dict(m, **{f"{k}_rel_dev": v for k, v in dev.items()}, n_draws=st["n_draws"], n_shade=st["n_shade"], n_shadow=st["n_shadow"]))
     bad = []
     if not (st["n_samples"] == ost["n_samples"] == w * h * spp): bad.append(("n_samples", st["n_samples"], ost["n_samples"]))
@@ -225,28 +224,24 @@ def test_exact_build_matches_the_reference_run_under_every_setting(scene):
 
 # ---------------------------------------------------------------- (c) product build vs the oracle, same stream
 def _product_film_and_row(scene):
-    """film, (min frac_within, max relMSE) and the counters' check: the scene's 96 x 96 x 64 row of test_gpu_fast.IMAGE_CASES; media_a has
-    none: the oracle leg of test_volumetric_product_build_vs_reference_run_and_oracle (its fixture's film, 16 spp)"""
+    """film, (min frac_within, max relMSE) and the counters' check: the scene's 96 x 96 x 64 row of parity_bounds.PRODUCT_IMAGE_CASES;
+    media_a has none: the oracle leg of test_volumetric_product_build_vs_reference_run_and_oracle (its fixture's film, 16 spp)"""
     if SC.SCENES[scene][3]:
-        b = product_tests.VPT_PRODUCT_BOUNDS
+        b = PB.VPT_PRODUCT_BOUNDS
         g = golden(f"vptscene_{scene}.npz")
-
-        def counters(st, ost):
-            for k in ("n_shade", "n_shadow", "n_draws"):
-                assert abs(st[k] - ost[k]) <= b["stat_tol"] * ost[k], (k, st[k], ost[k])
-        return (int(g["width"]), int(g["height"]), 16), (b["within"], b["rel"]), counters
-    rows = [r for r in product_tests.IMAGE_CASES if r[0] == scene and r[4] == {}]
+        return (int(g["width"]), int(g["height"]), 16), (b["within"], b["rel"]), lambda st, ost: counters_within(st, ost, b["stat_tol"], 0)
+    rows = [r for r in PB.PRODUCT_IMAGE_CASES if r[0] == scene and r[4] == {}]
     assert len(rows) == 1 and rows[0][1:4] == (96, 96, 64), rows
-    return rows[0][1:4], rows[0][5:7], product_tests.counters_within
+    return rows[0][1:4], rows[0][5:7], counters_within
 
 
 def _other_seed(case, env=None):
     """test_gpu_fast.test_statistical_cross_check_other_seed's criterion, film and spp on this case"""
-    w, h, spp = product_tests.OTHER_SEED_FILM
+    w, h, spp = OTHER_SEED_FILM
     cpu = {seed: _oracle(case, w, h, spp, seed=seed)[0].astype(np.float64) / spp for seed in (0, 1, 2)}
     acc, _, _ = _render(case, "fast", w, h, spp, env=env, seed=0)
-    frac = product_tests._SAME_SEED_FRACTION_OF_NOISE.get(case.scene)          # (media_a has no entry: 8(d)'s 1e-4 outright)
-    product_tests.other_seed_criterion(case.name, acc.astype(np.float64) / spp, cpu, frac)
+    frac = PB.SAME_SEED_FRACTION_OF_NOISE.get(case.scene)          # (media_a has no entry: 8(d)'s 1e-4 outright)
+    other_seed_criterion(case.name, acc.astype(np.float64) / spp, cpu, frac)
 
 
 N_PARTS = 4          # the twenty cases of a full-matrix scene in four test functions of a few seconds each (96 x 96 x 64 on the oracle)

@@ -29,7 +29,7 @@ import pytest
 import f64_models as M
 import texture_cases as TC
 from conftest import GOLDEN, record_metric
-from test_gpu_product_functions import AGG, FAMILIES, _ratio
+from product_function_cases import AGG, FAMILIES, _ratio
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32

@@ -4,12 +4,12 @@ determinism, checkpoints and the CLI export."""
 import os
 import subprocess
 import sys
-import xml.etree.ElementTree as xet
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, image_metrics, record_metric
+from transient_cases import _direct_light_scene, _predicted_times
 from adapt_amd.scene_pack import make_config
 
 pytestmark = pytest.mark.gpu
@@ -98,57 +98,6 @@ def test_exact_bins_match_oracle_same_stream(tag, renderer, parsed, oracle_scene
 
 
 # ---------------------------------------------------------------- 3./4. analytic arrival times of direct light
-def _point_light(pos, emission="10.0, 10.0, 10.0"):
-    from adapt_amd.emitters import SOURCE_MAP
-    return SOURCE_MAP["point"](xet.fromstring(f'<emitter type="point" id="p"><rgb name="emission" value="{emission}"/><rgb name="scaler" value="1.0"/>'
-                                              f'<point name="center" x="{pos[0]}" y="{pos[1]}" z="{pos[2]}"/></emitter>'))
-
-
-def _quad(z, outward_z, lo=-30.0, hi=35.0):
-    """two triangles spanning [lo, hi]^2 at depth z, normal (0, 0, outward_z)"""
-    a, b, c, d = (lo, lo, z), (hi, lo, z), (hi, hi, z), (lo, hi, z)
-    tris = np.float32([[a, b, c], [a, c, d]])
-    n = np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0])
-    flip = np.sign(n[:, 2]) != np.sign(outward_z)
-    tris[flip] = tris[flip][:, [0, 2, 1]]
-    return tris
-
-
-def _direct_light_scene(w, h, slab):
-    """a diffuse plane at z = 8 facing the camera (z = -8), a point light at z = 6 in front of it; with `slab` a glass slab of ior 1.5
-    fills 0 <= z <= 5 between them.  Anti-aliasing off: every pixel's ray goes through the pixel's centre."""
-    from adapt_amd.synth import _Builder, _brdf, _glass, _sensor
-    b = _Builder()
-    b.mesh(_quad(8.0, -1.0), _brdf("lambertian", "#BDBDBD"))
-    if slab:
-        b.mesh(np.concatenate([_quad(0.0, -1.0), _quad(5.0, 1.0)]), _glass(ior=1.5))
-    scene = b.finish([_point_light((2.78, 2.73, 6.0))], _sensor(w, h, 3 if slab else 1, 1))
-    scene[3]["anti_alias"] = False
-    return scene
-
-
-def _predicted_times(rc, light, slab):
-    """float64 optical length camera -> plane -> light per pixel [x, y]; with the slab also the same path with the slab's ior taken as 1"""
-    W, H = rc.width, rc.height
-    i, j = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64), indexing="ij")
-    cd = np.stack([(rc.half_w + 0.5 - i) * rc.inv_focal, (j - rc.half_h - 0.5) * rc.inv_focal, np.ones_like(i)], -1)
-    d = cd @ np.float64(rc.cam_r).T
-    d /= np.linalg.norm(d, axis=-1, keepdims=True)
-    cam, light = np.float64(rc.cam_t), np.float64(light)
-    if not slab:
-        x = cam + d * ((8.0 - cam[2]) / d[..., 2:3])
-        t = np.linalg.norm(x - cam, axis=-1) + np.linalg.norm(x - light, axis=-1)
-        return t, t
-    p1 = cam + d * ((0.0 - cam[2]) / d[..., 2:3])
-    tan = d[..., :2] / 1.5                                   # Snell at the faces z = const: tangential part scaled by 1 / ior
-    d2 = np.concatenate([tan, np.sqrt(1.0 - (tan ** 2).sum(-1, keepdims=True))], -1)
-    p2 = p1 + d2 * (5.0 / d2[..., 2:3])
-    p3 = p2 + d * ((8.0 - 5.0) / d[..., 2:3])                # leaves parallel to the camera ray
-    l1, l2, l3 = np.linalg.norm(p1 - cam, axis=-1), np.linalg.norm(p2 - p1, axis=-1), np.linalg.norm(p3 - p2, axis=-1)
-    rest = l1 + l3 + np.linalg.norm(p3 - light, axis=-1)
-    return rest + 1.5 * l2, rest + l2
-
-
 def _check_arrivals(cube, t_pred, lo, step, name):
     """every pixel's energy in the bin of its predicted time; the neighbour only within 1e-4 * interval of an edge"""
     n = cube.shape[0]

@@ -195,7 +195,7 @@ def _light_wall(w, h):
     hit at the camera ray's length, whose float32 time the oracle gives bit for bit"""
     from adapt_amd.emitters import SOURCE_MAP
     from adapt_amd.synth import _Builder, _brdf, _sensor
-    from test_gpu_transient import _quad
+    from transient_cases import _quad
     b = _Builder()
     b.mesh(_quad(8.0, -1.0), _brdf("lambertian", "#BDBDBD"), emitter=0)
     area = SOURCE_MAP["area"](xet.fromstring('<emitter type="area" id="a"><rgb name="emission" value="5.0, 5.0, 5.0"/></emitter>'))
@@ -306,7 +306,7 @@ def _edge_times(rng, lo, step, n, count):
 @pytest.mark.parametrize("build", BUILDS)
 def test_bin_probe_matches_the_rule(build):
     rng = np.random.default_rng(5)
-    from test_oracle_transient import _rounding_up_window
+    from transient_cases import _rounding_up_window
     lo_r, step_r, n_r, t_r = _rounding_up_window()
     windows = [(np.float32(2.5), np.float32(0.25), 8), (np.float32(-7.1), np.float32(0.013), 400), (np.float32(10.3), np.float32(0.7), 100),
                (np.float32(11.0), np.float32(0.05), 200), (lo_r, step_r, n_r)]

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import SCENES, golden
+from gpu_cases import bvhref_scene
 from adapt_amd.scene_pack import make_config
 from oracle import binding as ob
 
@@ -243,21 +244,6 @@ def test_grid_volume_matches_reference_run(name):
 # ---- the reference's BVH path (accelerator = bvh), tests/golden/bvhref_*.npz: the reference's OWN traversal code
 # (PathTracer.bvh_process -> convert_bvh_info -> ray_intersect_bvh / does_intersect_bvh, tracer/path_tracer.py:143-179,338-422,
 # tracer/ti_bvh.py) run on a reference-layout tree handed over by the `bvh_cpp` stand-in of the generator
-def bvhref_scene(tag):
-    """(scene 4-tuple, fixture): cbox carries its arrays; the bunny scenes are rebuilt by adapt_amd.synth and checked by hash"""
-    import hashlib
-    from adapt_amd.scene_pack import pack_scene
-    g = golden(f"bvhref_{tag}.npz")
-    if "prims" in g:
-        tup, _ = scene_from_golden(tag, prefix="bvhref")
-    else:
-        from adapt_amd.synth import three_bunnies
-        tup = three_bunnies({"bunnies1": 1, "bunnies3": 3}[tag])
-    fs = pack_scene(*tup)
-    assert hashlib.sha256(np.ascontiguousarray(fs.prims).tobytes()).hexdigest() == str(g["prims_sha256"]), "the fixture was recorded on other geometry"
-    return tup, fs, g
-
-
 @pytest.mark.parametrize("tag", ["cbox", "bunnies1", "bunnies3"])
 def test_reference_bvh_traversal_bit_exact(tag):
     """Oracle's restatement of the reference's BVH walk == the reference's own walk on the same tree: closest hits (object,

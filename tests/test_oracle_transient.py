@@ -93,10 +93,10 @@ def test_float32_time_tracks_the_float64_path_length(tag, logs):
 
 @pytest.mark.parametrize("slab", [False, True])
 def test_direct_light_times_match_the_analytic_path(slab):
-    """_direct_light_scene (test_gpu_transient.py): t64 of the light sample on the diffuse plane is the analytic optical length, the
+    """_direct_light_scene (tests/transient_cases.py): t64 of the light sample on the diffuse plane is the analytic optical length, the
     slab's in-glass segment weighted by its ior 1.5.  The analytic path uses exact ray directions, the oracle float32 ones: the two
     differ at float32 rounding of the camera ray (measured 2.1e-7 relative; the slab's ior moves the time by 0.5 x 5 / 23 ~ 1e-1)."""
-    from test_gpu_transient import _direct_light_scene, _predicted_times
+    from transient_cases import _direct_light_scene, _predicted_times
     w = h = 32
     scene = _direct_light_scene(w, h, slab)
     rc = make_config(scene[3], width=w, height=h)
@@ -134,18 +134,8 @@ def test_binning_edges_on_hand_picked_times():
     assert ob.transient_max_time(lo, step, n) != np.float32(lo + np.float32(step * np.float32(n)))
 
 
-def _rounding_up_window():
-    """a (min_time, interval, n_bins, t) with min_time < t < max_time whose quotient float32(t - min_time) / interval rounds to n_bins"""
-    rng = np.random.default_rng(7)
-    steps = rng.uniform(0.01, 3.0, 4096).astype(np.float32)
-    lo, n = _q(-7.1), 5
-    top = np.float32(float(lo) + steps.astype(np.float64) * n)
-    t = np.nextafter(top, np.float32(-np.inf))
-    k = int(np.flatnonzero((t - lo) / steps >= np.float32(n))[0])
-    return lo, steps[k], n, t[k]
-
-
 def test_a_quotient_that_rounds_up_stays_in_the_last_bin():
+    from transient_cases import _rounding_up_window
     lo, step, n, t = _rounding_up_window()
     assert lo < t < ob.transient_max_time(lo, step, n) and (t - lo) / step == np.float32(n)
     assert ob.transient_bin_index([t], lo, step, n).tolist() == [n - 1]

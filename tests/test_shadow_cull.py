@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from adapt_amd import _lib
-from test_flat_records import flat_records
+from flat_cases import _fma, flat_records, sections
 
 C2_NAMES = ["floor", "ceiling", "back", "green", "red", "smallbox", "largebox"]
 
@@ -30,16 +30,6 @@ def record_prims(prims, obj_info):
     counts, stream, tab = flat_records(prims, obj_info)
     ids = tab.reshape(-1, 28)[:, 8:10].copy().view(np.int32)
     return counts, stream, ids
-
-
-def sections(counts):
-    """per record: section (0 parallelogram, 1 convex quad, 2 triangle, 3 sphere) and its offset in the stream"""
-    n = [counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6]]
-    out, at = [], 0
-    for sec, w in enumerate((12, 18, 12, 4)):
-        for _ in range(n[sec]):
-            out.append((sec, at)); at += w
-    return out
 
 
 def pair_up(stream, counts, keep):
@@ -121,10 +111,6 @@ def test_refuses_a_plane_with_geometry_on_both_sides(poke):
 
 
 # ---- no left-out record ever blocks: flat_any1's float32 arithmetic in numpy
-
-def _fma(a, b, c):
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
-
 
 def _blocks(rec, sec, o, d, lim):
     """flat_blocks() of flat_any1's test of one record, float32 as the kernel (FMA chains, a reciprocal): -> bool per ray"""
