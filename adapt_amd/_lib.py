@@ -80,6 +80,7 @@ SYMBOLS = {
     "apt_flat_records": (C.c_int, [f32p, C.c_int32, i32p, C.c_int32, i32p, f32p, C.c_int32, f32p, C.c_int32, i32p, i32p]),
     "apt_flat_occluders": (C.c_int, [f32p, C.c_int32, i32p, C.c_int32, i32p, f32p, C.c_int32, C.c_int32, i32p, i32p, C.c_int32, f32p, C.c_int32, i32p, i32p]),
     "apt_camera_strips": (C.c_int, [f32p, C.c_int32, i32p, C.c_int32, C.POINTER(RenderCfg), C.c_int32, C.POINTER(C.c_uint64), C.c_int32, i32p, i32p]),
+    "apt_light_strips": (C.c_int, [f32p, C.c_int32, i32p, C.c_int32, i32p, f32p, C.c_int32, C.POINTER(RenderCfg), C.c_int32, C.POINTER(C.c_uint64), C.c_int32, i32p, i32p, f32p]),
     "apt_bvh_wide_export": (C.c_int, [C.c_void_p, u32p, i32p]),
     "apt_bvh_wide_frame": (C.c_int, [C.c_void_p, f32p, f32p]),
     "apt_bvh_free": (None, [C.c_void_p]),
@@ -123,6 +124,7 @@ SYMBOLS = {
     "apt_transient_bin_probe": (C.c_int, [C.c_int32, C.c_int32, f32p, C.c_float, C.c_float, C.c_int32, i32p]),
     "apt_renderer_info": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_int64), i32p, C.POINTER(C.c_char_p), i32p]),
     "apt_renderer_camera_fused": (C.c_int, [C.c_void_p, i32p]),
+    "apt_renderer_light_strips": (C.c_int, [C.c_void_p, i32p]),
     "apt_renderer_record_staged": (C.c_int, [C.c_void_p, i32p]),
     "apt_measure_sclk_mhz": (C.c_int, [C.c_int32, f32p]),
     "apt_last_error": (C.c_char_p, []),

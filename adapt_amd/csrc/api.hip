@@ -184,6 +184,7 @@ struct apt_scene {
     DevBuf flat_recs, flat_tab, flat_pairs;     // flat sweep (fast build, small scenes): records, the per-record table, the records two by two (traverse.hpp FlatScene)
     DevBuf flat_occ, flat_occ_tab;              // ... per emitter, the records that can block its light samples, two by two, and their table
     std::vector<float> h_prims, h_flat_recs, h_flat_tab; int h_flat_counts[7] = {0, 0, 0, 0, 0, 0, 0};      // ... and what a renderer builds its camera strip lists from (flat_build.cpp camera_strips)
+    std::vector<float> h_emit_pts; std::vector<int32_t> h_emit_off; std::vector<uint8_t> h_occ_keep; bool h_shadow_cull = false;      // ... and the strip masks of the camera vertex's light samples (flat_build.cpp light_strips): emitter points, the occluder lists' records
     bool has_flat = false;
     DevBuf uvs, tex_i, tex_f, atlas[3];      // image textures (empty when the scene has none)
     std::vector<int32_t> tex_type;       // ... per object and map, the texture's type (-255: none; apt_texture_probe refuses a lookup in one that is not there)
@@ -239,6 +240,7 @@ struct apt_renderer {
     int record_stage = 0;         // rays traced in place: 1 = the queue-fed shade kernel stages its record in LDS a row ahead (ShadeVariant::traced_staged; APT_RECORD_STAGE=0 switches it off)
     shade_traced_fn traced_fn = nullptr;      // the queue-fed kernel of a PIPE_TRACED render: shade->traced_staged or shade->traced
     int camera_fuse = 0;          // rays traced in place: 1 = the camera vertex is shaded by the kernel that traces the camera ray (k_shade_traced_cam; steady full-film renders with max_bounce >= 1, APT_CAMERA_FUSE=0 switches it off)
+    int light_strips = 0;         // rays traced in place, camera-fed: 1 = some strip mask of the camera vertex's light samples leaves a pair out (cam_strips' second part, flat_build.cpp light_strips; APT_LIGHT_STRIPS=0 switches them off)
     Counters host_counters{};
     int grid_small = 0, grid_trace = 0, nq = APT_MAX_NQ;
     const ShadeVariant* shade = nullptr;
@@ -587,6 +589,7 @@ static int pack_flat(const apt_scene_desc* d, apt_scene* s, const std::vector<in
     fl.defer_all = getenv("APT_FLAT_DEFER_ALL") ? atoi(getenv("APT_FLAT_DEFER_ALL")) : 0;
     fl.n_quads = fc[0]; fl.n_quads_tie = fc[1]; fl.n_gquads = fc[2]; fl.n_gquads_tie = fc[3]; fl.n_tris = fc[4]; fl.n_tris_tie = fc[5]; fl.n_spheres = fc[6];
     s->h_prims.assign(d->prims, d->prims + 9 * (size_t)N); s->h_flat_recs = fr; s->h_flat_tab = ft; memcpy(s->h_flat_counts, fc, sizeof(fc));
+    s->h_emit_pts = pts; s->h_emit_off = off; s->h_occ_keep = keep; s->h_shadow_cull = cull;
     s->has_flat = true;
     if (timer.on) fprintf(stderr, "[scene timing] flat records: %d + %d parallelograms, %d + %d convex quads, %d + %d triangles (plain + coplanar groups), %d spheres of %d primitives\n", fc[0], fc[1], fc[2], fc[3], fc[4], fc[5], fc[6], N);
     if (timer.on) for (int e = 0; e < s->n_sources; e++) fprintf(stderr, "[scene timing] occluders of emitter %d: %d parallelograms, %d convex quads, %d triangles, %d spheres\n", e, ot[8 * (size_t)e + 1], ot[8 * (size_t)e + 2], ot[8 * (size_t)e + 3], ot[8 * (size_t)e + 4]);
@@ -900,14 +903,34 @@ static int make_camera_strips(apt_renderer* r) {
     const apt_scene* sc = r->scene;
     const bool cull = !(getenv("APT_CAMERA_CULL") && atoi(getenv("APT_CAMERA_CULL")) == 0);
     std::vector<uint64_t> masks;
+    SceneTimer timer;
     if (apt::camera_strips(sc->h_prims.data(), sc->n_prims, sc->h_flat_recs, sc->h_flat_tab, sc->h_flat_counts, cam_film(r->cfg), cull, masks) != 0)
         return fail(APT_E_INVALID, "apt_renderer_create: camera strip lists: bad record or film");
-    hipError_t e = upload(r->cam_strips, masks);
-    if (e != hipSuccess) return fail(APT_E_HIP, std::string("upload camera strip lists: ") + hipGetErrorString(e));
+    timer.tick("camera strip lists");
     // the camera-fed bounce 0 (shade_stage.hpp shade_traced, CAM) wants every slot of the id space to be a live camera ray: an adaptive
     // round's or a crop window's dead slots would sit as idle lanes through a whole shading row - those keep k_generate_trace's compaction
     const bool want = !(getenv("APT_CAMERA_FUSE") && atoi(getenv("APT_CAMERA_FUSE")) == 0);
     r->camera_fuse = (want && !r->adaptive && !r->par.do_crop && r->par.max_bounce >= 1 && r->shade->traced_cam != nullptr) ? 1 : 0;
+    // ... and behind them, in the same buffer, the strip masks of the camera vertex's light samples (flat_build.cpp light_strips; read by the
+    // camera-fed kernel alone: stages.hpp light_strip_mask): row e of (npix + 63) / 64 words for emitter e < APT_LIGHT_STRIP_EMITTERS.
+    // APT_LIGHT_STRIPS=0, APT_SHADOW_CULL=0 (at scene creation): every bit set.
+    r->light_strips = 0;
+    if (r->camera_fuse) {
+        const bool lcull = sc->h_shadow_cull && !(getenv("APT_LIGHT_STRIPS") && atoi(getenv("APT_LIGHT_STRIPS")) == 0);
+        std::vector<uint64_t> lm; std::vector<int32_t> np;
+        if (apt::light_strips(sc->h_prims.data(), sc->n_prims, sc->h_flat_recs, sc->h_flat_tab, sc->h_flat_counts, cam_film(r->cfg), sc->h_emit_pts.data(), sc->h_emit_off.data(),
+                              sc->n_sources, sc->h_occ_keep.data(), lcull, lm, np, nullptr) != 0)
+            return fail(APT_E_INVALID, "apt_renderer_create: light strip masks: bad record or film");
+        const size_t nb = masks.size();
+        size_t set = 0, all = 0;
+        for (size_t k = 0; k < lm.size(); k++) { const int n = np[k / nb]; all += (size_t)std::min(n, 64); set += (size_t)__builtin_popcountll(n >= 64 ? lm[k] : (lm[k] & (((uint64_t)1 << n) - 1))); }
+        r->light_strips = set < all ? 1 : 0;
+        masks.insert(masks.end(), lm.begin(), lm.end());
+        if (timer.on) fprintf(stderr, "[scene timing] light strip masks: %.2f of %.2f pairs per strip and emitter on average\n", lm.empty() ? 0.0 : (double)set / (double)lm.size(), lm.empty() ? 0.0 : (double)all / (double)lm.size());
+        timer.tick("light strip masks");
+    }
+    hipError_t e = upload(r->cam_strips, masks);
+    if (e != hipSuccess) return fail(APT_E_HIP, std::string("upload camera strip lists: ") + hipGetErrorString(e));
     return APT_OK;
 }
 
@@ -926,6 +949,28 @@ APT_EXPORT int apt_camera_strips(const float* prims, int32_t n_prims, const int3
     *n_strips = (int32_t)m.size();
     *n_pairs = (cn[0] + cn[1] + 1) / 2 + (cn[2] + cn[3] + 1) / 2 + (cn[4] + cn[5] + 1) / 2 + (cn[6] + 1) / 2;
     if (masks) { if (masks_cap < (int32_t)m.size()) return fail(APT_E_INVALID, "apt_camera_strips: masks buffer too small"); memcpy(masks, m.data(), m.size() * 8); }
+    return APT_OK;
+}
+
+// ... and the strip masks of the camera vertex's light samples (flat_build.cpp light_strips; tests/test_light_strips.py): masks holds
+// min(n_sources, APT_LIGHT_STRIP_EMITTERS) rows of n_strips words, n_pairs one entry per emitter
+APT_EXPORT int apt_light_strips(const float* prims, int32_t n_prims, const int32_t* obj_info, int32_t n_objects, const int32_t* src_i, const float* src_f, int32_t n_sources,
+                                const apt_render_cfg* cfg, int32_t cull, uint64_t* masks, int32_t masks_cap, int32_t* n_strips, int32_t* n_pairs, float* origin_slack) {
+    if (!prims || !obj_info || !src_i || !src_f || !cfg || n_prims <= 0 || n_objects <= 0 || n_sources <= 0 || !n_strips) return fail(APT_E_INVALID, "apt_light_strips: bad argument");
+    apt_render_cfg c = *cfg;                                                  // defaults as apt_renderer_create
+    if (c.world_size <= 0) { c.world_size = 1; c.rank = 0; }
+    if (c.band_width <= 0) c.band_width = c.width;
+    if (c.width <= 0 || c.height <= 0 || c.rank < 0 || c.rank >= c.world_size || owned_columns(c) <= 0) return fail(APT_E_INVALID, "apt_light_strips: bad film or rank");
+    std::vector<float> st, tb, pts, pr; std::vector<int32_t> off, tab8, np; std::vector<uint8_t> kp; int cn[7];
+    if (apt::build_flat(prims, n_prims, obj_info, n_objects, nullptr, st, tb, cn) != 0) return fail(APT_E_INVALID, "apt_light_strips: obj_info range outside the primitive array");
+    apt::emitter_points(prims, obj_info, n_objects, src_i, src_f, n_sources, pts, off);
+    if (apt::flat_occluders(prims, n_prims, st, tb, cn, pts.data(), off.data(), n_sources, true, pr, tab8, kp) != 0) return fail(APT_E_INVALID, "apt_light_strips: bad record");
+    std::vector<uint64_t> m; double slack = 0.0;
+    if (apt::light_strips(prims, n_prims, st, tb, cn, cam_film(c), pts.data(), off.data(), n_sources, kp.data(), cull != 0, m, np, &slack) != 0) return fail(APT_E_INVALID, "apt_light_strips: bad record or film");
+    *n_strips = (int32_t)((owned_columns(c) * c.height + 63) / 64);
+    if (n_pairs) memcpy(n_pairs, np.data(), np.size() * 4);
+    if (origin_slack) *origin_slack = (float)slack;
+    if (masks) { if (masks_cap < (int32_t)m.size()) return fail(APT_E_INVALID, "apt_light_strips: masks buffer too small"); memcpy(masks, m.data(), m.size() * 8); }
     return APT_OK;
 }
 
@@ -1979,6 +2024,11 @@ APT_EXPORT int apt_measure_sclk_mhz(int32_t device, float* mhz) {
 APT_EXPORT int apt_renderer_camera_fused(const apt_renderer* r, int32_t* out) {
     if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_camera_fused: null argument");
     *out = r->camera_fuse;
+    return APT_OK;
+}
+APT_EXPORT int apt_renderer_light_strips(const apt_renderer* r, int32_t* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_light_strips: null argument");
+    *out = r->light_strips;
     return APT_OK;
 }
 APT_EXPORT int apt_renderer_record_staged(const apt_renderer* r, int32_t* out) {

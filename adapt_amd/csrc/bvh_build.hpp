@@ -94,4 +94,13 @@ int flat_occluders(const float* prims, int n_prims, const std::vector<float>& st
 struct CamFilm { float cam_r[9], cam_t[3], inv_focal, half_w, half_h; int width, height, n_cols, band_width, rank, world; };      // n_cols: the columns this rank owns
 int camera_strips(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7],
                   const CamFilm& cf, bool cull, std::vector<uint64_t>& masks);
+// Strip masks of the camera vertex's light samples: per emitter (the first APT_LIGHT_STRIP_EMITTERS) and block of 64 local
+// pixels, a bit per PAIR of the emitter's occluder list (flat_occluders: keep, in its order and pairing): clear = neither record of the
+// pair can block a light sample taken at a camera hit point of the block.  masks[e * n_blocks + b]; n_pairs: pairs per emitter's list;
+// origin_slack: how far off the clipped outlines a shadow-ray origin may lie under the rule's margin.
+#ifndef APT_LIGHT_STRIP_EMITTERS
+#define APT_LIGHT_STRIP_EMITTERS 16
+#endif
+int light_strips(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7], const CamFilm& cf,
+                 const float* pts, const int32_t* off, int n_emit, const uint8_t* keep, bool cull, std::vector<uint64_t>& masks, std::vector<int32_t>& n_pairs, double* origin_slack);
 }  // namespace apt

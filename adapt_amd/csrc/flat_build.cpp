@@ -405,6 +405,38 @@ int flat_occluders(const float* prims, int n_prims, const std::vector<float>& st
     return 0;
 }
 
+namespace {
+// The pyramid of block b (local pixels 64 b .. 64 b + 63) for camera_strips and light_strips below: the inward unit normals of the four
+// side planes through cam_t and the image-plane rectangle the block's pixels span, widened by `widen` pixels.  false: a singular camera matrix.
+double strip_widen(const CamFilm& cf) { return 64.0 * std::ldexp(1.0, -24) * ((double)cf.width + (double)cf.height + 1.0 / std::fabs((double)cf.inv_focal)); }
+bool strip_pyramid(const CamFilm& cf, int npix, int b, double widen, D3 n[4]) {
+    auto world = [&](double x, double y) -> D3 {
+        const float* R = cf.cam_r;
+        return {R[0] * x + R[1] * y + R[2], R[3] * x + R[4] * y + R[5], R[6] * x + R[7] * y + R[8]};
+    };
+    int i0 = 1 << 30, i1 = -(1 << 30), j0 = 1 << 30, j1 = -(1 << 30);
+    for (int lp = 64 * b; lp < std::min(npix, 64 * b + 64); lp++) {      // local_to_global (stages.hpp)
+        const int lc = lp / cf.height, j = lp % cf.height, i = (lc / cf.band_width * cf.world + cf.rank) * cf.band_width + lc % cf.band_width;
+        i0 = std::min(i0, i); i1 = std::max(i1, i); j0 = std::min(j0, j); j1 = std::max(j1, j);
+    }
+    // image-plane rectangle of the block: x = (half_w + vx - i) inv_focal, y = (j - half_h - vy) inv_focal, vx, vy in [0, 1]
+    const double f = cf.inv_focal;
+    double xa = ((double)cf.half_w - i1 - widen) * f, xb = ((double)cf.half_w + 1.0 - i0 + widen) * f;
+    double ya = ((double)j0 - cf.half_h - 1.0 - widen) * f, yb = ((double)j1 - cf.half_h + widen) * f;
+    if (xa > xb) std::swap(xa, xb);
+    if (ya > yb) std::swap(ya, yb);
+    const D3 c[4] = {world(xa, ya), world(xb, ya), world(xb, yb), world(xa, yb)}, mid = world(0.5 * (xa + xb), 0.5 * (ya + yb));
+    for (int k = 0; k < 4; k++) {
+        D3 m = cross(c[k], c[(k + 1) & 3]);
+        const double len = std::sqrt(dot(m, m));
+        if (!(len > 0.0) || !std::isfinite(len)) return false;
+        if (dot(m, mid) < 0.0) m = {-m.x, -m.y, -m.z};
+        n[k] = {m.x / len, m.y / len, m.z / len};
+    }
+    return true;
+}
+}  // namespace
+
 // Which record PAIRS of FlatScene::pairs a camera ray of a pixel strip can hit (stages.hpp generate_body, traverse.hpp flat_closest1's
 // mask).  A wave of k_generate_trace holds 64 consecutive local pixels; block b = local pixels 64 b .. 64 b + 63.  Every
 // ray of the block leaves cam_t with a direction R (x, y, 1), (x, y) inside the rectangle that the block's pixels span on the image
@@ -494,34 +526,10 @@ int camera_strips(const float* prims, int n_prims, const std::vector<float>& str
             recs[(size_t)r].margin = 16.0 * ((7.0 * u * absdot(T, ext) + 6.0 * u * L) / std::sqrt(dot(T, T)) + ovs);
         }
     }
-    const double widen = 64.0 * u * ((double)cf.width + (double)cf.height + 1.0 / std::fabs((double)cf.inv_focal));
-    auto world = [&](double x, double y) -> D3 {
-        const float* R = cf.cam_r;
-        return {R[0] * x + R[1] * y + R[2], R[3] * x + R[4] * y + R[5], R[6] * x + R[7] * y + R[8]};
-    };
+    const double widen = strip_widen(cf);
     for (int b = 0; b < n_blocks; b++) {
-        int i0 = 1 << 30, i1 = -(1 << 30), j0 = 1 << 30, j1 = -(1 << 30);
-        for (int lp = 64 * b; lp < std::min(npix, 64 * b + 64); lp++) {      // local_to_global (stages.hpp)
-            const int lc = lp / cf.height, j = lp % cf.height, i = (lc / cf.band_width * cf.world + cf.rank) * cf.band_width + lc % cf.band_width;
-            i0 = std::min(i0, i); i1 = std::max(i1, i); j0 = std::min(j0, j); j1 = std::max(j1, j);
-        }
-        // image-plane rectangle of the block: x = (half_w + vx - i) inv_focal, y = (j - half_h - vy) inv_focal, vx, vy in [0, 1]
-        const double f = cf.inv_focal;
-        double xa = ((double)cf.half_w - i1 - widen) * f, xb = ((double)cf.half_w + 1.0 - i0 + widen) * f;
-        double ya = ((double)j0 - cf.half_h - 1.0 - widen) * f, yb = ((double)j1 - cf.half_h + widen) * f;
-        if (xa > xb) std::swap(xa, xb);
-        if (ya > yb) std::swap(ya, yb);
-        const D3 c[4] = {world(xa, ya), world(xb, ya), world(xb, yb), world(xa, yb)}, mid = world(0.5 * (xa + xb), 0.5 * (ya + yb));
         D3 n[4];
-        bool ok = true;
-        for (int k = 0; k < 4; k++) {
-            D3 m = cross(c[k], c[(k + 1) & 3]);
-            const double len = std::sqrt(dot(m, m));
-            if (!(len > 0.0) || !std::isfinite(len)) { ok = false; break; }
-            if (dot(m, mid) < 0.0) m = {-m.x, -m.y, -m.z};
-            n[k] = {m.x / len, m.y / len, m.z / len};
-        }
-        if (!ok) continue;                                       // (a singular camera matrix: the full stream)
+        if (!strip_pyramid(cf, npix, b, widen, n)) continue;     // (a singular camera matrix: the full stream)
         uint64_t m = 0;
         for (const Rec& r : recs) {
             bool out = false;
@@ -533,6 +541,192 @@ int camera_strips(const float* prims, int n_prims, const std::vector<float>& str
             if (!out) m |= (uint64_t)1 << r.pair;
         }
         masks[(size_t)b] = m;
+    }
+    return 0;
+}
+
+// Which PAIRS of an emitter's occluder list (flat_occluders above, in its order and pairing) can block the light sample of a CAMERA
+// vertex of a pixel strip (shade_stage.hpp shade_traced<.., CAM>, traverse.hpp flat_any1's mask).  masks[e * n_blocks + b]
+// bit k is CLEAR when both records of pair k of emitter e's list are separated from every shadow segment block b can produce; the rows of
+// the first min(n_emit, APT_LIGHT_STRIP_EMITTERS) emitters are built.  Every bit of a word stays set when cull is false, the emitter has no
+// points (it sweeps the full stream), its list has more than 64 pairs, there are more than APT_LIGHT_STRIP_EMITTERS emitters, the camera
+// matrix is singular, or the block's pyramid meets a sphere record; a sphere record of the list is never separated.  It does not look at
+// the camera masks.
+//
+// The segments.  A shadow ray of the camera vertex runs from o = fl(d t + cam_t), the hit point of a camera ray on a planar record S
+// (flat_closest1 accepted it: inside S, t > 1e-4), to a light point l.  Patch = the outlines of ALL planar records (each of their
+// triangles), clipped in double (Sutherland-Hodgman) against the four side planes of the block's widened pyramid (strip_pyramid),
+// each plane moved OUT by E (below).  A record Q is separated when for one unit direction m
+//        max over Q's vertices of m . q  <  min over the patch's vertices and the emitter's points of m . x  -  margin,
+// i.e. a plane with normal m has patch and light points on its inner side and Q outside it by more than the margin.  Directions tried:
+// Q's own plane (the stored T row, both signs), the six axis directions and - for an emitter of ONE point l - the planes through l and
+// each edge (a, b) of a clipped polygon, (a - l) x (b - l), both signs: the faces of the cone the strip's shadow segments fill.
+//
+// Why a separated Q cannot block.  flat_blocks() accepts only `inside && 1e-4 < t < dist - 1e-4`.  Take the kernel's t for Q and the
+// exact point X = o + t dir.  With u = 2^-24, ext = the extent per axis of scene, camera and light points, L = |ext|, Mn = |largest
+// coordinates|, and eps_R of a planar record R as in camera_strips (height over R's plane of an accepted point,
+// (7 u sum|T| ext + 6 u L) / |T|, plus the inside test's overshoot over an edge, ovs_R), E = 16 max_R eps_R (the factor: corners, as there):
+//  * the camera ray's exact point Y = cam_t + t d is inside the pyramid (n_k . d >= 0, t > 0: camera_strips) and within E of S's
+//    outline; the outline's nearest point is then at most E outside every side plane, so it lies in the clipped outline: Y is within E
+//    of the patch's hull (the hit point's distance off its record and outside its outline, and the widening of the pyramid);
+//  * o = fl(fl(d t) + cam_t) per component: |o - Y| <= u (L + Mn), taken twice;
+//  * l: a point light's position is exact; an area-light sample is a rounded combination of its vertices, within 4 u Mn of their hull;
+//  * dir = fl((l - o) / fl(|l - o|)): three subtractions, the norm, three divisions (1 ulp in the product build) leave each component
+//    within 6 u of a positive multiple of the exact direction, and t < fl(|l - o|) - 1e-4 may pass the segment's end by 9 u |l - o|:
+//    X is within 16 u |l - o| of the segment from o to l - 32 u L taken;
+//  hence X is within rho = E + 2 u (L + Mn) + 4 u Mn + 32 u L of the hull of patch and light points: m . X >= min - rho;
+//  * the inside test of Q accepts X only within E of Q's outline (eps_Q with the corner factor): m . X <= max over Q + E.
+// With margin = (1 + 1e-3) (rho + E) both cannot hold, so the OR over the remaining pairs is the same boolean.  A degenerate record
+// (all-zero rows: t = NaN) accepts nothing and counts as separated.  origin_slack returns E + 2 u (L + Mn), the origin's share of rho.
+int light_strips(const float* prims, int n_prims, const std::vector<float>& stream, const std::vector<float>& tab, const int counts[7], const CamFilm& cf,
+                 const float* pts, const int32_t* off, int n_emit, const uint8_t* keep, bool cull, std::vector<uint64_t>& masks, std::vector<int32_t>& n_pairs, double* origin_slack) {
+    const double u = std::ldexp(1.0, -24);
+    const int nsec[4] = {counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6]};
+    const int n_rec = nsec[0] + nsec[1] + nsec[2] + nsec[3];
+    const int npix = cf.n_cols * cf.height, n_blocks = (npix + 63) / 64, rows = std::min(n_emit, (int)APT_LIGHT_STRIP_EMITTERS);
+    if (npix <= 0 || cf.height <= 0 || cf.band_width <= 0 || cf.world <= 0 || n_emit < 0) return -1;
+    masks.assign((size_t)n_blocks * (size_t)rows, ~(uint64_t)0);
+    n_pairs.assign((size_t)n_emit, 0);
+    if (origin_slack) *origin_slack = 0.0;
+    // the pair of every kept record in its emitter's list
+    std::vector<int> pair_of((size_t)n_emit * (size_t)n_rec, -1);
+    for (int e = 0; e < n_emit; e++) {
+        int pair0 = 0, r = 0;
+        for (int sec = 0; sec < 4; sec++) {
+            int kept = 0;
+            for (int j = 0; j < nsec[sec]; j++, r++) if (keep[(size_t)e * n_rec + r]) pair_of[(size_t)e * n_rec + r] = pair0 + (kept++) / 2;
+            pair0 += (kept + 1) / 2;
+        }
+        n_pairs[(size_t)e] = pair0;
+    }
+    if (!cull || n_emit > (int)APT_LIGHT_STRIP_EMITTERS) return 0;
+    const D3 cam = {cf.cam_t[0], cf.cam_t[1], cf.cam_t[2]};
+    struct Rec { int sec; std::vector<D3> vs; D3 P, T; double eps, sph_margin; };
+    std::vector<Rec> recs;
+    double lo[3] = {cam.x, cam.y, cam.z}, hi[3] = {cam.x, cam.y, cam.z}, M[3] = {std::fabs(cam.x), std::fabs(cam.y), std::fabs(cam.z)};
+    auto grow = [&](D3 p) { const double c[3] = {p.x, p.y, p.z}; for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], c[a]); hi[a] = std::max(hi[a], c[a]); M[a] = std::max(M[a], std::fabs(c[a])); } };
+    {
+        size_t at = 0;
+        for (int sec = 0, r = 0; sec < 4; sec++) for (int j = 0; j < nsec[sec]; j++, r++, at += (size_t)kRecordFloats[sec]) {
+            int32_t ids[2]; memcpy(ids, tab.data() + 28 * (size_t)r + 8, 8);
+            if (ids[0] < 0 || ids[0] >= n_prims || ids[1] >= n_prims) return -1;
+            const float* p = stream.data() + at;
+            Rec rc; rc.sec = sec; rc.eps = 0.0; rc.sph_margin = 0.0; rc.P = {p[0], p[1], p[2]}; rc.T = {0, 0, 0};
+            if (sec < 3) { rc.T = {p[9], p[10], p[11]}; for (int k : {ids[0], ids[1]}) if (k >= 0) for (int v = 0; v < 3; v++) rc.vs.push_back(vtx(prims, k, v)); }
+            else {                                               // the sphere's box, as camera_strips pads it
+                const float* c = prims + 9 * (size_t)ids[0];
+                const D3 dc = sub({c[0], c[1], c[2]}, cam);
+                const double D2 = dot(dc, dc), rr = std::sqrt((double)c[3] * (double)c[3] * (1.0 + 4.0 * u) + 1.1e-4 + 32.0 * u * D2);
+                for (int k = 0; k < 8; k++) rc.vs.push_back({c[0] + ((k & 1) ? rr : -rr), c[1] + ((k & 2) ? rr : -rr), c[2] + ((k & 4) ? rr : -rr)});
+                rc.sph_margin = 16.0 * 6.0 * u * (std::sqrt(D2) + rr);
+            }
+            for (const D3& q : rc.vs) grow(q);
+            recs.push_back(rc);
+        }
+    }
+    const int n_pts = n_emit > 0 ? off[n_emit] : 0;
+    for (int k = 0; k < n_pts; k++) grow({pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]});
+    const D3 ext = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    const double L = std::sqrt(dot(ext, ext)), Mn = std::sqrt(M[0] * M[0] + M[1] * M[1] + M[2] * M[2]);
+    auto absdot = [](D3 a, D3 b) { return std::fabs(a.x) * b.x + std::fabs(a.y) * b.y + std::fabs(a.z) * b.z; };
+    double E = 0.0;
+    {
+        size_t at = 0;
+        for (int sec = 0, r = 0; sec < 3; sec++) for (int j = 0; j < nsec[sec]; j++, r++, at += (size_t)kRecordFloats[sec]) {
+            const float* p = stream.data() + at;
+            const D3 U = {p[3], p[4], p[5]}, V = {p[6], p[7], p[8]}, T = {p[9], p[10], p[11]};
+            if (dot(T, T) == 0.0) continue;
+            std::vector<std::array<double, 3>> edges = {{1, 0, 0}, {0, 1, 0}};
+            if (sec == 0) { edges.push_back({1, 0, 0.5}); edges.push_back({0, 1, 0.5}); }
+            if (sec == 2) edges.push_back({1, 1, 1});
+            if (sec == 1) for (int e = 0; e < 2; e++) edges.push_back({p[12 + 3 * e], p[13 + 3 * e], p[14 + 3 * e]});
+            double ovs = 0.0;
+            for (const auto& g : edges) {
+                const D3 grad = add({g[0] * U.x, g[0] * U.y, g[0] * U.z}, {g[1] * V.x, g[1] * V.y, g[1] * V.z});
+                const double gl = std::sqrt(dot(grad, grad));
+                if (!(gl > 0.0)) return -1;
+                ovs = std::max(ovs, (5.0 * u * (std::fabs(g[0]) * absdot(U, ext) + std::fabs(g[1]) * absdot(V, ext)) + 3.0 * u * (std::fabs(g[0]) + std::fabs(g[1]) + std::fabs(g[2]))) / gl);
+            }
+            recs[(size_t)r].eps = (7.0 * u * absdot(T, ext) + 6.0 * u * L) / std::sqrt(dot(T, T)) + ovs;
+            E = std::max(E, 16.0 * recs[(size_t)r].eps);
+        }
+    }
+    const double rho = E + 2.0 * u * (L + Mn) + 4.0 * u * Mn + 32.0 * u * L, margin = (1.0 + 1e-3) * (rho + E);
+    if (origin_slack) *origin_slack = E + 2.0 * u * (L + Mn);
+    const double widen = strip_widen(cf);
+    std::vector<D3> patch;                                      // the vertices of the block's clipped outlines
+    std::vector<D3> poly, tmp;
+    std::vector<uint8_t> sep((size_t)n_rec);
+    for (int b = 0; b < n_blocks; b++) {
+        D3 n[4];
+        if (!strip_pyramid(cf, npix, b, widen, n)) continue;
+        bool sphere_seen = false;
+        for (const Rec& r : recs) if (r.sec == 3) {
+            bool out = false;
+            for (int k = 0; k < 4 && !out; k++) {
+                double top = -1e300;
+                for (const D3& p : r.vs) top = std::max(top, dot(n[k], sub(p, cam)));
+                out = top < -r.sph_margin;
+            }
+            if (!out) sphere_seen = true;
+        }
+        if (sphere_seen) continue;
+        patch.clear();
+        std::vector<std::array<D3, 2>> edges;
+        for (const Rec& r : recs) {
+            if (r.sec == 3 || dot(r.T, r.T) == 0.0) continue;
+            for (size_t t0 = 0; t0 + 3 <= r.vs.size(); t0 += 3) {
+                poly.assign(r.vs.begin() + (long)t0, r.vs.begin() + (long)t0 + 3);
+                for (int k = 0; k < 4 && !poly.empty(); k++) {   // keep n_k . (x - cam) >= -E
+                    tmp.clear();
+                    for (size_t i = 0; i < poly.size(); i++) {
+                        const D3 a = poly[i], c = poly[(i + 1) % poly.size()];
+                        const double ha = dot(n[k], sub(a, cam)) + E, hc = dot(n[k], sub(c, cam)) + E;
+                        if (ha >= 0.0) tmp.push_back(a);
+                        if ((ha >= 0.0) != (hc >= 0.0)) { const double s = ha / (ha - hc); tmp.push_back({a.x + s * (c.x - a.x), a.y + s * (c.y - a.y), a.z + s * (c.z - a.z)}); }
+                    }
+                    poly.swap(tmp);
+                }
+                for (size_t i = 0; i < poly.size(); i++) { patch.push_back(poly[i]); if (poly.size() > 1) edges.push_back({poly[i], poly[(i + 1) % poly.size()]}); }
+            }
+        }
+        for (int e = 0; e < rows; e++) {
+            const int p0 = off[e], p1 = off[e + 1], np_e = n_pairs[(size_t)e];
+            if (p1 <= p0 || np_e > 64) continue;
+            const uint8_t* kp = keep + (size_t)e * n_rec;
+            int open = 0;                                       // kept planar records not yet separated
+            for (int r = 0; r < n_rec; r++) { sep[(size_t)r] = (kp[r] && recs[(size_t)r].sec < 3 && dot(recs[(size_t)r].T, recs[(size_t)r].T) == 0.0) ? 1 : 0; if (kp[r] && recs[(size_t)r].sec < 3 && !sep[(size_t)r]) open++; }
+            auto try_dir = [&](D3 m) {
+                const double len = std::sqrt(dot(m, m));
+                if (!(len > 0.0) || !std::isfinite(len)) return;
+                m = {m.x / len, m.y / len, m.z / len};
+                double inner = 1e300;
+                for (const D3& x : patch) inner = std::min(inner, dot(m, x));
+                for (int k = p0; k < p1; k++) inner = std::min(inner, dot(m, {pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]}));
+                for (int r = 0; r < n_rec; r++) {
+                    if (!kp[r] || sep[(size_t)r] || recs[(size_t)r].sec == 3) continue;
+                    double top = -1e300;
+                    for (const D3& q : recs[(size_t)r].vs) top = std::max(top, dot(m, q));
+                    if (top < inner - margin) { sep[(size_t)r] = 1; open--; }
+                }
+            };
+            for (int a = 0; a < 3 && open > 0; a++) for (double s : {1.0, -1.0}) try_dir({a == 0 ? s : 0.0, a == 1 ? s : 0.0, a == 2 ? s : 0.0});
+            for (int r = 0; r < n_rec && open > 0; r++) {
+                if (!kp[r] || sep[(size_t)r] || recs[(size_t)r].sec == 3) continue;
+                const D3 T = recs[(size_t)r].T;
+                try_dir(T); if (!sep[(size_t)r]) try_dir({-T.x, -T.y, -T.z});
+            }
+            if (p1 - p0 == 1) {
+                const D3 l = {pts[3 * p0], pts[3 * p0 + 1], pts[3 * p0 + 2]};
+                for (size_t i = 0; i < edges.size() && open > 0; i++) {
+                    const D3 m = cross(sub(edges[i][0], l), sub(edges[i][1], l));
+                    try_dir(m); if (open > 0) try_dir({-m.x, -m.y, -m.z});
+                }
+            }
+            uint64_t w = 0;
+            for (int r = 0; r < n_rec; r++) if (kp[r] && !sep[(size_t)r]) w |= (uint64_t)1 << pair_of[(size_t)e * n_rec + r];
+            masks[(size_t)e * n_blocks + (size_t)b] = w;
+        }
     }
     return 0;
 }

@@ -331,6 +331,8 @@ APT_D void tally_flush(const ShadeTally& t, const uint32_t* s_draws, Counters* c
 // strip-mask rule holds as it stands; the row count is a closed form, no counter is read.  Camera rays the sweep cannot settle are staged
 // exactly as k_generate_trace stages them (top of the sub-queue's region of tr[0], n_tr[0][ncls]); the ordinary bounce-0 launch that
 // follows resolves them in its prologue and shades that handful.  This kernel runs no prologue: nothing is listed before it.
+// Its light samples all leave from what the wave's strip sees: where the wave's emitter is uniform they are swept against the pairs of
+// its occluder list that the strip's mask keeps (flat_build.cpp light_strips; the masks lie behind the strip lists in `strips`).
 //
 // STAGE, the staged record (queue-fed form only): a row's record - planes A to D, 64 entries of 16 bytes each: 1 KiB per
 // plane and wave - is requested a row AHEAD, by loads that write LDS directly (global_load_lds_dwordx4: no register holds the data in
@@ -568,7 +570,14 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
             bool occ = false;
             if (__any(f.want && !defer)) {
                 const FlatList ls = (occ_e >= 0) ? flat_occ_list((A_->sc).flat, occ_e) : flat_full_list((A_->sc).flat);
-                occ = flat_any1(ls, vx.hit_point, f.dir, shadow_limit(f.dist));
+                if constexpr (CAM) {
+                    // a camera vertex's light samples leave from the patch of surfaces its strip sees: the pairs of the emitter's list that
+                    // cannot lie between that patch and the light are skipped (flat_build.cpp light_strips); fetched here, scalar loads
+                    unsigned long long lmask = ~0ull;
+                    if (occ_e >= 0 && occ_e < APT_LIGHT_STRIP_EMITTERS)
+                        lmask = light_strip_mask((A_->p), strips, (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)sl.q, occ_e);
+                    occ = flat_any1<true>(ls, vx.hit_point, f.dir, shadow_limit(f.dist), lmask);
+                } else occ = flat_any1(ls, vx.hit_point, f.dir, shadow_limit(f.dist));
             }
             if (__any(defer)) {
                 const uint32_t spos = wave_append(defer, &cnt->n_fix_sh[cur][sl.q * CNT_PAD]);

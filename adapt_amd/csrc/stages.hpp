@@ -491,6 +491,16 @@ APT_D unsigned long long camera_strip_mask(const Params& p, const unsigned long 
     const uint32_t lp0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((w * 64u) % (uint32_t)p.npix)), lp1 = lp0 + 63u, last = (uint32_t)p.npix - 1u;
     return ((strip_ptr)strips)[lp0 >> 6] | ((strip_ptr)strips)[(lp1 < last ? lp1 : last) >> 6] | ((strip_ptr)strips)[lp1 > last ? 0u : (lp0 >> 6)];
 }
+// The pairs of emitter e's occluder list that can block a light sample taken at a camera hit point of id-space wave `w` (flat_build.cpp
+// light_strips): row e of the masks that lie behind the strip lists in the same buffer, one word per block of 64 local pixels; the OR
+// over the blocks the wave touches, as above.  Only emitters below APT_LIGHT_STRIP_EMITTERS have a row.
+#ifndef APT_LIGHT_STRIP_EMITTERS
+#define APT_LIGHT_STRIP_EMITTERS 16
+#endif
+APT_D unsigned long long light_strip_mask(const Params& p, const unsigned long long* strips, uint32_t w, int e) {
+    const uint32_t n_blocks = ((uint32_t)p.npix + 63u) >> 6;
+    return camera_strip_mask(p, strips + (size_t)((uint32_t)e + 1u) * n_blocks, w);
+}
 
 // ----------------------------------------------------------------- generate
 // wave w of the id space feeds sub-queue w % nq at position (w / nq) * 64 + lane: dense and

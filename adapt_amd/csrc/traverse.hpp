@@ -895,8 +895,15 @@ APT_D FlatList flat_occ_list(const FlatScene& fl, int e) {
 // Occlusion of ONE ray per lane below `lim`: the lane's ray against two records per packed instruction (a FlatList: FlatScene::pairs or
 // an emitter's occluder list) - the mirror image of flat_loop<true>, for kernels that hold one path per lane (the shade kernel that traces
 // its own rays: shade_stage.hpp "rays traced in place").  Same arithmetic per (ray, record) as flat_loop: the two answers are the same bit for bit.
-APT_D bool flat_any1(const FlatList& ls, f3 o, f3 d, float lim) {
+// MASKED: bit k of the wave-uniform `mask` clear = pair k of the list (counted across the sections) is skipped, the stream position moving
+// on as if it had been visited, as in flat_closest1<true> below.  A pair may be skipped when flat_blocks() is false for both its records
+// and every ray of the wave (flat_build.cpp light_strips): the OR over the remaining pairs is the same boolean.  (k & 63: a list of more
+// than 64 pairs comes with every bit set.)
+template <bool MASKED = false>
+APT_D bool flat_any1(const FlatList& ls, f3 o, f3 d, float lim, unsigned long long mask = ~0ull) {
     cf_ptr at = ls.pairs;
+    int k = 0;                                               // wave-uniform index of the pair
+    auto skip = [&](int pair) { return MASKED && ((mask >> (pair & 63)) & 1ull) == 0ull; };
     const v2f ox = sp2(o.x), oy = sp2(o.y), oz = sp2(o.z), dx = sp2(d.x), dy = sp2(d.y), dz = sp2(d.z);
     bool occ = false;
     auto solve = [&](cf_ptr r, v2f& t, v2f& u, v2f& v) {      // planar_solve() with the record pair in the halves and the ray broadcast
@@ -913,22 +920,26 @@ APT_D bool flat_any1(const FlatList& ls, f3 o, f3 d, float lim) {
         v = fma2(vx, px, fma2(vy, py, vz * pz));
     };
     const int nq = (ls.nq + 1) >> 1, ng = (ls.ng + 1) >> 1, nt = (ls.nt + 1) >> 1, ns = (ls.ns + 1) >> 1;
-    for (int j = 0; j < nq; j++, at += 24) {
+    for (int j = 0; j < nq; j++, at += 24, k++) {
+        if (skip(k)) continue;
         v2f t, u, v; solve(at, t, u, v);
         const v2f a = u - sp2(0.5f), b = v - sp2(0.5f);
         occ = occ || flat_blocks(fmaxf(fabsf(a.x), fabsf(b.x)) <= 0.5f, t.x, lim) || flat_blocks(fmaxf(fabsf(a.y), fabsf(b.y)) <= 0.5f, t.y, lim);
     }
-    for (int j = 0; j < ng; j++, at += 36) {
+    for (int j = 0; j < ng; j++, at += 36, k++) {
+        if (skip(k)) continue;
         v2f t, u, v; solve(at, t, u, v);
         const v2f e1 = fma2(ld2c(at + 24), u, fma2(ld2c(at + 26), v, ld2c(at + 28))), e2 = fma2(ld2c(at + 30), u, fma2(ld2c(at + 32), v, ld2c(at + 34)));
         occ = occ || flat_blocks(fminf(fminf(u.x, v.x), fminf(e1.x, e2.x)) >= 0.f, t.x, lim) || flat_blocks(fminf(fminf(u.y, v.y), fminf(e1.y, e2.y)) >= 0.f, t.y, lim);
     }
-    for (int j = 0; j < nt; j++, at += 24) {
+    for (int j = 0; j < nt; j++, at += 24, k++) {
+        if (skip(k)) continue;
         v2f t, u, v; solve(at, t, u, v);
         const v2f w = (sp2(1.0f) - u) - v;
         occ = occ || flat_blocks(fminf(fminf(u.x, v.x), w.x) >= 0.f, t.x, lim) || flat_blocks(fminf(fminf(u.y, v.y), w.y) >= 0.f, t.y, lim);
     }
-    for (int j = 0; j < ns; j++, at += 8) {                   // spheres: flat_loop's test (the reference's, tracer_base.py:184-199) on two spheres
+    for (int j = 0; j < ns; j++, at += 8, k++) {              // spheres: flat_loop's test (the reference's, tracer_base.py:184-199) on two spheres
+        if (skip(k)) continue;
         const v2f r2 = ld2c(at + 6);
         const v2f sx = ld2c(at) - ox, sy = ld2c(at + 2) - oy, sz = ld2c(at + 4) - oz;
         const v2f cn2 = (sx * sx + sy * sy) + sz * sz;

@@ -589,6 +589,13 @@ class Renderer:
         _lib.check(self.lib.apt_renderer_camera_fused(self.handle, C.byref(f)), "apt_renderer_camera_fused", self.lib)
         return bool(f.value)
 
+    def light_strips(self) -> bool:
+        """apt_renderer_light_strips: the camera-fed kernel sweeps the camera vertex's light samples against per-strip masks that leave
+        some pair of an occluder list out (APT_LIGHT_STRIPS=0 at creation switches them off; cropped and adaptive renders have none)."""
+        f = C.c_int32(0)
+        _lib.check(self.lib.apt_renderer_light_strips(self.handle, C.byref(f)), "apt_renderer_light_strips", self.lib)
+        return bool(f.value)
+
     def record_staged(self) -> bool:
         """apt_renderer_record_staged: the queue-fed shade kernel stages each row's path record in LDS a row ahead (rays traced in place,
         Lambertian surfaces under point lights; APT_RECORD_STAGE=0 at creation switches it off)."""

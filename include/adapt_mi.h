@@ -10,6 +10,7 @@
  *   apt_flat_records               tracer/tracer_base.py:117-134,184-212: the data of the brute-force intersector, as the flat sweep wants it
  *   apt_flat_occluders             (no upstream counterpart) per emitter, the flat records that can block its light samples
  *   apt_camera_strips              (no upstream counterpart) per 64 local pixels, the flat record pairs a camera ray can hit
+ *   apt_light_strips               (no upstream counterpart) per 64 local pixels and emitter, the occluder pairs a camera vertex's light sample can meet
  *   apt_scene_create               tracer/tracer_base.py:117-134 (load_primitives) +
  *                                   tracer/path_tracer.py:245-274 (initialze): numpy -> device fields
  *   apt_renderer_create            renderer/vanilla_renderer.py:26-30 / tracer_base.py:36-102 (film, crop, camera,
@@ -202,6 +203,15 @@ int apt_flat_occluders(const float* prims /* n_prims*9 */, int32_t n_prims, cons
 int apt_camera_strips(const float* prims /* n_prims*9 */, int32_t n_prims, const int32_t* obj_info /* n_objects*3 */, int32_t n_objects,
                       const apt_render_cfg* cfg, int32_t cull, uint64_t* masks, int32_t masks_cap, int32_t* n_strips, int32_t* n_pairs);
 
+/* Strip masks of the camera vertex's light samples (host only): per emitter e < min(n_sources, 16) and block b of 64
+ * consecutive local pixels, masks[e * n_strips + b]: bit k set = a record of pair k of emitter e's occluder list (apt_flat_occluders with
+ * cull = 1, its order and pairing) may block a light sample taken at a camera hit point of the block.  cull = 0: every bit set (what
+ * APT_LIGHT_STRIPS=0 gives a renderer).  n_pairs (n_sources entries): pairs per list; origin_slack: how far off the strip's clipped
+ * outlines the rule lets a shadow-ray origin lie.  masks, n_pairs, origin_slack may be NULL. */
+int apt_light_strips(const float* prims /* n_prims*9 */, int32_t n_prims, const int32_t* obj_info /* n_objects*3 */, int32_t n_objects,
+                     const int32_t* src_i, const float* src_f, int32_t n_sources, const apt_render_cfg* cfg, int32_t cull,
+                     uint64_t* masks, int32_t masks_cap, int32_t* n_strips, int32_t* n_pairs, float* origin_slack);
+
 /* ---- BVH build, reference layout: the drop-in for the pybind11 module itself.
  * Replaces bvh_cpp.bvh_build(obj_array, obj_info, world_min, world_max) (tracer/bvh/bvh.cpp:274-296), whose four flat arrays
  * PathTracer.bvh_process reshapes and loads into the LinearBVH / LinearNode fields (tracer/path_tracer.py:155-170,
@@ -308,6 +318,9 @@ int apt_renderer_info(const apt_renderer*, int32_t* spp_batch, int32_t* n_subque
 /* Rays traced in place: *fused = 1 when the renderer shades the camera vertex in the kernel that traces the camera ray (steady full-film
  * renders with max_bounce >= 1; env APT_CAMERA_FUSE=0, read at apt_renderer_create, selects generate + a queue-fed bounce 0), else 0. */
 int apt_renderer_camera_fused(const apt_renderer*, int32_t* fused);
+/* ... and *in_use = 1 when that kernel sweeps the camera vertex's light samples against strip masks that leave some pair of an occluder
+ * list out (apt_light_strips; env APT_LIGHT_STRIPS=0, read at apt_renderer_create, sets every bit), else 0 - always 0 without the fusion. */
+int apt_renderer_light_strips(const apt_renderer*, int32_t* in_use);
 /* Rays traced in place: *staged = 1 when the queue-fed shade kernel stages each row's path record in LDS a row ahead (the Lambertian /
  * point-light kernel; env APT_RECORD_STAGE=0, read at apt_renderer_create, selects the kernel that loads the record where it is used), else 0. */
 int apt_renderer_record_staged(const apt_renderer*, int32_t* staged);
