@@ -48,6 +48,7 @@ class RenderCfg(C.Structure):
                 ("inv_focal", C.c_float), ("half_w", C.c_float), ("half_h", C.c_float), ("seed", C.c_uint32),
                 ("band_width", C.c_int32), ("rank", C.c_int32), ("world_size", C.c_int32),
                 ("spp_per_batch", C.c_int32), ("device", C.c_int32), ("profile", C.c_int32), ("volumetric", C.c_int32),
+                ("path_lengths", C.c_int32),
                 ("adaptive_threshold", C.c_float), ("adaptive_min_spp", C.c_int32), ("adaptive_step", C.c_int32),
                 ("transient_bins", C.c_int32), ("transient_min_time", C.c_float), ("transient_interval", C.c_float)]
 
@@ -101,6 +102,8 @@ SYMBOLS = {
     "apt_reset": (C.c_int, [C.c_void_p]),
     "apt_read_transient": (C.c_int, [C.c_void_p, f32p]),
     "apt_set_transient": (C.c_int, [C.c_void_p, f32p]),
+    "apt_read_path_lengths": (C.c_int, [C.c_void_p, f32p]),
+    "apt_set_path_lengths": (C.c_int, [C.c_void_p, f32p]),
     "apt_read_sample_counts": (C.c_int, [C.c_void_p, i32p, u8p]),
     "apt_read_moments": (C.c_int, [C.c_void_p, f64p]),
     "apt_set_adaptive_state": (C.c_int, [C.c_void_p, i32p, f64p, u8p]),

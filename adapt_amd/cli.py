@@ -17,6 +17,9 @@ written as upstream's `export_transient_profile` writes them (render.py:36-56,16
 `--noise_threshold t` (with `--min_spp`, `--adaptive_step`): adaptive sampling; `--iter_num` is then the most samples
 any pixel gets, and the per-pixel sample counts are written as `<img_name>-<scene file stem>-<type>-spp.npy` (w, h) int32 next to the
 image (cropped like it).  Not with `--transient`.
+`--path_lengths` (with `--type pt`): the render split by path length: one image per length - segments, camera to
+emitter; 1 emission, 2 direct light, 3 and more indirect - as `<img_name>-<scene file stem>-pt-len01.<ext>` ..., both parts summed, cropped
+and normalised like the image, and the (lengths, 2, w, h, 3) array as `...-pt-lengths.npy`.  Not with `--transient` or `--noise_threshold`.
 `--denoise` (with `--type pt`; `--firefly_threshold t`, `--save_aov`): the frame through the firefly filter (t > 0) and the edge-avoiding
 a-trous filter, written as `<img_name>-<scene file stem>-<type>-denoised.<ext>` next to the image (cropped and normalised
 like it); `--save_aov` writes the feature buffers the filter was guided by as `...-<type>-aov.npz` (albedo, normal, depth, hit_fraction).
@@ -68,6 +71,7 @@ def get_options(argv=None):
     p.add_argument("--max_bounce", default=None, type=int)
     p.add_argument("--spp_per_batch", default=0, type=int, help="samples per wavefront batch (0: automatic)")
     p.add_argument("--transient", default=False, action="store_true", help="time-resolved output (pt only; the sensor's sample_count / min_time / interval)")
+    p.add_argument("--path_lengths", default=False, action="store_true", help="also write one image per path length (pt only): ...-len01.<ext> (emission), -len02 (direct), ... and ...-lengths.npy")
     p.add_argument("--noise_threshold", default=0., type=float, help="adaptive sampling: a pixel stops once the relative standard error of its mean is <= this (0: off)")
     p.add_argument("--min_spp", default=64, type=int, help="adaptive sampling: no pixel stops before this many samples")
     p.add_argument("--adaptive_step", default=32, type=int, help="adaptive sampling: pixels are retired at sample numbers that are multiples of this")
@@ -150,6 +154,15 @@ def main(argv=None) -> int:
     if opts.transient and opts.type != "pt":
         print(f"--transient: time-resolved output exists for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
         return 2
+    if opts.path_lengths and opts.type != "pt":
+        print(f"--path_lengths: path-length images exist for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
+        return 2
+    if opts.path_lengths and opts.transient:
+        print("--path_lengths with --transient: time x length cubes are not built; path-length images and --transient do not combine", file=sys.stderr)
+        return 2
+    if opts.path_lengths and opts.noise_threshold > 0:
+        print("--path_lengths with --noise_threshold: path-length images need every pixel's samples; adaptive sampling and --path_lengths do not combine", file=sys.stderr)
+        return 2
     if (opts.denoise or opts.save_aov) and opts.type != "pt":
         print(f"--denoise / --save_aov: feature buffers and the denoiser exist for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
         return 2
@@ -178,7 +191,7 @@ def main(argv=None) -> int:
           f"{len(emitters)} emitters, parsed in {time.time() - t0:.3f} s")
     rdr = Renderer(emitters, array_info, objs, cfg, device=opts.device, seed=opts.seed, profile=opts.profile,
                    width=opts.width, height=opts.height, max_bounce=opts.max_bounce, spp_per_batch=opts.spp_per_batch,
-                   transient=True if opts.transient else None, adaptive=adaptive)
+                   transient=True if opts.transient else None, adaptive=adaptive, path_lengths=opts.path_lengths)
     stem = opts.name[:-4]
     max_iter = (opts.iter_num if opts.iter_num > 0 else cfg.get("iter_num", 2000)) + 1          # render.py:80-81
     chk_file = os.path.join(_folder(opts.chkpt_path), f"{opts.img_name}-{stem}-{opts.type}.pkl")
@@ -232,8 +245,9 @@ def main(argv=None) -> int:
     if rdr.do_crop:
         img = img[rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y, :]
     print(f"[adapt_amd] pixel max value = {np.nanmax(img):.3f}")
-    if opts.normalize > 0.9:
-        img = img / np.quantile(img, opts.normalize)
+    scale = np.quantile(img, opts.normalize) if opts.normalize > 0.9 else None
+    if scale is not None:
+        img = img / scale
     if not opts.no_save_fig:
         out = os.path.join(_folder(opts.output_path), f"{opts.img_name}-{stem}-{opts.type}.{opts.img_ext}")
         write_image(img, out)
@@ -256,6 +270,18 @@ def main(argv=None) -> int:
         if opts.save_aov:
             np.savez(f"{base}-aov.npz", **{k: window(v) for k, v in rdr.aov().items()})
             print(f"[adapt_amd] wrote {base}-aov.npz")
+    if opts.path_lengths and not opts.no_save_fig:
+        base = os.path.join(opts.output_path, f"{opts.img_name}-{stem}-{opts.type}")
+        planes = rdr.path_lengths()
+        np.save(f"{base}-lengths.npy", planes)
+        frames = planes.sum(1)
+        if rdr.do_crop:
+            frames = frames[:, rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y, :]
+        if scale is not None:
+            frames = frames / scale             # the image's quantile: the written frames still add up to the written image
+        for i in range(frames.shape[0]):
+            write_image(frames[i], f"{base}-len{i + 1:02d}.{opts.img_ext}")
+        print(f"[adapt_amd] wrote {frames.shape[0]} path-length images {base}-len01.{opts.img_ext} ... and {base}-lengths.npy")
     if opts.transient:
         export_transient(rdr, opts.output_path, stem, opts.img_ext, opts.normalize)      # render.py:166: folder named after the scene file
     rdr.close()

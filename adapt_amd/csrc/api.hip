@@ -223,7 +223,7 @@ struct Lane {
 //   PIPE_SORTED      extend into per-class queues, the class kernels in groups, shadow  (render_surface)
 //   PIPE_TRACED      the shade kernel traces its rays itself: one launch per bounce     (render_surface; product build, shade_stage.hpp "rays traced in place")
 //   PIPE_VOLUMETRIC  extend, k_vevent, one kernel per event queue, transmittance walk   (render_volumetric)
-// Transient and adaptive renders are modifiers on top of it (apt_renderer::transient, ::adaptive).
+// Transient, path-length and adaptive renders are modifiers on top of it (apt_renderer::transient, ::lengths, ::adaptive).
 enum Pipeline { PIPE_STAGED, PIPE_SORTED, PIPE_TRACED, PIPE_VOLUMETRIC };
 
 struct apt_renderer {
@@ -281,6 +281,11 @@ struct apt_renderer {
     TransQ tq{};
     DevBuf tr_pool, tr_bins;              // per-path time / record arrays (cap-sized), the bins (n_bins x owned pixels float4)
     group_tr_fn group_tr_[APT_N_GROUPS] = {};
+    // path-length render (apt_render_cfg.path_lengths; stages.hpp k_bin_lengths): what a transient render selects - its shade
+    // twins, its per-path arrays (tq, tr_pool), one lane -, the records settled by segment count instead of by time
+    int lengths = 0;
+    DevBuf len_planes;                    // (max_bounce + 1) x 2 x owned pixels float4
+    bool split() const { return transient || lengths; }      // the TR shade twins run: every bounce's contributions are kept apart
     // adaptive sampling (apt_render_cfg.adaptive_threshold > 0; stages.hpp AdaptQ)
     int adaptive = 0;
     AdaptQ aq{};
@@ -739,7 +744,7 @@ static int plan_film(apt_renderer* r) {
     if (r->npix <= 0) { return fail(APT_E_INVALID, "apt_renderer_create: this rank owns no pixels"); }
     r->n_lanes = 3;   // measured on C2: 1 lane 1 827, 2 lanes 2 196, 3 lanes 2 268, 4 lanes 2 178 Msamples/s (round 2, 64 spp per lane-batch); round 5, 32 Mi paths per lane-batch: C2 4 559 / 4 590 / 4 287 with 2 / 3 / 4, C5 1 844 / 2 028 / 2 129 with 1 / 2 / 3; volumetric scenes with null surfaces ran four lanes in rounds 3-4 (the fourth hid the host read-backs of their tails): at this batch size V1 1 374 with three, 1 299 with four
     if (const char* nl = getenv("APT_LANES")) r->n_lanes = std::min(4, std::max(1, atoi(nl)));
-    if (c.transient_bins > 0) r->n_lanes = 1;      // the bins are shared by every batch and added to per bounce: one lane keeps the adds in order
+    if (c.transient_bins > 0 || c.path_lengths) r->n_lanes = 1;      // the bins (the length planes) are shared by every batch and added to per bounce: one lane keeps the adds in order
     const size_t nq = (size_t)r->nq;
     // queue capacity of a batch of b: whole waves, dealt over the sub-queues (generate: wave w -> sub-queue w % nq)
     auto subcap_of = [&](int b) { const size_t n_waves = ((size_t)r->npix * (size_t)b + 63) / 64; return ((n_waves + nq - 1) / nq) * 64; };
@@ -833,7 +838,7 @@ static int pick_shading(apt_renderer* r) {
         if (want == 1) fprintf(stderr, "adapt_mi: APT_FUSED=1 (light samples only traced in place) was retired in round 5; running the staged pipeline (APT_FUSED=0). Use 2 for rays traced in place.\n");
         want_traced = want >= 2;
     }
-    const bool can_trace = r->trace_mode == TRACE_FLAT && S == 1 && !r->transient && r->shade->traced != nullptr;
+    const bool can_trace = r->trace_mode == TRACE_FLAT && S == 1 && !r->split() && r->shade->traced != nullptr;
     r->pipeline = c.volumetric ? PIPE_VOLUMETRIC : (sorted ? PIPE_SORTED : ((can_trace && want_traced) ? PIPE_TRACED : PIPE_STAGED));
     p.traced = (r->pipeline == PIPE_TRACED) ? 1 : 0;
     const bool want_stage = !(getenv("APT_RECORD_STAGE") && atoi(getenv("APT_RECORD_STAGE")) == 0);
@@ -841,8 +846,8 @@ static int pick_shading(apt_renderer* r) {
     r->traced_fn = r->record_stage ? r->shade->traced_staged : r->shade->traced;
     // flat sweep with several light samples per vertex: the samples are queued by vertex and the shadow kernel adds a vertex's samples with
     // one read-modify-write (stages.hpp k_shadow_flat); otherwise 2-4 samples per vertex add into one radiance plane each (stages.hpp
-    // APT_EXCLUSIVE_L) - a transient render always, its bins want the samples apart
-    p.nee_vm = (!c.volumetric && !r->transient && r->trace_mode == TRACE_FLAT && S > 1) ? 1 : 0;
+    // APT_EXCLUSIVE_L) - a transient or path-length render always, its bins want the samples apart
+    p.nee_vm = (!c.volumetric && !r->split() && r->trace_mode == TRACE_FLAT && S > 1) ? 1 : 0;
     p.l_planes = (!p.nee_vm && S >= 2 && S <= 4) ? S : 1;
     if (r->pipeline == PIPE_VOLUMETRIC) {
         if (c.max_bounce > 255) { return fail(APT_E_INVALID, "apt_renderer_create: the volumetric tracer keeps the bounce count in 8 bits (max_bounce <= 255)"); }
@@ -881,6 +886,7 @@ static int pick_shading(apt_renderer* r) {
     }
     if (r->transient) r->shade_name += " [transient]";
     if (r->adaptive) r->shade_name += " [adaptive]";
+    if (r->lengths) r->shade_name += " [path lengths]";
     // (sorted: extend appends every hit path's record to the packed queue of its material class, Queues::cq)
     const int si = (r->pipeline == PIPE_SORTED) ? 1 : 0;
     r->extend = r->dyn_fetch ? kExtendDyn[si] : (r->trace_mode == TRACE_FLAT ? kExtendFlatHot[si] : kExtend[r->trace_mode][si]);
@@ -1043,7 +1049,6 @@ static void transient_window(TransQ& t, int32_t n_bins, float min_time, float in
     t.max_time = (float)((double)min_time + (double)interval * (double)n_bins);
 }
 
-// Transient render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the bins, all zero-filled.
 // Adaptive sampling state: n_p = 0, S2 = 0 and every owned pixel inside the crop window active (a fresh render, apt_reset).
 static int adaptive_restart(apt_renderer* r) {
     HIP_TRY(hipMemsetAsync(r->ad_n.p, 0, r->ad_n.bytes, r->stream()));
@@ -1077,19 +1082,24 @@ static int make_adaptive(apt_renderer* r) {
     return adaptive_restart(r);
 }
 
+// Transient render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the bins, all zero-filled.  A
+// path-length render takes the same per-path arrays and, in place of the bins, its length planes.
 static int make_transient(apt_renderer* r) {
-    if (!r->transient) return APT_OK;
+    if (!r->split()) return APT_OK;
     const apt_render_cfg& c = r->cfg;
     const size_t cap = r->par.cap, planes = (size_t)r->par.l_planes;
-    const size_t words = cap + 4 * cap + planes * cap, bins = (size_t)c.transient_bins * (size_t)r->npix * 4;
+    const size_t words = cap + 4 * cap + planes * cap;
+    DevBuf& out = r->transient ? r->tr_bins : r->len_planes;
+    const size_t cells = (r->transient ? (size_t)c.transient_bins : ((size_t)c.max_bounce + 1) * 2) * (size_t)r->npix;
     hipError_t e;
-    if ((e = r->tr_pool.alloc(words * 4)) != hipSuccess || (e = r->tr_bins.alloc(bins * 4)) != hipSuccess)
-        return fail(APT_E_NOMEM, std::string("transient bins: ") + hipGetErrorString(e));
+    if ((e = r->tr_pool.alloc(words * 4)) != hipSuccess || (e = out.alloc(cells * 16)) != hipSuccess)
+        return fail(APT_E_NOMEM, std::string(r->transient ? "transient bins: " : "path-length planes: ") + hipGetErrorString(e));
     HIP_TRY(hipMemsetAsync(r->tr_pool.p, 0, words * 4, r->stream()));
-    HIP_TRY(hipMemsetAsync(r->tr_bins.p, 0, bins * 4, r->stream()));
+    HIP_TRY(hipMemsetAsync(out.p, 0, cells * 16, r->stream()));
     float* base = r->tr_pool.as<float>();
     TransQ& t = r->tq;
     t.t_path = base; t.emit = reinterpret_cast<float4*>(base + cap); t.t_light = base + 5 * cap;
+    if (!r->transient) return APT_OK;      // (a path-length render: no bins, no window - the times the twins store are not read)
     t.bins = r->tr_bins.as<float4>();
     transient_window(t, c.transient_bins, c.transient_min_time, c.transient_interval);
     return APT_OK;
@@ -1217,6 +1227,16 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
         if (!(c.transient_interval > 0.f) || !std::isfinite(c.transient_interval) || !std::isfinite(c.transient_min_time))
             return fail(APT_E_INVALID, "apt_renderer_create: transient_interval must be positive and finite, transient_min_time finite");
     }
+    if (c.path_lengths != 0 && c.path_lengths != 1) return fail(APT_E_INVALID, "apt_renderer_create: path_lengths must be 0 (off) or 1");
+    if (c.path_lengths) {
+        if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: path-length images are a surface-renderer mode (volumetric = 0)");
+        if (c.num_shadow_ray > 4) return fail(APT_E_INVALID, "apt_renderer_create: path-length images take at most 4 light samples per vertex (num_shadow_ray <= 4)");
+        if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: path-length images run on one rank (world_size = 1)");
+        if (c.transient_bins > 0)
+            return fail(APT_E_INVALID, "apt_renderer_create: path-length images and transient rendering do not combine (transient_bins must be 0 when path_lengths = 1)");
+        if (c.adaptive_threshold > 0.f)
+            return fail(APT_E_INVALID, "apt_renderer_create: path-length images and adaptive sampling do not combine (adaptive_threshold must be 0 when path_lengths = 1)");
+    }
     if (!std::isfinite(c.adaptive_threshold)) return fail(APT_E_INVALID, "apt_renderer_create: adaptive_threshold must be finite (> 0: adaptive sampling, <= 0: off)");
     if (c.adaptive_threshold > 0.f) {
         if (c.transient_bins > 0)
@@ -1228,7 +1248,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     apt_renderer* r = new apt_renderer();
     struct Owner { apt_renderer* r; ~Owner() { if (r) apt_renderer_destroy(r); } } owner{r};     // every early return below releases streams, events and queue pools
     r->scene = sc; r->cfg = c;
-    r->adaptive = c.adaptive_threshold > 0.f ? 1 : 0; r->transient = c.transient_bins > 0 ? 1 : 0;
+    r->adaptive = c.adaptive_threshold > 0.f ? 1 : 0; r->transient = c.transient_bins > 0 ? 1 : 0; r->lengths = c.path_lengths ? 1 : 0;
     if (int rc = plan_film(r)) return rc;
     pick_traversal(r);
     if (int rc = pick_shading(r)) return rc;
@@ -1469,18 +1489,23 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
         }
         // transient: a bounce's records are binned once its light samples are all settled - after its shadow launch, or with the flat sweep
         // after the next bounce's fix-up launch (it serves the deferred ones) - and before the next shade launch writes new ones
-        auto bin = [&]() { LaunchTimer t(r, APT_K_FINALIZE, st, false); hipLaunchKernelGGL(k_bin_transient, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->accum.as<float>()); };
+        // path lengths: the same launch points; `settled` is the bounce whose records they are (with the flat sweep the previous one)
+        auto bin = [&](int settled) {
+            LaunchTimer t(r, APT_K_FINALIZE, st, false);
+            if (r->lengths) hipLaunchKernelGGL(k_bin_lengths, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->len_planes.as<float4>(), settled, r->accum.as<float>());
+            else hipLaunchKernelGGL(k_bin_transient, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->accum.as<float>());
+        };
         int cur = 0;
         for (int b = 0; b < p.max_bounce; b++) {
             // (the walk kernels reset each other's work counters - k_shadow_dyn the next bounce's closest-hit counter, k_extend_dyn this bounce's any-hit counter; without light samples the host does)
             if (r->dyn_fetch && !(p.S > 0)) { unchain(r, st); HIP_TRY(hipMemsetAsync(cnt->n_work[0], 0, sizeof(cnt->n_work[0]), st)); }
             launch_extend(r, ln, p, total, cur);
-            if (r->transient && r->trace_mode == TRACE_FLAT && b > 0) bin();
+            if (r->split() && r->trace_mode == TRACE_FLAT && b > 0) bin(b - 1);
             if (r->pipeline != PIPE_SORTED) {
                 ShadeIn in = {q.ray_o[cur], q.ray_d[cur], q.thr[cur], q.id[cur], q.meta[cur], q.pdf[cur],
                               q.hit_t, q.hit_prim, q.hit_u, q.hit_v, (const uint32_t*)cnt->n_active[cur]};
                 LaunchTimer t(r, APT_K_SHADE, st);
-                if (r->transient) hipLaunchKernelGGL(r->shade->transient, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, in, cur, b, r->tq);
+                if (r->split()) hipLaunchKernelGGL(r->shade->transient, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, in, cur, b, r->tq);
                 else hipLaunchKernelGGL(r->shade->fn, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, in, cur, b);
             } else {
                 for (int g = 0; g < APT_N_GROUPS; g++) {       // one launch per register-footprint group: its workgroups walk the member classes' queues one after the other
@@ -1488,7 +1513,7 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
                     for (int k = 0; k < APT_GROUP_SLOTS; k++) { const int c = r->group_cls[g][k]; gi.cls[k] = c; gi.counts[k] = c >= 0 ? (const uint32_t*)cnt->n_cls[c] : nullptr; any = any || c >= 0; }
                     if (!any) continue;
                     LaunchTimer t(r, APT_K_SHADE, st);
-                    if (r->transient) hipLaunchKernelGGL(r->group_tr_[g], dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, gi, cur, b, r->tq);
+                    if (r->split()) hipLaunchKernelGGL(r->group_tr_[g], dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, gi, cur, b, r->tq);
                     else hipLaunchKernelGGL(r->group_fn_[g], dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, gi, cur, b);
                 }
                 if (p.S <= 0) { unchain(r, st); HIP_TRY(hipMemsetAsync(cnt->n_cls, 0, sizeof(cnt->n_cls), st)); }      // normally k_shadow recycles these
@@ -1499,13 +1524,13 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
                 p.fix_par = cur;
                 LaunchTimer t(r, APT_K_SHADOW, st); hipLaunchKernelGGL(kShadow[r->trace_mode], dim3(grid_for(total * (size_t)p.S, r->grid_shadow, nq, r->trace_items)), dim3(r->trace_nt), r->lds_bytes_any, st, sc, p, q, cnt, ln.plan);
             }
-            if (r->transient && r->trace_mode != TRACE_FLAT) bin();
+            if (r->split() && r->trace_mode != TRACE_FLAT) bin(b);
             cur ^= 1;
         }
         if (r->trace_mode == TRACE_FLAT && p.S > 0 && p.max_bounce > 0) {     // the last bounce's shadow list (the extend list of this parity is empty)
             LaunchTimer t(r, APT_K_SHADOW, st, false); hipLaunchKernelGGL(r->fix, dim3(r->grid_fix), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, (const uint32_t*)cnt->n_active[cur], ln.plan);
         }
-        if (r->transient && r->trace_mode == TRACE_FLAT && p.max_bounce > 0) bin();
+        if (r->split() && r->trace_mode == TRACE_FLAT && p.max_bounce > 0) bin(p.max_bounce - 1);
         }
         if (int rc = finalize_batch(r, ln, p, prev_fin)) return rc;
         r->cnt += B; done += B; batch++;
@@ -1630,11 +1655,26 @@ APT_EXPORT int apt_set_transient(apt_renderer* r, const float* in) {
     HIP_TRY(hipMemcpyAsync(r->tr_bins.p, in, r->tr_bins.bytes, hipMemcpyHostToDevice, r->stream()));
     return resolve_events(r);
 }
+APT_EXPORT int apt_read_path_lengths(apt_renderer* r, float* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_read_path_lengths: bad argument");
+    if (!r->lengths) return fail(APT_E_STATE, "apt_read_path_lengths: the renderer was created with path_lengths = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(out, r->len_planes.p, r->len_planes.bytes, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
+APT_EXPORT int apt_set_path_lengths(apt_renderer* r, const float* in) {
+    if (!r || !in) return fail(APT_E_INVALID, "apt_set_path_lengths: bad argument");
+    if (!r->lengths) return fail(APT_E_STATE, "apt_set_path_lengths: the renderer was created with path_lengths = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(r->len_planes.p, in, r->len_planes.bytes, hipMemcpyHostToDevice, r->stream()));
+    return resolve_events(r);
+}
 APT_EXPORT int apt_reset(apt_renderer* r) {
     if (!r) return fail(APT_E_INVALID, "apt_reset: null handle");
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
     if (r->transient) HIP_TRY(hipMemsetAsync(r->tr_bins.p, 0, r->tr_bins.bytes, r->stream()));
+    if (r->lengths) HIP_TRY(hipMemsetAsync(r->len_planes.p, 0, r->len_planes.bytes, r->stream()));
     if (r->aov_sum.p) HIP_TRY(hipMemsetAsync(r->aov_sum.p, 0, r->aov_sum.bytes, r->stream()));
     for (Lane& ln : r->lanes) HIP_TRY(hipMemsetAsync(ln.counters.p, 0, sizeof(Counters), r->stream()));      // lanes are idle between render calls
     r->cnt = 0;

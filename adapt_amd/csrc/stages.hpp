@@ -1229,6 +1229,45 @@ __global__ void __launch_bounds__(BLOCK) k_bin_transient(Params p, Queues q, Tra
     }
 }
 
+// ------------------------------------------------------------ path-length planes
+// k_bin_transient's sibling: the same records, visited at the same points of the bounce loop, keyed by the bounce the host names instead of
+// by time.  A path's length is its number of segments, camera to emitter: the emitter hit at vertex `bounce` has length bounce + 1 and goes
+// to plane `bounce`, part 0 (reached by a sampled ray); the vertex's light samples have length bounce + 2 and go, all of them, to plane
+// bounce + 1, part 1 (reached by a light sample).  planes is [plane * 2 + part][local pixel] float4 - summed rgb and the number of
+// contributions -, so a wave's 64 pixels touch 1 KiB in a row.  A batch's contributions to a cell are summed in registers, samples in order,
+// and added once; the framebuffer takes the records' sum in k_bin_transient's order.  The pixel owns its cells: no atomics.  The host
+// keeps bounce < max_bounce, so plane bounce + 1 is the last of the max_bounce + 1 at most.
+__global__ void __launch_bounds__(BLOCK) k_bin_lengths(Params p, Queues q, TransQ tq, float4* planes, int bounce, float* accum) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride) {
+        f3 sum = splat3(0.f);
+        float4 part[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+        auto land = [&](float4 c, float4& cell) {
+            const f3 v = mk3(isnan(c.x) ? 0.f : c.x, isnan(c.y) ? 0.f : c.y, isnan(c.z) ? 0.f : c.z);
+            if (v.x == 0.f && v.y == 0.f && v.z == 0.f) return;
+            sum = sum + v;
+            cell = make_float4(cell.x + v.x, cell.y + v.y, cell.z + v.z, cell.w + 1.f);
+        };
+        for (int s = 0; s < p.spp_batch; s++) {
+            const uint32_t slot = (uint32_t)s * (uint32_t)p.npix + lp;
+            const float4 e = tq.emit[slot];
+            if (e.x != 0.f || e.y != 0.f || e.z != 0.f) { land(e, part[0]); tq.emit[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }      // (NaN != 0: cleared too)
+            for (int pl = 0; pl < p.l_planes; pl++) {      // light samples in sample order
+                float4* l4 = reinterpret_cast<float4*>(L_slot(q.L, p.cap, (slot << 2) | (uint32_t)pl));
+                const float4 c = *l4;
+                if (c.x != 0.f || c.y != 0.f || c.z != 0.f) { land(c, part[1]); *l4 = make_float4(0.f, 0.f, 0.f, 0.f); }
+            }
+        }
+        for (int k = 0; k < 2; k++) {
+            if (part[k].w == 0.f) continue;
+            float4* cell = planes + (size_t)((bounce + k) * 2 + k) * (size_t)p.npix + lp;
+            const float4 a = *cell;
+            *cell = make_float4(a.x + part[k].x, a.y + part[k].y, a.z + part[k].z, a.w + part[k].w);
+        }
+        if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
+    }
+}
+
 __global__ void k_divide(const float* accum, float* out, uint32_t n, float cnt) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = accum[i] / cnt;        // pixels = color / cnt (vanilla_renderer.py:120)

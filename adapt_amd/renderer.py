@@ -16,6 +16,13 @@ contribution by its optical length, camera to emitter, as AdaPT's BDPT does in T
     rdr.transient()                # (n_bins, w, h, 3) float32 [t, x, y]: summed radiance of bin t / cnt
     rdr.transient_counts()         # (n_bins, w, h) float32: contributions per bin (upstream's time_cnts)
 
+Path-length images, `pt` only: `Renderer(..., path_lengths=True)` also keeps the render split by path length - the number
+of segments, camera to emitter - and by how the emitter was reached (part 0: by a sampled ray, part 1: by a light sample):
+
+    rdr.path_lengths()             # (max_bounce + 1, 2, w, h, 3) float32 [length - 1, part, x, y]; .sum((0, 1)) is `pixels`
+    rdr.path_length_counts()       # (max_bounce + 1, 2, w, h) float32: contributions per cell
+    rdr.emission(), rdr.direct(), rdr.indirect()      # (w, h, 3): length 1, length 2, lengths 3 and more
+
 Adaptive sampling, `pt` and `vpt`: `Renderer(..., adaptive={"threshold": 0.02, "min_spp": 64, "step": 32})` retires a pixel
 once the relative standard error of its mean is at most `threshold`; decisions fall on global sample numbers that are multiples of `step`
 and >= `min_spp`.  `render(n)` still advances `cnt` by n (the most samples any pixel has); `pixels` divides by each pixel's own count:
@@ -254,9 +261,11 @@ class Renderer:
                  seed: int = 0, spp_per_batch: int = 0, profile: bool = False,
                  width: Optional[int] = None, height: Optional[int] = None,
                  max_bounce: Optional[int] = None, num_shadow_ray: Optional[int] = None, volumetric: Optional[bool] = None,
-                 exact: Optional[bool] = None, transient=None, adaptive=None, aov_spp: int = 32):
+                 exact: Optional[bool] = None, transient=None, adaptive=None, aov_spp: int = 32, path_lengths: bool = False):
         # transient = None / False: steady state; True: time bins from the sensor's sample_count / min_time / interval; a dict overrides them
         # (scene_pack.transient_config).  Surface renderer, at most 4 light samples per vertex, one rank: apt_renderer_create refuses the rest.
+        # path_lengths = True: also keep one image per path length and part; the same limits as transient, and not with it
+        # or with adaptive: apt_renderer_create refuses the rest.
         # exact = True: the bit-parity build (the reference's float32 arithmetic operation for operation; debugging and the exact
         # parity tests), False: the fast build, None: whatever adapt_amd._lib currently hands out (fast unless APT_EXACT=1)
         # adaptive = None: every pixel takes every sample; a dict {"threshold", "min_spp", "step"}: adaptive sampling (adaptive_config)
@@ -267,7 +276,8 @@ class Renderer:
             volumetric = self.VOLUMETRIC
         self.flat: FlatScene = pack_scene(emitters, array_info, objects, prop)
         self.rc: RenderConfig = make_config(prop, width=width, height=height, max_bounce=max_bounce,
-                                            num_shadow_ray=num_shadow_ray, seed=seed, volumetric=bool(volumetric), transient=transient)
+                                            num_shadow_ray=num_shadow_ray, seed=seed, volumetric=bool(volumetric), transient=transient,
+                                            path_lengths=bool(path_lengths))
         self.volumetric = bool(volumetric)
         rc = self.rc
         # attributes the reference's callers read (watermark.py:23-30, render.py:129, path_tracer.py:181-193)
@@ -305,6 +315,8 @@ class Renderer:
         cfg.volumetric = int(self.volumetric)
         cfg.transient_bins, cfg.transient_min_time, cfg.transient_interval = int(rc.transient_bins), float(rc.transient_min_time), float(rc.transient_interval)
         self.n_bins, self.min_time, self.interval = rc.transient_bins, rc.transient_min_time, rc.transient_interval
+        cfg.path_lengths = int(bool(rc.path_lengths))
+        self.n_lengths = rc.max_bounce + 1 if rc.path_lengths else 0          # planes kept: lengths 1 .. max_bounce + 1
         if self.adaptive:
             cfg.adaptive_threshold = self.adaptive["threshold"]
             cfg.adaptive_min_spp, cfg.adaptive_step = self.adaptive["min_spp"], self.adaptive["step"]
@@ -335,7 +347,7 @@ class Renderer:
         self._clear_aov()
 
     def clear(self):
-        """Zero the accumulation, the sample counter, the statistics, the transient bins and the feature buffers."""
+        """Zero the accumulation, the sample counter, the statistics, the transient bins, the path-length planes and the feature buffers."""
         _lib.check(self.lib.apt_reset(self.handle), "apt_reset", self.lib)
         self._cnt = 0
         self._aov_n = 0
@@ -448,6 +460,45 @@ class Renderer:
     def _set_transient(self, cube: np.ndarray):
         cube = np.ascontiguousarray(cube, np.float32)
         _lib.check(self.lib.apt_set_transient(self.handle, _fp(cube)), "apt_set_transient", self.lib)
+
+    # ----------------------------------------------------------- path lengths
+    def _need_path_lengths(self):
+        if not self.n_lengths:
+            raise RuntimeError("this renderer was created without path_lengths=True: there are no path-length planes")
+
+    def tile_path_lengths(self) -> np.ndarray:
+        """This rank's raw planes, (max_bounce + 1, 2, n_cols, h, 4) float32, index [length - 1, part, x, y]: summed r, g, b and the number
+        of contributions.  Part 0: the emitter was reached by a sampled ray, part 1: by a light sample."""
+        self._need_path_lengths()
+        out = np.empty((self.n_lengths, 2, self.n_cols, self.h, 4), np.float32)
+        _lib.check(self.lib.apt_read_path_lengths(self.handle, _fp(out)), "apt_read_path_lengths", self.lib)
+        return out
+
+    def path_lengths(self) -> np.ndarray:
+        """(max_bounce + 1, 2, w, h, 3) float32: the radiance that arrived over paths of each length, by part, divided by the sample count
+        like `pixels`; summed over lengths and parts it is `pixels` up to float summation order."""
+        planes = self.tile_path_lengths()[..., :3]
+        return planes / np.float32(self._cnt if self._cnt > 0 else 1)
+
+    def path_length_counts(self) -> np.ndarray:
+        """(max_bounce + 1, 2, w, h) float32: the number of contributions per cell."""
+        return np.ascontiguousarray(self.tile_path_lengths()[..., 3])
+
+    def emission(self) -> np.ndarray:
+        """(w, h, 3): length 1, the emitters as the camera sees them."""
+        return self.path_lengths()[0].sum(0)
+
+    def direct(self) -> np.ndarray:
+        """(w, h, 3): length 2, direct illumination - both parts, the two MIS strategies ((w, h, 3) of zeros with max_bounce = 0)."""
+        return self.path_lengths()[1:2].sum((0, 1))
+
+    def indirect(self) -> np.ndarray:
+        """(w, h, 3): lengths 3 and more."""
+        return self.path_lengths()[2:].sum((0, 1))
+
+    def _set_path_lengths(self, planes: np.ndarray):
+        planes = np.ascontiguousarray(planes, np.float32)
+        _lib.check(self.lib.apt_set_path_lengths(self.handle, _fp(planes)), "apt_set_path_lengths", self.lib)
 
     def _set_cnt(self, v: int):
         self._steady_only("cnt[None] = ...")
@@ -611,6 +662,7 @@ class Renderer:
                 "cam_orient": np.array(self.cam_orient), "src_num": self.src_num, "cam_t": np.array(self.cam_t),
                 "accumulation": self.color.to_numpy(), "counter": self._cnt,
                 **({"transient_bins": self.tile_transient()} if self.n_bins else {}),
+                **({"path_length_planes": self.tile_path_lengths()} if self.n_lengths else {}),
                 **({"aov_sums": self.tile_aov(), "aov_samples": self._aov_n} if self._aov_n else {}),
                 **(self._adaptive_check_point() if self.adaptive else {})}
 
@@ -627,7 +679,7 @@ class Renderer:
         if not self.adaptive and any(k in check_point for k in self._ADAPTIVE_KEYS):
             raise ValueError("this checkpoint is an adaptive render's: continue it with Renderer(..., adaptive=...)")
         for key, val in check_point.items():
-            if key in ("accumulation", "counter", "transient_bins", "aov_sums", "aov_samples") + self._ADAPTIVE_KEYS:
+            if key in ("accumulation", "counter", "transient_bins", "path_length_planes", "aov_sums", "aov_samples") + self._ADAPTIVE_KEYS:
                 continue
             if key in ("cam_t", "cam_orient"):
                 ok = np.abs(np.asarray(val) - np.asarray(getattr(self, key))).max() < 1e-4
@@ -648,6 +700,9 @@ class Renderer:
         cube = check_point.get("transient_bins")
         if self.n_bins and cube is not None and np.shape(cube) == (self.n_bins, self.n_cols, self.h, 4):
             self._set_transient(cube)           # (a checkpoint of another bin layout, or of a steady render, leaves the bins as they are)
+        planes = check_point.get("path_length_planes")
+        if self.n_lengths and planes is not None and np.shape(planes) == (self.n_lengths, 2, self.n_cols, self.h, 4):
+            self._set_path_lengths(planes)      # (likewise: another layout, or none, leaves the planes as they are)
 
     def summary(self) -> str:
         self.synchronize()
