@@ -85,12 +85,14 @@ SYMBOLS = {
     "apt_bvh_wide_export": (C.c_int, [C.c_void_p, u32p, i32p]),
     "apt_bvh_wide_frame": (C.c_int, [C.c_void_p, f32p, f32p]),
     "apt_bvh_free": (None, [C.c_void_p]),
+    "apt_bvh_build_device": (C.c_int, [f32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), i32p]),
     "apt_bvh_build_linear": (C.c_int, [f32p, C.c_int32, i32p, i32p, C.c_int32, f32p, f32p, C.POINTER(C.c_void_p)]),
     "apt_linear_bvh_counts": (C.c_int, [C.c_void_p, i32p, i32p]),
     "apt_linear_bvh_export": (C.c_int, [C.c_void_p, f32p, f32p, i32p, i32p]),
     "apt_linear_bvh_free": (None, [C.c_void_p]),
     "apt_scene_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     "apt_scene_destroy": (None, [C.c_void_p]),
+    "apt_scene_bvh_builder": (C.c_int, [C.c_void_p, i32p]),
     "apt_renderer_create": (C.c_int, [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(C.c_void_p)]),
     "apt_renderer_destroy": (None, [C.c_void_p]),
     "apt_render": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -180,6 +180,7 @@ struct apt_scene {
     int device = 0;
     DevScene dev{};
     int bvh_levels = 0;                  // levels of the 8-wide tree the kernels walk (the renderers size their traversal stacks by it)
+    int bvh_builder = 0;                 // what built the binary tree under it, after any fallback: 0 host SAH, 1 device LBVH, 2 device PLOC (apt_scene_bvh_builder)
     DevBuf nodes, prims, slot_prim, normals, vnormals, precom, prim_obj, prim_class, obj_info, emitter_id, bxdf, src, sweep_recs, sweep_tab;
     DevBuf flat_recs, flat_tab, flat_pairs;     // flat sweep (fast build, small scenes): records, the per-record table, the records two by two (traverse.hpp FlatScene)
     DevBuf flat_occ, flat_occ_tab;              // ... per emitter, the records that can block its light samples, two by two, and their table
@@ -432,7 +433,7 @@ static int map_objects(const apt_scene_desc* d, std::vector<int>& prim_obj, std:
 // The 8-wide tree the kernels walk, collapsed from a binary tree of single-primitive leaves.  Builder: binned SAH on the host (best tree) below a million primitives, PLOC on the device above (scene-load time); APT_BVH_BUILDER=sah|ploc|lbvh overrides.
 // Measured on one MI355X (Msamples/s, C4 95 k / C5 285 k triangles): SAH 1303 / 1216, PLOC 1287 / 1157, LBVH 1186 / 1048; apt_scene_create at 1.14 M
 // primitives: SAH ~800 ms, PLOC or LBVH ~500 ms (what is left is the 8-wide collapse and the table uploads, shared by all three)
-static int build_tree(const apt_scene_desc* d, int device, apt::WideBvhData& wide, SceneTimer& timer) {
+static int build_tree(const apt_scene_desc* d, int device, apt::WideBvhData& wide, SceneTimer& timer, int& builder) {
     const int N = d->n_prims, O = d->n_objects;
     const int max_leaf = 1;               // primitives per leaf of the binary tree: the 64-byte node's leaf child IS one primitive (measured 1 / 2 / 3 per leaf on the 80-byte node, rounds 2 and 5: C4 1274 / 1236 / 1228, C5 1117 / 1073 / 1043 Msamples/s; C4 extend 34.1 / 33.5 / 33.5 ms, C5's any-hit walk 25.7 / 27.9 / 28.9)
     bool gpu_build = N >= 1000000;
@@ -440,11 +441,12 @@ static int build_tree(const apt_scene_desc* d, int device, apt::WideBvhData& wid
     if (const char* bb = getenv("APT_BVH_BUILDER")) { gpu_build = (!strcmp(bb, "lbvh") || !strcmp(bb, "ploc")) && N >= 2; gpu_algo = !strcmp(bb, "ploc") ? 1 : 0; }
     apt::BvhData bvh;
     int rc = 0;
-    if (gpu_build && (rc = apt::build_bvh_gpu(d->prims, N, d->obj_info, O, device, bvh, gpu_algo)) != 0) {    // a valid scene must load: the host builder takes over (slower, never fails on valid input)
+    if (gpu_build && (rc = apt::build_bvh_gpu(d->prims, N, d->obj_info, O, device, bvh, gpu_algo, &gpu_algo)) != 0) {    // a valid scene must load: the host builder takes over (slower, never fails on valid input)
         fprintf(stderr, "adapt_mi: device BVH build failed (%d), falling back to the host SAH builder\n", rc);
         gpu_build = false;
     }
     if (!gpu_build && apt::build_bvh(d->prims, N, d->obj_info, O, bvh, max_leaf) != 0) return fail(APT_E_INVALID, "apt_scene_create: BVH build failed");
+    builder = gpu_build ? 1 + gpu_algo : 0;        // after the PLOC -> LBVH retry and the host fallback: what apt_scene_bvh_builder reports
     timer.tick(gpu_build ? (gpu_algo ? "binary tree (PLOC, device)" : "binary tree (LBVH, device)") : "binary tree (SAH, host)");
     if (apt::build_wide_bvh(bvh, wide) != 0) return fail(APT_E_INVALID, "apt_scene_create: BVH collapse failed");
     timer.tick("8-wide collapse");
@@ -708,7 +710,7 @@ APT_EXPORT int apt_scene_create(const apt_scene_desc* d, int32_t device, apt_sce
     std::vector<int> prim_obj, prim_class; std::vector<uint8_t> sphere; std::vector<float> prec;     // per primitive: object, material class, sphere flag, precom row
     apt::WideBvhData wide;
     if (int rc = map_objects(d, prim_obj, sphere)) return rc;
-    if (int rc = build_tree(d, device, wide, timer)) return rc;
+    if (int rc = build_tree(d, device, wide, timer, s->bvh_builder)) return rc;
     if (int rc = pack_materials(d, s, prim_obj, prim_class)) return rc;
     if (int rc = pack_primitives(d, s, wide, sphere, prim_obj, prim_class, prec)) return rc;
     timer.tick("primitive records");
@@ -726,6 +728,11 @@ APT_EXPORT int apt_scene_create(const apt_scene_desc* d, int32_t device, apt_sce
     return APT_OK;
 }
 APT_EXPORT void apt_scene_destroy(apt_scene* s) { if (s) { (void)hipSetDevice(s->device); delete s; } }
+APT_EXPORT int apt_scene_bvh_builder(const apt_scene* s, int32_t* builder) {
+    if (!s || !builder) return fail(APT_E_INVALID, "apt_scene_bvh_builder: bad argument");
+    *builder = s->bvh_builder;
+    return APT_OK;
+}
 
 // ---- renderer
 static int owned_columns(const apt_render_cfg& c) {
@@ -1943,6 +1950,46 @@ static int use_device(const char* who, int device) {
     if (int rc = count_device(&ndev)) return rc;
     if (device < 0 || device >= ndev) return fail(APT_E_INVALID, std::string(who) + ": device ordinal out of range");
     HIP_TRY(hipSetDevice(device));
+    return APT_OK;
+}
+// Depth of an exported binary tree (bvh_build.cpp's count: the root node at 0, a leaf one below its node), or -1 when the links do not
+// form a tree of single-primitive leaves over the node array: a link out of range, a node reached twice, a leaf that is not one slot of
+// prim_order (the 8-wide collapse indexes prim_order with it).
+static int binary_tree_depth(const apt::BvhData& t) {
+    const int n_nodes = t.n_nodes(), n_slots = (int)t.prim_order.size();
+    std::vector<uint8_t> seen((size_t)n_nodes, 0);
+    std::vector<std::pair<int32_t, int>> stack{{0, 0}};
+    int depth = 0;
+    while (!stack.empty()) {
+        const auto [node, d] = stack.back(); stack.pop_back();
+        if (node < 0 || node >= n_nodes || seen[(size_t)node]) return -1;
+        seen[(size_t)node] = 1;
+        for (int c = 0; c < 2; c++) {
+            int32_t link; memcpy(&link, &t.nodes[16 * (size_t)node + 12 + (size_t)c], 4);
+            if (link >= 0) { stack.push_back({link, d + 1}); continue; }
+            if (((~link) & 15) != 1 || ((~link) >> 4) >= n_slots) return -1;
+            depth = std::max(depth, d + 1);
+        }
+    }
+    return depth;
+}
+// The device builders of csrc/bvh_gpu.hip on their own, for the tree tests: the handle of apt_bvh_build, filled with the device-built
+// binary tree (single-primitive leaves; `data` and `bin3` are the same tree) and its 8-wide collapse.  No host fallback: a failed
+// device build is an error.  *algo_used: the algorithm whose tree it is (a PLOC build that gave up was retried as LBVH).
+APT_EXPORT int apt_bvh_build_device(const float* prims, int32_t n_prims, const int32_t* obj_info, int32_t n_objects, int32_t device, int32_t algo,
+                                    apt_bvh** out, int32_t* algo_used) {
+    if (!prims || !obj_info || !out || !algo_used || n_prims < 2 || n_objects <= 0 || algo < 0 || algo > 1) return fail(APT_E_INVALID, "apt_bvh_build_device: bad argument");
+    if (n_prims >= (1 << 24)) return fail(APT_E_INVALID, "apt_bvh_build_device: more than 16 777 215 primitives (24-bit indices in the 64-byte tree nodes)");
+    if (int rc = use_device("apt_bvh_build_device", device)) return rc;
+    std::unique_ptr<apt_bvh> b(new apt_bvh());
+    int used = algo;
+    if (const int rc = apt::build_bvh_gpu(prims, n_prims, obj_info, n_objects, device, b->data, algo, &used))
+        return fail(rc <= -10 ? APT_E_HIP : APT_E_STATE, "apt_bvh_build_device: device build failed (" + std::to_string(rc) + (rc <= -10 ? std::string(": ") + hipGetErrorString((hipError_t)(-10 - rc)) : std::string()) + ")");
+    if (b->data.n_nodes() != n_prims - 1 || (b->data.max_depth = binary_tree_depth(b->data)) < 0) return fail(APT_E_STATE, "apt_bvh_build_device: the device build's links do not form a tree");
+    b->bin3 = b->data;
+    if (apt::build_wide_bvh(b->bin3, b->wide) != 0) return fail(APT_E_INVALID, "apt_bvh_build_device: BVH collapse failed");
+    *algo_used = used;
+    *out = b.release();
     return APT_OK;
 }
 struct Probe {

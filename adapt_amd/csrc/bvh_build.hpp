@@ -44,8 +44,9 @@ struct BvhData {
 int build_bvh(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, BvhData& out, int max_leaf = 4);
 
 // bvh_gpu.hip: the same binary tree (single-primitive leaves) built on the device.  algo 0: LBVH (Morton sort + Karras' radix tree +
-// bottom-up fit); algo 1: PLOC (Morton sort + rounds of nearest-neighbour merging by union area: SAH-class quality)
-int build_bvh_gpu(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, int device, BvhData& out, int algo = 0);
+// bottom-up fit); algo 1: PLOC (Morton sort + rounds of nearest-neighbour merging by union area: SAH-class quality).  A PLOC build that
+// gives up is retried as LBVH; *algo_used (may be null) says which of the two built the tree that `out` holds.
+int build_bvh_gpu(const float* prims, int n_prims, const int32_t* obj_info, int n_objects, int device, BvhData& out, int algo = 0, int* algo_used = nullptr);
 
 // 8-wide tree with quantised child boxes, what the traversal kernels walk (bvh_wide.cpp; layout in traverse.hpp).
 struct WideFrame { float gmin[3], gstep[3]; };      // the global grid the node corners live on: world = gmin + gstep * grid (power-of-two steps)

@@ -316,9 +316,11 @@ static int build_bvh_gpu_impl(const float* prims, int n, const int32_t* obj_info
     out.max_depth = 64;                 // a radix tree over 62-bit keys is at most that deep; nobody sizes anything by it (the 8-wide collapse recounts)
     return 0;
 }
-int build_bvh_gpu(const float* prims, int n, const int32_t* obj_info, int n_objects, int device, BvhData& out, int algo) {
+int build_bvh_gpu(const float* prims, int n, const int32_t* obj_info, int n_objects, int device, BvhData& out, int algo, int* algo_used) {
+    int used = algo;
     int rc = build_bvh_gpu_impl(prims, n, obj_info, n_objects, device, out, algo);
-    if (rc != 0 && rc > -10 && algo == 1) rc = build_bvh_gpu_impl(prims, n, obj_info, n_objects, device, out, 0);      // PLOC gave up (-3 .. -5): the radix tree always builds
+    if (rc != 0 && rc > -10 && algo == 1) { used = 0; rc = build_bvh_gpu_impl(prims, n, obj_info, n_objects, device, out, 0); }      // PLOC gave up (-3 .. -5): the radix tree always builds
+    if (algo_used) *algo_used = used;       // the algorithm whose tree `out` holds (meaningful when rc == 0)
     return rc;
 }
 

@@ -63,6 +63,7 @@ ADAPTIVE_DEFAULTS = {"min_spp": 64, "step": 32}
 DENOISE_DEFAULTS = {"firefly_threshold": 0.0, "iterations": 3, "sigma_n": 128.0, "sigma_z": 0.1, "sigma_a": 0.1, "sigma_c": 1.0, "demodulate": True}
 # apt_renderer_info's trace_mode -> name: TRACE_BVH, TRACE_SWEEP, TRACE_TILE, TRACE_FLAT (csrc/stages.hpp), the words of csrc/api.hip kTraversalName in its order
 TRAVERSAL_NAMES = dict(enumerate(("bvh", "sweep", "tile", "flat")))
+BVH_BUILDER_NAMES = dict(enumerate(("sah", "lbvh", "ploc")))      # apt_scene_bvh_builder: what built the scene's tree, after any fallback
 
 
 def adaptive_config(adaptive) -> Optional[dict]:
@@ -628,9 +629,11 @@ class Renderer:
         qb = C.c_int64(0)
         name = C.c_char_p()
         _lib.check(self.lib.apt_renderer_info(self.handle, C.byref(b), C.byref(nq), C.byref(qb), C.byref(lds), C.byref(name), C.byref(tm)), "apt_renderer_info", self.lib)
+        bb = C.c_int32(0)
+        _lib.check(self.lib.apt_scene_bvh_builder(self.scene.handle, C.byref(bb)), "apt_scene_bvh_builder", self.lib)
         return {"spp_per_batch": b.value, "n_subqueues": nq.value, "queue_bytes": qb.value, "lds_bytes": lds.value,
                 "shade_variant": name.value.decode() if name.value else "",
-                "traversal": TRAVERSAL_NAMES.get(tm.value, str(tm.value)), "arithmetic": self.arithmetic,
+                "traversal": TRAVERSAL_NAMES.get(tm.value, str(tm.value)), "bvh_builder": BVH_BUILDER_NAMES.get(bb.value, str(bb.value)), "arithmetic": self.arithmetic,
                 "sampling": "adaptive" if self.adaptive else "uniform", **({"adaptive": dict(self.adaptive)} if self.adaptive else {})}
 
     def camera_fused(self) -> bool:

@@ -7,6 +7,7 @@
  *   apt_bvh_build_linear / apt_linear_bvh_*   tracer/bvh/bvh.cpp:274-296  bvh_cpp.bvh_build(...) (pybind11 module), called from
  *                                   tracer/path_tracer.py:143-179 (bvh_process): the same four arrays in the same layout
  *   apt_bvh_build / apt_bvh_*      the same builder's role for this library's own kernels (binary SAH tree -> 8-wide quantised tree)
+ *   apt_bvh_build_device           (no upstream counterpart) the same handle filled by the device builders (LBVH, PLOC), for the tree tests
  *   apt_flat_records               tracer/tracer_base.py:117-134,184-212: the data of the brute-force intersector, as the flat sweep wants it
  *   apt_flat_occluders             (no upstream counterpart) per emitter, the flat records that can block its light samples
  *   apt_camera_strips              (no upstream counterpart) per 64 local pixels, the flat record pairs a camera ray can hit
@@ -182,6 +183,13 @@ int apt_bvh_wide_counts(const apt_bvh*, int32_t* n_nodes, int32_t* n_levels);
 int apt_bvh_wide_export(const apt_bvh*, uint32_t* nodes /* n_nodes*16 */, int32_t* prim_order /* n_prims */);
 int apt_bvh_wide_frame(const apt_bvh*, float gmin[3], float gstep[3]);
 void apt_bvh_free(apt_bvh*);
+/* The device builders on their own (csrc/bvh_gpu.hip; algo 0 = LBVH, 1 = PLOC): the handle apt_bvh_build fills, holding the device-built
+ * binary tree with single-primitive leaves (apt_bvh_counts / apt_bvh_export; max_depth is the tree's real depth) and its 8-wide collapse
+ * (apt_bvh_wide_*).  Needs n_prims >= 2.  Never falls back to the host builder: a failed device build is an error.  *algo_used: the
+ * algorithm that produced the tree (a PLOC build that gives up is retried as LBVH and reports 0).  Arguments are checked before the device
+ * is looked for; a device ordinal outside 0..count-1 is APT_E_INVALID, "apt_bvh_build_device: device ordinal out of range". */
+int apt_bvh_build_device(const float* prims /* n_prims*9 */, int32_t n_prims, const int32_t* obj_info /* n_objects*3 */, int32_t n_objects,
+                         int32_t device, int32_t algo, apt_bvh** out, int32_t* algo_used);
 
 /* ---- records of the flat sweep (host; csrc/flat_build.cpp).  What the product build's small-scene intersector reads instead of the
  * reference's `prims` / `precom_vec` (tracer/tracer_base.py:117-134,184-212): per planar primitive its corner and the rows of
@@ -238,6 +246,9 @@ void apt_linear_bvh_free(apt_linear_bvh*);
 /* ---- scene / renderer lifetime */
 int apt_scene_create(const apt_scene_desc* desc, int32_t device, apt_scene** out);
 void apt_scene_destroy(apt_scene*);
+/* What built the binary tree under the scene's 8-wide tree, after any fallback: 0 = binned SAH on the host, 1 = LBVH, 2 = PLOC on the device
+ * (the default from a million primitives up; env APT_BVH_BUILDER=sah|lbvh|ploc, read at apt_scene_create, overrides). */
+int apt_scene_bvh_builder(const apt_scene*, int32_t* builder);
 int apt_renderer_create(const apt_scene*, const apt_render_cfg* cfg, apt_renderer** out);
 void apt_renderer_destroy(apt_renderer*);
 

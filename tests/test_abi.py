@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+from bvh_checks import check_binary_tree, check_wide_tree, decode_wide, prim_bounds
 from conftest import ROOT, has_gpu
 from adapt_amd import _lib
 
@@ -170,8 +171,8 @@ def test_volume_probe_checks_its_arguments_before_the_device():
         assert call() == -2 and b"no HIP device" in lib.apt_last_error()
 
 
-ORDINAL_ENTRY_POINTS = ["apt_rng_stream", "apt_bxdf_probe", "apt_transient_bin_probe", "apt_medium_probe", "apt_measure_sclk_mhz"]
-SCENE_ENTRY_POINTS = ["apt_emitter_probe", "apt_texture_probe", "apt_surface_maps_probe"]
+ORDINAL_ENTRY_POINTS = ["apt_rng_stream", "apt_bxdf_probe", "apt_transient_bin_probe", "apt_medium_probe", "apt_measure_sclk_mhz", "apt_bvh_build_device"]
+SCENE_ENTRY_POINTS = ["apt_emitter_probe", "apt_texture_probe", "apt_surface_maps_probe", "apt_scene_bvh_builder"]
 EMITTER_ROW = np.float32([0, 0.1, 0.2, 0.3, 0, 1, 0, 0, -1, 0, 1])       # emitter 0, hit_pos, normal, ray_d, min_depth
 
 
@@ -185,7 +186,10 @@ def _unit_calls(lib):
     vi, vf, vg, in10 = np.int32([2, 2, 2, 2, 0]), np.zeros(33, np.float32), np.zeros(2 * 2 * 2 * 3, np.float32), np.zeros(10, np.float32)
     vf[21:24] = 1
     in10[3:6] = (0, 0, 1)
+    tris, tri_info, handle = np.float32([[[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 0, 1], [1, 0, 1], [0, 1, 1]]]), np.int32([[0, 2, 0]]), C.c_void_p()
     return {
+        "apt_bvh_build_device": lambda dev, n=1: lib.apt_bvh_build_device(fp(tris), 2 * n, ip(tri_info), 1, dev, 1, C.byref(handle), ip(i1)),      # (n = 0: no primitives)
+        "apt_scene_bvh_builder": lambda dev, n=1: lib.apt_scene_bvh_builder(None, ip(i1)),
         "apt_rng_stream": lambda dev, n=1: lib.apt_rng_stream(dev, 0, 0, 0, n, u32.ctypes.data_as(_lib.u32p)),
         "apt_bxdf_probe": lambda dev, n=1: lib.apt_bxdf_probe(dev, n, ip(bi), fp(bf), fp(dirs), 1.0, 0, 0, fp(out)),
         "apt_transient_bin_probe": lambda dev, n=1: lib.apt_transient_bin_probe(dev, n, fp(f1), 0.0, 1.0, 4, ip(i1)),
@@ -207,6 +211,32 @@ def test_unit_entry_point_checks_its_arguments_before_the_device(name):
     assert call(0, 0) == -1 and name.encode() + b": bad argument" in lib.apt_last_error(), lib.apt_last_error()
     if name in ORDINAL_ENTRY_POINTS and not has_gpu():
         assert call(0) == -2 and b"no HIP device" in lib.apt_last_error(), lib.apt_last_error()
+
+
+def test_device_bvh_build_refuses_each_bad_argument_before_the_device():
+    """apt_bvh_build_device: fewer than two primitives, a null array, no objects, an algorithm outside 0..1, a null result pointer - each
+    is APT_E_INVALID with the function's name, the handle stays null, and none of it needs a device.  Without one, a well-formed call
+    fails loudly at the device check: there is no host fallback behind this entry point."""
+    lib = _lib.load()
+    fp, ip = (lambda a: a.ctypes.data_as(_lib.f32p)), (lambda a: a.ctypes.data_as(_lib.i32p))
+    tris, info, used = np.float32([[[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 0, 1], [1, 0, 1], [0, 1, 1]]]), np.int32([[0, 2, 0]]), np.full(1, -7, np.int32)
+    h = C.c_void_p()
+    good = dict(prims=fp(tris), n=2, info=ip(info), n_obj=1, algo=1, out=C.byref(h), used=ip(used))
+
+    def call(**kw):
+        a = {**good, **kw}
+        return lib.apt_bvh_build_device(a["prims"], a["n"], a["info"], a["n_obj"], 0, a["algo"], a["out"], a["used"])
+
+    for kw in ({"n": 1}, {"n": 0}, {"n": -3}, {"prims": None}, {"info": None}, {"n_obj": 0}, {"algo": -1}, {"algo": 2}, {"out": None}, {"used": None}):
+        assert call(**kw) == -1 and b"apt_bvh_build_device: bad argument" in lib.apt_last_error(), (kw, lib.apt_last_error())
+        assert not h.value and used[0] == -7
+    assert call(n=1 << 24) == -1 and b"apt_bvh_build_device: more than 16 777 215 primitives" in lib.apt_last_error()      # the count alone: no array is read
+    if not has_gpu():
+        assert call() == -2 and b"no HIP device" in lib.apt_last_error() and not h.value and used[0] == -7
+        with pytest.raises(_lib.AptError):
+            _lib.check(call(), "apt_bvh_build_device")
+    builder = np.full(1, -7, np.int32)
+    assert lib.apt_scene_bvh_builder(None, ip(builder)) == -1 and b"apt_scene_bvh_builder: bad argument" in lib.apt_last_error() and builder[0] == -7
 
 
 @pytest.mark.gpu
@@ -284,46 +314,12 @@ def build_bvh(fs):
     return nodes, order, dep.value
 
 
-def prim_bounds(fs, k, sphere):
-    v = fs.prims[k]
-    if sphere:
-        return v[0] - v[1], v[0] + v[1]
-    return v.min(axis=0), v.max(axis=0)
-
-
 @pytest.mark.parametrize("tag", ["cbox", "balls_mono", "glass_box"])
 def test_own_bvh_invariants(tag, flat):
-    """Own builder (csrc/bvh_build.cpp): every primitive in exactly one leaf, child boxes bound their subtree."""
+    """Own builder (csrc/bvh_build.cpp): every primitive in exactly one leaf, child boxes bound their subtree (the walker: bvh_checks.py)."""
     fs = flat(tag)
     nodes, order, depth = build_bvh(fs)
-    assert sorted(order.tolist()) == list(range(fs.n_prims))
-    sphere = np.repeat(fs.obj_info[:, 2], fs.obj_info[:, 1]).astype(bool)
-    links = nodes[:, 12:14].copy().view(np.int32)
-    seen_nodes, seen_slots = set(), []
-
-    def walk(link, lo, hi, d):
-        assert d <= depth + 1
-        if link < 0:
-            code = ~int(link)
-            first, count = code >> 4, code & 15
-            assert 0 < count <= 4 or fs.n_prims == 0
-            for s in range(first, first + count):
-                plo, phi = prim_bounds(fs, order[s], sphere[order[s]])
-                assert np.all(plo >= lo) and np.all(phi <= hi)
-                seen_slots.append(s)
-            return
-        assert link not in seen_nodes
-        seen_nodes.add(int(link))
-        nd = nodes[link]
-        for c, (a, b) in enumerate(((0, 3), (6, 9))):
-            clo, chi = nd[a:a + 3], nd[b:b + 3]
-            if lo is not None:
-                assert np.all(clo >= lo - 1e-6) and np.all(chi <= hi + 1e-6)
-            walk(int(links[link, c]), clo, chi, d + 1)
-
-    nd0 = nodes[0]
-    walk(0, None, None, 0)
-    assert sorted(seen_slots) == list(range(fs.n_prims)) and len(seen_nodes) == nodes.shape[0]
+    check_binary_tree(fs, nodes, order, depth)
 
 
 def test_bvh_on_subdivided_mesh():
@@ -491,65 +487,19 @@ def build_wide(fs):
     return nodes, order, lv.value, (gmin, gstep)
 
 
-def decode_wide(nodes):
-    """64-byte nodes (csrc/bvh_wide.cpp) -> per node: corner (3,) in grid units, scale (3,) = 2^e in grid units, leaf mask, inner mask,
-    child_base, tri_base, qlo (3, 8), qhi (3, 8)"""
-    w = nodes.astype(np.int64)
-    corner = np.stack([w[:, 0] & 0xffff, w[:, 0] >> 16, w[:, 1] & 0xffff], 1)
-    lmask, imask = (w[:, 1] >> 16) & 0xff, w[:, 1] >> 24
-    ex = np.stack([(w[:, 2] >> 24) & 15, w[:, 2] >> 28, (w[:, 3] >> 24) & 15], 1)
-    assert ((w[:, 3] >> 28) == 0).all()
-    by = np.ascontiguousarray(nodes[:, 4:16]).view(np.uint8).reshape(-1, 6, 8)
-    return corner, np.ldexp(1.0, ex), lmask, imask, w[:, 2] & 0xffffff, w[:, 3] & 0xffffff, by[:, 0:3], by[:, 3:6]
-
-
 @pytest.mark.parametrize("scene", ["cbox", "balls_mono", "bunnies1"])
 def test_wide_bvh_invariants(scene, flat):
     """Every primitive sits in exactly one leaf child (one primitive per leaf, at most eight per node); inner children are consecutive and
     counted by the inner-slot mask, leaf primitives by the leaf-slot mask; every decoded child box contains the boxes of all primitives
-    below it (the quantisation rounds outwards, the 16-bit corner lies at or below the node's box)."""
+    below it (the quantisation rounds outwards, the 16-bit corner lies at or below the node's box).  The walker: bvh_checks.py."""
     if scene == "bunnies1":
         from adapt_amd.scene_pack import pack_scene
         from adapt_amd.synth import three_bunnies
         fs = pack_scene(*three_bunnies(1))
     else:
         fs = flat(scene)
-    nodes, order, levels, (gmin, gstep) = build_wide(fs)
-    assert sorted(order.tolist()) == list(range(fs.n_prims))
-    assert np.all(np.log2(gstep.astype(np.float64)) % 1 == 0)                           # power-of-two steps: the grid transform is exact
-    corner, sc, lmask, imask, cbase, tbase, qlo, qhi = decode_wide(nodes)
-    assert (corner >= 0).all() and (corner <= 65535).all() and (lmask & imask == 0).all()
-    sphere = np.repeat(fs.obj_info[:, 2], fs.obj_info[:, 1]).astype(bool)
-    seen_nodes, seen_slots, depth_seen = set(), [], [0]
-    g0, gs = gmin.astype(np.float64), gstep.astype(np.float64)
-
-    def walk(n, d):
-        assert n not in seen_nodes and d <= levels
-        seen_nodes.add(n); depth_seen[0] = max(depth_seen[0], d)
-        lo_all, hi_all = np.full(3, np.inf), np.full(3, -np.inf)
-        rank, tri_next = 0, 0
-        for s in range(8):
-            leaf, inner = bool((lmask[n] >> s) & 1), bool((imask[n] >> s) & 1)
-            if not (leaf or inner):
-                assert (qlo[n, :, s] == 255).all() and (qhi[n, :, s] == 0).all()          # inverted box: never hit
-                continue
-            blo = g0 + gs * (corner[n] + qlo[n, :, s].astype(np.float64) * sc[n])            # world = gmin + gstep * (corner + q * 2^e), exact in double
-            bhi = g0 + gs * (corner[n] + qhi[n, :, s].astype(np.float64) * sc[n])
-            if inner:
-                clo, chi = walk(int(cbase[n]) + rank, d + 1)
-                rank += 1
-            else:
-                slot = int(tbase[n]) + tri_next
-                a, b = prim_bounds(fs, order[slot], sphere[order[slot]])
-                clo, chi = a.astype(np.float64), b.astype(np.float64)
-                seen_slots.append(slot)
-                tri_next += 1
-            assert np.all(blo <= clo) and np.all(bhi >= chi), (n, s)
-            lo_all, hi_all = np.minimum(lo_all, clo), np.maximum(hi_all, chi)
-        return lo_all, hi_all
-
-    walk(0, 1)
-    assert sorted(seen_slots) == list(range(fs.n_prims)) and len(seen_nodes) == nodes.shape[0] and depth_seen[0] == levels
+    nodes, order, levels, frame = build_wide(fs)
+    check_wide_tree(fs, nodes, order, levels, frame)
     if fs.n_prims > 1000:
         assert nodes.shape[0] < fs.n_prims / 2.5 and levels <= 12         # 64-byte nodes over single-primitive leaves
 

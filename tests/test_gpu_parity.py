@@ -915,11 +915,13 @@ def test_device_bvh_builder_gives_the_same_answers(bunnies_small, monkeypatch):
     for builder in ("sah", "lbvh", "ploc"):
         monkeypatch.setenv("APT_BVH_BUILDER", builder)
         r = Renderer(*bunnies_small, width=64, height=64)
+        assert r.info()["bvh_builder"] == builder                 # the builder asked for built the tree: no PLOC -> LBVH retry, no host fallback
         prim, t, uv = r.intersect(o, d)
         assert np.array_equal(prim, prim_o) and np.array_equal(t, t_o) and np.array_equal(uv[prim >= 0], uv_o[prim >= 0]), builder
         assert np.array_equal(r.occluded(o, d, tmax), occ_o), builder
         r.close()
         f = Renderer(field[0], field[1], field[2], cfg)
+        assert f.info()["bvh_builder"] == builder
         f.render(n_spp=3)
         images[builder] = f.color.to_numpy()
         assert f.stats()["n_samples"] == 3 * 120 * 80
@@ -951,6 +953,7 @@ def test_million_primitive_scene_takes_the_device_builder(monkeypatch):
         r = Renderer(field[0], field[1], field[2], cfg)
         try:
             assert r.info()["traversal"] == "bvh"
+            assert r.info()["bvh_builder"] == ("ploc" if builder is None else "sah")      # what the test's name says: otherwise it compares the SAH tree with itself
             prim, t, uv = r.intersect(o, d)
             occ = r.occluded(o, d, tmax)
             r.render(n_spp=2)
@@ -984,6 +987,17 @@ def test_tree_builders_on_degenerate_inputs(builder, monkeypatch):
     scenes.append(b.finish(light, _sensor(64, 64, 4, 1)))
     b = _Builder(); b.mesh(np.concatenate([tri, tri + np.float32([0.3, 0.2, 0.8])]), white)
     scenes.append(b.finish(light, _sensor(64, 64, 4, 1)))
+    # the room plus 30 spheres (the builders' sphere branch): tiny, large, overlapping, concentric, and two identical ones
+    b = _Builder(); _room(b, white, white, white)
+    rs = np.random.RandomState(32)
+    balls = [((2.3, 1.8, 2.7), 1e-3), ((3.2, 2.9, 2.4), 2e-3), ((2.6, 1.6, 2.8), 1.1), ((1.6, 2.6, 3.0), 0.9)]                   # tiny, large (and overlapping)
+    balls += [((1.4, 1.0, 2.4), r) for r in (0.05, 0.2, 0.4, 0.6)]                                                               # concentric
+    balls += [((3.3, 3.3, 2.3), 0.3)] * 2                                                                                       # identical
+    balls += [(tuple(rs.uniform([1.0, 0.5, 2.0], [3.6, 3.6, 3.4])), float(rs.uniform(0.05, 0.5))) for _ in range(30 - len(balls))]
+    assert len(balls) == 30
+    for centre, radius in balls:
+        b.sphere(centre, radius, white)
+    scenes.append(b.finish(light, _sensor(64, 64, 4, 1)))
     rs = np.random.RandomState(31)
     for tup in scenes:
         n = 6000
@@ -991,14 +1005,18 @@ def test_tree_builders_on_degenerate_inputs(builder, monkeypatch):
         tgt = rs.uniform([1.0, 0.5, 2.0], [3.6, 3.6, 3.4], size=(n, 3)).astype(np.float32)
         d = tgt - o; d /= np.linalg.norm(d, axis=1, keepdims=True)
         tmax = rs.uniform(0.5, 8.0, n).astype(np.float32)
-        sc = ob.OracleScene(pack_scene(*tup), make_config(tup[3]).cam_t)
+        fs = pack_scene(*tup)
+        sc = ob.OracleScene(fs, make_config(tup[3]).cam_t)
         _, prim_o, t_o, uv_o, _ = sc.intersect(o, d)
+        is_sphere_prim = np.repeat(fs.obj_info[:, 2], fs.obj_info[:, 1]).astype(bool)
         r = Renderer(*tup, width=32, height=32)
         try:
-            assert r.info()["traversal"] == "bvh"
+            assert r.info()["traversal"] == "bvh" and r.info()["bvh_builder"] == builder        # the builder asked for, not a fallback
             prim, t, uv = r.intersect(o, d)
             assert (prim_o >= 0).sum() > n // 10
-            assert np.array_equal(prim, prim_o) and np.array_equal(t, t_o) and np.array_equal(uv[prim >= 0], uv_o[prim >= 0])
+            tri_hit = (prim >= 0) & ~is_sphere_prim[np.maximum(prim, 0)]    # barycentrics are only defined (and used) for triangles
+            assert is_sphere_prim.sum() in (0, 30) and (not is_sphere_prim.any() or (is_sphere_prim[prim_o[prim_o >= 0]]).sum() > n // 10)
+            assert np.array_equal(prim, prim_o) and np.array_equal(t, t_o) and np.array_equal(uv[tri_hit], uv_o[tri_hit])
             assert np.array_equal(r.occluded(o, d, tmax), sc.occluded(o, d, tmax))
             r.render(n_spp=2)
             assert np.isfinite(r.color.to_numpy()).all()
