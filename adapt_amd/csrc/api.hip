@@ -45,16 +45,17 @@ typedef void (*shade_cam_fn)(DevScene, Params, Queues, Counters*, const unsigned
 typedef void (*shade_tr_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int, TransQ);
 // transient: fn's time-resolved twin (k_shade_tr); traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced:
 // flat sweep, one light sample per vertex); traced_cam: traced's camera-fed twin (k_shade_traced_cam: bounce 0 of a steady full-film batch, no k_generate_trace in front of it);
-// traced_staged: traced with its record staged in LDS a row ahead (shade_traced, STAGE; null: the variant has no such form)
-struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; shade_traced_fn traced; shade_cam_fn traced_cam; shade_traced_fn traced_staged; };
+// traced_staged: traced with its record staged in LDS a row ahead (shade_traced, STAGE; null: the variant has no such form);
+// traced_staged_live, traced_cam_live: traced_staged and traced_cam with live rows (shade_traced, LIVE; null: no such form)
+struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; shade_traced_fn traced; shade_cam_fn traced_cam; shade_traced_fn traced_staged, traced_staged_live; shade_cam_fn traced_cam_live; };
 #if APT_FAST
 #define APT_FLAT_FN(...) __VA_ARGS__
 #else
 #define APT_FLAT_FN(...) nullptr          // the flat sweep exists in the fast build only (traverse.hpp), and with it the shade kernels that trace their rays on its records
 #endif
 #define APT_TRACED_PAIR(STEM, ...) APT_FLAT_FN(STEM<__VA_ARGS__>), APT_FLAT_FN(STEM##_cam<__VA_ARGS__>)
-#define APT_TRACED_PLAIN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced, BM, SM, TEX), nullptr
-#define APT_TRACED_LEAN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced_lean, BM, SM), APT_FLAT_FN(k_shade_traced_lean_staged<BM, SM>)
+#define APT_TRACED_PLAIN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced, BM, SM, TEX), nullptr, nullptr, nullptr
+#define APT_TRACED_LEAN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced_lean, BM, SM), APT_FLAT_FN(k_shade_traced_lean_staged<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_staged_live<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_cam_live<BM, SM>)
 #define APT_SHADE_VARIANT(BM, SM, TEX, NAME, TRACED) {BM, SM, NAME, k_shade<BM, SM, TEX>, k_shade_tr<BM, SM, TEX>, APT_TRACED_##TRACED(BM, SM, TEX)}
 static const ShadeVariant kShadeVariants[] = {
     APT_SHADE_VARIANT(APT_BX_LAMBERTIAN, APT_SRC_POINT, 0, "lambertian/point", LEAN),
@@ -239,7 +240,9 @@ struct apt_renderer {
     DevBuf accum, scratch, pix_key;
     DevBuf cam_strips;            // rays traced in place: per 64 local pixels, the record pairs a camera ray can hit (flat_build.cpp camera_strips)
     int record_stage = 0;         // rays traced in place: 1 = the queue-fed shade kernel stages its record in LDS a row ahead (ShadeVariant::traced_staged; APT_RECORD_STAGE=0 switches it off)
-    shade_traced_fn traced_fn = nullptr;      // the queue-fed kernel of a PIPE_TRACED render: shade->traced_staged or shade->traced
+    shade_traced_fn traced_fn = nullptr;      // the queue-fed kernel of a PIPE_TRACED render: shade->traced_staged[_live] or shade->traced
+    int live_rows = 0;            // rays traced in place: 1 = the staged and the camera-fed shade kernel run their live-row form (ShadeVariant::traced_staged_live, traced_cam_live; APT_LIVE_ROWS=0 switches it off)
+    shade_cam_fn traced_cam_fn = nullptr;     // the camera-fed kernel of a PIPE_TRACED render: shade->traced_cam_live or shade->traced_cam
     int camera_fuse = 0;          // rays traced in place: 1 = the camera vertex is shaded by the kernel that traces the camera ray (k_shade_traced_cam; steady full-film renders with max_bounce >= 1, APT_CAMERA_FUSE=0 switches it off)
     int light_strips = 0;         // rays traced in place, camera-fed: 1 = some strip mask of the camera vertex's light samples leaves a pair out (cam_strips' second part, flat_build.cpp light_strips; APT_LIGHT_STRIPS=0 switches them off)
     Counters host_counters{};
@@ -850,7 +853,10 @@ static int pick_shading(apt_renderer* r) {
     p.traced = (r->pipeline == PIPE_TRACED) ? 1 : 0;
     const bool want_stage = !(getenv("APT_RECORD_STAGE") && atoi(getenv("APT_RECORD_STAGE")) == 0);
     r->record_stage = (p.traced && want_stage && r->shade->traced_staged != nullptr) ? 1 : 0;
-    r->traced_fn = r->record_stage ? r->shade->traced_staged : r->shade->traced;
+    const bool want_live = !(getenv("APT_LIVE_ROWS") && atoi(getenv("APT_LIVE_ROWS")) == 0);
+    r->live_rows = (p.traced && want_live && r->shade->traced_staged_live != nullptr && r->shade->traced_cam_live != nullptr) ? 1 : 0;
+    r->traced_fn = r->record_stage ? (r->live_rows ? r->shade->traced_staged_live : r->shade->traced_staged) : r->shade->traced;
+    r->traced_cam_fn = r->live_rows ? r->shade->traced_cam_live : r->shade->traced_cam;
     // flat sweep with several light samples per vertex: the samples are queued by vertex and the shadow kernel adds a vertex's samples with
     // one read-modify-write (stages.hpp k_shadow_flat); otherwise 2-4 samples per vertex add into one radiance plane each (stages.hpp
     // APT_EXCLUSIVE_L) - a transient or path-length render always, its bins want the samples apart
@@ -1473,7 +1479,7 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
             if (r->camera_fuse) {
                 // the camera vertex in one launch (no k_generate_trace, no record of the camera ray), then the ordinary bounce-0 launch for the
                 // handful of camera rays it staged for the reference-order code: that launch's prologue resolves them, its loop shades them
-                { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->shade->traced_cam, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips); }
+                { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->traced_cam_fn, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips); }
                 { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->traced_fn, dim3(r->grid_fix), dim3(BLOCK), 0, st, sc, p, q, cnt, 0, 0); }
                 cur = 1; b0 = 1;
             } else {
@@ -2121,6 +2127,11 @@ APT_EXPORT int apt_renderer_light_strips(const apt_renderer* r, int32_t* out) {
 APT_EXPORT int apt_renderer_record_staged(const apt_renderer* r, int32_t* out) {
     if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_record_staged: null argument");
     *out = r->record_stage;
+    return APT_OK;
+}
+APT_EXPORT int apt_renderer_live_rows(const apt_renderer* r, int32_t* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_live_rows: null argument");
+    *out = r->live_rows;
     return APT_OK;
 }
 APT_EXPORT int apt_renderer_info(const apt_renderer* r, int32_t* spp_batch, int32_t* n_subqueues, int64_t* queue_bytes, int32_t* lds_bytes, const char** shade_variant, int32_t* trace_mode) {

@@ -303,6 +303,64 @@ APT_D f3 emit_and_scatter(const ShadeArgs3* A_, Vertex& vx, R& rng, float& new_p
     vx.thr = vx.thr * fdiv3(spec, new_pdf);
     return new_d;
 }
+// ---- the live-row forms of steps 1 and 2 (shade_traced, LIVE): every lane of a row holds a valid record - a lane past the queue's end the
+// last entry's, a path the roulette ended its own - and computes on it straight-line; `alive` masks what a dead lane must not do: vote,
+// count, append, store.  Written as `if (alive) {compute} else {defaults}` the steps make the compiler give every value a dead lane "has"
+// a definition (v_mov of 0 / 1.0 / -1 and the phi copies behind them: a quarter of the moves of C2's row loop), because sweeps and stores
+// behind read them unconditionally.  Per live lane the arithmetic is the parent's, operation for operation.
+// Draw-window vertices only (Lambertian surfaces, emitters that draw nothing): the emission MIS weight has no reader there.
+// -> the vertex is still alive; where the roulette or the throughput cut ended it, rng.draw - vx.draw0 is what it drew (one word or none).
+template <int BM, int SM>
+APT_D bool open_vertex_live(const ShadeArgs3* A_, Vertex& vx, DrawWindow& rng, f3 rec_kd, uint32_t pm, int bounce, bool alive, const uint32_t* jitter_tail = nullptr) {
+    static_assert(BM == APT_BX_LAMBERTIAN && !(SM & APT_SRC_AREA), "a draw window serves [roulette] index [index] u1 u2: Lambertian surfaces, emitters that draw nothing");
+    vx.bx.k_d = rec_kd;
+    const uint32_t lp = vx.id & ((1u << (A_->p).pix_bits) - 1u), s = vx.id >> (A_->p).pix_bits;
+    vx.l_off = (s * (uint32_t)(A_->p).npix + lp) << 2;
+    vx.draw0 = (pm >> 8) & 0xffffu;
+    const uint32_t key0 = ((A_->p).world == 1) ? lp : ldq((A_->p).pix_key, lp << 2), ctr0 = (uint32_t)((A_->p).cnt_base + (int)s + 1);
+    bool roulette = false; float mx = 0.f;
+    if ((A_->p).use_rr) { mx = max3(vx.thr); roulette = mx < (A_->p).rr_threshold && bounce >= (A_->p).rr_bounce_th; }
+    else alive = alive && !(max3(vx.thr) < 1e-4f);
+    const bool relight = vx.hit_light >= 0 && (A_->sc).n_sources > 1;
+    const bool have_first = jitter_tail != nullptr && (A_->p).anti_alias != 0;
+    uint32_t c[4] = {0u, 0u, have_first ? jitter_tail[0] : 0u, have_first ? jitter_tail[1] : 0u};
+    // (the second block's vote counts the lanes the parent's branch would hold)
+    const bool live = window_open(rng, key0, (A_->p).seed, ctr0, vx.draw0, roulette, mx, relight, c, have_first, [alive](bool v) { return __any(v && alive) != 0; });
+    if (roulette) vx.thr = vx.thr * srcp(mx + 1e-7f);
+    return alive && live;
+}
+template <int BM, int SM, typename R>
+APT_D LightSample sample_light_live(const ShadeArgs3* A_, Vertex& vx, R& rng, const EmitterGeom& geom, const DevSrc src_only, bool active) {
+    LightSample ls;
+    const int ns = (A_->sc).n_sources;
+    int sidx = rng_int(rng);
+    sidx = (ns == 1) ? 0 : pymod(sidx, ns);
+    float emitter_pdf = (A_->p).inv_ns;
+    if (ns <= 1) active = active && vx.hit_light < 0;        // on the scene's only light: one index drawn, nothing sampled
+    else if (vx.hit_light >= 0) {
+        sidx = rng_int(rng);
+        sidx = (ns == 2) ? 0 : pymod(sidx, ns - 1);
+        if (sidx >= vx.hit_light) sidx += 1;
+        emitter_pdf = (A_->p).inv_ns1;
+    }
+    DevSrc src = src_only;
+    if (ns != 1) src = (A_->sc).src[sidx];
+    ls.src = sidx;
+    f3 shadow_int; float direct_pdf;
+    const f3 to_emitter = emitter_sample_hit<SM>(src, geom, vx.hit_point, rng, shadow_int, direct_pdf) - vx.hit_point;
+    ls.dist = fnorm(to_emitter);
+    ls.dir = fdiv3(to_emitter, ls.dist);
+    ls.sampled = active;
+    const f3 direct_spec = surface_eval<BM>(vx.bx, vx.it, vx.d, ls.dir, (A_->sc).world_ior, (A_->p).two_sides);
+    ls.mis_w = 1.0f;
+    if ((A_->p).use_mis && !(src.bool_bits & 0x01)) ls.mis_w = balance(emitter_pdf * direct_pdf, surface_pdf<BM>(vx.bx, vx.it, ls.dir, vx.d, (A_->sc).world_ior, (A_->p).two_sides));
+    ls.poisoned = active && isnan(ls.mis_w);
+    f3 c = (direct_spec * shadow_int) * ls.mis_w;
+    if (ns != 1) c = fdiv3(c, emitter_pdf);
+    ls.contrib = (c * (A_->p).inv_S) * vx.thr;
+    ls.want = active && !ls.poisoned && !(ls.contrib.x == 0.f && ls.contrib.y == 0.f && ls.contrib.z == 0.f);
+    return ls;
+}
 // a shadow-queue entry (k_shadow / shadow_flat_body read these planes)
 APT_D void shadow_store(const Queues& q, uint32_t so, f3 o, f3 dir, float dist, f3 contrib) {
     st3q(q.sh_o, q.sh_cap, so, o); st3q(q.sh_d, q.sh_cap, so, dir); stq(q.sh_tmax, so, dist); st3q(q.sh_c, q.sh_cap, so, contrib);
@@ -343,9 +401,18 @@ APT_D void tally_flush(const ShadeTally& t, const uint32_t* s_draws, Counters* c
 // the row, before its stores (a wait at the next row's top would also wait for those stores to be acknowledged: one in-order counter).
 // Lanes past the queue's end stage its last entry, never used: no address leaves the sub-queue's region; nothing is staged for an empty
 // sub-queue or behind the last row.  STAGE = false is the kernel with the direct loads, instruction for instruction.
-template <int BM, int SM, int TEX, bool CAM = false, bool STAGE = false>
+//
+// LIVE, live rows (the staged and the camera-fed form of the lean kernels): every lane of a row shades a valid record
+// straight-line - a lane past the queue's end the last entry's, which it staged; a lane past the id space's end the ray of its pixel; a
+// path the roulette ended its own - and `alive` masks effects only: votes, tallies, appends, stores (open_vertex_live, sample_light_live
+// above).  vertex_reset is no default provider there: what it writes is overwritten for every lane, or a constant of the Lambertian
+// kernel.  At the last bounce the continuation is not sampled; `draw` moves on by its two words.  LIVE = false is the parent's kernel,
+// instruction for instruction.
+template <int BM, int SM, int TEX, bool CAM = false, bool STAGE = false, bool LIVE_ = false>
 APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, const unsigned long long* strips = nullptr) {
     static_assert(!(CAM && STAGE), "a camera-fed row loads no record");
+    static_assert(!LIVE_ || ((CAM || STAGE) && TEX == 0), "live rows: the staged and the camera-fed form of the lean kernels");
+    constexpr bool LIVE = LIVE_ && APT_DRAW_WINDOW != 0;      // (live rows are written for the draw window: a build without it, -DAPT_DRAW_WINDOW=0, keeps the parent's form under the live kernels' names)
     const ShadeArgs3* A_ = args_fresh(A0);                      // scene, parameters, queues: read through the kernel-argument segment, re-fetched per phase (APT_ARGS_PHASE)
     const int cur = CAM ? 0 : cur_, bounce = CAM ? 0 : bounce_;
     const int nxt = cur ^ 1;
@@ -431,7 +498,51 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         f3 Lc = splat3(0.f);                                   // the radiance the path has gathered so far (camera rays carry none: nothing is read at bounce 0)
         bool entry = alive;
         float ray_pdf = 1.f;
-        if constexpr (CAM) {
+        if constexpr (CAM && LIVE) {
+            // ---- the camera vertex, live rows: a lane past the id space's end makes the ray of its pixel, and a ray that hit nothing or is left
+            // to the reference-order code is shaded on whatever record the resolve gives it; `valid`, `c_defer`, `alive` mask the effects
+            const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)sl.q;
+            const uint32_t id_ = w * 64u + lane_id();
+            const bool valid = alive && id_ < cam_total;
+            uint32_t draws = 0;
+            uint32_t jitter_tail[2] = {0u, 0u};
+            const uint32_t lp = id_ % (uint32_t)(A_->p).npix, s = id_ / (uint32_t)(A_->p).npix;      // (past the end: a pixel of the film all the same, a sample no batch holds)
+            int i, j; local_to_global((A_->p), lp, i, j);
+            if (valid) for (int pl = 0; pl < (A_->p).l_planes; pl++) stL((A_->q).L, (A_->p).cap, (id_ << 2) | (uint32_t)pl, splat3(0.f));
+            const f3 dir = camera_ray_dir((A_->p), i, j, s, draws, WINDOW ? jitter_tail : nullptr);
+            vx.id = (s << (A_->p).pix_bits) | lp;
+            if (valid && draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
+            const f3 cam_o = mk3((A_->p).cam_t[0], (A_->p).cam_t[1], (A_->p).cam_t[2]);
+            float c_t = 0.f; int c_run = -1, c_idx = -1;
+            if (__any(valid)) c_idx = flat_closest1<true>((A_->sc).flat, cam_o, dir, 1e7f, c_t, c_run, camera_strip_mask((A_->p), strips, w));
+            const bool c_defer = valid && (c_run >= 0 || flat_needs_cull((A_->sc).flat, dir));
+            HitRec hr; int hit_cls = 0;
+            flat_resolve((A_->sc).flat, max(c_idx, 0), c_t, cam_o, dir, hr, hit_cls);
+            { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
+            if (__any(c_defer)) {                             // left to the reference-order code: staged with an empty hit record, as k_generate_trace stages it
+                const int ncls = (A_->q).tr_ncls;
+                const uint32_t dpos = wave_append(c_defer, &cnt->n_tr[0][ncls][sl.q * CNT_PAD]);
+                if (c_defer) {
+                    const uint32_t slot = (A_->q).tr_stage_top ? qbase + (A_->p).subcap - 1u - dpos : (uint32_t)ncls * (A_->p).cap + qbase + dpos, so = slot << 4;
+                    float one = 1.f, far_ = 1e7f, zero = 0.f;
+                    asm volatile("" : "+v"(one), "+v"(far_), "+v"(zero));      // (made here, in the rare branch: as constants the words are hoisted in front of the row loop and spilled there, see the parent's form below)
+                    stq((A_->q).tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, far_));
+                    stq((A_->q).tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(-1, draws, false))));
+                    stq((A_->q).tr[0][2], so, make_float4(one, one, one, __uint_as_float(vx.id)));
+                    stq((A_->q).tr[0][3], so, make_float4(zero, zero, zero, one));
+                    if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = zero; uv_.y = zero; stq((A_->q).tr_uv[0], slot << 3, uv_); }
+                }
+            }
+            entry = valid && !c_defer;
+            alive = entry && c_idx >= 0 && hr.prim >= 0;      // nothing hit: the path ends where it began, nothing gathered
+            vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
+            f3 rec_kd;
+            build_hit((A_->sc), max(hr.prim, 0), hr.t, hr.u, hr.v, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+            const bool opened = alive;
+            alive = open_vertex_live<BM, SM>(A_, vx, rng, rec_kd, tr_pack(hr.prim, draws, false), 0, alive, WINDOW ? jitter_tail : nullptr);
+            if (opened && !alive && rng.draw != vx.draw0) atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);      // the roulette's word of a path it ended
+        }
+        if constexpr (CAM && !LIVE) {
             // ---- the camera vertex: the ray is made, swept against its strip's records and, where that settles it, shaded right here
             const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)sl.q;
             const uint32_t id_ = w * 64u + lane_id();
@@ -483,10 +594,24 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
             // (the record landed before the row in front of this one stored its own - staged_wait below; nothing at a row's top waits on vector memory)
             staged_read(s_rec + lane_id(), sa, sb, sc_, sd);    // (plane D's words are read at bounce 0 too, where nothing was staged into them: never used)
             { const int rp = max(tr_prim(__float_as_uint(sb.w)), 0); rec4 pa, pb; staged_read2(s_prim + 2 * rp, pa, pb); cu_ra = make_float4(pa.x, pa.y, pa.z, pa.w); cu_rb = make_float4(pb.x, pb.y, pb.z, pb.w); }
-            if (alive && bounce > 0) { Lc = mk3(sd.x, sd.y, sd.z); if (SM & APT_SRC_AREA) ray_pdf = sd.w; }
+            if constexpr (!LIVE) if (alive && bounce > 0) { Lc = mk3(sd.x, sd.y, sd.z); if (SM & APT_SRC_AREA) ray_pdf = sd.w; }
+        }
+        if constexpr (LIVE && STAGE) {
+            // every lane unpacks the record it staged; `alive` goes on to mask the row's effects
+            if (bounce > 0) Lc = mk3(sd.x, sd.y, sd.z);
+            vx.o = mk3(sa.x, sa.y, sa.z); vx.d = mk3(sb.x, sb.y, sb.z); vx.thr = mk3(sc_.x, sc_.y, sc_.z); vx.id = __float_as_uint(sc_.w);
+            const uint32_t pm = __float_as_uint(sb.w);
+            const int prim = tr_prim(pm);
+            alive = alive && prim >= 0;                          // nothing hit: path ends (vanilla_renderer.py:49)
+            f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
+            if ((A_->sc).has_vn) { if (alive) uv = ldq((A_->q).tr_uv[cur], idx << 3); }
+            build_hit_rec((A_->sc), cu_ra, cu_rb, max(prim, 0), sa.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+            const bool opened = alive;
+            alive = open_vertex_live<BM, SM>(A_, vx, rng, rec_kd, pm, bounce, alive);
+            if (opened && !alive && rng.draw != vx.draw0) lds_add_unordered(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);      // the roulette's word of a path it ended
         }
         if (!CAM && !STAGE && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & APT_SRC_AREA) ray_pdf = dd.w; }
-        if (!CAM && alive) {
+        if (!CAM && !LIVE && alive) {
             float4 a, b_, c;
             if constexpr (STAGE) { a = make_float4(sa.x, sa.y, sa.z, sa.w); b_ = make_float4(sb.x, sb.y, sb.z, sb.w); c = make_float4(sc_.x, sc_.y, sc_.z, sc_.w); }
             else { a = ldq(trA, idx << 4); b_ = ldq(trB, idx << 4); c = ldq(trC, idx << 4); }
@@ -509,14 +634,16 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
 #ifdef APT_NEAR_STATS      // diagnostic build (tools/gpu_near_probe.py): shaded vertices that sit within 2e-3 of the vertex before them - rays that re-hit the surface they left
         t_near += wave_count(alive && bounce > 0 && vx.it.min_depth < 2e-3f);
 #endif
-        if (alive) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
+        if (LIVE || alive) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
 
         APT_ARGS_PHASE();
         // ---- next-event estimation: the vertex's light sample waits in registers and is swept at the end of the row, when little else is live
         bool break_flag = false;
         DevSrc src_only;                                      // the scene's only light, read once through the scalar path
         if ((A_->sc).n_sources == 1) src_only = ld_src_uniform((A_->sc).src);
-        const LightSample f = sample_light<BM, SM, false>(A_, vx, rng, geom, src_only, alive, break_flag);      // (one light sample per vertex: api.hip pick_shading, PIPE_TRACED)
+        LightSample f;                                         // (one light sample per vertex: api.hip pick_shading, PIPE_TRACED)
+        if constexpr (LIVE) f = sample_light_live<BM, SM>(A_, vx, rng, geom, src_only, alive);
+        else f = sample_light<BM, SM, false>(A_, vx, rng, geom, src_only, alive, break_flag);
         if (f.poisoned) Lc = splat3(f.mis_w);
         tl.shadow += wave_count(f.sampled); tl.poison += wave_count(f.poisoned);
         // the records the row's light samples are swept against (traverse.hpp flat_occ_list): the occluder list of the emitter that every
@@ -540,11 +667,19 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         bool cont = false, is_spec = false;
         f3 new_d = mk3(0.f, 1.f, 0.f);
         float new_pdf = 1.f;
-        if (alive) {
+        if constexpr (LIVE) {
+            // the last bounce's continuation has no reader: its two words are passed over (wave-uniform)
+            if ((bounce + 1) < (A_->p).max_bounce) { new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { Lc = Lc + add; }); cont = alive; }
+            else rng.draw += 2u;
+            if (alive) {
+                if constexpr (STAGE) lds_add_unordered(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
+                else atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
+            }
+        } else if (alive) {
             new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { Lc = Lc + add; });
             cont = (bounce + 1) < (A_->p).max_bounce;
         }
-        if (rng.draw != vx.draw0) {                            // also paths that died in the roulette
+        if (!LIVE && rng.draw != vx.draw0) {                   // also paths that died in the roulette
             if constexpr (STAGE) lds_add_unordered(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
             else atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
         }
@@ -795,6 +930,11 @@ template <int BM, int SM>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_WAVES, APT_TRACED_WAVES))) k_shade_traced_lean_staged(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) {
     shade_traced<BM, SM, 0, false, true>(kernel_args3(), cnt, cur, bounce);
 }
+// ... and the staged kernel with live rows (shade_traced, LIVE); APT_LIVE_ROWS=0 selects the kernel above
+template <int BM, int SM>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_WAVES, APT_TRACED_WAVES))) k_shade_traced_lean_staged_live(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) {
+    shade_traced<BM, SM, 0, false, true, true>(kernel_args3(), cnt, cur, bounce);
+}
 // ... and their camera-fed twins (shade_traced, CAM): bounce 0 of a steady full-film batch, in place of k_generate_trace + the first launch above
 template <int BM, int SM, int TEX = 0>
 __global__ void __launch_bounds__(BLOCK) k_shade_traced_cam(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) {
@@ -806,6 +946,10 @@ __global__ void __launch_bounds__(BLOCK) k_shade_traced_cam(DevScene sc, Params 
 template <int BM, int SM>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_CAM_WAVES, APT_TRACED_CAM_WAVES))) k_shade_traced_lean_cam(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) {
     shade_traced<BM, SM, 0, true>(kernel_args3(), cnt, 0, 0, strips);
+}
+template <int BM, int SM>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_CAM_WAVES, APT_TRACED_CAM_WAVES))) k_shade_traced_lean_cam_live(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) {
+    shade_traced<BM, SM, 0, true, false, true>(kernel_args3(), cnt, 0, 0, strips);
 }
 #endif
 

@@ -657,6 +657,13 @@ class Renderer:
         _lib.check(self.lib.apt_renderer_record_staged(self.handle, C.byref(f)), "apt_renderer_record_staged", self.lib)
         return bool(f.value)
 
+    def live_rows(self) -> bool:
+        """apt_renderer_live_rows: the staged and the camera-fed shade kernel run their live-row form (rays traced in place, Lambertian
+        surfaces under point lights; APT_LIVE_ROWS=0 at creation selects the kernels that give dead lanes default values)."""
+        f = C.c_int32(0)
+        _lib.check(self.lib.apt_renderer_live_rows(self.handle, C.byref(f)), "apt_renderer_live_rows", self.lib)
+        return bool(f.value)
+
     # ------------------------------------------------------------ checkpoint
     def get_check_point(self) -> dict:
         """Same keys as the reference's pickle (path_tracer.py:181-193)."""

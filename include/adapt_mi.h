@@ -347,6 +347,10 @@ int apt_renderer_light_strips(const apt_renderer*, int32_t* in_use);
 /* Rays traced in place: *staged = 1 when the queue-fed shade kernel stages each row's path record in LDS a row ahead (the Lambertian /
  * point-light kernel; env APT_RECORD_STAGE=0, read at apt_renderer_create, selects the kernel that loads the record where it is used), else 0. */
 int apt_renderer_record_staged(const apt_renderer*, int32_t* staged);
+/* Rays traced in place: *live = 1 when the staged and the camera-fed shade kernel run their live-row form - every lane of a row computes on a
+ * valid record, a dead lane's effects are masked (the Lambertian / point-light kernels; env APT_LIVE_ROWS=0, read at apt_renderer_create,
+ * selects the kernels that give dead lanes default values), else 0. */
+int apt_renderer_live_rows(const apt_renderer*, int32_t* live);
 
 /* Shader clock (MHz) with every CU busy: cycle counter against the 100 MHz wall clock over a full-grid FMA chain (~1 ms).
  * bench.py prices the VALU roofline of the trace kernels with it.  (No reference counterpart.) */
