@@ -48,7 +48,7 @@ class RenderCfg(C.Structure):
                 ("inv_focal", C.c_float), ("half_w", C.c_float), ("half_h", C.c_float), ("seed", C.c_uint32),
                 ("band_width", C.c_int32), ("rank", C.c_int32), ("world_size", C.c_int32),
                 ("spp_per_batch", C.c_int32), ("device", C.c_int32), ("profile", C.c_int32), ("volumetric", C.c_int32),
-                ("path_lengths", C.c_int32),
+                ("light_groups", C.c_int32), ("path_lengths", C.c_int32),
                 ("adaptive_threshold", C.c_float), ("adaptive_min_spp", C.c_int32), ("adaptive_step", C.c_int32),
                 ("transient_bins", C.c_int32), ("transient_min_time", C.c_float), ("transient_interval", C.c_float)]
 
@@ -57,10 +57,10 @@ class Stats(C.Structure):
     _fields_ = [("n_samples", C.c_int64), ("n_extend", C.c_int64), ("n_shade", C.c_int64), ("n_shadow", C.c_int64),
                 ("n_shadow_traced", C.c_int64), ("n_lit", C.c_int64), ("n_draws", C.c_int64), ("n_poisoned", C.c_int64),
                 ("launches", C.c_int64 * APT_N_KERNELS), ("kernel_ms", C.c_double * APT_N_KERNELS), ("render_ms", C.c_double),
-                ("n_track", C.c_int64)]
+                ("n_track", C.c_int64), ("n_stray_light", C.c_int64)]
 
     def as_dict(self):
-        d = {k: int(getattr(self, k)) for k in ("n_samples", "n_extend", "n_shade", "n_shadow", "n_shadow_traced", "n_lit", "n_draws", "n_poisoned", "n_track")}
+        d = {k: int(getattr(self, k)) for k in ("n_samples", "n_extend", "n_shade", "n_shadow", "n_shadow_traced", "n_lit", "n_draws", "n_poisoned", "n_track", "n_stray_light")}
         d["launches"] = dict(zip(KERNEL_NAMES, [int(x) for x in self.launches]))
         d["kernel_ms"] = dict(zip(KERNEL_NAMES, [float(x) for x in self.kernel_ms]))
         d["render_ms"] = float(self.render_ms)
@@ -106,6 +106,9 @@ SYMBOLS = {
     "apt_set_transient": (C.c_int, [C.c_void_p, f32p]),
     "apt_read_path_lengths": (C.c_int, [C.c_void_p, f32p]),
     "apt_set_path_lengths": (C.c_int, [C.c_void_p, f32p]),
+    "apt_read_light_groups": (C.c_int, [C.c_void_p, f32p]),
+    "apt_set_light_groups": (C.c_int, [C.c_void_p, f32p]),
+    "apt_relight": (C.c_int, [C.c_void_p, f32p, f32p]),
     "apt_read_sample_counts": (C.c_int, [C.c_void_p, i32p, u8p]),
     "apt_read_moments": (C.c_int, [C.c_void_p, f64p]),
     "apt_set_adaptive_state": (C.c_int, [C.c_void_p, i32p, f64p, u8p]),

@@ -20,6 +20,10 @@ image (cropped like it).  Not with `--transient`.
 `--path_lengths` (with `--type pt`): the render split by path length: one image per length - segments, camera to
 emitter; 1 emission, 2 direct light, 3 and more indirect - as `<img_name>-<scene file stem>-pt-len01.<ext>` ..., both parts summed, cropped
 and normalised like the image, and the (lengths, 2, w, h, 3) array as `...-pt-lengths.npy`.  Not with `--transient` or `--noise_threshold`.
+`--light_groups` (with `--type pt`): the render split by emitter: one image per emitter of the scene file, in its order, as
+`<img_name>-<scene file stem>-pt-light00.<ext>` ..., both parts summed, cropped and normalised like the image, and the (emitters, 2, w, h, 3)
+array as `...-pt-lights.npy`.  `--light_gain id=g` or `id=r,g,b` (repeatable; `id` is the emitter's XML id, the others keep gain 1) also writes
+the image relit with those gains as `...-pt-relit.<ext>`.  Not with `--transient`, `--path_lengths` or `--noise_threshold`.
 `--denoise` (with `--type pt`; `--firefly_threshold t`, `--save_aov`): the frame through the firefly filter (t > 0) and the edge-avoiding
 a-trous filter, written as `<img_name>-<scene file stem>-<type>-denoised.<ext>` next to the image (cropped and normalised
 like it); `--save_aov` writes the feature buffers the filter was guided by as `...-<type>-aov.npz` (albedo, normal, depth, hit_fraction).
@@ -72,6 +76,8 @@ def get_options(argv=None):
     p.add_argument("--spp_per_batch", default=0, type=int, help="samples per wavefront batch (0: automatic)")
     p.add_argument("--transient", default=False, action="store_true", help="time-resolved output (pt only; the sensor's sample_count / min_time / interval)")
     p.add_argument("--path_lengths", default=False, action="store_true", help="also write one image per path length (pt only): ...-len01.<ext> (emission), -len02 (direct), ... and ...-lengths.npy")
+    p.add_argument("--light_groups", default=False, action="store_true", help="also write one image per emitter (pt only): ...-light00.<ext>, -light01, ... and ...-lights.npy")
+    p.add_argument("--light_gain", default=[], action="append", metavar="ID=G", help="with --light_groups: also write ...-relit.<ext>, the image with emitter ID's share times G (one number, or r,g,b); repeatable")
     p.add_argument("--noise_threshold", default=0., type=float, help="adaptive sampling: a pixel stops once the relative standard error of its mean is <= this (0: off)")
     p.add_argument("--min_spp", default=64, type=int, help="adaptive sampling: no pixel stops before this many samples")
     p.add_argument("--adaptive_step", default=32, type=int, help="adaptive sampling: pixels are retired at sample numbers that are multiples of this")
@@ -146,6 +152,21 @@ def _folder(path: str) -> str:
     return path
 
 
+def parse_light_gains(items) -> dict:
+    """["id=g", "id=r,g,b", ...] -> {id: g or (r, g, b)}; ValueError names the item it cannot read."""
+    gains = {}
+    for item in items:
+        key, sep, val = item.partition("=")
+        try:
+            nums = [float(v) for v in val.split(",")]
+        except ValueError:
+            nums = []
+        if not sep or not key or len(nums) not in (1, 3) or not all(np.isfinite(nums)):
+            raise ValueError(f"{item!r} is not id=g or id=r,g,b with finite numbers")
+        gains[key] = nums[0] if len(nums) == 1 else tuple(nums)
+    return gains
+
+
 def main(argv=None) -> int:
     opts = get_options(argv)
     if opts.type not in ("pt", "vpt"):
@@ -162,6 +183,26 @@ def main(argv=None) -> int:
         return 2
     if opts.path_lengths and opts.noise_threshold > 0:
         print("--path_lengths with --noise_threshold: path-length images need every pixel's samples; adaptive sampling and --path_lengths do not combine", file=sys.stderr)
+        return 2
+    if opts.light_groups and opts.type != "pt":
+        print(f"--light_groups: light groups exist for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
+        return 2
+    if opts.light_groups and opts.transient:
+        print("--light_groups with --transient: time x emitter cubes are not built; light groups and --transient do not combine", file=sys.stderr)
+        return 2
+    if opts.light_groups and opts.path_lengths:
+        print("--light_groups with --path_lengths: length x emitter planes are not built; light groups and --path_lengths do not combine", file=sys.stderr)
+        return 2
+    if opts.light_groups and opts.noise_threshold > 0:
+        print("--light_groups with --noise_threshold: light groups need every pixel's samples; adaptive sampling and --light_groups do not combine", file=sys.stderr)
+        return 2
+    if opts.light_gain and not opts.light_groups:
+        print("--light_gain: relighting needs the per-emitter planes; give --light_groups as well", file=sys.stderr)
+        return 2
+    try:
+        light_gains = parse_light_gains(opts.light_gain)
+    except ValueError as e:
+        print(f"--light_gain: {e}", file=sys.stderr)
         return 2
     if (opts.denoise or opts.save_aov) and opts.type != "pt":
         print(f"--denoise / --save_aov: feature buffers and the denoiser exist for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
@@ -189,9 +230,13 @@ def main(argv=None) -> int:
     emitters, array_info, objs, cfg = scene_parsing(os.path.join(opts.input_path, opts.scene), opts.name)
     print(f"[adapt_amd] scene '{opts.scene}/{opts.name}': {array_info['primitives'].shape[0]} primitives, {len(objs)} objects, "
           f"{len(emitters)} emitters, parsed in {time.time() - t0:.3f} s")
+    unknown = [k for k in light_gains if k not in [e.id for e in emitters]]
+    if unknown:
+        print(f"--light_gain: no emitter with id {unknown[0]!r} in {opts.name}; it has {[e.id for e in emitters]}", file=sys.stderr)
+        return 2
     rdr = Renderer(emitters, array_info, objs, cfg, device=opts.device, seed=opts.seed, profile=opts.profile,
                    width=opts.width, height=opts.height, max_bounce=opts.max_bounce, spp_per_batch=opts.spp_per_batch,
-                   transient=True if opts.transient else None, adaptive=adaptive, path_lengths=opts.path_lengths)
+                   transient=True if opts.transient else None, adaptive=adaptive, path_lengths=opts.path_lengths, light_groups=opts.light_groups)
     stem = opts.name[:-4]
     max_iter = (opts.iter_num if opts.iter_num > 0 else cfg.get("iter_num", 2000)) + 1          # render.py:80-81
     chk_file = os.path.join(_folder(opts.chkpt_path), f"{opts.img_name}-{stem}-{opts.type}.pkl")
@@ -282,6 +327,21 @@ def main(argv=None) -> int:
         for i in range(frames.shape[0]):
             write_image(frames[i], f"{base}-len{i + 1:02d}.{opts.img_ext}")
         print(f"[adapt_amd] wrote {frames.shape[0]} path-length images {base}-len01.{opts.img_ext} ... and {base}-lengths.npy")
+    if opts.light_groups and not opts.no_save_fig:
+        base = os.path.join(opts.output_path, f"{opts.img_name}-{stem}-{opts.type}")
+
+        def shown(a):                           # cropped and scaled like the image: the written frames still add up to the written image
+            a = a[..., rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y, :] if rdr.do_crop else a
+            return a / scale if scale is not None else a
+        planes = rdr.light_groups()
+        np.save(f"{base}-lights.npy", planes)
+        frames = shown(planes.sum(1))
+        for i in range(frames.shape[0]):
+            write_image(frames[i], f"{base}-light{i:02d}.{opts.img_ext}")
+        print(f"[adapt_amd] wrote {frames.shape[0]} light-group images {base}-light00.{opts.img_ext} ... (emitters {rdr.emitter_ids}) and {base}-lights.npy")
+        if light_gains:
+            write_image(shown(rdr.relit(light_gains)), f"{base}-relit.{opts.img_ext}")
+            print(f"[adapt_amd] wrote {base}-relit.{opts.img_ext} (gains {light_gains})")
     if opts.transient:
         export_transient(rdr, opts.output_path, stem, opts.img_ext, opts.normalize)      # render.py:166: folder named after the scene file
     rdr.close()

@@ -225,7 +225,7 @@ struct Lane {
 //   PIPE_SORTED      extend into per-class queues, the class kernels in groups, shadow  (render_surface)
 //   PIPE_TRACED      the shade kernel traces its rays itself: one launch per bounce     (render_surface; product build, shade_stage.hpp "rays traced in place")
 //   PIPE_VOLUMETRIC  extend, k_vevent, one kernel per event queue, transmittance walk   (render_volumetric)
-// Transient, path-length and adaptive renders are modifiers on top of it (apt_renderer::transient, ::lengths, ::adaptive).
+// Transient, path-length, light-group and adaptive renders are modifiers on top of it (apt_renderer::transient, ::lengths, ::light_groups, ::adaptive).
 enum Pipeline { PIPE_STAGED, PIPE_SORTED, PIPE_TRACED, PIPE_VOLUMETRIC };
 
 struct apt_renderer {
@@ -289,7 +289,12 @@ struct apt_renderer {
     // twins, its per-path arrays (tq, tr_pool), one lane -, the records settled by segment count instead of by time
     int lengths = 0;
     DevBuf len_planes;                    // (max_bounce + 1) x 2 x owned pixels float4
-    bool split() const { return transient || lengths; }      // the TR shade twins run: every bounce's contributions are kept apart
+    // light-group render (apt_render_cfg.light_groups; stages.hpp k_bin_lights / k_relight): the same selection once more, the
+    // twins storing emitter indices (TransQ::by_light), the records settled by emitter
+    int light_groups = 0;
+    DevBuf lg_planes;                     // n_sources x 2 x owned pixels float4
+    DevBuf lg_aux;                        // 16 bytes: the stray-record tally (uint32) | n_sources x 3 gains | owned pixels x 3 relit image
+    bool split() const { return transient || lengths || light_groups; }      // the TR shade twins run: every bounce's contributions are kept apart
     // adaptive sampling (apt_render_cfg.adaptive_threshold > 0; stages.hpp AdaptQ)
     int adaptive = 0;
     AdaptQ aq{};
@@ -754,7 +759,7 @@ static int plan_film(apt_renderer* r) {
     if (r->npix <= 0) { return fail(APT_E_INVALID, "apt_renderer_create: this rank owns no pixels"); }
     r->n_lanes = 3;   // measured on C2: 1 lane 1 827, 2 lanes 2 196, 3 lanes 2 268, 4 lanes 2 178 Msamples/s (round 2, 64 spp per lane-batch); round 5, 32 Mi paths per lane-batch: C2 4 559 / 4 590 / 4 287 with 2 / 3 / 4, C5 1 844 / 2 028 / 2 129 with 1 / 2 / 3; volumetric scenes with null surfaces ran four lanes in rounds 3-4 (the fourth hid the host read-backs of their tails): at this batch size V1 1 374 with three, 1 299 with four
     if (const char* nl = getenv("APT_LANES")) r->n_lanes = std::min(4, std::max(1, atoi(nl)));
-    if (c.transient_bins > 0 || c.path_lengths) r->n_lanes = 1;      // the bins (the length planes) are shared by every batch and added to per bounce: one lane keeps the adds in order
+    if (c.transient_bins > 0 || c.path_lengths || c.light_groups) r->n_lanes = 1;      // the bins (the length planes, the light-group planes) are shared by every batch and added to per bounce: one lane keeps the adds in order
     const size_t nq = (size_t)r->nq;
     // queue capacity of a batch of b: whole waves, dealt over the sub-queues (generate: wave w -> sub-queue w % nq)
     auto subcap_of = [&](int b) { const size_t n_waves = ((size_t)r->npix * (size_t)b + 63) / 64; return ((n_waves + nq - 1) / nq) * 64; };
@@ -900,6 +905,7 @@ static int pick_shading(apt_renderer* r) {
     if (r->transient) r->shade_name += " [transient]";
     if (r->adaptive) r->shade_name += " [adaptive]";
     if (r->lengths) r->shade_name += " [path lengths]";
+    if (r->light_groups) r->shade_name += " [light groups]";
     // (sorted: extend appends every hit path's record to the packed queue of its material class, Queues::cq)
     const int si = (r->pipeline == PIPE_SORTED) ? 1 : 0;
     r->extend = r->dyn_fetch ? kExtendDyn[si] : (r->trace_mode == TRACE_FLAT ? kExtendFlatHot[si] : kExtend[r->trace_mode][si]);
@@ -1096,23 +1102,30 @@ static int make_adaptive(apt_renderer* r) {
 }
 
 // Transient render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the bins, all zero-filled.  A
-// path-length render takes the same per-path arrays and, in place of the bins, its length planes.
+// path-length render takes the same per-path arrays and, in place of the bins, its length planes; a light-group render its per-emitter
+// planes, and the twins are told to store emitter indices in place of times (TransQ::by_light).
 static int make_transient(apt_renderer* r) {
     if (!r->split()) return APT_OK;
     const apt_render_cfg& c = r->cfg;
     const size_t cap = r->par.cap, planes = (size_t)r->par.l_planes;
     const size_t words = cap + 4 * cap + planes * cap;
-    DevBuf& out = r->transient ? r->tr_bins : r->len_planes;
-    const size_t cells = (r->transient ? (size_t)c.transient_bins : ((size_t)c.max_bounce + 1) * 2) * (size_t)r->npix;
+    DevBuf& out = r->transient ? r->tr_bins : (r->lengths ? r->len_planes : r->lg_planes);
+    const size_t cells = (r->transient ? (size_t)c.transient_bins : (r->lengths ? (size_t)c.max_bounce + 1 : (size_t)r->scene->n_sources) * 2) * (size_t)r->npix;
     hipError_t e;
     if ((e = r->tr_pool.alloc(words * 4)) != hipSuccess || (e = out.alloc(cells * 16)) != hipSuccess)
-        return fail(APT_E_NOMEM, std::string(r->transient ? "transient bins: " : "path-length planes: ") + hipGetErrorString(e));
+        return fail(APT_E_NOMEM, std::string(r->transient ? "transient bins: " : (r->lengths ? "path-length planes: " : "light-group planes: ")) + hipGetErrorString(e));
     HIP_TRY(hipMemsetAsync(r->tr_pool.p, 0, words * 4, r->stream()));
     HIP_TRY(hipMemsetAsync(out.p, 0, cells * 16, r->stream()));
     float* base = r->tr_pool.as<float>();
     TransQ& t = r->tq;
     t.t_path = base; t.emit = reinterpret_cast<float4*>(base + cap); t.t_light = base + 5 * cap;
-    if (!r->transient) return APT_OK;      // (a path-length render: no bins, no window - the times the twins store are not read)
+    t.by_light = r->light_groups;
+    if (r->light_groups) {                 // the tally of records that named no emitter, and the relight kernel's gains and image
+        if ((e = r->lg_aux.alloc(16 + (size_t)r->scene->n_sources * 12 + (size_t)r->npix * 12)) != hipSuccess)
+            return fail(APT_E_NOMEM, std::string("light-group planes: ") + hipGetErrorString(e));
+        HIP_TRY(hipMemsetAsync(r->lg_aux.p, 0, 16, r->stream()));
+    }
+    if (!r->transient) return APT_OK;      // (a path-length or light-group render: no bins, no window - the times the twins store are not read)
     t.bins = r->tr_bins.as<float4>();
     transient_window(t, c.transient_bins, c.transient_min_time, c.transient_interval);
     return APT_OK;
@@ -1250,6 +1263,20 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
         if (c.adaptive_threshold > 0.f)
             return fail(APT_E_INVALID, "apt_renderer_create: path-length images and adaptive sampling do not combine (adaptive_threshold must be 0 when path_lengths = 1)");
     }
+    if (c.light_groups != 0 && c.light_groups != 1) return fail(APT_E_INVALID, "apt_renderer_create: light_groups must be 0 (off) or 1");
+    if (c.light_groups) {
+        if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: light groups are a surface-renderer mode (volumetric = 0)");
+        if (c.num_shadow_ray > 4) return fail(APT_E_INVALID, "apt_renderer_create: light groups take at most 4 light samples per vertex (num_shadow_ray <= 4)");
+        if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: light groups run on one rank (world_size = 1)");
+        if (c.transient_bins > 0)
+            return fail(APT_E_INVALID, "apt_renderer_create: light groups and transient rendering do not combine (transient_bins must be 0 when light_groups = 1)");
+        if (c.path_lengths)
+            return fail(APT_E_INVALID, "apt_renderer_create: light groups and path-length images do not combine (path_lengths must be 0 when light_groups = 1)");
+        if (c.adaptive_threshold > 0.f)
+            return fail(APT_E_INVALID, "apt_renderer_create: light groups and adaptive sampling do not combine (adaptive_threshold must be 0 when light_groups = 1)");
+        if (sc->n_sources <= 0) return fail(APT_E_INVALID, "apt_renderer_create: light groups need a scene with emitters (n_sources > 0)");
+        if (sc->n_sources >= (1 << 24)) return fail(APT_E_INVALID, "apt_renderer_create: light groups keep the emitter index in a float (n_sources < 2^24)");
+    }
     if (!std::isfinite(c.adaptive_threshold)) return fail(APT_E_INVALID, "apt_renderer_create: adaptive_threshold must be finite (> 0: adaptive sampling, <= 0: off)");
     if (c.adaptive_threshold > 0.f) {
         if (c.transient_bins > 0)
@@ -1261,7 +1288,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     apt_renderer* r = new apt_renderer();
     struct Owner { apt_renderer* r; ~Owner() { if (r) apt_renderer_destroy(r); } } owner{r};     // every early return below releases streams, events and queue pools
     r->scene = sc; r->cfg = c;
-    r->adaptive = c.adaptive_threshold > 0.f ? 1 : 0; r->transient = c.transient_bins > 0 ? 1 : 0; r->lengths = c.path_lengths ? 1 : 0;
+    r->adaptive = c.adaptive_threshold > 0.f ? 1 : 0; r->transient = c.transient_bins > 0 ? 1 : 0; r->lengths = c.path_lengths ? 1 : 0; r->light_groups = c.light_groups ? 1 : 0;
     if (int rc = plan_film(r)) return rc;
     pick_traversal(r);
     if (int rc = pick_shading(r)) return rc;
@@ -1503,9 +1530,11 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
         // transient: a bounce's records are binned once its light samples are all settled - after its shadow launch, or with the flat sweep
         // after the next bounce's fix-up launch (it serves the deferred ones) - and before the next shade launch writes new ones
         // path lengths: the same launch points; `settled` is the bounce whose records they are (with the flat sweep the previous one)
+        // light groups: the same launch points
         auto bin = [&](int settled) {
             LaunchTimer t(r, APT_K_FINALIZE, st, false);
-            if (r->lengths) hipLaunchKernelGGL(k_bin_lengths, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->len_planes.as<float4>(), settled, r->accum.as<float>());
+            if (r->light_groups) hipLaunchKernelGGL(k_bin_lights, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->lg_planes.as<float4>(), r->scene->n_sources, r->lg_aux.as<unsigned int>(), r->accum.as<float>());
+            else if (r->lengths) hipLaunchKernelGGL(k_bin_lengths, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->len_planes.as<float4>(), settled, r->accum.as<float>());
             else hipLaunchKernelGGL(k_bin_transient, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->accum.as<float>());
         };
         int cur = 0;
@@ -1682,12 +1711,41 @@ APT_EXPORT int apt_set_path_lengths(apt_renderer* r, const float* in) {
     HIP_TRY(hipMemcpyAsync(r->len_planes.p, in, r->len_planes.bytes, hipMemcpyHostToDevice, r->stream()));
     return resolve_events(r);
 }
+APT_EXPORT int apt_read_light_groups(apt_renderer* r, float* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_read_light_groups: bad argument");
+    if (!r->light_groups) return fail(APT_E_STATE, "apt_read_light_groups: the renderer was created with light_groups = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(out, r->lg_planes.p, r->lg_planes.bytes, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
+APT_EXPORT int apt_set_light_groups(apt_renderer* r, const float* in) {
+    if (!r || !in) return fail(APT_E_INVALID, "apt_set_light_groups: bad argument");
+    if (!r->light_groups) return fail(APT_E_STATE, "apt_set_light_groups: the renderer was created with light_groups = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(r->lg_planes.p, in, r->lg_planes.bytes, hipMemcpyHostToDevice, r->stream()));
+    return resolve_events(r);
+}
+// out = the owned tile relit: every emitter's planes times its rgb gain, summed, / cnt (stages.hpp k_relight); [local col][y][rgb] like apt_read_pixels
+APT_EXPORT int apt_relight(apt_renderer* r, const float* gains, float* out) {
+    if (!r || !gains || !out) return fail(APT_E_INVALID, "apt_relight: bad argument");
+    if (!r->light_groups) return fail(APT_E_STATE, "apt_relight: the renderer was created with light_groups = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    const int ne = r->scene->n_sources;
+    float* d_gain = reinterpret_cast<float*>(static_cast<char*>(r->lg_aux.p) + 16);
+    float* d_out = d_gain + 3 * (size_t)ne;
+    HIP_TRY(hipMemcpyAsync(d_gain, gains, (size_t)ne * 12, hipMemcpyHostToDevice, r->stream()));
+    hipLaunchKernelGGL(k_relight, dim3((unsigned)(((size_t)r->npix + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, r->stream(), (const float4*)r->lg_planes.as<float4>(), (const float*)d_gain, d_out, r->npix, ne, (float)(r->cnt > 0 ? r->cnt : 1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)r->npix * 12, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
 APT_EXPORT int apt_reset(apt_renderer* r) {
     if (!r) return fail(APT_E_INVALID, "apt_reset: null handle");
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
     if (r->transient) HIP_TRY(hipMemsetAsync(r->tr_bins.p, 0, r->tr_bins.bytes, r->stream()));
     if (r->lengths) HIP_TRY(hipMemsetAsync(r->len_planes.p, 0, r->len_planes.bytes, r->stream()));
+    if (r->light_groups) { HIP_TRY(hipMemsetAsync(r->lg_planes.p, 0, r->lg_planes.bytes, r->stream())); HIP_TRY(hipMemsetAsync(r->lg_aux.p, 0, 16, r->stream())); }
     if (r->aov_sum.p) HIP_TRY(hipMemsetAsync(r->aov_sum.p, 0, r->aov_sum.bytes, r->stream()));
     for (Lane& ln : r->lanes) HIP_TRY(hipMemsetAsync(ln.counters.p, 0, sizeof(Counters), r->stream()));      // lanes are idle between render calls
     r->cnt = 0;
@@ -1774,6 +1832,7 @@ APT_EXPORT int apt_get_stats(apt_renderer* r, apt_stats* out) {
 #endif
     for (int k = 0; k < APT_N_KERNELS; k++) { out->launches[k] = r->launches[k]; out->kernel_ms[k] = r->kernel_ms[k]; }
     out->render_ms = r->render_ms;
+    if (r->light_groups) { unsigned int stray = 0; HIP_TRY(hipMemcpy(&stray, r->lg_aux.p, 4, hipMemcpyDeviceToHost)); out->n_stray_light = (int64_t)stray; }
     if (n_overflow > 0) return fail(APT_E_STATE, "apt_get_stats: " + std::to_string((long long)n_overflow) + " volumetric path(s) drew more than 2^23 random numbers: the draw index wrapped and those paths re-used part of their stream");
     return APT_OK;
 }

@@ -775,7 +775,8 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
 // (126 -> 129 VGPRs) in every scene WITHOUT textures, and out of line it costs a call frame in scratch.
 // TR: transient render (stages.hpp TransQ): the vertex's optical length is carried by slot, each light sample's time is kept next to its
 // radiance plane, and the emitter-hit contribution goes to the slot's record with its time instead of into L.  TR = false is the steady
-// kernel, unchanged.
+// kernel, unchanged.  In a light-group render (TransQ::by_light, wave-uniform) the two stored words name the emitter - LightSample::src,
+// Vertex::hit_light, as floats: exact below 2^24 - where a transient render stores a time; every other word is the transient twin's.
 template <int BM, int SM, int TEX, bool CQ, bool TR = false>
 APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur, int bounce, TransQ tq = TransQ{}) {
     const ShadeArgs3* A_ = args_fresh(A0);                      // scene, parameters, queues: read through the kernel-argument segment, re-fetched per phase (APT_ARGS_PHASE)
@@ -870,7 +871,7 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
                     stq((A_->q).sh_id, so, vx.l_off | (((A_->p).l_planes > 1) ? (uint32_t)s : 0u));
                     // its time: the vertex's plus the connection segment's length in the world's medium (an unoccluded segment crosses no
                     // surface: bdpt.py:372,397 with vpt.py track_ray); kept by radiance plane, which only this sample adds into this bounce
-                    if constexpr (TR) tq.t_light[(size_t)(((A_->p).l_planes > 1) ? s : 0) * (A_->p).cap + (vx.l_off >> 2)] = t_vx + ls.dist * (A_->sc).world_ior;
+                    if constexpr (TR) tq.t_light[(size_t)(((A_->p).l_planes > 1) ? s : 0) * (A_->p).cap + (vx.l_off >> 2)] = tq.by_light ? (float)ls.src : t_vx + ls.dist * (A_->sc).world_ior;      // (a light-group render: the emitter sampled, k_bin_lights)
                 }
             }
         }
@@ -880,7 +881,7 @@ APT_D void shade_staged(args3_ptr A0, Counters* cnt, const ShadeIn& in, int cur,
         f3 new_d = mk3(0.f, 1.f, 0.f);
         float new_pdf = 1.f;
         if (alive) {
-            if constexpr (TR) new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { tq.emit[vx.l_off >> 2] = make_float4(add.x, add.y, add.z, t_vx); });      // binned at the vertex's time (k_bin_transient)
+            if constexpr (TR) new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { tq.emit[vx.l_off >> 2] = make_float4(add.x, add.y, add.z, tq.by_light ? (float)vx.hit_light : t_vx); });      // binned at the vertex's time (k_bin_transient), or by the emitter hit (k_bin_lights)
             else new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { add_radiance((A_->q).L, (A_->p).cap, vx.l_off, add, true); });      // (nothing else touches the path's slot while its shade kernel runs)
             cont = (bounce + 1) < (A_->p).max_bounce;
             if constexpr (TR) if (cont) tq.t_path[vx.l_off >> 2] = t_vx;

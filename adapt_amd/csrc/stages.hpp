@@ -148,6 +148,7 @@ struct TransQ {
     float4* bins;             // [bin][local pixel]: summed rgb of the contributions that landed in the bin, and their number
     int n_bins;
     float min_time, interval, max_time;      // max_time = min_time + interval * n_bins, rounded to float as upstream stores it (bdpt.py:99)
+    int by_light;             // light-group render: emit[].w and t_light[] take the emitter's index instead of a time (wave-uniform)
 };
 // bdpt.py:164-165: a contribution at time t lands in bin int((t - min_time) / interval) when min_time < t < max_time (float32, IEEE
 // division in both builds); -1: outside the window.  The clamp keeps a t that rounds up to the window's end inside the last bin.
@@ -1266,6 +1267,63 @@ __global__ void __launch_bounds__(BLOCK) k_bin_lengths(Params p, Queues q, Trans
         }
         if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
     }
+}
+
+// ------------------------------------------------------------ light groups
+// The third sibling: the same records at the same points of the bounce loop, keyed by the emitter the light came from.  In this mode the
+// shade twins store the emitter's index where a transient render stores a time (TransQ::by_light): emit[slot].w names the emitter the
+// vertex sits on, t_light[plane * cap + slot] the one light sample `plane` drew.  The emitter-hit record goes to cell [e][0] (reached by
+// a sampled ray), a light sample's radiance plane to [e][1] (reached by a light sample).  planes is [emitter * 2 + part][local pixel]
+// float4 - summed rgb and the number of contributions.  The cell a record lands in is only known per record, so each one is a
+// read-modify-write of its cell, samples in order, as k_bin_transient's bins are; the framebuffer takes the records' sum in
+// k_bin_transient's order.  The pixel owns its cells: no atomics on floats.  A non-zero record whose index is not in [0, n_emitters)
+// writes nowhere and is counted in *n_stray (an integer tally, tested to stay 0); the framebuffer still takes it.
+__global__ void __launch_bounds__(BLOCK) k_bin_lights(Params p, Queues q, TransQ tq, float4* planes, int n_emitters, unsigned int* n_stray, float* accum) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride) {
+        f3 sum = splat3(0.f);
+        uint32_t stray = 0;
+        auto land = [&](float4 c, float who, int part) {
+            const f3 v = mk3(isnan(c.x) ? 0.f : c.x, isnan(c.y) ? 0.f : c.y, isnan(c.z) ? 0.f : c.z);
+            if (v.x == 0.f && v.y == 0.f && v.z == 0.f) return;
+            sum = sum + v;
+            if (!(who >= 0.f && who < (float)n_emitters)) { stray++; return; }      // (NaN fails both)
+            float4* cell = planes + (size_t)((int)who * 2 + part) * (size_t)p.npix + lp;
+            const float4 a = *cell;
+            *cell = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + 1.f);
+        };
+        for (int s = 0; s < p.spp_batch; s++) {
+            const uint32_t slot = (uint32_t)s * (uint32_t)p.npix + lp;
+            const float4 e = tq.emit[slot];
+            if (e.x != 0.f || e.y != 0.f || e.z != 0.f) { land(e, e.w, 0); tq.emit[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }      // (NaN != 0: cleared too)
+            for (int pl = 0; pl < p.l_planes; pl++) {      // light samples in sample order
+                float4* l4 = reinterpret_cast<float4*>(L_slot(q.L, p.cap, (slot << 2) | (uint32_t)pl));
+                const float4 c = *l4;
+                if (c.x != 0.f || c.y != 0.f || c.z != 0.f) { land(c, tq.t_light[(size_t)pl * p.cap + slot], 1); *l4 = make_float4(0.f, 0.f, 0.f, 0.f); }
+            }
+        }
+        if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
+        if (stray) atomicAdd(n_stray, stray);
+    }
+}
+// Relighting: out[pixel] = sum over emitters e of gain[e] * (planes[e][0] + planes[e][1]).rgb, / cnt - the image the scene would have given
+// with emitter e's intensity multiplied by gain[e] (rgb), on the same random stream: no part of a path but the emitter's intensity reads
+// it.  One thread per owned pixel; e ascending, part 0 then part 1, each product added as it comes.  A channel whose gain is exactly 0
+// is skipped, so a switched-off emitter's inf or NaN does not reach the pixel.
+__global__ void __launch_bounds__(BLOCK) k_relight(const float4* planes, const float* gains, float* out, int npix, int n_emitters, float cnt) {
+    const uint32_t lp = blockIdx.x * BLOCK + threadIdx.x;
+    if (lp >= (uint32_t)npix) return;
+    f3 acc = splat3(0.f);
+    for (int e = 0; e < n_emitters; e++) {
+        const f3 g = mk3(gains[3 * e], gains[3 * e + 1], gains[3 * e + 2]);
+        for (int part = 0; part < 2; part++) {
+            const float4 c = planes[(size_t)(e * 2 + part) * (size_t)npix + lp];
+            if (g.x != 0.f) acc.x += g.x * c.x;
+            if (g.y != 0.f) acc.y += g.y * c.y;
+            if (g.z != 0.f) acc.z += g.z * c.z;
+        }
+    }
+    out[3 * lp] = acc.x / cnt; out[3 * lp + 1] = acc.y / cnt; out[3 * lp + 2] = acc.z / cnt;
 }
 
 __global__ void k_divide(const float* accum, float* out, uint32_t n, float cnt) {

@@ -23,6 +23,14 @@ of segments, camera to emitter - and by how the emitter was reached (part 0: by 
     rdr.path_length_counts()       # (max_bounce + 1, 2, w, h) float32: contributions per cell
     rdr.emission(), rdr.direct(), rdr.indirect()      # (w, h, 3): length 1, length 2, lengths 3 and more
 
+Light groups, `pt` only: `Renderer(..., light_groups=True)` also keeps the render split by the emitter the light came
+from - in the order of the `emitters` list, named by `rdr.emitter_ids` - and by how it was reached (part 0: by a sampled ray, part 1: by a
+light sample), and relights it on the device:
+
+    rdr.light_groups()             # (n_emitters, 2, w, h, 3) float32 [emitter, part, x, y]; .sum((0, 1)) is `pixels`
+    rdr.light_group_counts()       # (n_emitters, 2, w, h) float32: contributions per cell
+    rdr.relit({"spot": 0.0, "pt": (2.0, 1.5, 1.0)})      # (w, h, 3): the image with those emitters' intensities scaled; the others keep gain 1
+
 Adaptive sampling, `pt` and `vpt`: `Renderer(..., adaptive={"threshold": 0.02, "min_spp": 64, "step": 32})` retires a pixel
 once the relative standard error of its mean is at most `threshold`; decisions fall on global sample numbers that are multiples of `step`
 and >= `min_spp`.  `render(n)` still advances `cnt` by n (the most samples any pixel has); `pixels` divides by each pixel's own count:
@@ -262,11 +270,13 @@ class Renderer:
                  seed: int = 0, spp_per_batch: int = 0, profile: bool = False,
                  width: Optional[int] = None, height: Optional[int] = None,
                  max_bounce: Optional[int] = None, num_shadow_ray: Optional[int] = None, volumetric: Optional[bool] = None,
-                 exact: Optional[bool] = None, transient=None, adaptive=None, aov_spp: int = 32, path_lengths: bool = False):
+                 exact: Optional[bool] = None, transient=None, adaptive=None, aov_spp: int = 32, path_lengths: bool = False,
+                 light_groups: bool = False):
         # transient = None / False: steady state; True: time bins from the sensor's sample_count / min_time / interval; a dict overrides them
         # (scene_pack.transient_config).  Surface renderer, at most 4 light samples per vertex, one rank: apt_renderer_create refuses the rest.
         # path_lengths = True: also keep one image per path length and part; the same limits as transient, and not with it
         # or with adaptive: apt_renderer_create refuses the rest.
+        # light_groups = True: also keep one image per emitter and part; the same limits again, and not with path_lengths.
         # exact = True: the bit-parity build (the reference's float32 arithmetic operation for operation; debugging and the exact
         # parity tests), False: the fast build, None: whatever adapt_amd._lib currently hands out (fast unless APT_EXACT=1)
         # adaptive = None: every pixel takes every sample; a dict {"threshold", "min_spp", "step"}: adaptive sampling (adaptive_config)
@@ -278,7 +288,7 @@ class Renderer:
         self.flat: FlatScene = pack_scene(emitters, array_info, objects, prop)
         self.rc: RenderConfig = make_config(prop, width=width, height=height, max_bounce=max_bounce,
                                             num_shadow_ray=num_shadow_ray, seed=seed, volumetric=bool(volumetric), transient=transient,
-                                            path_lengths=bool(path_lengths))
+                                            path_lengths=bool(path_lengths), light_groups=bool(light_groups))
         self.volumetric = bool(volumetric)
         rc = self.rc
         # attributes the reference's callers read (watermark.py:23-30, render.py:129, path_tracer.py:181-193)
@@ -318,6 +328,9 @@ class Renderer:
         self.n_bins, self.min_time, self.interval = rc.transient_bins, rc.transient_min_time, rc.transient_interval
         cfg.path_lengths = int(bool(rc.path_lengths))
         self.n_lengths = rc.max_bounce + 1 if rc.path_lengths else 0          # planes kept: lengths 1 .. max_bounce + 1
+        cfg.light_groups = int(bool(rc.light_groups))
+        self.n_groups = self.flat.n_sources if rc.light_groups else 0           # planes kept: one pair per emitter
+        self.emitter_ids = [getattr(e, "id", None) for e in emitters]           # the emitters' XML ids, in plane order
         if self.adaptive:
             cfg.adaptive_threshold = self.adaptive["threshold"]
             cfg.adaptive_min_spp, cfg.adaptive_step = self.adaptive["min_spp"], self.adaptive["step"]
@@ -348,7 +361,7 @@ class Renderer:
         self._clear_aov()
 
     def clear(self):
-        """Zero the accumulation, the sample counter, the statistics, the transient bins, the path-length planes and the feature buffers."""
+        """Zero the accumulation, the sample counter, the statistics, the transient bins, the path-length and light-group planes and the feature buffers."""
         _lib.check(self.lib.apt_reset(self.handle), "apt_reset", self.lib)
         self._cnt = 0
         self._aov_n = 0
@@ -500,6 +513,60 @@ class Renderer:
     def _set_path_lengths(self, planes: np.ndarray):
         planes = np.ascontiguousarray(planes, np.float32)
         _lib.check(self.lib.apt_set_path_lengths(self.handle, _fp(planes)), "apt_set_path_lengths", self.lib)
+
+    # ----------------------------------------------------------- light groups
+    def _need_light_groups(self):
+        if not self.n_groups:
+            raise RuntimeError("this renderer was created without light_groups=True: there are no light-group planes")
+
+    def tile_light_groups(self) -> np.ndarray:
+        """This rank's raw planes, (n_emitters, 2, n_cols, h, 4) float32, index [emitter, part, x, y]: summed r, g, b and the number of
+        contributions.  Part 0: the emitter was reached by a sampled ray, part 1: by a light sample."""
+        self._need_light_groups()
+        out = np.empty((self.n_groups, 2, self.n_cols, self.h, 4), np.float32)
+        _lib.check(self.lib.apt_read_light_groups(self.handle, _fp(out)), "apt_read_light_groups", self.lib)
+        return out
+
+    def light_groups(self) -> np.ndarray:
+        """(n_emitters, 2, w, h, 3) float32: the radiance that came from each emitter, by part, divided by the sample count like `pixels`;
+        summed over emitters and parts it is `pixels` up to float summation order."""
+        planes = self.tile_light_groups()[..., :3]
+        return planes / np.float32(self._cnt if self._cnt > 0 else 1)
+
+    def light_group_counts(self) -> np.ndarray:
+        """(n_emitters, 2, w, h) float32: the number of contributions per cell."""
+        return np.ascontiguousarray(self.tile_light_groups()[..., 3])
+
+    def light_gains(self, gains) -> np.ndarray:
+        """-> (n_emitters, 3) float32 from a scalar per emitter, an rgb triple per emitter, or a dict from emitter id to either (emitters
+        the dict does not name keep gain 1)."""
+        self._need_light_groups()
+        out = np.ones((self.n_groups, 3), np.float32)
+        if isinstance(gains, dict):
+            for key, g in gains.items():
+                if key not in self.emitter_ids:
+                    raise KeyError(f"no emitter with id {key!r}; this scene has {self.emitter_ids}")
+                out[self.emitter_ids.index(key)] = np.broadcast_to(np.asarray(g, np.float32), (3,))
+            return out
+        g = np.asarray(gains, np.float32)
+        if g.shape == (self.n_groups,):
+            g = g[:, None]
+        if g.shape not in ((self.n_groups, 1), (self.n_groups, 3)):
+            raise ValueError(f"gains: one scalar or one rgb triple per emitter ({self.n_groups} emitters), or a dict by emitter id; got shape {g.shape}")
+        out[:] = g
+        return out
+
+    def relit(self, gains) -> np.ndarray:
+        """(w, h, 3) float32: the image with every emitter's share multiplied by its gain (`light_gains`), combined on the device
+        (apt_relight) - what `pixels` would be had the emitters' intensities been scaled, on the same random stream."""
+        g = np.ascontiguousarray(self.light_gains(gains))
+        out = np.empty((self.n_cols, self.h, 3), np.float32)
+        _lib.check(self.lib.apt_relight(self.handle, _fp(g), _fp(out)), "apt_relight", self.lib)
+        return out
+
+    def _set_light_groups(self, planes: np.ndarray):
+        planes = np.ascontiguousarray(planes, np.float32)
+        _lib.check(self.lib.apt_set_light_groups(self.handle, _fp(planes)), "apt_set_light_groups", self.lib)
 
     def _set_cnt(self, v: int):
         self._steady_only("cnt[None] = ...")
@@ -673,6 +740,7 @@ class Renderer:
                 "accumulation": self.color.to_numpy(), "counter": self._cnt,
                 **({"transient_bins": self.tile_transient()} if self.n_bins else {}),
                 **({"path_length_planes": self.tile_path_lengths()} if self.n_lengths else {}),
+                **({"light_group_planes": self.tile_light_groups()} if self.n_groups else {}),
                 **({"aov_sums": self.tile_aov(), "aov_samples": self._aov_n} if self._aov_n else {}),
                 **(self._adaptive_check_point() if self.adaptive else {})}
 
@@ -689,7 +757,7 @@ class Renderer:
         if not self.adaptive and any(k in check_point for k in self._ADAPTIVE_KEYS):
             raise ValueError("this checkpoint is an adaptive render's: continue it with Renderer(..., adaptive=...)")
         for key, val in check_point.items():
-            if key in ("accumulation", "counter", "transient_bins", "path_length_planes", "aov_sums", "aov_samples") + self._ADAPTIVE_KEYS:
+            if key in ("accumulation", "counter", "transient_bins", "path_length_planes", "light_group_planes", "aov_sums", "aov_samples") + self._ADAPTIVE_KEYS:
                 continue
             if key in ("cam_t", "cam_orient"):
                 ok = np.abs(np.asarray(val) - np.asarray(getattr(self, key))).max() < 1e-4
@@ -713,6 +781,9 @@ class Renderer:
         planes = check_point.get("path_length_planes")
         if self.n_lengths and planes is not None and np.shape(planes) == (self.n_lengths, 2, self.n_cols, self.h, 4):
             self._set_path_lengths(planes)      # (likewise: another layout, or none, leaves the planes as they are)
+        planes = check_point.get("light_group_planes")
+        if self.n_groups and planes is not None and np.shape(planes) == (self.n_groups, 2, self.n_cols, self.h, 4):
+            self._set_light_groups(planes)      # (likewise)
 
     def summary(self) -> str:
         self.synchronize()

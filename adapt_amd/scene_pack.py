@@ -117,6 +117,7 @@ class RenderConfig:
     transient_min_time: float = 0.0
     transient_interval: float = 0.0
     path_lengths: bool = False        # True: also keep one image per path length
+    light_groups: bool = False        # True: also keep one image per emitter
 
 
 _SRC_IDS = {"point": 0, "area": 1, "spot": 2, "collimated": 4}
@@ -274,10 +275,10 @@ def transient_bin_index(t, min_time: float, interval: float, n_bins: int) -> np.
 def make_config(prop: dict, *, width: Optional[int] = None, height: Optional[int] = None,
                 max_bounce: Optional[int] = None, num_shadow_ray: Optional[int] = None,
                 seed: int = 0, use_bvh: Optional[bool] = None, volumetric: bool = False, transient=None,
-                path_lengths: bool = False) -> RenderConfig:
+                path_lengths: bool = False, light_groups: bool = False) -> RenderConfig:
     """Sensor dict -> RenderConfig.  Keyword overrides exist because the BASELINE
     configs differ from the values stored in the scene files.  `transient`: see transient_config; `path_lengths`: keep the
-    path-length planes."""
+    path-length planes; `light_groups`: keep the per-emitter planes."""
     t_bins, t_min, t_int = transient_config(prop, transient)
     film = prop["film"]
     w = int(width if width is not None else film["width"])
@@ -305,4 +306,4 @@ def make_config(prop: dict, *, width: Optional[int] = None, height: Optional[int
         cam_r=np.ascontiguousarray(cam_r, np.float32), cam_t=np.float32(prop["transform"][1]), cam_orient=orient,
         focal=float(focal), inv_focal=float(1. / focal), half_w=w / 2, half_h=h / 2, seed=int(seed), volumetric=bool(volumetric),
         crop_x=crop_x, crop_y=crop_y, crop_rx=crop_rx, crop_ry=crop_ry,
-        transient_bins=t_bins, transient_min_time=t_min, transient_interval=t_int, path_lengths=bool(path_lengths))
+        transient_bins=t_bins, transient_min_time=t_min, transient_interval=t_int, path_lengths=bool(path_lengths), light_groups=bool(light_groups))

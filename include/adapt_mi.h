@@ -22,6 +22,7 @@
  *   apt_get_accum / apt_set_accum  tracer/path_tracer.py:181-211  get_check_point / load_check_point
  *   apt_read_transient             renderer/bdpt.py:57-58,164-166  time_bins / time_cnts (TRANSIENT_CAM), for the `pt` renderer
  *   apt_read_path_lengths / apt_set_path_lengths   (none; the `pt` render split by path length - emission, direct, n-bounce -)
+ *   apt_read_light_groups / apt_set_light_groups / apt_relight   (none; the `pt` render split by emitter - light groups - and relit on the device)
  *   apt_read_sample_counts / apt_read_moments / apt_set_adaptive_state   (none; adaptive sampling)
  *   apt_render_aov / apt_read_aov / apt_set_aov / apt_clear_aov   (none; per-pixel albedo, normal and depth of the camera rays' first hits)
  *   apt_denoise                    post_processing.py:15-32 (the firefly filter: stage 1) + an edge-avoiding a-trous filter guided by those buffers (stage 2; none upstream)
@@ -111,6 +112,12 @@ typedef struct apt_render_cfg {
     int32_t volumetric;                           /* 0 = Renderer.render (renderer/vanilla_renderer.py:32-120); 1 = VolumeRenderer.render
                                                      (renderer/vpt.py:145-258): free-path sampling in homogeneous media, null surfaces,
                                                      transmittance-tracked light samples */
+    /* Light groups, surface renderer only: every path contribution is also added to the plane of the emitter its light came
+       from - emitter e is row e of apt_scene_desc.src_f - and, within it, to the part that says how the emitter was reached (0: by a sampled
+       ray, 1: by a light sample).  Needs volumetric = 0, num_shadow_ray <= 4, world_size = 1, path_lengths = 0, transient_bins = 0 and
+       adaptive_threshold = 0; runs the staged pipeline on one render lane.  The planes take n_sources * 2 * owned pixels * 16 bytes.  (It sits
+       before the blocks that were there when it was added: they keep their places at the end.) */
+    int32_t light_groups;                         /* 0 = off, 1 = keep the n_sources x 2 planes (apt_read_light_groups, apt_relight) */
     /* Path-length images, surface renderer only: every path contribution is also added to the plane of its length - its
        number of segments, camera to emitter - and, within it, to the part that says how the emitter was reached (0: by a sampled ray,
        1: by a light sample).  Needs volumetric = 0, num_shadow_ray <= 4, world_size = 1, transient_bins = 0 and adaptive_threshold = 0;
@@ -149,6 +156,7 @@ typedef struct apt_stats {
     double  kernel_ms[APT_N_KERNELS];   /* summed HIP-event time per kernel (profile=1 only) */
     double  render_ms;                  /* HIP-event time of all apt_render calls so far */
     int64_t n_track;                    /* volumetric: closest-hit queries made by the transmittance walk of the light samples */
+    int64_t n_stray_light;              /* light-group renders: non-zero records that named no emitter of the scene and went to no plane (0 unless something is broken) */
 } apt_stats;
 
 /* Denoiser settings.  Stage 1, the firefly filter, is upstream's rule (post_processing.py:15-32): on the zero-padded film a pixel
@@ -259,7 +267,7 @@ int apt_tile_shape(const apt_renderer*, int32_t* n_cols, int32_t* height);   /* 
 int apt_read_pixels(apt_renderer*, float* out);           /* owned tile, [local col][y][rgb], color / cnt (adaptive: color / n_p, 0 where n_p = 0) */
 int apt_get_accum(apt_renderer*, float* out, int32_t* cnt);
 int apt_set_accum(apt_renderer*, const float* in, int32_t cnt);
-int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0, transient bins = 0, path-length planes = 0, adaptive state = start, feature buffers = 0 */
+int apt_reset(apt_renderer*);                             /* color = 0, cnt = 0, stats = 0, transient bins = 0, path-length planes = 0, light-group planes = 0, adaptive state = start, feature buffers = 0 */
 /* transient renders: the owned tile's bins, [bin][local col][y][rgba] - summed r, g, b (divide by cnt for radiance, as pixels) and the
    number of contributions (a); transient_bins * n_cols * height * 4 floats.  apt_set_transient restores them (checkpoints). */
 int apt_read_transient(apt_renderer*, float* out);
@@ -269,6 +277,14 @@ int apt_set_transient(apt_renderer*, const float* in);
    Summed over lengths and parts they are the accumulation.  apt_set_path_lengths restores them (checkpoints). */
 int apt_read_path_lengths(apt_renderer*, float* out);
 int apt_set_path_lengths(apt_renderer*, const float* in);
+/* light-group renders (light_groups = 1; APT_E_STATE otherwise): the owned tile's planes, [emitter][part][local col][y][rgba] - summed r, g, b
+   (divide by cnt for radiance, as pixels) and the number of contributions (a); n_sources * 2 * n_cols * height * 4 floats.  Summed over emitters
+   and parts they are the accumulation.  apt_set_light_groups restores them (checkpoints).  apt_relight: out = the owned tile, [local col][y][rgb],
+   with emitter e's share multiplied by gains[3e .. 3e+2] (rgb): sum over e, part 0 then part 1, of gain * plane, / cnt - what apt_read_pixels would
+   hand out had emitter e's intensity been scaled by its gain, on the same random stream.  A channel with gain 0 is skipped (no 0 * inf). */
+int apt_read_light_groups(apt_renderer*, float* out);
+int apt_set_light_groups(apt_renderer*, const float* in);
+int apt_relight(apt_renderer*, const float* gains /* n_sources*3 */, float* out /* n_cols*height*3 */);
 /* adaptive renders (adaptive_threshold > 0; APT_E_STATE otherwise), owned tile in [local col][y] order: the per-pixel sample counts n_p and
    (active may be NULL) whether each pixel still samples; the float64 sums of squared sample values, 3 per pixel (S2; S1 is the accumulation).
    apt_set_adaptive_state restores all three (checkpoints; after apt_set_accum). */
