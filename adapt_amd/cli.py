@@ -152,6 +152,39 @@ def _folder(path: str) -> str:
     return path
 
 
+def write_planes(planes: np.ndarray, shown, base: str, cube: str, frame: str, first: int, ext: str) -> int:
+    """A split render's planes (n, 2, w, h, 3): the whole array as <base>-<cube>.npy, and one image per leading index - its two parts
+    summed, through `shown` - as <base>-<frame>NN.<ext>, NN counting from `first`.  Returns n."""
+    np.save(f"{base}-{cube}.npy", planes)
+    frames = shown(planes.sum(1))
+    for i in range(frames.shape[0]):
+        write_image(frames[i], f"{base}-{frame}{i + first:02d}.{ext}")
+    return frames.shape[0]
+
+
+# The split renders' switches in the order their refusals are tried: option, what it writes (with its verb), its axis in a combined split.
+SPLIT_OPTIONS = (("transient", "time-resolved output", "exists", "time"),
+                 ("path_lengths", "path-length images", "exist", "length"),
+                 ("light_groups", "light groups", "exist", "emitter"))
+
+
+def split_refusal(opts) -> str:
+    """Why this combination of split switches is not rendered, or "": each is `pt` only, no two combine, and (--transient says so
+    itself, where the adaptive options are read) none combines with adaptive sampling."""
+    for k, (opt, noun, verb, axis) in enumerate(SPLIT_OPTIONS):
+        if not getattr(opts, opt):
+            continue
+        if opts.type != "pt":
+            return f"--{opt}: {noun} {verb} for the surface renderer only (--type pt), not for --type {opts.type}"
+        for other, _, _, other_axis in SPLIT_OPTIONS[:k]:
+            if getattr(opts, other):
+                return (f"--{opt} with --{other}: {other_axis} x {axis} {'cubes' if other == 'transient' else 'planes'} are not built; "
+                        f"{noun} and --{other} do not combine")
+        if opt != "transient" and opts.noise_threshold > 0:
+            return f"--{opt} with --noise_threshold: {noun} need every pixel's samples; adaptive sampling and --{opt} do not combine"
+    return ""
+
+
 def parse_light_gains(items) -> dict:
     """["id=g", "id=r,g,b", ...] -> {id: g or (r, g, b)}; ValueError names the item it cannot read."""
     gains = {}
@@ -172,29 +205,9 @@ def main(argv=None) -> int:
     if opts.type not in ("pt", "vpt"):
         print(f"--type {opts.type}: only the `pt` and `vpt` renderers exist in this build (bdpt/ao are outside its scope)", file=sys.stderr)
         return 2
-    if opts.transient and opts.type != "pt":
-        print(f"--transient: time-resolved output exists for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
-        return 2
-    if opts.path_lengths and opts.type != "pt":
-        print(f"--path_lengths: path-length images exist for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
-        return 2
-    if opts.path_lengths and opts.transient:
-        print("--path_lengths with --transient: time x length cubes are not built; path-length images and --transient do not combine", file=sys.stderr)
-        return 2
-    if opts.path_lengths and opts.noise_threshold > 0:
-        print("--path_lengths with --noise_threshold: path-length images need every pixel's samples; adaptive sampling and --path_lengths do not combine", file=sys.stderr)
-        return 2
-    if opts.light_groups and opts.type != "pt":
-        print(f"--light_groups: light groups exist for the surface renderer only (--type pt), not for --type {opts.type}", file=sys.stderr)
-        return 2
-    if opts.light_groups and opts.transient:
-        print("--light_groups with --transient: time x emitter cubes are not built; light groups and --transient do not combine", file=sys.stderr)
-        return 2
-    if opts.light_groups and opts.path_lengths:
-        print("--light_groups with --path_lengths: length x emitter planes are not built; light groups and --path_lengths do not combine", file=sys.stderr)
-        return 2
-    if opts.light_groups and opts.noise_threshold > 0:
-        print("--light_groups with --noise_threshold: light groups need every pixel's samples; adaptive sampling and --light_groups do not combine", file=sys.stderr)
+    refusal = split_refusal(opts)
+    if refusal:
+        print(refusal, file=sys.stderr)
         return 2
     if opts.light_gain and not opts.light_groups:
         print("--light_gain: relighting needs the per-emitter planes; give --light_groups as well", file=sys.stderr)
@@ -315,33 +328,21 @@ def main(argv=None) -> int:
         if opts.save_aov:
             np.savez(f"{base}-aov.npz", **{k: window(v) for k, v in rdr.aov().items()})
             print(f"[adapt_amd] wrote {base}-aov.npz")
-    if opts.path_lengths and not opts.no_save_fig:
-        base = os.path.join(opts.output_path, f"{opts.img_name}-{stem}-{opts.type}")
-        planes = rdr.path_lengths()
-        np.save(f"{base}-lengths.npy", planes)
-        frames = planes.sum(1)
-        if rdr.do_crop:
-            frames = frames[:, rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y, :]
-        if scale is not None:
-            frames = frames / scale             # the image's quantile: the written frames still add up to the written image
-        for i in range(frames.shape[0]):
-            write_image(frames[i], f"{base}-len{i + 1:02d}.{opts.img_ext}")
-        print(f"[adapt_amd] wrote {frames.shape[0]} path-length images {base}-len01.{opts.img_ext} ... and {base}-lengths.npy")
-    if opts.light_groups and not opts.no_save_fig:
+    if (opts.path_lengths or opts.light_groups) and not opts.no_save_fig:
         base = os.path.join(opts.output_path, f"{opts.img_name}-{stem}-{opts.type}")
 
-        def shown(a):                           # cropped and scaled like the image: the written frames still add up to the written image
+        def shown(a):                           # cropped and scaled like the image (its quantile): the written frames still add up to the written image
             a = a[..., rdr.start_x:rdr.end_x, rdr.start_y:rdr.end_y, :] if rdr.do_crop else a
             return a / scale if scale is not None else a
-        planes = rdr.light_groups()
-        np.save(f"{base}-lights.npy", planes)
-        frames = shown(planes.sum(1))
-        for i in range(frames.shape[0]):
-            write_image(frames[i], f"{base}-light{i:02d}.{opts.img_ext}")
-        print(f"[adapt_amd] wrote {frames.shape[0]} light-group images {base}-light00.{opts.img_ext} ... (emitters {rdr.emitter_ids}) and {base}-lights.npy")
-        if light_gains:
-            write_image(shown(rdr.relit(light_gains)), f"{base}-relit.{opts.img_ext}")
-            print(f"[adapt_amd] wrote {base}-relit.{opts.img_ext} (gains {light_gains})")
+        if opts.path_lengths:
+            n = write_planes(rdr.path_lengths(), shown, base, "lengths", "len", 1, opts.img_ext)
+            print(f"[adapt_amd] wrote {n} path-length images {base}-len01.{opts.img_ext} ... and {base}-lengths.npy")
+        if opts.light_groups:
+            n = write_planes(rdr.light_groups(), shown, base, "lights", "light", 0, opts.img_ext)
+            print(f"[adapt_amd] wrote {n} light-group images {base}-light00.{opts.img_ext} ... (emitters {rdr.emitter_ids}) and {base}-lights.npy")
+            if light_gains:
+                write_image(shown(rdr.relit(light_gains)), f"{base}-relit.{opts.img_ext}")
+                print(f"[adapt_amd] wrote {base}-relit.{opts.img_ext} (gains {light_gains})")
     if opts.transient:
         export_transient(rdr, opts.output_path, stem, opts.img_ext, opts.normalize)      # render.py:166: folder named after the scene file
     rdr.close()

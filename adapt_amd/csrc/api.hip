@@ -225,8 +225,26 @@ struct Lane {
 //   PIPE_SORTED      extend into per-class queues, the class kernels in groups, shadow  (render_surface)
 //   PIPE_TRACED      the shade kernel traces its rays itself: one launch per bounce     (render_surface; product build, shade_stage.hpp "rays traced in place")
 //   PIPE_VOLUMETRIC  extend, k_vevent, one kernel per event queue, transmittance walk   (render_volumetric)
-// Transient, path-length, light-group and adaptive renders are modifiers on top of it (apt_renderer::transient, ::lengths, ::light_groups, ::adaptive).
+// A split render (apt_renderer::split_mode) and an adaptive one (::adaptive) are modifiers on top of it.
 enum Pipeline { PIPE_STAGED, PIPE_SORTED, PIPE_TRACED, PIPE_VOLUMETRIC };
+
+// A split render keeps a surface render's contributions apart: by arrival time, by segment count or by emitter.  One
+// mechanism - the TR shade twins, the per-path records (stages.hpp TransQ), a binning kernel per settled bounce, one render lane - and per
+// mode the cells the records land in and the words below.
+enum SplitMode { SPLIT_NONE, SPLIT_TRANSIENT, SPLIT_LENGTHS, SPLIT_LIGHTS };
+struct SplitWords {
+    const char* noun;         // allocation errors
+    const char* subject;      // the refusals of apt_renderer_create ...
+    bool plural;              // ... and their verb forms
+    const char* field;        // the apt_render_cfg field that switches the mode on
+    const char* tag;          // shade_name
+};
+static constexpr SplitWords kSplit[] = {
+    {"", "", false, "", ""},
+    {"transient bins", "transient rendering", false, "transient_bins", " [transient]"},
+    {"path-length planes", "path-length images", true, "path_lengths", " [path lengths]"},
+    {"light-group planes", "light groups", true, "light_groups", " [light groups]"},
+};
 
 struct apt_renderer {
     const apt_scene* scene = nullptr;
@@ -280,21 +298,14 @@ struct apt_renderer {
     double render_ms = 0.0;
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
     bool render_pending = false;
-    // transient render (apt_render_cfg.transient_bins > 0; stages.hpp TransQ): one render lane, never rays traced in place
-    int transient = 0;
+    // split render (apt_render_cfg.transient_bins > 0, .path_lengths, .light_groups; stages.hpp TransQ, k_bin_*): one render lane, never rays traced in place
+    SplitMode split_mode = SPLIT_NONE;
+    bool split() const { return split_mode != SPLIT_NONE; }      // the TR shade twins run: every bounce's contributions are kept apart
     TransQ tq{};
-    DevBuf tr_pool, tr_bins;              // per-path time / record arrays (cap-sized), the bins (n_bins x owned pixels float4)
+    DevBuf tr_pool;                       // per-path time / record arrays (cap-sized)
+    DevBuf split_cells;                   // float4 per owned pixel x (transient: n_bins | path lengths: (max_bounce + 1) x 2 | light groups: n_sources x 2), see split_cell_rows
     group_tr_fn group_tr_[APT_N_GROUPS] = {};
-    // path-length render (apt_render_cfg.path_lengths; stages.hpp k_bin_lengths): what a transient render selects - its shade
-    // twins, its per-path arrays (tq, tr_pool), one lane -, the records settled by segment count instead of by time
-    int lengths = 0;
-    DevBuf len_planes;                    // (max_bounce + 1) x 2 x owned pixels float4
-    // light-group render (apt_render_cfg.light_groups; stages.hpp k_bin_lights / k_relight): the same selection once more, the
-    // twins storing emitter indices (TransQ::by_light), the records settled by emitter
-    int light_groups = 0;
-    DevBuf lg_planes;                     // n_sources x 2 x owned pixels float4
-    DevBuf lg_aux;                        // 16 bytes: the stray-record tally (uint32) | n_sources x 3 gains | owned pixels x 3 relit image
-    bool split() const { return transient || lengths || light_groups; }      // the TR shade twins run: every bounce's contributions are kept apart
+    DevBuf lg_aux;                        // light groups: 16 bytes: the stray-record tally (uint32) | n_sources x 3 gains | owned pixels x 3 relit image (k_relight)
     // adaptive sampling (apt_render_cfg.adaptive_threshold > 0; stages.hpp AdaptQ)
     int adaptive = 0;
     AdaptQ aq{};
@@ -759,7 +770,7 @@ static int plan_film(apt_renderer* r) {
     if (r->npix <= 0) { return fail(APT_E_INVALID, "apt_renderer_create: this rank owns no pixels"); }
     r->n_lanes = 3;   // measured on C2: 1 lane 1 827, 2 lanes 2 196, 3 lanes 2 268, 4 lanes 2 178 Msamples/s (round 2, 64 spp per lane-batch); round 5, 32 Mi paths per lane-batch: C2 4 559 / 4 590 / 4 287 with 2 / 3 / 4, C5 1 844 / 2 028 / 2 129 with 1 / 2 / 3; volumetric scenes with null surfaces ran four lanes in rounds 3-4 (the fourth hid the host read-backs of their tails): at this batch size V1 1 374 with three, 1 299 with four
     if (const char* nl = getenv("APT_LANES")) r->n_lanes = std::min(4, std::max(1, atoi(nl)));
-    if (c.transient_bins > 0 || c.path_lengths || c.light_groups) r->n_lanes = 1;      // the bins (the length planes, the light-group planes) are shared by every batch and added to per bounce: one lane keeps the adds in order
+    if (r->split()) r->n_lanes = 1;      // a split render's cells are shared by every batch and added to per bounce: one lane keeps the adds in order
     const size_t nq = (size_t)r->nq;
     // queue capacity of a batch of b: whole waves, dealt over the sub-queues (generate: wave w -> sub-queue w % nq)
     auto subcap_of = [&](int b) { const size_t n_waves = ((size_t)r->npix * (size_t)b + 63) / 64; return ((n_waves + nq - 1) / nq) * 64; };
@@ -902,10 +913,8 @@ static int pick_shading(apt_renderer* r) {
         r->shade_name = r->shade->name;
         if (r->pipeline == PIPE_TRACED) r->shade_name += " [rays traced in place]";
     }
-    if (r->transient) r->shade_name += " [transient]";
+    r->shade_name += kSplit[r->split_mode].tag;
     if (r->adaptive) r->shade_name += " [adaptive]";
-    if (r->lengths) r->shade_name += " [path lengths]";
-    if (r->light_groups) r->shade_name += " [light groups]";
     // (sorted: extend appends every hit path's record to the packed queue of its material class, Queues::cq)
     const int si = (r->pipeline == PIPE_SORTED) ? 1 : 0;
     r->extend = r->dyn_fetch ? kExtendDyn[si] : (r->trace_mode == TRACE_FLAT ? kExtendFlatHot[si] : kExtend[r->trace_mode][si]);
@@ -1101,33 +1110,40 @@ static int make_adaptive(apt_renderer* r) {
     return adaptive_restart(r);
 }
 
-// Transient render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the bins, all zero-filled.  A
-// path-length render takes the same per-path arrays and, in place of the bins, its length planes; a light-group render its per-emitter
-// planes, and the twins are told to store emitter indices in place of times (TransQ::by_light).
-static int make_transient(apt_renderer* r) {
+// Split render: the per-path time and record arrays (TransQ, indexed by radiance slot like L) and the mode's cells, all zero-filled.
+static size_t split_cell_rows(const apt_renderer* r) {
+    switch (r->split_mode) {
+        case SPLIT_TRANSIENT: return (size_t)r->cfg.transient_bins;
+        case SPLIT_LENGTHS: return ((size_t)r->cfg.max_bounce + 1) * 2;
+        case SPLIT_LIGHTS: return (size_t)r->scene->n_sources * 2;
+        default: return 0;
+    }
+}
+static int make_split(apt_renderer* r) {
     if (!r->split()) return APT_OK;
     const apt_render_cfg& c = r->cfg;
     const size_t cap = r->par.cap, planes = (size_t)r->par.l_planes;
     const size_t words = cap + 4 * cap + planes * cap;
-    DevBuf& out = r->transient ? r->tr_bins : (r->lengths ? r->len_planes : r->lg_planes);
-    const size_t cells = (r->transient ? (size_t)c.transient_bins : (r->lengths ? (size_t)c.max_bounce + 1 : (size_t)r->scene->n_sources) * 2) * (size_t)r->npix;
+    const size_t cells = split_cell_rows(r) * (size_t)r->npix;
+    const char* noun = kSplit[r->split_mode].noun;
     hipError_t e;
-    if ((e = r->tr_pool.alloc(words * 4)) != hipSuccess || (e = out.alloc(cells * 16)) != hipSuccess)
-        return fail(APT_E_NOMEM, std::string(r->transient ? "transient bins: " : (r->lengths ? "path-length planes: " : "light-group planes: ")) + hipGetErrorString(e));
+    if ((e = r->tr_pool.alloc(words * 4)) != hipSuccess || (e = r->split_cells.alloc(cells * 16)) != hipSuccess)
+        return fail(APT_E_NOMEM, std::string(noun) + ": " + hipGetErrorString(e));
     HIP_TRY(hipMemsetAsync(r->tr_pool.p, 0, words * 4, r->stream()));
-    HIP_TRY(hipMemsetAsync(out.p, 0, cells * 16, r->stream()));
+    HIP_TRY(hipMemsetAsync(r->split_cells.p, 0, cells * 16, r->stream()));
     float* base = r->tr_pool.as<float>();
     TransQ& t = r->tq;
     t.t_path = base; t.emit = reinterpret_cast<float4*>(base + cap); t.t_light = base + 5 * cap;
-    t.by_light = r->light_groups;
-    if (r->light_groups) {                 // the tally of records that named no emitter, and the relight kernel's gains and image
+    t.by_light = r->split_mode == SPLIT_LIGHTS;      // the twins store emitter indices in place of times
+    if (r->split_mode == SPLIT_LIGHTS) {   // the tally of records that named no emitter, and the relight kernel's gains and image
         if ((e = r->lg_aux.alloc(16 + (size_t)r->scene->n_sources * 12 + (size_t)r->npix * 12)) != hipSuccess)
-            return fail(APT_E_NOMEM, std::string("light-group planes: ") + hipGetErrorString(e));
+            return fail(APT_E_NOMEM, std::string(noun) + ": " + hipGetErrorString(e));
         HIP_TRY(hipMemsetAsync(r->lg_aux.p, 0, 16, r->stream()));
     }
-    if (!r->transient) return APT_OK;      // (a path-length or light-group render: no bins, no window - the times the twins store are not read)
-    t.bins = r->tr_bins.as<float4>();
-    transient_window(t, c.transient_bins, c.transient_min_time, c.transient_interval);
+    if (r->split_mode == SPLIT_TRANSIENT) {           // (the other modes: no window - the times the twins store are not read)
+        t.bins = r->split_cells.as<float4>();
+        transient_window(t, c.transient_bins, c.transient_min_time, c.transient_interval);
+    }
     return APT_OK;
 }
 
@@ -1234,6 +1250,36 @@ APT_EXPORT void apt_renderer_destroy(apt_renderer* r) {
     if (r->ad_live_host) (void)hipHostFree(r->ad_live_host);
     delete r;
 }
+// The split mode a configuration asks for, or its refusal.  The modes are tried in table order; per mode: its switch's range, the limits
+// all three share, no mode before it is on (two split modes do not combine), no adaptive sampling, then what only that mode asks.
+// (Adaptive x transient is refused in apt_renderer_create, worded from the adaptive side.)
+static int check_split(const apt_scene* sc, const apt_render_cfg& c, SplitMode* mode) {
+    auto refuse = [](std::initializer_list<const char*> words) {
+        std::string msg = "apt_renderer_create: ";
+        for (const char* w : words) msg += w;
+        return fail(APT_E_INVALID, msg);
+    };
+    if (c.transient_bins < 0) return refuse({"transient_bins must be >= 0 (0 = steady state)"});
+    const int32_t value[] = {0, c.transient_bins > 0 ? 1 : 0, c.path_lengths, c.light_groups};
+    for (int m = SPLIT_TRANSIENT; m <= SPLIT_LIGHTS; m++) {
+        const SplitWords& w = kSplit[m];
+        if (value[m] != 0 && value[m] != 1) return refuse({w.field, " must be 0 (off) or 1"});
+        if (!value[m]) continue;
+        if (c.volumetric) return refuse({w.subject, w.plural ? " are" : " is", " a surface-renderer mode (volumetric = 0)"});
+        if (c.num_shadow_ray > 4) return refuse({w.subject, w.plural ? " take" : " takes", " at most 4 light samples per vertex (num_shadow_ray <= 4)"});
+        if (c.world_size > 1) return refuse({w.subject, w.plural ? " run" : " runs", " on one rank (world_size = 1)"});
+        if (m == SPLIT_TRANSIENT && (!(c.transient_interval > 0.f) || !std::isfinite(c.transient_interval) || !std::isfinite(c.transient_min_time)))
+            return refuse({"transient_interval must be positive and finite, transient_min_time finite"});
+        if (*mode != SPLIT_NONE)
+            return refuse({w.subject, " and ", kSplit[*mode].subject, " do not combine (", kSplit[*mode].field, " must be 0 when ", w.field, " = 1)"});
+        if (m != SPLIT_TRANSIENT && c.adaptive_threshold > 0.f)
+            return refuse({w.subject, " and adaptive sampling do not combine (adaptive_threshold must be 0 when ", w.field, " = 1)"});
+        if (m == SPLIT_LIGHTS && sc->n_sources <= 0) return refuse({"light groups need a scene with emitters (n_sources > 0)"});
+        if (m == SPLIT_LIGHTS && sc->n_sources >= (1 << 24)) return refuse({"light groups keep the emitter index in a float (n_sources < 2^24)"});
+        *mode = (SplitMode)m;
+    }
+    return APT_OK;
+}
 APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cfg, apt_renderer** out) {
     if (!sc || !cfg || !out) return fail(APT_E_INVALID, "apt_renderer_create: null argument");
     apt_render_cfg c = *cfg;
@@ -1245,38 +1291,8 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     if (c.band_width <= 0) c.band_width = c.width;
     if (c.rank < 0 || c.rank >= c.world_size) return fail(APT_E_INVALID, "apt_renderer_create: rank outside world_size");
     if (c.device != sc->device) return fail(APT_E_INVALID, "apt_renderer_create: renderer and scene must live on the same device");
-    if (c.transient_bins < 0) return fail(APT_E_INVALID, "apt_renderer_create: transient_bins must be >= 0 (0 = steady state)");
-    if (c.transient_bins > 0) {
-        if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: transient rendering is a surface-renderer mode (volumetric = 0)");
-        if (c.num_shadow_ray > 4) return fail(APT_E_INVALID, "apt_renderer_create: transient rendering takes at most 4 light samples per vertex (num_shadow_ray <= 4)");
-        if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: transient rendering runs on one rank (world_size = 1)");
-        if (!(c.transient_interval > 0.f) || !std::isfinite(c.transient_interval) || !std::isfinite(c.transient_min_time))
-            return fail(APT_E_INVALID, "apt_renderer_create: transient_interval must be positive and finite, transient_min_time finite");
-    }
-    if (c.path_lengths != 0 && c.path_lengths != 1) return fail(APT_E_INVALID, "apt_renderer_create: path_lengths must be 0 (off) or 1");
-    if (c.path_lengths) {
-        if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: path-length images are a surface-renderer mode (volumetric = 0)");
-        if (c.num_shadow_ray > 4) return fail(APT_E_INVALID, "apt_renderer_create: path-length images take at most 4 light samples per vertex (num_shadow_ray <= 4)");
-        if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: path-length images run on one rank (world_size = 1)");
-        if (c.transient_bins > 0)
-            return fail(APT_E_INVALID, "apt_renderer_create: path-length images and transient rendering do not combine (transient_bins must be 0 when path_lengths = 1)");
-        if (c.adaptive_threshold > 0.f)
-            return fail(APT_E_INVALID, "apt_renderer_create: path-length images and adaptive sampling do not combine (adaptive_threshold must be 0 when path_lengths = 1)");
-    }
-    if (c.light_groups != 0 && c.light_groups != 1) return fail(APT_E_INVALID, "apt_renderer_create: light_groups must be 0 (off) or 1");
-    if (c.light_groups) {
-        if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: light groups are a surface-renderer mode (volumetric = 0)");
-        if (c.num_shadow_ray > 4) return fail(APT_E_INVALID, "apt_renderer_create: light groups take at most 4 light samples per vertex (num_shadow_ray <= 4)");
-        if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: light groups run on one rank (world_size = 1)");
-        if (c.transient_bins > 0)
-            return fail(APT_E_INVALID, "apt_renderer_create: light groups and transient rendering do not combine (transient_bins must be 0 when light_groups = 1)");
-        if (c.path_lengths)
-            return fail(APT_E_INVALID, "apt_renderer_create: light groups and path-length images do not combine (path_lengths must be 0 when light_groups = 1)");
-        if (c.adaptive_threshold > 0.f)
-            return fail(APT_E_INVALID, "apt_renderer_create: light groups and adaptive sampling do not combine (adaptive_threshold must be 0 when light_groups = 1)");
-        if (sc->n_sources <= 0) return fail(APT_E_INVALID, "apt_renderer_create: light groups need a scene with emitters (n_sources > 0)");
-        if (sc->n_sources >= (1 << 24)) return fail(APT_E_INVALID, "apt_renderer_create: light groups keep the emitter index in a float (n_sources < 2^24)");
-    }
+    SplitMode split_mode = SPLIT_NONE;
+    if (int rc = check_split(sc, c, &split_mode)) return rc;
     if (!std::isfinite(c.adaptive_threshold)) return fail(APT_E_INVALID, "apt_renderer_create: adaptive_threshold must be finite (> 0: adaptive sampling, <= 0: off)");
     if (c.adaptive_threshold > 0.f) {
         if (c.transient_bins > 0)
@@ -1288,13 +1304,13 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     apt_renderer* r = new apt_renderer();
     struct Owner { apt_renderer* r; ~Owner() { if (r) apt_renderer_destroy(r); } } owner{r};     // every early return below releases streams, events and queue pools
     r->scene = sc; r->cfg = c;
-    r->adaptive = c.adaptive_threshold > 0.f ? 1 : 0; r->transient = c.transient_bins > 0 ? 1 : 0; r->lengths = c.path_lengths ? 1 : 0; r->light_groups = c.light_groups ? 1 : 0;
+    r->adaptive = c.adaptive_threshold > 0.f ? 1 : 0; r->split_mode = split_mode;
     if (int rc = plan_film(r)) return rc;
     pick_traversal(r);
     if (int rc = pick_shading(r)) return rc;
     if (int rc = make_camera_strips(r)) return rc;
     if (int rc = make_lanes(r)) return rc;
-    if (int rc = make_transient(r)) return rc;
+    if (int rc = make_split(r)) return rc;
     if (int rc = make_adaptive(r)) return rc;
     if (int rc = plan_lds_and_grids(r)) return rc;
     if (int rc = make_overflow_stacks(r)) return rc;
@@ -1527,15 +1543,19 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
             if (r->adaptive) hipLaunchKernelGGL(k_generate_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, cnt, (const uint8_t*)r->aq.active);
             else hipLaunchKernelGGL(k_generate, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, cnt);
         }
-        // transient: a bounce's records are binned once its light samples are all settled - after its shadow launch, or with the flat sweep
-        // after the next bounce's fix-up launch (it serves the deferred ones) - and before the next shade launch writes new ones
-        // path lengths: the same launch points; `settled` is the bounce whose records they are (with the flat sweep the previous one)
-        // light groups: the same launch points
+        // split render: a bounce's records are binned once its light samples are all settled - after its shadow launch, or with the flat sweep
+        // after the next bounce's fix-up launch (it serves the deferred ones) - and before the next shade launch writes new ones;
+        // `settled` is the bounce whose records they are (with the flat sweep the previous one)
         auto bin = [&](int settled) {
             LaunchTimer t(r, APT_K_FINALIZE, st, false);
-            if (r->light_groups) hipLaunchKernelGGL(k_bin_lights, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->lg_planes.as<float4>(), r->scene->n_sources, r->lg_aux.as<unsigned int>(), r->accum.as<float>());
-            else if (r->lengths) hipLaunchKernelGGL(k_bin_lengths, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->len_planes.as<float4>(), settled, r->accum.as<float>());
-            else hipLaunchKernelGGL(k_bin_transient, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->tq, r->accum.as<float>());
+            const dim3 grid(grid_for((size_t)r->npix, r->grid_small, 1));
+            float4* cells = r->split_cells.as<float4>();
+            switch (r->split_mode) {
+                case SPLIT_TRANSIENT: hipLaunchKernelGGL(k_bin_transient, grid, dim3(BLOCK), 0, st, p, q, r->tq, r->accum.as<float>()); break;
+                case SPLIT_LENGTHS: hipLaunchKernelGGL(k_bin_lengths, grid, dim3(BLOCK), 0, st, p, q, r->tq, cells, settled, r->accum.as<float>()); break;
+                case SPLIT_LIGHTS: hipLaunchKernelGGL(k_bin_lights, grid, dim3(BLOCK), 0, st, p, q, r->tq, cells, r->scene->n_sources, r->lg_aux.as<unsigned int>(), r->accum.as<float>()); break;
+                case SPLIT_NONE: break;
+            }
         };
         int cur = 0;
         for (int b = 0; b < p.max_bounce; b++) {
@@ -1683,58 +1703,31 @@ APT_EXPORT int apt_set_accum(apt_renderer* r, const float* in, int32_t cnt) {
     r->cnt = cnt;
     return resolve_events(r);
 }
-APT_EXPORT int apt_read_transient(apt_renderer* r, float* out) {
-    if (!r || !out) return fail(APT_E_INVALID, "apt_read_transient: bad argument");
-    if (!r->transient) return fail(APT_E_STATE, "apt_read_transient: the renderer was created with transient_bins = 0");
+// The six exports that read or set a split render's cells: `who` the export's name, `mode` the mode it serves, exactly one of out / in.
+static int copy_split_cells(const char* who, SplitMode mode, apt_renderer* r, float* out, const float* in) {
+    if (!r || (!out && !in)) return fail(APT_E_INVALID, std::string(who) + ": bad argument");
+    if (r->split_mode != mode) return fail(APT_E_STATE, std::string(who) + ": the renderer was created with " + kSplit[mode].field + " = 0");
     HIP_TRY(hipSetDevice(r->cfg.device));
-    HIP_TRY(hipMemcpyAsync(out, r->tr_bins.p, r->tr_bins.bytes, hipMemcpyDeviceToHost, r->stream()));
+    if (out) HIP_TRY(hipMemcpyAsync(out, r->split_cells.p, r->split_cells.bytes, hipMemcpyDeviceToHost, r->stream()));
+    else HIP_TRY(hipMemcpyAsync(r->split_cells.p, in, r->split_cells.bytes, hipMemcpyHostToDevice, r->stream()));
     return resolve_events(r);
 }
-APT_EXPORT int apt_set_transient(apt_renderer* r, const float* in) {
-    if (!r || !in) return fail(APT_E_INVALID, "apt_set_transient: bad argument");
-    if (!r->transient) return fail(APT_E_STATE, "apt_set_transient: the renderer was created with transient_bins = 0");
-    HIP_TRY(hipSetDevice(r->cfg.device));
-    HIP_TRY(hipMemcpyAsync(r->tr_bins.p, in, r->tr_bins.bytes, hipMemcpyHostToDevice, r->stream()));
-    return resolve_events(r);
-}
-APT_EXPORT int apt_read_path_lengths(apt_renderer* r, float* out) {
-    if (!r || !out) return fail(APT_E_INVALID, "apt_read_path_lengths: bad argument");
-    if (!r->lengths) return fail(APT_E_STATE, "apt_read_path_lengths: the renderer was created with path_lengths = 0");
-    HIP_TRY(hipSetDevice(r->cfg.device));
-    HIP_TRY(hipMemcpyAsync(out, r->len_planes.p, r->len_planes.bytes, hipMemcpyDeviceToHost, r->stream()));
-    return resolve_events(r);
-}
-APT_EXPORT int apt_set_path_lengths(apt_renderer* r, const float* in) {
-    if (!r || !in) return fail(APT_E_INVALID, "apt_set_path_lengths: bad argument");
-    if (!r->lengths) return fail(APT_E_STATE, "apt_set_path_lengths: the renderer was created with path_lengths = 0");
-    HIP_TRY(hipSetDevice(r->cfg.device));
-    HIP_TRY(hipMemcpyAsync(r->len_planes.p, in, r->len_planes.bytes, hipMemcpyHostToDevice, r->stream()));
-    return resolve_events(r);
-}
-APT_EXPORT int apt_read_light_groups(apt_renderer* r, float* out) {
-    if (!r || !out) return fail(APT_E_INVALID, "apt_read_light_groups: bad argument");
-    if (!r->light_groups) return fail(APT_E_STATE, "apt_read_light_groups: the renderer was created with light_groups = 0");
-    HIP_TRY(hipSetDevice(r->cfg.device));
-    HIP_TRY(hipMemcpyAsync(out, r->lg_planes.p, r->lg_planes.bytes, hipMemcpyDeviceToHost, r->stream()));
-    return resolve_events(r);
-}
-APT_EXPORT int apt_set_light_groups(apt_renderer* r, const float* in) {
-    if (!r || !in) return fail(APT_E_INVALID, "apt_set_light_groups: bad argument");
-    if (!r->light_groups) return fail(APT_E_STATE, "apt_set_light_groups: the renderer was created with light_groups = 0");
-    HIP_TRY(hipSetDevice(r->cfg.device));
-    HIP_TRY(hipMemcpyAsync(r->lg_planes.p, in, r->lg_planes.bytes, hipMemcpyHostToDevice, r->stream()));
-    return resolve_events(r);
-}
+APT_EXPORT int apt_read_transient(apt_renderer* r, float* out) { return copy_split_cells("apt_read_transient", SPLIT_TRANSIENT, r, out, nullptr); }
+APT_EXPORT int apt_set_transient(apt_renderer* r, const float* in) { return copy_split_cells("apt_set_transient", SPLIT_TRANSIENT, r, nullptr, in); }
+APT_EXPORT int apt_read_path_lengths(apt_renderer* r, float* out) { return copy_split_cells("apt_read_path_lengths", SPLIT_LENGTHS, r, out, nullptr); }
+APT_EXPORT int apt_set_path_lengths(apt_renderer* r, const float* in) { return copy_split_cells("apt_set_path_lengths", SPLIT_LENGTHS, r, nullptr, in); }
+APT_EXPORT int apt_read_light_groups(apt_renderer* r, float* out) { return copy_split_cells("apt_read_light_groups", SPLIT_LIGHTS, r, out, nullptr); }
+APT_EXPORT int apt_set_light_groups(apt_renderer* r, const float* in) { return copy_split_cells("apt_set_light_groups", SPLIT_LIGHTS, r, nullptr, in); }
 // out = the owned tile relit: every emitter's planes times its rgb gain, summed, / cnt (stages.hpp k_relight); [local col][y][rgb] like apt_read_pixels
 APT_EXPORT int apt_relight(apt_renderer* r, const float* gains, float* out) {
     if (!r || !gains || !out) return fail(APT_E_INVALID, "apt_relight: bad argument");
-    if (!r->light_groups) return fail(APT_E_STATE, "apt_relight: the renderer was created with light_groups = 0");
+    if (r->split_mode != SPLIT_LIGHTS) return fail(APT_E_STATE, "apt_relight: the renderer was created with light_groups = 0");
     HIP_TRY(hipSetDevice(r->cfg.device));
     const int ne = r->scene->n_sources;
     float* d_gain = reinterpret_cast<float*>(static_cast<char*>(r->lg_aux.p) + 16);
     float* d_out = d_gain + 3 * (size_t)ne;
     HIP_TRY(hipMemcpyAsync(d_gain, gains, (size_t)ne * 12, hipMemcpyHostToDevice, r->stream()));
-    hipLaunchKernelGGL(k_relight, dim3((unsigned)(((size_t)r->npix + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, r->stream(), (const float4*)r->lg_planes.as<float4>(), (const float*)d_gain, d_out, r->npix, ne, (float)(r->cnt > 0 ? r->cnt : 1));
+    hipLaunchKernelGGL(k_relight, dim3((unsigned)(((size_t)r->npix + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, r->stream(), (const float4*)r->split_cells.as<float4>(), (const float*)d_gain, d_out, r->npix, ne, (float)(r->cnt > 0 ? r->cnt : 1));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)r->npix * 12, hipMemcpyDeviceToHost, r->stream()));
     return resolve_events(r);
@@ -1743,9 +1736,8 @@ APT_EXPORT int apt_reset(apt_renderer* r) {
     if (!r) return fail(APT_E_INVALID, "apt_reset: null handle");
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
-    if (r->transient) HIP_TRY(hipMemsetAsync(r->tr_bins.p, 0, r->tr_bins.bytes, r->stream()));
-    if (r->lengths) HIP_TRY(hipMemsetAsync(r->len_planes.p, 0, r->len_planes.bytes, r->stream()));
-    if (r->light_groups) { HIP_TRY(hipMemsetAsync(r->lg_planes.p, 0, r->lg_planes.bytes, r->stream())); HIP_TRY(hipMemsetAsync(r->lg_aux.p, 0, 16, r->stream())); }
+    if (r->split()) HIP_TRY(hipMemsetAsync(r->split_cells.p, 0, r->split_cells.bytes, r->stream()));
+    if (r->split_mode == SPLIT_LIGHTS) HIP_TRY(hipMemsetAsync(r->lg_aux.p, 0, 16, r->stream()));
     if (r->aov_sum.p) HIP_TRY(hipMemsetAsync(r->aov_sum.p, 0, r->aov_sum.bytes, r->stream()));
     for (Lane& ln : r->lanes) HIP_TRY(hipMemsetAsync(ln.counters.p, 0, sizeof(Counters), r->stream()));      // lanes are idle between render calls
     r->cnt = 0;
@@ -1832,7 +1824,7 @@ APT_EXPORT int apt_get_stats(apt_renderer* r, apt_stats* out) {
 #endif
     for (int k = 0; k < APT_N_KERNELS; k++) { out->launches[k] = r->launches[k]; out->kernel_ms[k] = r->kernel_ms[k]; }
     out->render_ms = r->render_ms;
-    if (r->light_groups) { unsigned int stray = 0; HIP_TRY(hipMemcpy(&stray, r->lg_aux.p, 4, hipMemcpyDeviceToHost)); out->n_stray_light = (int64_t)stray; }
+    if (r->split_mode == SPLIT_LIGHTS) { unsigned int stray = 0; HIP_TRY(hipMemcpy(&stray, r->lg_aux.p, 4, hipMemcpyDeviceToHost)); out->n_stray_light = (int64_t)stray; }
     if (n_overflow > 0) return fail(APT_E_STATE, "apt_get_stats: " + std::to_string((long long)n_overflow) + " volumetric path(s) drew more than 2^23 random numbers: the draw index wrapped and those paths re-used part of their stream");
     return APT_OK;
 }

@@ -1195,114 +1195,80 @@ __global__ void k_divide_ad(const float* accum, const int32_t* n, float* out, ui
     if (i < n3) { const int c = n[i / 3u]; out[i] = c > 0 ? accum[i] / (float)c : 0.f; }
 }
 
-// ------------------------------------------------------------ transient bins
-// Once per bounce, after that bounce's light samples are settled (flat sweep: after the next bounce's fix-up launch, which serves the
-// deferred ones): one thread per owned pixel walks the batch's samples in order and, per sample, the emitter-hit record and the radiance
-// planes of the light samples; every non-zero contribution (NaN components dropped, as k_finalize drops them) is added to its time bin
-// and to the steady framebuffer, and the record is cleared for the next bounce.  The pixel owns its bins and its framebuffer entry: no
-// atomics, and the order of the adds depends on the batch split only.  (Binning at batch end instead would keep every bounce's records:
-// cap x bounces x (1 + S) float4.)  The render runs one lane in this mode, so no other batch adds to the bins meanwhile.
-__global__ void __launch_bounds__(BLOCK) k_bin_transient(Params p, Queues q, TransQ tq, float* accum) {
-    const uint32_t stride = gridDim.x * BLOCK;
-    for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride) {
-        f3 sum = splat3(0.f);
-        auto land = [&](float4 c, float t) {
-            const f3 v = mk3(isnan(c.x) ? 0.f : c.x, isnan(c.y) ? 0.f : c.y, isnan(c.z) ? 0.f : c.z);
-            if (v.x == 0.f && v.y == 0.f && v.z == 0.f) return;
-            sum = sum + v;
-            const int b = transient_bin(tq, t);
-            if (b < 0) return;
-            float4* bin = tq.bins + (size_t)b * (size_t)p.npix + lp;
-            const float4 a = *bin;
-            *bin = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + 1.f);
-        };
-        for (int s = 0; s < p.spp_batch; s++) {
-            const uint32_t slot = (uint32_t)s * (uint32_t)p.npix + lp;
-            const float4 e = tq.emit[slot];
-            if (e.x != 0.f || e.y != 0.f || e.z != 0.f) { land(e, e.w); tq.emit[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }      // (NaN != 0: cleared too)
-            for (int pl = 0; pl < p.l_planes; pl++) {      // light samples in sample order
-                float4* l4 = reinterpret_cast<float4*>(L_slot(q.L, p.cap, (slot << 2) | (uint32_t)pl));
-                const float4 c = *l4;
-                if (c.x != 0.f || c.y != 0.f || c.z != 0.f) { land(c, tq.t_light[(size_t)pl * p.cap + slot]); *l4 = make_float4(0.f, 0.f, 0.f, 0.f); }
-            }
+// ------------------------------------------------------------ split renders: transient bins, path-length planes, light groups
+// One mechanism, three modes.  Once per bounce, after that bounce's light samples are settled (flat sweep: after the next bounce's fix-up
+// launch, which serves the deferred ones), the mode's binning kernel runs: one thread per owned pixel walks the batch's samples in order
+// and, per sample, the emitter-hit record and then the radiance planes of the light samples.  Every non-zero contribution (NaN components
+// dropped, as k_finalize drops them) is handed to the mode's landing rule - land(rgb, key, part): key is the record's fourth component
+// (emit[].w, t_light[]), part 0 an emitter hit reached by a sampled ray, 1 a light sample - and summed for the steady framebuffer; the
+// record is cleared for the next bounce.  The pixel owns its cells and its framebuffer entry: no atomics on floats, and the order of the
+// adds depends on the batch split only.  (Binning at batch end instead would keep every bounce's records: cap x bounces x (1 + S)
+// float4.)  A split render runs one lane, so no other batch adds to the cells meanwhile.
+template <typename Land>
+APT_D void walk_split_records(const Params& p, const Queues& q, const TransQ& tq, uint32_t lp, float* accum, Land land) {
+    f3 sum = splat3(0.f);
+    auto take = [&](float4 c, float key, int part) {
+        const f3 v = mk3(isnan(c.x) ? 0.f : c.x, isnan(c.y) ? 0.f : c.y, isnan(c.z) ? 0.f : c.z);
+        if (v.x == 0.f && v.y == 0.f && v.z == 0.f) return;
+        sum = sum + v;
+        land(v, key, part);
+    };
+    for (int s = 0; s < p.spp_batch; s++) {
+        const uint32_t slot = (uint32_t)s * (uint32_t)p.npix + lp;
+        const float4 e = tq.emit[slot];
+        if (e.x != 0.f || e.y != 0.f || e.z != 0.f) { take(e, e.w, 0); tq.emit[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }      // (NaN != 0: cleared too)
+        for (int pl = 0; pl < p.l_planes; pl++) {      // light samples in sample order
+            float4* l4 = reinterpret_cast<float4*>(L_slot(q.L, p.cap, (slot << 2) | (uint32_t)pl));
+            const float4 c = *l4;
+            if (c.x != 0.f || c.y != 0.f || c.z != 0.f) { take(c, tq.t_light[(size_t)pl * p.cap + slot], 1); *l4 = make_float4(0.f, 0.f, 0.f, 0.f); }
         }
-        if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
     }
+    if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
+}
+// one contribution into a cell the pixel owns: summed rgb, and the number of contributions
+APT_D void add_to_cell(float4* cell, f3 v, float n) {
+    const float4 a = *cell;
+    *cell = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + n);
 }
 
-// ------------------------------------------------------------ path-length planes
-// k_bin_transient's sibling: the same records, visited at the same points of the bounce loop, keyed by the bounce the host names instead of
-// by time.  A path's length is its number of segments, camera to emitter: the emitter hit at vertex `bounce` has length bounce + 1 and goes
-// to plane `bounce`, part 0 (reached by a sampled ray); the vertex's light samples have length bounce + 2 and go, all of them, to plane
-// bounce + 1, part 1 (reached by a light sample).  planes is [plane * 2 + part][local pixel] float4 - summed rgb and the number of
-// contributions -, so a wave's 64 pixels touch 1 KiB in a row.  A batch's contributions to a cell are summed in registers, samples in order,
-// and added once; the framebuffer takes the records' sum in k_bin_transient's order.  The pixel owns its cells: no atomics.  The host
-// keeps bounce < max_bounce, so plane bounce + 1 is the last of the max_bounce + 1 at most.
+// Transient bins: key is the contribution's time; it lands in tq.bins[transient_bin(time)][local pixel], a read-modify-write per record;
+// outside the window it lands nowhere (the framebuffer still takes it).
+__global__ void __launch_bounds__(BLOCK) k_bin_transient(Params p, Queues q, TransQ tq, float* accum) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride)
+        walk_split_records(p, q, tq, lp, accum, [&](f3 v, float t, int) {
+            const int b = transient_bin(tq, t);
+            if (b >= 0) add_to_cell(tq.bins + (size_t)b * (size_t)p.npix + lp, v, 1.f);
+        });
+}
+
+// Path-length planes: keyed by the bounce the host names, the key is not read.  A path's length is its number of
+// segments, camera to emitter: the emitter hit at vertex `bounce` has length bounce + 1 and goes to plane `bounce`, part 0; the vertex's
+// light samples have length bounce + 2 and go, all of them, to plane bounce + 1, part 1.  planes is [plane * 2 + part][local pixel]
+// float4, so a wave's 64 pixels touch 1 KiB in a row.  Only two cells can take a batch's records: they are summed in registers, samples
+// in order, and added once.  The host keeps bounce < max_bounce, so plane bounce + 1 is the last of the max_bounce + 1 at most.
 __global__ void __launch_bounds__(BLOCK) k_bin_lengths(Params p, Queues q, TransQ tq, float4* planes, int bounce, float* accum) {
     const uint32_t stride = gridDim.x * BLOCK;
     for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride) {
-        f3 sum = splat3(0.f);
         float4 part[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-        auto land = [&](float4 c, float4& cell) {
-            const f3 v = mk3(isnan(c.x) ? 0.f : c.x, isnan(c.y) ? 0.f : c.y, isnan(c.z) ? 0.f : c.z);
-            if (v.x == 0.f && v.y == 0.f && v.z == 0.f) return;
-            sum = sum + v;
-            cell = make_float4(cell.x + v.x, cell.y + v.y, cell.z + v.z, cell.w + 1.f);
-        };
-        for (int s = 0; s < p.spp_batch; s++) {
-            const uint32_t slot = (uint32_t)s * (uint32_t)p.npix + lp;
-            const float4 e = tq.emit[slot];
-            if (e.x != 0.f || e.y != 0.f || e.z != 0.f) { land(e, part[0]); tq.emit[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }      // (NaN != 0: cleared too)
-            for (int pl = 0; pl < p.l_planes; pl++) {      // light samples in sample order
-                float4* l4 = reinterpret_cast<float4*>(L_slot(q.L, p.cap, (slot << 2) | (uint32_t)pl));
-                const float4 c = *l4;
-                if (c.x != 0.f || c.y != 0.f || c.z != 0.f) { land(c, part[1]); *l4 = make_float4(0.f, 0.f, 0.f, 0.f); }
-            }
-        }
-        for (int k = 0; k < 2; k++) {
-            if (part[k].w == 0.f) continue;
-            float4* cell = planes + (size_t)((bounce + k) * 2 + k) * (size_t)p.npix + lp;
-            const float4 a = *cell;
-            *cell = make_float4(a.x + part[k].x, a.y + part[k].y, a.z + part[k].z, a.w + part[k].w);
-        }
-        if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
+        walk_split_records(p, q, tq, lp, accum, [&](f3 v, float, int k) { part[k] = make_float4(part[k].x + v.x, part[k].y + v.y, part[k].z + v.z, part[k].w + 1.f); });
+        for (int k = 0; k < 2; k++)
+            if (part[k].w != 0.f) add_to_cell(planes + (size_t)((bounce + k) * 2 + k) * (size_t)p.npix + lp, mk3(part[k].x, part[k].y, part[k].z), part[k].w);
     }
 }
 
-// ------------------------------------------------------------ light groups
-// The third sibling: the same records at the same points of the bounce loop, keyed by the emitter the light came from.  In this mode the
-// shade twins store the emitter's index where a transient render stores a time (TransQ::by_light): emit[slot].w names the emitter the
-// vertex sits on, t_light[plane * cap + slot] the one light sample `plane` drew.  The emitter-hit record goes to cell [e][0] (reached by
-// a sampled ray), a light sample's radiance plane to [e][1] (reached by a light sample).  planes is [emitter * 2 + part][local pixel]
-// float4 - summed rgb and the number of contributions.  The cell a record lands in is only known per record, so each one is a
-// read-modify-write of its cell, samples in order, as k_bin_transient's bins are; the framebuffer takes the records' sum in
-// k_bin_transient's order.  The pixel owns its cells: no atomics on floats.  A non-zero record whose index is not in [0, n_emitters)
-// writes nowhere and is counted in *n_stray (an integer tally, tested to stay 0); the framebuffer still takes it.
+// Light groups: in this mode the shade twins store the emitter's index where a transient render stores a time
+// (TransQ::by_light), so key names the emitter the vertex sits on (part 0) or the one the light sample drew (part 1).  planes is
+// [emitter * 2 + part][local pixel] float4; a read-modify-write per record.  A non-zero record whose index is not in [0, n_emitters)
+// lands nowhere and is counted in *n_stray (an integer tally, tested to stay 0); the framebuffer still takes it.
 __global__ void __launch_bounds__(BLOCK) k_bin_lights(Params p, Queues q, TransQ tq, float4* planes, int n_emitters, unsigned int* n_stray, float* accum) {
     const uint32_t stride = gridDim.x * BLOCK;
     for (uint32_t lp = blockIdx.x * BLOCK + threadIdx.x; lp < (uint32_t)p.npix; lp += stride) {
-        f3 sum = splat3(0.f);
         uint32_t stray = 0;
-        auto land = [&](float4 c, float who, int part) {
-            const f3 v = mk3(isnan(c.x) ? 0.f : c.x, isnan(c.y) ? 0.f : c.y, isnan(c.z) ? 0.f : c.z);
-            if (v.x == 0.f && v.y == 0.f && v.z == 0.f) return;
-            sum = sum + v;
+        walk_split_records(p, q, tq, lp, accum, [&](f3 v, float who, int part) {
             if (!(who >= 0.f && who < (float)n_emitters)) { stray++; return; }      // (NaN fails both)
-            float4* cell = planes + (size_t)((int)who * 2 + part) * (size_t)p.npix + lp;
-            const float4 a = *cell;
-            *cell = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + 1.f);
-        };
-        for (int s = 0; s < p.spp_batch; s++) {
-            const uint32_t slot = (uint32_t)s * (uint32_t)p.npix + lp;
-            const float4 e = tq.emit[slot];
-            if (e.x != 0.f || e.y != 0.f || e.z != 0.f) { land(e, e.w, 0); tq.emit[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }      // (NaN != 0: cleared too)
-            for (int pl = 0; pl < p.l_planes; pl++) {      // light samples in sample order
-                float4* l4 = reinterpret_cast<float4*>(L_slot(q.L, p.cap, (slot << 2) | (uint32_t)pl));
-                const float4 c = *l4;
-                if (c.x != 0.f || c.y != 0.f || c.z != 0.f) { land(c, tq.t_light[(size_t)pl * p.cap + slot], 1); *l4 = make_float4(0.f, 0.f, 0.f, 0.f); }
-            }
-        }
-        if (sum.x != 0.f || sum.y != 0.f || sum.z != 0.f) { accum[3 * lp] += sum.x; accum[3 * lp + 1] += sum.y; accum[3 * lp + 2] += sum.z; }
+            add_to_cell(planes + (size_t)((int)who * 2 + part) * (size_t)p.npix + lp, v, 1.f);
+        });
         if (stray) atomicAdd(n_stray, stray);
     }
 }

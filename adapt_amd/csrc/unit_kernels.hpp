@@ -83,7 +83,7 @@ __global__ void k_surface_maps_probe(DevScene sc, int n, const int* prim_first, 
     float* o = out7 + 7 * k;
     o[0] = kd.x; o[1] = kd.y; o[2] = kd.z; o[3] = it.n_s.x; o[4] = it.n_s.y; o[5] = it.n_s.z; o[6] = (float)applied;
 }
-// stages.hpp transient_bin on explicit times (the window as make_transient sets it up)
+// stages.hpp transient_bin on explicit times (the window as make_split sets it up)
 __global__ void k_transient_bin_probe(TransQ tq, int n, const float* t, int* out) {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;

@@ -56,6 +56,7 @@ from __future__ import annotations
 
 import ctypes as C
 import time
+from collections import namedtuple
 from typing import List, Optional
 
 import numpy as np
@@ -72,6 +73,18 @@ DENOISE_DEFAULTS = {"firefly_threshold": 0.0, "iterations": 3, "sigma_n": 128.0,
 # apt_renderer_info's trace_mode -> name: TRACE_BVH, TRACE_SWEEP, TRACE_TILE, TRACE_FLAT (csrc/stages.hpp), the words of csrc/api.hip kTraversalName in its order
 TRAVERSAL_NAMES = dict(enumerate(("bvh", "sweep", "tile", "flat")))
 BVH_BUILDER_NAMES = dict(enumerate(("sah", "lbvh", "ploc")))      # apt_scene_bvh_builder: what built the scene's tree, after any fallback
+# The split renders, by the Renderer option that switches one on.  n: the attribute with the number of leading planes
+# (0: the mode is off); inner: the plane shape between it and (n_cols, h, 4); read / set: the library's entry points; key: the planes'
+# checkpoint key; missing: what a renderer created without the option says.
+_Split = namedtuple("_Split", "n inner read set key missing")
+SPLIT_MODES = {
+    "transient": _Split("n_bins", (), "apt_read_transient", "apt_set_transient", "transient_bins",
+                        "this renderer was created without transient=...: there are no time bins"),
+    "path_lengths": _Split("n_lengths", (2,), "apt_read_path_lengths", "apt_set_path_lengths", "path_length_planes",
+                           "this renderer was created without path_lengths=True: there are no path-length planes"),
+    "light_groups": _Split("n_groups", (2,), "apt_read_light_groups", "apt_set_light_groups", "light_group_planes",
+                           "this renderer was created without light_groups=True: there are no light-group planes"),
+}
 
 
 def adaptive_config(adaptive) -> Optional[dict]:
@@ -449,54 +462,59 @@ class Renderer:
         from .tiles import gather_image
         return gather_image(self, normalised)          # (adaptive: divided by the gathered per-pixel counts)
 
-    # ----------------------------------------------------------- transient
-    def _need_transient(self):
-        if not self.n_bins:
-            raise RuntimeError("this renderer was created without transient=...: there are no time bins")
+    # ----------------------------------------------------------- split renders (SPLIT_MODES)
+    def _need_split(self, mode: str):
+        if not getattr(self, SPLIT_MODES[mode].n):
+            raise RuntimeError(SPLIT_MODES[mode].missing)
+
+    def _split_shape(self, mode: str) -> tuple:
+        m = SPLIT_MODES[mode]
+        return (getattr(self, m.n), *m.inner, self.n_cols, self.h, 4)
+
+    def _read_split(self, mode: str) -> np.ndarray:
+        """this rank's raw cells: summed r, g, b and the number of contributions"""
+        self._need_split(mode)
+        out = np.empty(self._split_shape(mode), np.float32)
+        _lib.check(getattr(self.lib, SPLIT_MODES[mode].read)(self.handle, _fp(out)), SPLIT_MODES[mode].read, self.lib)
+        return out
+
+    def _set_split(self, mode: str, cells: np.ndarray):
+        cells = np.ascontiguousarray(cells, np.float32)
+        _lib.check(getattr(self.lib, SPLIT_MODES[mode].set)(self.handle, _fp(cells)), SPLIT_MODES[mode].set, self.lib)
+
+    def _split_radiance(self, mode: str) -> np.ndarray:
+        """the cells' rgb divided by the sample count like `pixels`"""
+        return self._read_split(mode)[..., :3] / np.float32(self._cnt if self._cnt > 0 else 1)
+
+    def _split_counts(self, mode: str) -> np.ndarray:
+        return np.ascontiguousarray(self._read_split(mode)[..., 3])
 
     def tile_transient(self) -> np.ndarray:
         """This rank's raw bins, (n_bins, n_cols, h, 4) float32: summed r, g, b and the number of contributions."""
-        self._need_transient()
-        out = np.empty((self.n_bins, self.n_cols, self.h, 4), np.float32)
-        _lib.check(self.lib.apt_read_transient(self.handle, _fp(out)), "apt_read_transient", self.lib)
-        return out
+        return self._read_split("transient")
 
     def transient(self) -> np.ndarray:
         """(n_bins, w, h, 3) float32, index [t, x, y]: the radiance that arrived in time bin t, divided by the sample count like `pixels`.
         With a window that holds every path the bins sum to the steady image."""
-        cube = self.tile_transient()[..., :3]
-        return cube / np.float32(self._cnt if self._cnt > 0 else 1)
+        return self._split_radiance("transient")
 
     def transient_counts(self) -> np.ndarray:
         """(n_bins, w, h) float32: the number of contributions per bin (divide transient() * cnt by it for bdpt.py's copy_average)."""
-        return np.ascontiguousarray(self.tile_transient()[..., 3])
-
-    def _set_transient(self, cube: np.ndarray):
-        cube = np.ascontiguousarray(cube, np.float32)
-        _lib.check(self.lib.apt_set_transient(self.handle, _fp(cube)), "apt_set_transient", self.lib)
-
-    # ----------------------------------------------------------- path lengths (DESIGN.md §4.8)
-    def _need_path_lengths(self):
-        if not self.n_lengths:
-            raise RuntimeError("this renderer was created without path_lengths=True: there are no path-length planes")
+        return self._split_counts("transient")
 
     def tile_path_lengths(self) -> np.ndarray:
         """This rank's raw planes, (max_bounce + 1, 2, n_cols, h, 4) float32, index [length - 1, part, x, y]: summed r, g, b and the number
         of contributions.  Part 0: the emitter was reached by a sampled ray, part 1: by a light sample."""
-        self._need_path_lengths()
-        out = np.empty((self.n_lengths, 2, self.n_cols, self.h, 4), np.float32)
-        _lib.check(self.lib.apt_read_path_lengths(self.handle, _fp(out)), "apt_read_path_lengths", self.lib)
-        return out
+        return self._read_split("path_lengths")
 
     def path_lengths(self) -> np.ndarray:
         """(max_bounce + 1, 2, w, h, 3) float32: the radiance that arrived over paths of each length, by part, divided by the sample count
         like `pixels`; summed over lengths and parts it is `pixels` up to float summation order."""
-        planes = self.tile_path_lengths()[..., :3]
-        return planes / np.float32(self._cnt if self._cnt > 0 else 1)
+        return self._split_radiance("path_lengths")
 
     def path_length_counts(self) -> np.ndarray:
         """(max_bounce + 1, 2, w, h) float32: the number of contributions per cell."""
-        return np.ascontiguousarray(self.tile_path_lengths()[..., 3])
+        return self._split_counts("path_lengths")
 
     def emission(self) -> np.ndarray:
         """(w, h, 3): length 1, the emitters as the camera sees them."""
@@ -510,37 +528,24 @@ class Renderer:
         """(w, h, 3): lengths 3 and more."""
         return self.path_lengths()[2:].sum((0, 1))
 
-    def _set_path_lengths(self, planes: np.ndarray):
-        planes = np.ascontiguousarray(planes, np.float32)
-        _lib.check(self.lib.apt_set_path_lengths(self.handle, _fp(planes)), "apt_set_path_lengths", self.lib)
-
-    # ----------------------------------------------------------- light groups (DESIGN.md §4.9)
-    def _need_light_groups(self):
-        if not self.n_groups:
-            raise RuntimeError("this renderer was created without light_groups=True: there are no light-group planes")
-
     def tile_light_groups(self) -> np.ndarray:
         """This rank's raw planes, (n_emitters, 2, n_cols, h, 4) float32, index [emitter, part, x, y]: summed r, g, b and the number of
         contributions.  Part 0: the emitter was reached by a sampled ray, part 1: by a light sample."""
-        self._need_light_groups()
-        out = np.empty((self.n_groups, 2, self.n_cols, self.h, 4), np.float32)
-        _lib.check(self.lib.apt_read_light_groups(self.handle, _fp(out)), "apt_read_light_groups", self.lib)
-        return out
+        return self._read_split("light_groups")
 
     def light_groups(self) -> np.ndarray:
         """(n_emitters, 2, w, h, 3) float32: the radiance that came from each emitter, by part, divided by the sample count like `pixels`;
         summed over emitters and parts it is `pixels` up to float summation order."""
-        planes = self.tile_light_groups()[..., :3]
-        return planes / np.float32(self._cnt if self._cnt > 0 else 1)
+        return self._split_radiance("light_groups")
 
     def light_group_counts(self) -> np.ndarray:
         """(n_emitters, 2, w, h) float32: the number of contributions per cell."""
-        return np.ascontiguousarray(self.tile_light_groups()[..., 3])
+        return self._split_counts("light_groups")
 
     def light_gains(self, gains) -> np.ndarray:
         """-> (n_emitters, 3) float32 from a scalar per emitter, an rgb triple per emitter, or a dict from emitter id to either (emitters
         the dict does not name keep gain 1)."""
-        self._need_light_groups()
+        self._need_split("light_groups")
         out = np.ones((self.n_groups, 3), np.float32)
         if isinstance(gains, dict):
             for key, g in gains.items():
@@ -563,10 +568,6 @@ class Renderer:
         out = np.empty((self.n_cols, self.h, 3), np.float32)
         _lib.check(self.lib.apt_relight(self.handle, _fp(g), _fp(out)), "apt_relight", self.lib)
         return out
-
-    def _set_light_groups(self, planes: np.ndarray):
-        planes = np.ascontiguousarray(planes, np.float32)
-        _lib.check(self.lib.apt_set_light_groups(self.handle, _fp(planes)), "apt_set_light_groups", self.lib)
 
     def _set_cnt(self, v: int):
         self._steady_only("cnt[None] = ...")
@@ -738,9 +739,7 @@ class Renderer:
                 "crop_ry": self.crop_ry, "focal": self.focal, "num_objects": self.num_objects, "num_prims": self.num_prims,
                 "cam_orient": np.array(self.cam_orient), "src_num": self.src_num, "cam_t": np.array(self.cam_t),
                 "accumulation": self.color.to_numpy(), "counter": self._cnt,
-                **({"transient_bins": self.tile_transient()} if self.n_bins else {}),
-                **({"path_length_planes": self.tile_path_lengths()} if self.n_lengths else {}),
-                **({"light_group_planes": self.tile_light_groups()} if self.n_groups else {}),
+                **{m.key: self._read_split(mode) for mode, m in SPLIT_MODES.items() if getattr(self, m.n)},
                 **({"aov_sums": self.tile_aov(), "aov_samples": self._aov_n} if self._aov_n else {}),
                 **(self._adaptive_check_point() if self.adaptive else {})}
 
@@ -757,7 +756,7 @@ class Renderer:
         if not self.adaptive and any(k in check_point for k in self._ADAPTIVE_KEYS):
             raise ValueError("this checkpoint is an adaptive render's: continue it with Renderer(..., adaptive=...)")
         for key, val in check_point.items():
-            if key in ("accumulation", "counter", "transient_bins", "path_length_planes", "light_group_planes", "aov_sums", "aov_samples") + self._ADAPTIVE_KEYS:
+            if key in ("accumulation", "counter", "aov_sums", "aov_samples") + tuple(m.key for m in SPLIT_MODES.values()) + self._ADAPTIVE_KEYS:
                 continue
             if key in ("cam_t", "cam_orient"):
                 ok = np.abs(np.asarray(val) - np.asarray(getattr(self, key))).max() < 1e-4
@@ -775,15 +774,10 @@ class Renderer:
             sums = np.ascontiguousarray(sums, np.float32)
             _lib.check(self.lib.apt_set_aov(self.handle, _fp(sums)), "apt_set_aov", self.lib)
             self._aov_n = int(check_point["aov_samples"])
-        cube = check_point.get("transient_bins")
-        if self.n_bins and cube is not None and np.shape(cube) == (self.n_bins, self.n_cols, self.h, 4):
-            self._set_transient(cube)           # (a checkpoint of another bin layout, or of a steady render, leaves the bins as they are)
-        planes = check_point.get("path_length_planes")
-        if self.n_lengths and planes is not None and np.shape(planes) == (self.n_lengths, 2, self.n_cols, self.h, 4):
-            self._set_path_lengths(planes)      # (likewise: another layout, or none, leaves the planes as they are)
-        planes = check_point.get("light_group_planes")
-        if self.n_groups and planes is not None and np.shape(planes) == (self.n_groups, 2, self.n_cols, self.h, 4):
-            self._set_light_groups(planes)      # (likewise)
+        for mode, m in SPLIT_MODES.items():      # (a checkpoint of another layout, or of a render without the mode, leaves the cells as they are)
+            cells = check_point.get(m.key)
+            if getattr(self, m.n) and cells is not None and np.shape(cells) == self._split_shape(mode):
+                self._set_split(mode, cells)
 
     def summary(self) -> str:
         self.synchronize()
