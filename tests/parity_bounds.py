@@ -58,6 +58,34 @@ PRODUCT_IMAGE_CASES = [
     ("microfacet", 64, 48, 16, {}, 0.989, 8e-5),
 ]
 
+# The capacity scenes of tests/flat_cases.py (96 primitives, tests/test_gpu_flat_capacity.py) have no measured row of their own: each
+# variant is held to the row of the bundled scene whose pipeline it runs - `lean` (Lambertian surfaces, one point light: the lean traced
+# kernels) to cbox at 96 x 96, `delta` (a glass box, mirrors: the non-lean traced kernel) to glass_box, `sorted` (three material classes,
+# area emitters, four light samples per vertex: the class-sorted pipeline) to balls_mono - and `volumetric` to VPT_PRODUCT_BOUNDS below.
+# What they measure at 48 x 40 x 8 spp stands in profiles/NOTES.md ("The flat sweep at capacity").
+CAPACITY_PRODUCT_ROWS = {"lean": ("cbox", 96), "delta": ("glass_box", 96), "sorted": ("balls_mono", 96)}
+# One case misses the row it borrows, on the per-pixel fraction alone: capacity_mixed `sorted` measures 98.65 % and relMSE 4.0e-7 (inside
+# balls_mono's 1e-6) against the oracle, its path statistics equal to the last count.  Per-pixel evidence: the 26 pixels outside are
+# outside by 1.06 .. 3.5 times the threshold, the size of ONE of a vertex's 4 x 8 light samples changing between lit and blocked
+# (n_lit 143 774 against 143 818 of the same build's reference-order sweep, 3e-4 of them); the same build with its traversal forced to
+# `sweep` - the exact build's intersector under the product build's shading arithmetic - measures 98.75 % against the oracle, on 24
+# pixels of which 17 are the same: the flips come with the product build's 1-ulp shading arithmetic, not with the flat sweep.  Their
+# likely seat - what the scene has and balls_mono has not - is the SPHERE emitter: the reference samples its whole surface, a sample near the silhouette reaches it
+# at a grazing angle, where a sphere hit is uncertain by ~sqrt(2^-24) of the distance (flat_build.cpp flat_occluders) - more than the
+# 1e-4 the shadow test leaves before the light -, and 54 shards put silhouettes in front of both emitters.  Noise of that geometry, as
+# the features_* rows above carry for their sphere light: the measured fraction with the table's margin of two on the failing part, the
+# borrowed relMSE kept.  The all-triangle scene (a mesh emitter alone) holds balls_mono's row as it stands: 99.95 %, 6.7e-7.
+CAPACITY_MEASURED_WITHIN = {("capacity_mixed", "sorted"): 0.9729}
+
+
+def capacity_product_row(name, variant):
+    """-> (min fraction of pixels within 1e-3 (1 + |x|), max relMSE): the PRODUCT_IMAGE_CASES row the variant borrows, with the one
+    measured fraction above in its place"""
+    tag, width = CAPACITY_PRODUCT_ROWS[variant]
+    (row,) = [c for c in PRODUCT_IMAGE_CASES if c[0] == tag and c[1] == width]
+    return CAPACITY_MEASURED_WITHIN.get((name, variant), row[5]), row[6]
+
+
 COUNTER_TOL = (5e-4, 150)          # path statistics against the oracle on the same stream: relative, and an absolute floor for small renders
 
 # same-seed relMSE bound at 48 x 48 x 64 spp as a fraction of the seed-to-seed noise floor (measured x 2, recorded by record_metric): the scenes

@@ -154,15 +154,38 @@ def flat_tags(flat):
     return [t for t in ALL_TAGS if flat(t).prims.reshape(-1, 9).shape[0] <= FLAT_MAX_PRIMS]
 
 
+CAPACITY_FILMS = ("64x64", "50x30")     # the films the 96-primitive scenes of tests/flat_cases.py are checked on (their host time is that of three bundled scenes)
+
+
+def flat_scenes(flat, parsed, film):
+    """what the cull tests loop over on a film: (name, packed scene, sensor dict) of every bundled scene with flat records and, on
+    CAPACITY_FILMS, of the capacity scenes (variant `lean`: one point light)"""
+    for tag in flat_tags(flat):
+        yield tag, flat(tag), parsed(tag)[3]
+    if film in CAPACITY_FILMS:
+        from flat_cases import CAPACITY_SCENES, capacity
+        for name in CAPACITY_SCENES:
+            tup, fs = capacity(name)
+            yield name, fs, tup[3]
+
+
+def upper_half(masks, lo, hi):
+    """of the strip words `masks`: (does some word have a SET bit, does some word have a CLEARED bit) among bits max(lo, 32) .. hi - 1 -
+    the half of the word no bundled scene reaches (their streams end at pair 9)"""
+    lo, hi = max(int(lo), 32), int(hi)
+    assert 32 <= lo < hi <= 64, (lo, hi)
+    field = np.uint64(((1 << (hi - lo)) - 1) << lo)
+    return bool(((masks & field) != 0).any()), bool(((masks & field) != field).any())
+
+
 @pytest.mark.parametrize("film", list(FILMS))
 def test_every_candidate_of_a_strip_is_in_its_list(film, flat, parsed):
-    tags = flat_tags(flat)
-    assert "cbox" in tags
+    scenes = list(flat_scenes(flat, parsed, film))
+    assert "cbox" in [tag for tag, _, _ in scenes]
     n_culled = 0
-    for tag in tags:
-        fs = flat(tag)
+    for tag, fs, prop in scenes:
         prims = fs.prims.reshape(-1, 9)
-        cfg = _cfg(parsed(tag)[3], FILMS[film])
+        cfg = _cfg(prop, FILMS[film])
         counts, stream, _ = flat_records(prims, fs.obj_info)
         masks, n_pairs = camera_strips(prims, fs.obj_info, cfg)
         pair, n_pairs_py = pair_of_record(counts)
@@ -200,3 +223,19 @@ def test_the_cornell_box_strips_are_shorter_than_the_stream(flat, parsed):
     assert masks.size == 4096 and n_pairs == 9
     assert lengths.mean() < n_pairs, lengths.mean()
     print(f"cbox 512x512: {lengths.mean():.2f} of {n_pairs} pairs per strip on average (min {lengths.min()}, max {lengths.max()})")
+
+
+def test_the_capacity_scenes_set_and_clear_bits_in_the_upper_half_of_the_word(parsed):
+    """capacity_mixed at 64 x 64: 41 pairs, the triangles in pairs 10 .. 38 and the spheres in 39 and 40.  Some strip lists a pair at bit
+    32 or above, some strip leaves one out - among the triangle pairs and among the sphere pairs alike; the all-triangle scene likewise
+    over its 48 pairs."""
+    from flat_cases import capacity
+    for name, n_expect, first_sphere in (("capacity_mixed", 41, 39), ("capacity_tris", 48, 48)):
+        tup, fs = capacity(name)
+        assert fs.prims.shape[0] == FLAT_MAX_PRIMS
+        masks, n_pairs = camera_strips(fs.prims, fs.obj_info, _cfg(tup[3], FILMS["64x64"]))
+        assert n_pairs == n_expect and masks.size == 64
+        assert upper_half(masks, 32, n_pairs) == (True, True), name
+        assert upper_half(masks, 32, first_sphere) == (True, True), name             # triangle pairs
+        if first_sphere < n_pairs: assert upper_half(masks, first_sphere, n_pairs) == (True, True), name
+        assert not (masks >> np.uint64(n_pairs)).any()

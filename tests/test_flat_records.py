@@ -6,7 +6,7 @@ not), the far-edge functions of convex quads, the per-triangle barycentric maps,
 import numpy as np
 import pytest
 
-from flat_cases import flat_records
+from flat_cases import flat_records, sections
 
 
 def sweep_records(counts, stream, tab, o, d):
@@ -106,3 +106,79 @@ def test_flat_records_merge_convex_pairs_only(seed):
     assert tuple(counts) == (3, 0, 8, 0, 23, 0, 0)
     sc = ob.OracleScene(fs, make_config(tup[3]).cam_t)
     check(counts, stream, tab, sc.intersect, np.zeros(fs.prims.shape[0], bool), fs.normals, 20 + seed)
+
+
+# ---- the stream at its capacity (tests/flat_cases.py capacity_mixed, capacity_tris): 96 primitives, odd section tails, over 40 pairs
+CAPACITY_COUNTS = {"capacity_mixed": (11, 2, 3, 2, 55, 2, 3), "capacity_tris": (0, 0, 0, 0, 96, 0, 0)}
+CAPACITY_PAIRS = {"capacity_mixed": 41, "capacity_tris": 48}
+
+
+def _capacity_records(name):
+    from flat_cases import capacity
+    tup, fs = capacity(name)
+    return tup, fs, flat_records(fs.prims, fs.obj_info)
+
+
+@pytest.mark.parametrize("name", list(CAPACITY_COUNTS))
+def test_capacity_scenes_reproduce_the_brute_force_hits(name):
+    from test_camera_cull import FLAT_MAX_PRIMS, pair_of_record
+    from adapt_amd.scene_pack import make_config
+    from oracle import binding as ob
+    tup, fs, (counts, stream, tab) = _capacity_records(name)
+    assert fs.prims.shape[0] == FLAT_MAX_PRIMS and tuple(counts) == CAPACITY_COUNTS[name]
+    assert pair_of_record(counts)[1] == CAPACITY_PAIRS[name] >= 40
+    sph = np.zeros(fs.prims.shape[0], bool)
+    for first, cnt, is_s in fs.obj_info: sph[first:first + cnt] = bool(is_s)
+    assert np.isfinite(fs.normals).all()
+    check(counts, stream, tab, ob.OracleScene(fs, make_config(tup[3]).cam_t).intersect, sph, fs.normals, 31)
+
+
+def test_the_mixed_capacity_scene_has_odd_tails_and_pairs_across_the_group_border():
+    _, fs, (counts, stream, tab) = _capacity_records("capacity_mixed")
+    totals = (counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6])
+    assert all(n % 2 == 1 for n in totals), totals                                  # every section ends in a lone record
+    assert counts[1] > 0 and counts[3] > 0 and counts[5] > 0                        # all three coplanar-group sub-sections
+    assert all(counts[2 * s] % 2 == 1 and counts[2 * s + 1] > 0 for s in range(3))  # a pair holds the last plain and the first group record
+    # the zero-area triangle keeps its slot with all-zero rows (flat_build.cpp build_flat): no ray can hit it
+    ids = tab.reshape(-1, 28)[:, 8:10].copy().view(np.int32)
+    tris = fs.prims.reshape(-1, 3, 3)
+    flat_ones = [k for k in range(tris.shape[0]) if not fs.obj_info[np.searchsorted(np.cumsum(fs.obj_info[:, 1]), k, side="right"), 2]
+                 and not np.cross(tris[k, 1] - tris[k, 0], tris[k, 2] - tris[k, 0]).any()]
+    assert len(flat_ones) == 1
+    (r,) = np.flatnonzero(ids[:, 0] == flat_ones[0])
+    sec, at = sections(counts)[r]
+    assert sec == 2 and ids[r, 1] == -1 and not stream[at:at + 12].any()
+
+
+@pytest.mark.parametrize("name", list(CAPACITY_COUNTS))
+def test_the_pair_layout_repeats_each_record_once_and_an_odd_tail_twice(name):
+    """FlatScene::pairs (flat_build.cpp flat_pairs, here through the occluder list of an emitter with the cull switched off, which is
+    flat_pairs of the whole stream): per section, pair j interleaves the floats of records 2j and 2j + 1; an odd tail interleaves its
+    last record with itself."""
+    from test_camera_cull import pair_of_record
+    from test_shadow_cull import occluders, pair_up
+    _, fs, (counts, stream, _) = _capacity_records(name)
+    table, keep, pairs = occluders(fs.prims, fs.obj_info, fs.src_i, fs.src_f, cull=0)
+    assert keep.all()
+    totals = [counts[0] + counts[1], counts[2] + counts[3], counts[4] + counts[5], counts[6]]
+    assert table[0, :5].tolist() == [0] + totals
+    np.testing.assert_array_equal(pairs, pair_up(stream, counts, keep[0]))
+    # and float by float, without pair_up: walk the pairs, find each half in the stream
+    pair, n_pairs = pair_of_record(counts)
+    recs = sections(counts)
+    at, seen = 0, np.zeros(len(recs), int)
+    for j in range(n_pairs):
+        mine = np.flatnonzero(pair == j)
+        sec = recs[mine[0]][0]
+        w = (12, 18, 12, 4)[sec]
+        both = pairs[at:at + 2 * w].reshape(w, 2)
+        first, second = mine[0], mine[-1]                                           # a lone record: both halves
+        assert mine.size == (1 if first == second else 2) and recs[second][0] == sec
+        np.testing.assert_array_equal(both[:, 0], stream[recs[first][1]:recs[first][1] + w])
+        np.testing.assert_array_equal(both[:, 1], stream[recs[second][1]:recs[second][1] + w])
+        seen[first] += 1; seen[second] += 1
+        at += 2 * w
+    assert at == pairs.size
+    tails = [sum(totals[:s + 1]) - 1 for s in range(4) if totals[s] % 2]
+    assert (np.delete(seen, tails) == 1).all() and (seen[tails] == 2).all()
+    if name == "capacity_mixed": assert len(tails) == 4

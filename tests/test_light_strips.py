@@ -13,7 +13,7 @@ import pytest
 
 from adapt_amd import _lib
 from flat_cases import _fma, flat_records, sections
-from test_camera_cull import _EDGE, FILMS, _cfg, camera_dirs, flat_tags, local_pixels
+from test_camera_cull import _EDGE, FILMS, FLAT_MAX_PRIMS, _cfg, camera_dirs, flat_scenes, local_pixels, upper_half
 from test_shadow_cull import occluders
 
 STRIP_EMITTERS = 16                     # bvh_build.hpp APT_LIGHT_STRIP_EMITTERS
@@ -184,11 +184,11 @@ def check_film(tag, film, fs, cfg, stats):
 
 @pytest.mark.parametrize("film", list(FILMS))
 def test_every_blocker_of_a_strip_is_in_its_mask(film, flat, parsed):
-    tags = flat_tags(flat)
-    assert "cbox" in tags
+    scenes = list(flat_scenes(flat, parsed, film))
+    assert "cbox" in [tag for tag, _, _ in scenes]
     stats = {"origins": 0, "blocked": 0, "set": 0, "of": 0}
-    for tag in tags:
-        check_film(tag, film, flat(tag), _cfg(parsed(tag)[3], FILMS[film]), stats)
+    for tag, fs, prop in scenes:
+        check_film(tag, film, fs, _cfg(prop, FILMS[film]), stats)
     assert stats["origins"] > 0 and stats["blocked"] > 0                        # the restatement sees hits and blocked samples at all
     assert stats["set"] < stats["of"], stats                                    # ... and the masks leave pairs out
     print(f"{film}: {stats}")
@@ -202,3 +202,36 @@ def test_the_cornell_box_masks_are_shorter_than_the_list(flat, parsed):
     assert masks.shape == (1, 4096) and n_pairs[0] == 6
     assert lengths.mean() < n_pairs[0], lengths.mean()
     print(f"cbox 512x512: {lengths.mean():.2f} of {n_pairs[0]} pairs per strip on average (min {lengths.min()}, max {lengths.max()}, {100.0 * (lengths == 0).mean():.1f} % of the strips keep none)")
+
+
+def test_the_capacity_scene_sets_and_clears_mask_bits_in_the_upper_half_of_the_word():
+    """capacity_mixed under its point light at 64 x 64: the light's occluder list has 39 pairs - 37 planar ones, then the two sphere
+    pairs, which a mask never leaves out.  Among the strips that see no sphere (the others keep every pair) some keep a planar pair at
+    bit 32 or above and some leave one out."""
+    from flat_cases import capacity
+    tup, fs = capacity("capacity_mixed")
+    masks, n_pairs, _ = light_strips(fs, _cfg(tup[3], FILMS["64x64"]))
+    assert masks.shape == (1, 64) and n_pairs[0] == 39
+    real = masks[0][masks[0] != ALL]
+    assert 0 < real.size < 64                                                       # strips with a sphere in view, and strips without
+    assert upper_half(real, 32, n_pairs[0]) == (True, True)
+    assert upper_half(real, 32, 37) == (True, True)                                 # the planar pairs of the upper half
+    assert upper_half(real, 37, 39) == (True, False)                                # the sphere pairs: always kept
+
+
+@pytest.mark.parametrize("n", [16, 17])
+def test_sixteen_lights_get_mask_rows_and_seventeen_get_none(n):
+    """APT_LIGHT_STRIP_EMITTERS: with 16 emitters every one has a row of masks that leave pairs out; one more and no emitter is culled by
+    strip (16 rows of all-ones words), while every emitter still gets its list's pair count"""
+    from flat_cases import many_lights
+    from adapt_amd.scene_pack import pack_scene
+    tup = many_lights(n)
+    fs = pack_scene(*tup)
+    assert fs.src_i.shape[0] == n and fs.prims.shape[0] == FLAT_MAX_PRIMS
+    masks, n_pairs, _ = light_strips(fs, _cfg(tup[3], FILMS["64x64"]))
+    assert masks.shape == (STRIP_EMITTERS, 64) and n_pairs.shape == (n,) and (n_pairs >= 33).all() and (n_pairs <= 41).all()
+    if n == 16:
+        assert all((row != ALL).any() for row in masks)
+        assert all(upper_half(row[row != ALL], 32, int(np_e) - 2) == (True, True) for row, np_e in zip(masks, n_pairs))
+    else:
+        assert (masks == ALL).all()

@@ -153,9 +153,28 @@ def _light_points(fs, e, rs, n):
     return np.concatenate([_points_on(fs.prims.reshape(-1, 9), [k], rs, 1) for k in tri])
 
 
-@pytest.mark.parametrize("tag", ["cbox", "glass_box", "features_c"])
+def test_the_capacity_scene_s_occluder_list_reaches_the_upper_half_of_a_strip_word():
+    """capacity_mixed under its point light: the rule leaves out the floor, the bottom of the box resting on it and the back wall (the
+    other walls are nearer to the light than its worst-case rounding allows, as the Cornell box's ceiling above).  What stays is 39 pairs,
+    so the light-strip masks over this list (tests/test_light_strips.py) have bits at 32 and above to set and clear."""
+    from flat_cases import capacity
+    _, fs = capacity("capacity_mixed")
+    counts, stream, ids = record_prims(fs.prims, fs.obj_info)
+    table, keep, pairs = occluders(fs.prims, fs.obj_info, fs.src_i, fs.src_f)
+    assert fs.src_i.shape[0] == 1 and fs.src_i[0, 0] == 0                            # one point light
+    kept = table[0, 1:5]
+    n_pairs = int(((kept + 1) // 2).sum())
+    assert n_pairs >= 33 and kept.sum() == keep[0].sum(), (kept, n_pairs)
+    assert kept.tolist() == [10, 5, 57, 3] and n_pairs == 39                        # (three of its sections end in a lone record)
+    obj_of = np.repeat(np.arange(fs.obj_info.shape[0]), fs.obj_info[:, 1])
+    assert sorted(int(obj_of[ids[r, 0]]) for r in np.flatnonzero(~keep[0])) == [0, 2, 6]      # floor, back wall, box
+    np.testing.assert_array_equal(pairs, pair_up(stream, counts, keep[0]))
+
+
+@pytest.mark.parametrize("tag", ["cbox", "glass_box", "features_c", "capacity_mixed", "capacity_tris"])
 def test_left_out_records_never_block(tag, flat):
-    fs = flat(tag)
+    from flat_cases import CAPACITY_SCENES, capacity
+    fs = capacity(tag)[1] if tag in CAPACITY_SCENES else flat(tag)
     prims = fs.prims.reshape(-1, 9)
     counts, stream, ids = record_prims(prims, fs.obj_info)
     _, keep, _ = occluders(prims, fs.obj_info, fs.src_i, fs.src_f)
