@@ -94,6 +94,7 @@ class Margin:
     def __init__(self):
         self.m = math.inf
         self.amp = 1.0
+        self.amp_mask = None          # outputs the cancellation factor applies to (None: all of them)
 
     def cancel(self, val, mag):
         """a sum `val` of terms whose magnitudes add up to `mag`: its relative rounding is amplified by mag / |val|"""
@@ -866,6 +867,141 @@ def emitter_solid_angle_pdf(src_type, inv_area, ray_d, normal, min_depth):
     return np.array([a * float(min_depth) ** 2 / d if d > 0 else 0.0]), Margin()
 
 
+INV_4PI = 0.25 / math.pi
+EMITTER_TYPES = {0: "point", 1: "area", 2: "spot", 4: "collimated"}
+EMITTER_DRAWS = {"point": 0, "mesh": 3, "sphere": 2, "spot": 0, "collimated": 0}
+
+
+def emitter_geom(scene, k):
+    """what sample_hit reads of the object emitter k is attached to, as the float32 values the device holds: None (no object),
+    ("sphere", centre, radius) or ("mesh", dv1, dv2, v0, normals) with dv = the precomputed float32 edge vectors"""
+    if int(scene.src_i[k][0]) != 1:
+        return None
+    first, count, kind = (int(x) for x in scene.obj_info[int(scene.src_i[k][2])])
+    P = np.asarray(scene.prims, np.float32).reshape(-1, 3, 3)
+    if kind:
+        return ("sphere", P[first, 0].copy(), float(P[first, 1, 0]))
+    T = P[first:first + count]
+    return ("mesh", T[:, 1] - T[:, 0], T[:, 2] - T[:, 0], T[:, 0].copy(), np.asarray(scene.normals, np.float32).reshape(-1, 3)[first:first + count].copy())
+
+
+def emitter_kind(src_type, geom):
+    return geom[0] if int(src_type) == 1 else EMITTER_TYPES[int(src_type)]
+
+
+def _at_f32(mg, x, thr, err):
+    """a decision on a float32 operand whose error bound is `err`: the row is within a knife edge where the operand is within KNIFE of
+    the threshold or within four error bounds of it"""
+    if math.isfinite(x):
+        d = abs(x - thr)
+        mg.m = min(mg.m, d, d * KNIFE / (4.0 * err) if err > 0 else math.inf)
+    return x
+
+
+def sample_on_triangle(dv1, dv2, u1, u2, mg=None, fold=None):
+    """(point relative to v0, barycentrics of dv1 and dv2 after the fold); the fold is decided on the float32 sum, as every build does"""
+    if mg is not None:
+        mg.at(u1 + u2, 1.0)
+    if (float(F32(u1) + F32(u2)) > 1.0) if fold is None else fold:
+        u1, u2 = 1.0 - u1, 1.0 - u2
+    return add(mul(dv1, u1), mul(dv2, u2)), (u1, u2)
+
+
+def uniform_sphere_local(u0, u1, mg=None):
+    """sample_uniform_sphere: +y is the pole; phi is the float32 product 2 pi u every build forms"""
+    cos_t = 2.0 * u0 - 1.0
+    s2 = 1.0 - cos_t * cos_t
+    if mg is not None:
+        mg.cancel(s2, 1.0 + cos_t * cos_t)
+    sin_t = math.sqrt(max(s2, 0.0))
+    phi = float(F32(2.0 * math.pi) * F32(u1))
+    return (math.cos(phi) * sin_t, cos_t, math.sin(phi) * sin_t)
+
+
+def emitter_sample_hit(src_type, src_f, geom, hit_pos, words, dn=ZERO, force=None):
+    """emitter_sample_hit (shading.hpp; emitters/abtract_source.py:81-158) -> ((pos xyz, intensity rgb, pdf, draws), Margin).
+    `words`: the row's Philox words; `dn`: an absolute perturbation of the direction a sphere light constructs (reference()'s
+    dir_cols); `force`: {decision: bool} takes the named branch whatever the operands say (the rows placed on an edge, where float32
+    decides either way): "dl" (facing away), "pdf" (pdf > 0), "cone", "proj", "rim", "fold", "n2", "depth"."""
+    mg = Margin()
+    mg.amp_mask = np.array([0, 0, 0, 1, 1, 1, 1, 0], bool)       # hit - pos cancels in the intensity and the pdf, not in the position
+    f = [float(x) for x in src_f]
+    inten, direc, pos, inv_area, rad = tuple(f[0:3]), tuple(f[3:6]), tuple(f[6:9]), f[9], f[10]
+    hit = v(hit_pos)
+    t = int(src_type)
+    pdf, draws = 1.0, 0
+    force = force or {}
+    dec = lambda name, cond: force.get(name, cond)
+    eps5 = float(F32(1e-5))
+    if t == 0:
+        x = sub(hit, pos)
+        mg.cancel(norm(x), norm(hit) + norm(pos))
+        n2 = mg.at(dot(x, x), eps5)
+        att = 1.0 / (n2 if dec("n2", n2 > eps5) else eps5)
+        mg.at(att, 1.0)
+        inten = mul(inten, min(att, 1.0))
+    elif t == 1:
+        pdf = inv_area
+        if geom[0] == "sphere":
+            centre, radius = v(geom[1]), geom[2]
+            to_hit = normalize(sub(hit, centre))
+            local = uniform_sphere_local(_rf(words[0]), _rf(words[1]), mg)
+            normal = add(delocalize(to_hit, local, mg), v(dn))
+            pos = add(centre, mul(normal, radius))
+            pdf = INV_4PI / (radius * radius)
+            draws = 2
+            e_pos = [U * (abs(centre[a]) + 2.0 * abs(pos[a])) + 4.0 * U * abs(radius) for a in range(3)]
+            e_n = 4.0 * U
+        else:
+            dv1, dv2, v0, normals = geom[1:]
+            tri = int(np.int32(np.uint32(words[0]))) % len(dv1)          # pymod of the raw word read as int32
+            a1, a2 = v(dv1[tri]), v(dv2[tri])
+            pt, (b1, b2) = sample_on_triangle(a1, a2, _rf(words[1]), _rf(words[2]), mg, force.get("fold"))
+            pos = add(pt, v(v0[tri]))
+            normal = v(normals[tri])
+            draws = 3
+            # rounding of the point: two products and a sum, the fold's two sums, then + v0 (exact where the point's component is 0)
+            e_pos = [U * (3.0 * (abs(a1[a]) + abs(a2[a])) + (abs(pos[a]) if pt[a] != 0.0 else 0.0)) for a in range(3)]
+            e_n = 0.0
+        diff = sub(hit, pos)
+        nd = norm(diff)
+        mg.cancel(nd, norm(hit) + norm(pos))
+        dl = dot(normalize(diff), normal)
+        # float32 error of dl: the position's rounding and the subtraction's through the normal, the direction's own, the dot product's
+        e_dl = (sum(abs(normal[a]) * (e_pos[a] + U * abs(diff[a])) for a in range(3)) / nd + e_n + 4.0 * U * abs(dl)) if nd > 0 else 0.0
+        _at_f32(mg, dl, 0.0, e_dl)
+        if dec("dl", dl <= 0.0):
+            inten, pdf = ZERO, 1.0
+        else:
+            pdf = pdf * (nd * nd / dl) if dl != 0 else math.inf
+            inten = mul(inten, 1.0 / pdf) if dec("pdf", pdf > 0.0) and pdf != 0 else ZERO
+    elif t == 2:
+        th = sub(hit, pos)
+        mg.cancel(norm(th), norm(hit) + norm(pos))
+        depth = mg.at(norm(th), eps5)
+        depth = depth if dec("depth", depth > eps5) else eps5
+        cos_v = dot(mul(th, 1.0 / depth), direc)
+        mg.at(cos_v, rad)
+        inten = mul(inten, 1.0 / (depth * depth)) if dec("cone", cos_v > rad) else ZERO
+    elif t == 4:
+        pdf = 0.0
+        if rad > 0.0:
+            th = sub(hit, pos)
+            proj = dot(th, direc)
+            _at_f32(mg, proj, 0.0, 4.0 * U * sum(abs(th[a] * direc[a]) for a in range(3)))       # hit and pos are inputs: the products and sums round
+            if dec("proj", proj > 0.0):
+                d2 = mg.cancel(dot(th, th) - proj * proj, dot(th, th) + proj * proj)
+                dist = math.sqrt(d2) if d2 >= 0 else math.nan
+                # float32 error of dist: the two squares' roundings over 2 dist
+                _at_f32(mg, dist, rad, 4.0 * U * (dot(th, th) + proj * proj) / (2.0 * dist) if dist > 0 else math.inf)
+                if dec("rim", dist < rad):
+                    pos = sub(hit, mul(direc, proj))
+                else:
+                    inten = ZERO
+        else:
+            inten = ZERO
+    return np.array([*pos, *inten, pdf, float(draws)]), mg
+
 # ------------------------------------------------------------------ conditioning
 def reference(fn, cols, float_cols, trials=4, seed=0, dir_cols=(), dir_eps=4 * U):
     """Run a row function over the rows of `cols` -> r (n, k), S (n, k), margin (n,).
@@ -892,7 +1028,7 @@ def reference(fn, cols, float_cols, trials=4, seed=0, dir_cols=(), dir_eps=4 * U
                 dlt = np.abs(np.asarray(fn(*a)[0], np.float64) - r) / U
             s = np.maximum(s, np.where(np.isnan(r), 0.0, np.where(np.isfinite(dlt), dlt, np.inf)))
         with np.errstate(invalid="ignore"):
-            s = np.maximum(s, np.nan_to_num(np.abs(r) * mg.amp, nan=0.0))
+            s = np.maximum(s, np.nan_to_num(np.abs(r) * (mg.amp if mg.amp_mask is None else np.where(mg.amp_mask, mg.amp, 1.0)), nan=0.0))
         R.append(r); S.append(s); M.append(mg.m)
     return np.array(R), np.array(S), np.array(M)
 
@@ -1111,3 +1247,67 @@ def emitter_sweep(src_i, src_f, seed=0, n=64):
             X.append(np.concatenate([np.full((n, 1), k), hp, _f32n(nrm), _f32n(rd), md[:, None]], axis=1).astype(np.float32))
             st.append(np.full(n, f"src{k}_t{t}/{stn}", object))
     return np.concatenate(X), np.concatenate(st).astype(str)
+
+
+def emitter_sample_sweep(scene, seed=0, n=64):
+    """hit points for emitter_sample_hit, aimed at every emitter's own edges -> rows (m,4) float32 = (src index, hit_pos), stratum (m,)
+    str = "src<k>_<kind>/<stratum>", on_edge (m,) bool.  `scene`: prims, normals, obj_info, src_i, src_f as adapt_amd.scene_pack packs
+    them.  Offsets at an area light are relative to its extent (a mesh's largest box side, a sphere's radius).  The rows flagged on_edge
+    sit ON a float32 decision (height 0 over a mesh light, its vertices, a sphere's centre, a beam's axis, a cone's cosine): float32
+    decides them either way, and they are held to the two-branch rule (tests/emitter_cases.py), never left out."""
+    rs = np.random.RandomState(seed)
+    X, st, edge = [], [], []
+
+    def put(k, kind, name, hp, on_edge=False):
+        hp = np.asarray(hp, np.float64).reshape(-1, 3)
+        X.append(np.concatenate([np.full((len(hp), 1), k), hp], axis=1).astype(np.float32))
+        st.append(np.full(len(hp), f"src{k}_{kind}/{name}", object)); edge.append(np.full(len(hp), on_edge))
+
+    pick = lambda vals: rs.choice(vals, n)[:, None]
+    for k in range(len(scene.src_i)):
+        t = int(scene.src_i[k][0])
+        sf = np.float64(scene.src_f[k])
+        pos, dr, rr = sf[6:9], sf[3:6], float(sf[10])
+        geom = emitter_geom(scene, k)
+        kind = emitter_kind(t, geom)
+        if kind == "mesh":
+            dv1, dv2, v0, nrm = (np.float64(a) for a in geom[1:])
+            verts = np.concatenate([v0, v0 + dv1, v0 + dv2])
+            cen, ext = 0.5 * (verts.min(0) + verts.max(0)), float((verts.max(0) - verts.min(0)).max())
+            nn = np.repeat(nrm[:1], n, 0)
+            ta, tb = _frame(nn)
+            over = lambda w: cen + ext * (rs.uniform(-w, w, (n, 1)) * ta + rs.uniform(-w, w, (n, 1)) * tb)
+            put(k, kind, "bulk", cen + ext * _unit(rs, n) * rs.uniform(0.3, 6, (n, 1)))
+            put(k, kind, "plane", over(0.75) + nn * ext * pick([1e-5, -1e-5, 1e-4, -1e-4, 1e-2, -1e-2]))
+            put(k, kind, "behind", over(0.75) - nn * ext * rs.uniform(0.1, 3, (n, 1)))
+            put(k, kind, "front_close", over(0.4) + nn * ext * 10.0 ** rs.uniform(-3, -1, (n, 1)))
+            put(k, kind, "far", cen + 1e3 * ext * _dir_at_cos(rs, nn, rs.uniform(0.05, 1, n)))
+            put(k, kind, "edge_height0", over(0.3), True)
+            put(k, kind, "edge_vertex", verts[rs.randint(0, len(verts), n)], True)
+        elif kind == "sphere":
+            cen, rad = np.float64(geom[1]), abs(geom[2])
+            put(k, kind, "bulk", cen + rad * _unit(rs, n) * rs.uniform(1.2, 6, (n, 1)))
+            put(k, kind, "skin", cen + rad * _unit(rs, n) * (1.0 + pick([1e-4, 1e-2])))
+            put(k, kind, "inside", cen + rad * _unit(rs, n) * rs.uniform(0.01, 0.99, (n, 1)))
+            ang = rs.choice([2e-3, 4e-3, 5e-3, 1e-2, 0.1], n)
+            ax = np.zeros((n, 3)); ax[:, 1] = rs.choice([-1.0, 1.0], n)
+            put(k, kind, "pole", cen + rad * _dir_at_cos(rs, ax, np.cos(ang)) * rs.uniform(1.5, 4, (n, 1)))
+            put(k, kind, "edge_centre", np.repeat(cen[None], 8, 0), True)
+        elif kind in ("point", "spot"):
+            put(k, kind, "bulk", pos + rs.uniform(-3, 3, (n, 3)))
+            put(k, kind, "near", pos + _unit(rs, n) * pick([0.0, 1e-4, 1e-3, 1e-2, 0.9, 1.1]))
+            if kind == "spot":
+                axis = np.repeat(dr[None], n, 0)
+                put(k, kind, "cone_edge", pos + _dir_at_cos(rs, axis, rr + rs.choice([-1.0, 1.0], n) * rs.uniform(2e-5, 1e-4, n)) * rs.uniform(0.5, 3, (n, 1)))
+                put(k, kind, "edge_cone", pos + _dir_at_cos(rs, axis, np.full(n, rr)) * rs.uniform(0.5, 3, (n, 1)), True)
+        else:
+            axis = np.repeat(dr[None], n, 0)
+            ta, tb = _frame(axis)
+            phi = rs.uniform(0, 2 * np.pi, (n, 1))
+            radial = np.cos(phi) * ta + np.sin(phi) * tb
+            put(k, kind, "bulk", pos + rs.uniform(-3, 3, (n, 3)))
+            # (along the beam by no more than two radii: the float32 error of dist grows with |to_hit|^2 / dist, and 1e-5 must stay decidable)
+            put(k, kind, "rim", pos + axis * (rr if rr > 0 else 0.25) * rs.uniform(0.2, 2, (n, 1)) + radial * np.abs(rr + pick([1e-5, -1e-5, 1e-4, -1e-4])))
+            put(k, kind, "base", pos + axis * pick([1e-5, -1e-5, 1e-3, -1e-3]) + radial * rr * rs.uniform(0, 0.9, (n, 1)))
+            put(k, kind, "edge_axis", pos + axis * rs.uniform(0.5, 2, (n, 1)) + radial * pick([0.0, 1e-7, 1e-5]), True)
+    return np.concatenate(X), np.concatenate(st).astype(str), np.concatenate(edge)

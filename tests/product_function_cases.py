@@ -22,6 +22,12 @@ FAMILIES = {
     # solid-angle pdf: one sdiv = v_rcp (1 ulp) AND a multiplication whose rounding the IEEE quotient does not have; the budget of
     # "1 per v_rcp" leaves that rounding out (measured 1.07 against a budget of 1), so it is counted here: 1 + 1
     "emitter_pdf":   2,
+    # emitter_sample_hit per emitter type (tests/test_gpu_emitter_samples.py), counted along the longest chain to an output:
+    "emitter_sample_point":      1,   # srcp = v_rcp (1); the oracle takes the same reciprocal, then the same min and product
+    "emitter_sample_mesh":       3,   # fnormalize(diff) = v_rsq (1), sdiv(|diff|^2, dl) = v_rcp (1), fdiv3(intensity, pdf) = v_rcp (1)
+    "emitter_sample_sphere":     8,   # sin_t = v_sqrt (1), sincos (OCML, 2), the frame's fnormalize = v_rsq (1), sdiv(p, r^2) = v_rcp (1), then the mesh light's 3
+    "emitter_sample_spot":       2,   # fnorm = v_sqrt (1), fdiv3(intensity, depth^2) = v_rcp (1); the cone test's v_rcp feeds a decision only
+    "emitter_sample_collimated": 1,   # the ssqrt feeds the rim decision only: no output substitutes anything
     # shade_stage.hpp surface_maps (tests/test_gpu_texture_chain.py): a frame is R = c I + k n n^T + [axis]x with n = fnormalize(axis), and
     # fnormalize is axis * v_rsq in the product build.  The one v_rsq (1 ulp = up to 2 u relative) scales n, n enters every entry twice
     # (k n_i n_j: 4 u), and k = 1 - c reaches 2 where the target is next to -Y, where c + k n_i^2 = -1 + 2 is a result of the size of the

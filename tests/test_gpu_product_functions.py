@@ -375,6 +375,9 @@ def test_golden_emitter_vectors_on_the_product_build(tag, parsed):
 
 @pytest.mark.parametrize("tag", ["features_a", "cbox"])
 def test_emitters_against_model(tag, parsed, oracle_scene):
+    """eval_le and solid_angle_pdf against their float64 models; sample_hit only within close() of the oracle on hit points placed
+    relative to src pos - the weaker statement.  sample_hit against its own float64 model, at every emitter's edges and on a synthetic
+    emitter scene: tests/test_gpu_emitter_samples.py."""
     from adapt_amd.renderer import Renderer
     from adapt_amd.scene_pack import pack_scene
     fs = pack_scene(*parsed(tag))
