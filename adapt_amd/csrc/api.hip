@@ -43,19 +43,20 @@ typedef void (*shade_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int)
 typedef void (*shade_traced_fn)(DevScene, Params, Queues, Counters*, int, int);
 typedef void (*shade_cam_fn)(DevScene, Params, Queues, Counters*, const unsigned long long*);
 typedef void (*shade_tr_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, int, TransQ);
-// transient: fn's time-resolved twin (k_shade_tr); traced: the kernel that traces its light sample and its continuation ray itself (shade_stage.hpp k_shade_traced:
-// flat sweep, one light sample per vertex); traced_cam: traced's camera-fed twin (k_shade_traced_cam: bounce 0 of a steady full-film batch, no k_generate_trace in front of it);
-// traced_staged: traced with its record staged in LDS a row ahead (shade_traced, STAGE; null: the variant has no such form);
-// traced_staged_live, traced_cam_live: traced_staged and traced_cam with live rows (shade_traced, LIVE; null: no such form)
-struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; shade_traced_fn traced; shade_cam_fn traced_cam; shade_traced_fn traced_staged, traced_staged_live; shade_cam_fn traced_cam_live; };
+// The kernels of a variant that trace their own rays (shade_stage.hpp shade_traced: flat sweep, one light sample per vertex), by form; null: no such form.
+//   queue[stage][live]  the queue-fed kernel: [0][0] direct loads (k_shade_traced), [1][0] its record staged in LDS a row ahead (STAGE), [1][1] staged with live rows (LIVE)
+//   cam[live]           the camera-fed twin (CAM: bounce 0 of a steady full-film batch, no k_generate_trace in front of it), [1] with live rows
+struct TracedKernels { shade_traced_fn queue[2][2]; shade_cam_fn cam[2]; };
+// transient: fn's time-resolved twin (k_shade_tr)
+struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; TracedKernels traced; };
 #if APT_FAST
 #define APT_FLAT_FN(...) __VA_ARGS__
 #else
 #define APT_FLAT_FN(...) nullptr          // the flat sweep exists in the fast build only (traverse.hpp), and with it the shade kernels that trace their rays on its records
 #endif
-#define APT_TRACED_PAIR(STEM, ...) APT_FLAT_FN(STEM<__VA_ARGS__>), APT_FLAT_FN(STEM##_cam<__VA_ARGS__>)
-#define APT_TRACED_PLAIN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced, BM, SM, TEX), nullptr, nullptr, nullptr
-#define APT_TRACED_LEAN(BM, SM, TEX) APT_TRACED_PAIR(k_shade_traced_lean, BM, SM), APT_FLAT_FN(k_shade_traced_lean_staged<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_staged_live<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_cam_live<BM, SM>)
+#define APT_TRACED_PLAIN(BM, SM, TEX) {{{APT_FLAT_FN(k_shade_traced<BM, SM, TEX>), nullptr}, {nullptr, nullptr}}, {APT_FLAT_FN(k_shade_traced_cam<BM, SM, TEX>), nullptr}}
+#define APT_TRACED_LEAN(BM, SM, TEX) {{{APT_FLAT_FN(k_shade_traced_lean<BM, SM>), nullptr}, {APT_FLAT_FN(k_shade_traced_lean_staged<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_staged_live<BM, SM>)}}, \
+                                      {APT_FLAT_FN(k_shade_traced_lean_cam<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_cam_live<BM, SM>)}}
 #define APT_SHADE_VARIANT(BM, SM, TEX, NAME, TRACED) {BM, SM, NAME, k_shade<BM, SM, TEX>, k_shade_tr<BM, SM, TEX>, APT_TRACED_##TRACED(BM, SM, TEX)}
 static const ShadeVariant kShadeVariants[] = {
     APT_SHADE_VARIANT(APT_BX_LAMBERTIAN, APT_SRC_POINT, 0, "lambertian/point", LEAN),
@@ -257,10 +258,10 @@ struct apt_renderer {
     hipStream_t stream() const { return lanes[0].stream; }
     DevBuf accum, scratch, pix_key;
     DevBuf cam_strips;            // rays traced in place: per 64 local pixels, the record pairs a camera ray can hit (flat_build.cpp camera_strips)
-    int record_stage = 0;         // rays traced in place: 1 = the queue-fed shade kernel stages its record in LDS a row ahead (ShadeVariant::traced_staged; APT_RECORD_STAGE=0 switches it off)
-    shade_traced_fn traced_fn = nullptr;      // the queue-fed kernel of a PIPE_TRACED render: shade->traced_staged[_live] or shade->traced
-    int live_rows = 0;            // rays traced in place: 1 = the staged and the camera-fed shade kernel run their live-row form (ShadeVariant::traced_staged_live, traced_cam_live; APT_LIVE_ROWS=0 switches it off)
-    shade_cam_fn traced_cam_fn = nullptr;     // the camera-fed kernel of a PIPE_TRACED render: shade->traced_cam_live or shade->traced_cam
+    int record_stage = 0;         // rays traced in place: 1 = the queue-fed shade kernel stages its record in LDS a row ahead (TracedKernels::queue[1]; APT_RECORD_STAGE=0 switches it off)
+    shade_traced_fn traced_fn = nullptr;      // the queue-fed kernel of a PIPE_TRACED render (pick_traced_kernels)
+    int live_rows = 0;            // rays traced in place: 1 = the staged and the camera-fed shade kernel run their live-row form (TracedKernels::queue[1][1], cam[1]; APT_LIVE_ROWS=0 switches it off)
+    shade_cam_fn traced_cam_fn = nullptr;     // the camera-fed kernel of a PIPE_TRACED render (pick_traced_kernels)
     int camera_fuse = 0;          // rays traced in place: 1 = the camera vertex is shaded by the kernel that traces the camera ray (k_shade_traced_cam; steady full-film renders with max_bounce >= 1, APT_CAMERA_FUSE=0 switches it off)
     int light_strips = 0;         // rays traced in place, camera-fed: 1 = some strip mask of the camera vertex's light samples leaves a pair out (cam_strips' second part, flat_build.cpp light_strips; APT_LIGHT_STRIPS=0 switches them off)
     Counters host_counters{};
@@ -837,6 +838,19 @@ static void pick_traversal(apt_renderer* r) {
     if (const char* f = getenv("APT_DYN_FETCH")) r->dyn_fetch = (atoi(f) != 0 && r->trace_mode == TRACE_BVH) ? 1 : 0;
 }
 
+// The traced kernels of a render: which forms of the variant's (TracedKernels) run.  The staged record and live rows are on wherever the
+// variant has the form; APT_RECORD_STAGE=0 / APT_LIVE_ROWS=0 switch them off (live rows need both live kernels; unstaged, only the camera-fed one runs).
+static void pick_traced_kernels(apt_renderer* r) {
+    const TracedKernels& t = r->shade->traced;
+    const bool traced = r->pipeline == PIPE_TRACED;
+    const bool want_stage = !(getenv("APT_RECORD_STAGE") && atoi(getenv("APT_RECORD_STAGE")) == 0);
+    const bool want_live = !(getenv("APT_LIVE_ROWS") && atoi(getenv("APT_LIVE_ROWS")) == 0);
+    r->record_stage = (traced && want_stage && t.queue[1][0] != nullptr) ? 1 : 0;
+    r->live_rows = (traced && want_live && t.queue[1][1] != nullptr && t.cam[1] != nullptr) ? 1 : 0;
+    r->traced_fn = t.queue[r->record_stage][r->record_stage & r->live_rows];
+    r->traced_cam_fn = t.cam[r->live_rows];
+}
+
 // Shading pipeline: shade kernel, the Pipeline (assigned here, once, and asked for by everything after), how a vertex's light samples are
 // queued and added, and the closest-hit kernel that feeds it.
 static int pick_shading(apt_renderer* r) {
@@ -864,15 +878,10 @@ static int pick_shading(apt_renderer* r) {
         if (want == 1) fprintf(stderr, "adapt_mi: APT_FUSED=1 (light samples only traced in place) was retired in round 5; running the staged pipeline (APT_FUSED=0). Use 2 for rays traced in place.\n");
         want_traced = want >= 2;
     }
-    const bool can_trace = r->trace_mode == TRACE_FLAT && S == 1 && !r->split() && r->shade->traced != nullptr;
+    const bool can_trace = r->trace_mode == TRACE_FLAT && S == 1 && !r->split() && r->shade->traced.queue[0][0] != nullptr;
     r->pipeline = c.volumetric ? PIPE_VOLUMETRIC : (sorted ? PIPE_SORTED : ((can_trace && want_traced) ? PIPE_TRACED : PIPE_STAGED));
     p.traced = (r->pipeline == PIPE_TRACED) ? 1 : 0;
-    const bool want_stage = !(getenv("APT_RECORD_STAGE") && atoi(getenv("APT_RECORD_STAGE")) == 0);
-    r->record_stage = (p.traced && want_stage && r->shade->traced_staged != nullptr) ? 1 : 0;
-    const bool want_live = !(getenv("APT_LIVE_ROWS") && atoi(getenv("APT_LIVE_ROWS")) == 0);
-    r->live_rows = (p.traced && want_live && r->shade->traced_staged_live != nullptr && r->shade->traced_cam_live != nullptr) ? 1 : 0;
-    r->traced_fn = r->record_stage ? (r->live_rows ? r->shade->traced_staged_live : r->shade->traced_staged) : r->shade->traced;
-    r->traced_cam_fn = r->live_rows ? r->shade->traced_cam_live : r->shade->traced_cam;
+    pick_traced_kernels(r);
     // flat sweep with several light samples per vertex: the samples are queued by vertex and the shadow kernel adds a vertex's samples with
     // one read-modify-write (stages.hpp k_shadow_flat); otherwise 2-4 samples per vertex add into one radiance plane each (stages.hpp
     // APT_EXCLUSIVE_L) - a transient or path-length render always, its bins want the samples apart
@@ -944,7 +953,7 @@ static int make_camera_strips(apt_renderer* r) {
     // the camera-fed bounce 0 (shade_stage.hpp shade_traced, CAM) wants every slot of the id space to be a live camera ray: an adaptive
     // round's or a crop window's dead slots would sit as idle lanes through a whole shading row - those keep k_generate_trace's compaction
     const bool want = !(getenv("APT_CAMERA_FUSE") && atoi(getenv("APT_CAMERA_FUSE")) == 0);
-    r->camera_fuse = (want && !r->adaptive && !r->par.do_crop && r->par.max_bounce >= 1 && r->shade->traced_cam != nullptr) ? 1 : 0;
+    r->camera_fuse = (want && !r->adaptive && !r->par.do_crop && r->par.max_bounce >= 1 && r->shade->traced.cam[0] != nullptr) ? 1 : 0;
     // ... and behind them, in the same buffer, the strip masks of the camera vertex's light samples (flat_build.cpp light_strips; read by the
     // camera-fed kernel alone: stages.hpp light_strip_mask): row e of (npix + 63) / 64 words for emitter e < APT_LIGHT_STRIP_EMITTERS.
     // APT_LIGHT_STRIPS=0, APT_SHADOW_CULL=0 (at scene creation): every bit set.

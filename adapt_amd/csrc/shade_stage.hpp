@@ -149,8 +149,7 @@ APT_D void fix_prologue(const DevScene& sc, const Params& p, const Queues& q, Co
             stq(q.tr[cur][2], so, rc); stq(q.tr[cur][3], so, rd);
             if (need_uv) { float2 uv_; uv_.x = r0.u; uv_.y = r0.v; stq(q.tr_uv[cur], slot << 3, uv_); }
         } else if (valid && !(rd.x == 0.f && rd.y == 0.f && rd.z == 0.f)) {      // nothing hit: the path ends, its radiance goes to its slot
-            const uint32_t id = __float_as_uint(rc.w), lp_ = id & ((1u << p.pix_bits) - 1u), s_ = id >> p.pix_bits;
-            add_radiance(q.L, p.cap, (s_ * (uint32_t)p.npix + lp_) << 2, mk3(rd.x, rd.y, rd.z), true);
+            add_radiance(q.L, p.cap, radiance_slot(p, __float_as_uint(rc.w)), mk3(rd.x, rd.y, rd.z), true);
         }
     }
     uint32_t t_lit = 0;
@@ -213,7 +212,7 @@ APT_D bool open_vertex(const ShadeArgs3* A_, Vertex& vx, RNG& rng, int prim, f3 
     else vx.bx = ld_bxdf_lane((A_->sc).bxdf + vx.it.obj_id);
     if (TEX && (A_->sc).tex_i != nullptr) surface_maps((A_->sc), vx.it, prim, uv.x, uv.y, bounce == 0, vx.bx.k_d);      // the scene declares image textures (TEX kernels only)
     const uint32_t lp = vx.id & ((1u << (A_->p).pix_bits) - 1u), s = vx.id >> (A_->p).pix_bits;
-    vx.l_off = (s * (uint32_t)(A_->p).npix + lp) << 2;
+    vx.l_off = radiance_slot((A_->p), vx.id);
     vx.draw0 = meta & 0xffffu;
     const uint32_t key0 = ((A_->p).world == 1) ? lp : ldq((A_->p).pix_key, lp << 2), ctr0 = (uint32_t)((A_->p).cnt_base + (int)s + 1);
     rng_init(rng, key0, (A_->p).seed, ctr0, vx.draw0);
@@ -315,7 +314,7 @@ APT_D bool open_vertex_live(const ShadeArgs3* A_, Vertex& vx, DrawWindow& rng, f
     static_assert(BM == APT_BX_LAMBERTIAN && !(SM & APT_SRC_AREA), "a draw window serves [roulette] index [index] u1 u2: Lambertian surfaces, emitters that draw nothing");
     vx.bx.k_d = rec_kd;
     const uint32_t lp = vx.id & ((1u << (A_->p).pix_bits) - 1u), s = vx.id >> (A_->p).pix_bits;
-    vx.l_off = (s * (uint32_t)(A_->p).npix + lp) << 2;
+    vx.l_off = radiance_slot((A_->p), vx.id);
     vx.draw0 = (pm >> 8) & 0xffffu;
     const uint32_t key0 = ((A_->p).world == 1) ? lp : ldq((A_->p).pix_key, lp << 2), ctr0 = (uint32_t)((A_->p).cnt_base + (int)s + 1);
     bool roulette = false; float mx = 0.f;
@@ -380,7 +379,94 @@ APT_D void tally_flush(const ShadeTally& t, const uint32_t* s_draws, Counters* c
 // here (one ray per lane against two records per packed instruction, traverse.hpp flat_any1), after the continuation has been sampled and
 // traced, when little else is live.  The rare rays whose answer needs the reference-order sweep (flat_needs_cull) still leave as
 // shadow-queue entries, counted by n_fix_sh[cur], and are served by the next launch's prologue.
+// A row is a sequence of phases, each a function below, in the order shade_traced takes them; the forms of the kernel - CAM, STAGE, LIVE -
+// differ in which function a phase is.  (Lane flags leave a phase as its return value: a bool behind a reference stays a byte in a lane
+// register instead of a mask in scalar ones - measured: up to ten vector instructions of a lean kernel's row loop.)
 //
+// ROW HEAD, the queue-fed forms.  The record of the row at `b` that this lane reads: its own, or past the queue's end the last entry's
+// (never used; LIVE: shaded with its effects masked) - no address leaves the sub-queue's region.
+APT_D uint32_t row_lane(uint32_t b, uint32_t n) { return min(b + threadIdx.x, n - 1u); }
+struct RecordPlanes { const float4 *a, *b, *c, *d; };             // planes A to D of the queue a launch reads (Queues::tr[cur])
+// PFP: the next row's packed word - hit primitive, draw index, specular flag - is requested one row ahead (one register), so that a row's
+// shading record can be requested together with its queue record instead of a round trip after it.  (Rounds 2-4 prefetched the Lambertian
+// kernel's whole record: thirteen registers.  Without them the kernel allocates 91 VGPRs - five waves per SIMD instead of four - and three
+// render lanes gain 6 %: C2 4 310 -> 4 560 Msamples/s on the same box.)
+APT_D uint32_t prefetch_prim(const RecordPlanes& tr, uint32_t qbase, uint32_t b, uint32_t n) { return ldq(reinterpret_cast<const uint32_t*>(tr.b), ((qbase + row_lane(b, n)) << 4) + 12u); }
+// STAGE, the staged record (queue-fed form only, DESIGN.md 4.2): a row's record - planes A to D, 64 entries of 16 bytes each: 1 KiB per
+// plane and wave - is requested a row AHEAD, by loads that write LDS directly (global_load_lds_dwordx4: no register holds the data in
+// flight), into 4 KiB that the wave owns; the scene's shading records (at most 96 x 32 bytes) sit in LDS too, one copy per workgroup.
+// A row then opens with LDS reads only - its lane's four words into the registers the direct loads fill, the shading record of the hit
+// primitive, which arrives with plane B (the word requested ahead on its own, PFP, and its register are gone) - and waits on no
+// vector memory: the next row's loads are issued behind the light sample, in front of the two sweeps, and waited for at the end of
+// the row, before its stores (a wait at the next row's top would also wait for those stores to be acknowledged: one in-order counter).
+// Nothing is staged for an empty sub-queue or behind the last row.  STAGE = false is the kernel with the direct loads, instruction for instruction.
+struct StagedRecord { rec4* rec; rec4* prim; };                   // plane k of this wave's row at rec[64 * k + lane]; the shading records (DevScene::prim_shade)
+APT_D StagedRecord staged_record_open(const ShadeArgs3* A_) {      // (before the prologue: every wave of the workgroup passes here, none has a staged load in flight)
+    __shared__ rec4 s_stage[(BLOCK / 64) * 4 * 64]; __shared__ rec4 s_shade[2 * APT_FLAT_MAX_PRIMS];
+    static_assert(2 * APT_FLAT_MAX_PRIMS <= BLOCK, "one shading-record word per thread");
+    if ((int)threadIdx.x < 2 * min((A_->sc).n_prims, APT_FLAT_MAX_PRIMS)) { const float4 w_ = (A_->sc).prim_shade[threadIdx.x]; s_shade[threadIdx.x] = rec4{w_.x, w_.y, w_.z, w_.w}; }
+    __syncthreads();
+    return StagedRecord{s_stage + (threadIdx.x >> 6) * (4 * 64), s_shade};
+}
+APT_D void stage_row(const StagedRecord& s, const RecordPlanes& tr, uint32_t qbase, uint32_t b, uint32_t n, int bounce) {      // (wave-uniform: b < n)
+    const uint32_t off = (qbase + row_lane(b, n)) << 4;
+    stage_plane(tr.a, off, s.rec); stage_plane(tr.b, off, s.rec + 64); stage_plane(tr.c, off, s.rec + 128);
+    if (bounce > 0) stage_plane(tr.d, off, s.rec + 192);
+}
+// this lane's words of the row's record and the shading record of its hit primitive (plane D's words are read at bounce 0 too, where
+// nothing was staged into them: never used)
+APT_D void staged_row_read(const StagedRecord& s, float4& a, float4& b, float4& c, float4& d, float4& ra, float4& rb) {
+    rec4 sa, sb, sc_, sd, pa, pb;
+    staged_read(s.rec + lane_id(), sa, sb, sc_, sd);
+    staged_read2(s.prim + 2 * max(tr_prim(__float_as_uint(sb.w)), 0), pa, pb);
+    a = make_float4(sa.x, sa.y, sa.z, sa.w); b = make_float4(sb.x, sb.y, sb.z, sb.w); c = make_float4(sc_.x, sc_.y, sc_.z, sc_.w); d = make_float4(sd.x, sd.y, sd.z, sd.w);
+    ra = make_float4(pa.x, pa.y, pa.z, pa.w); rb = make_float4(pb.x, pb.y, pb.z, pb.w);
+}
+// staged_wait; in the diagnostic build -DAPT_ROWTOP_STATS=1 between two stamps: per wave, the clock ticks spent waiting for its rows'
+// records (stats[12]), those of the row loop (stats[13]) and the rows (stats[14])
+struct RowTop { unsigned long long wait, rows, loop0; };
+APT_D void staged_wait_stamped(RowTop& rt, bool row) {
+#ifdef APT_ROWTOP_STATS
+    const unsigned long long t0_ = __builtin_amdgcn_s_memtime(); staged_wait(); rt.wait += __builtin_amdgcn_s_memtime() - t0_; rt.rows += row ? 1u : 0u;
+#else
+    staged_wait();
+#endif
+}
+// a vertex's draws into the wave's tally; UNORDERED (the kernels that stage their record): by an LDS add that waits for no staged load
+template <bool UNORDERED> APT_D void tally_draws(uint32_t* s_draws, uint32_t n) { if constexpr (UNORDERED) lds_add_unordered(&s_draws[threadIdx.x >> 6], n); else atomicAdd(&s_draws[threadIdx.x >> 6], n); }
+// planes A to C of a record -> the vertex's ray, throughput and path id (A.w, the hit distance, and B.w, the packed word, go to the hit)
+APT_D void unpack_record(float4 a, float4 b, float4 c, Vertex& vx) { vx.o = mk3(a.x, a.y, a.z); vx.d = mk3(b.x, b.y, b.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = __float_as_uint(c.w); }
+// a record's words -> its opened vertex; false: the path ends here.  pm: the packed word; REC: ra, rb hold the hit primitive's shading record
+template <int BM, int SM, int TEX, bool REC, typename RNG>
+APT_D bool open_record(const ShadeArgs3* A_, Vertex& vx, RNG& rng, float4 a, float4 b, float4 c, uint32_t pm, float4 ra, float4 rb, int cur, uint32_t idx, float ray_pdf, int bounce) {
+    unpack_record(a, b, c, vx);
+    const int prim = tr_prim(pm);
+    if (prim < 0) return false;                              // nothing hit: path ends (vanilla_renderer.py:49)
+    f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
+    if ((A_->sc).has_vn || (TEX && (A_->sc).tex_i != nullptr)) uv = ldq((A_->q).tr_uv[cur], idx << 3);      // otherwise nobody reads the barycentrics (and nobody wrote them)
+    if (REC) build_hit_rec((A_->sc), ra, rb, prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+    else build_hit((A_->sc), prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+    return open_vertex<BM, SM, TEX>(A_, vx, rng, prim, rec_kd, tr_meta(pm, (uint32_t)bounce), ray_pdf, uv, bounce);
+}
+// LIVE, live rows (the staged and the camera-fed form of the lean kernels, DESIGN.md 4.2): every lane of a row shades a valid record
+// straight-line - a lane past the queue's end the last entry's, which it staged; a lane past the id space's end the ray of its pixel; a
+// path the roulette ended its own - and `alive` masks effects only: votes, tallies, appends, stores (open_vertex_live, sample_light_live
+// above).  vertex_reset is no default provider there: what it writes is overwritten for every lane, or a constant of the Lambertian
+// kernel.  At the last bounce the continuation is not sampled; `draw` moves on by its two words.  LIVE = false is the parent's kernel,
+// instruction for instruction.
+template <int BM, int SM, typename RNG>
+APT_D bool open_record_live(const ShadeArgs3* A_, Vertex& vx, RNG& rng, float4 a, float4 b, float4 c, float4 d, float4 ra, float4 rb, int cur, uint32_t idx, int bounce, bool alive, uint32_t* s_draws, f3& Lc) {
+    if (bounce > 0) Lc = mk3(d.x, d.y, d.z);
+    unpack_record(a, b, c, vx);
+    const uint32_t pm = __float_as_uint(b.w); const int prim = tr_prim(pm);
+    alive = alive && prim >= 0;                              // nothing hit: path ends (vanilla_renderer.py:49)
+    f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
+    if ((A_->sc).has_vn) { if (alive) uv = ldq((A_->q).tr_uv[cur], idx << 3); }
+    build_hit_rec((A_->sc), ra, rb, max(prim, 0), a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+    const bool opened = alive; alive = open_vertex_live<BM, SM>(A_, vx, rng, rec_kd, pm, bounce, alive);
+    if (opened && !alive && rng.draw != vx.draw0) tally_draws<true>(s_draws, rng.draw - vx.draw0);      // the roulette's word of a path it ended
+    return alive;
+}
 // CAM, the camera-fed form (steady full-film batches): bounce 0 with no queue in front of it.  Every slot of the id space is
 // a live camera ray then, so a row MAKES its 64 records instead of loading them - pixel, jitter, direction, the slot's radiance zeroed, the
 // sweep against the strip's records, all as k_generate_trace does them (stages.hpp camera_ray_dir / camera_strip_mask) - and shades the hits
@@ -391,70 +477,204 @@ APT_D void tally_flush(const ShadeTally& t, const uint32_t* s_draws, Counters* c
 // follows resolves them in its prologue and shades that handful.  This kernel runs no prologue: nothing is listed before it.
 // Its light samples all leave from what the wave's strip sees: where the wave's emitter is uniform they are swept against the pairs of
 // its occluder list that the strip's mask keeps (flat_build.cpp light_strips; the masks lie behind the strip lists in `strips`).
-//
-// STAGE, the staged record (queue-fed form only, DESIGN.md 4.2): a row's record - planes A to D, 64 entries of 16 bytes each: 1 KiB per
-// plane and wave - is requested a row AHEAD, by loads that write LDS directly (global_load_lds_dwordx4: no register holds the data in
-// flight), into 4 KiB that the wave owns; the scene's shading records (at most 96 x 32 bytes) sit in LDS too, one copy per workgroup.
-// A row then opens with LDS reads only - its lane's four words into the registers the direct loads fill, the shading record of the hit
-// primitive, which arrives with plane B (the word requested ahead on its own, PFP, and its register are gone) - and waits on no
-// vector memory: the next row's loads are issued behind the light sample, in front of the two sweeps, and waited for at the end of
-// the row, before its stores (a wait at the next row's top would also wait for those stores to be acknowledged: one in-order counter).
-// Lanes past the queue's end stage its last entry, never used: no address leaves the sub-queue's region; nothing is staged for an empty
-// sub-queue or behind the last row.  STAGE = false is the kernel with the direct loads, instruction for instruction.
-//
-// LIVE, live rows (the staged and the camera-fed form of the lean kernels, DESIGN.md 4.2): every lane of a row shades a valid record
-// straight-line - a lane past the queue's end the last entry's, which it staged; a lane past the id space's end the ray of its pixel; a
-// path the roulette ended its own - and `alive` masks effects only: votes, tallies, appends, stores (open_vertex_live, sample_light_live
-// above).  vertex_reset is no default provider there: what it writes is overwritten for every lane, or a constant of the Lambertian
-// kernel.  At the last bounce the continuation is not sampled; `draw` moves on by its two words.  LIVE = false is the parent's kernel,
-// instruction for instruction.
+APT_D uint32_t cam_wave(const ShadeArgs3* A_, uint32_t pos, int q) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)q; }      // (wave-uniform: scalar registers)
+// slot `id_` of the id space -> its sample and pixel, the path's id word; `zero`: the slot's radiance is zeroed
+APT_D uint32_t cam_path(const ShadeArgs3* A_, uint32_t id_, bool zero, uint32_t& s, int& i, int& j) {
+    const uint32_t lp = id_ % (uint32_t)(A_->p).npix; s = id_ / (uint32_t)(A_->p).npix;
+    local_to_global((A_->p), lp, i, j);
+    if (zero) for (int pl = 0; pl < (A_->p).l_planes; pl++) stL((A_->q).L, (A_->p).cap, (id_ << 2) | (uint32_t)pl, splat3(0.f));
+    return (s << (A_->p).pix_bits) | lp;
+}
+// the camera ray against the records of its strip (id-space wave w) -> c_idx, c_t; true: the ray is left to the reference-order code
+APT_D bool cam_sweep(const ShadeArgs3* A_, const unsigned long long* strips, uint32_t w, bool valid, f3 cam_o, f3 dir, float& c_t, int& c_idx) {
+    int c_run = -1; c_t = 0.f; c_idx = -1;
+    if (__any(valid)) c_idx = flat_closest1<true>((A_->sc).flat, cam_o, dir, 1e7f, c_t, c_run, camera_strip_mask((A_->p), strips, w));
+    return valid && (c_run >= 0 || flat_needs_cull((A_->sc).flat, dir));
+}
+// a camera ray left to the reference-order code is staged.  The words the two callers store differently come from `words`, called in the
+// rare branch, where their register notes want them made: A.w; B.w's primitive; the barycentrics; planes C (one, one, one, id) and D (zero, zero, zero, one_d)
+struct StagedRayWords { float t; int prim; float u, v, one, zero, one_d; };
+template <typename Words>
+APT_D void stage_camera_ray(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qbase, bool c_defer, f3 cam_o, f3 dir, uint32_t draws, uint32_t id, Words&& words) {
+    if (!__any(c_defer)) return;
+    const int ncls = (A_->q).tr_ncls; const uint32_t dpos = wave_append(c_defer, &cnt->n_tr[0][ncls][q * CNT_PAD]);
+    if (c_defer) {
+        const uint32_t slot = (A_->q).tr_stage_top ? qbase + (A_->p).subcap - 1u - dpos : (uint32_t)ncls * (A_->p).cap + qbase + dpos, so = slot << 4;
+        const StagedRayWords w = words();
+        stq((A_->q).tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, w.t));
+        stq((A_->q).tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(w.prim, draws, false))));
+        stq((A_->q).tr[0][2], so, make_float4(w.one, w.one, w.one, __uint_as_float(id)));
+        stq((A_->q).tr[0][3], so, make_float4(w.zero, w.zero, w.zero, w.one_d));
+        if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = w.u; uv_.y = w.v; stq((A_->q).tr_uv[0], slot << 3, uv_); }
+    }
+}
+// the camera vertex: the ray is made, swept against its strip's records and, where that settles it, shaded right here.
+// -> alive; entry: the lane holds a path this launch shades (valid, not left to the reference-order code)
+template <int BM, int SM, int TEX, bool WINDOW, typename RNG>
+APT_D bool camera_vertex(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qbase, uint32_t pos, bool in_row, uint32_t cam_total, const unsigned long long* strips, Vertex& vx, RNG& rng, uint32_t* s_draws, uint32_t& t_samples, uint32_t& t_extend, bool& entry) {
+    const uint32_t w = cam_wave(A_, pos, q), id_ = w * 64u + lane_id(); const bool valid = in_row && id_ < cam_total;
+    f3 dir = mk3(0.f, 0.f, 1.f); uint32_t draws = 0, jitter_tail[2] = {0u, 0u};
+    if (valid) { uint32_t s; int i, j; vx.id = cam_path(A_, id_, true, s, i, j); dir = camera_ray_dir((A_->p), i, j, s, draws, WINDOW ? jitter_tail : nullptr); }
+    if (draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
+    const f3 cam_o = mk3((A_->p).cam_t[0], (A_->p).cam_t[1], (A_->p).cam_t[2]);
+    float c_t; int c_idx, hit_cls = 0;
+    const bool c_defer = cam_sweep(A_, strips, w, valid, cam_o, dir, c_t, c_idx);
+    HitRec hr; hr.t = 1e7f; hr.prim = -1; hr.u = hr.v = 0.f;
+    if (valid && !c_defer && c_idx >= 0) flat_resolve((A_->sc).flat, c_idx, c_t, cam_o, dir, hr, hit_cls);
+    { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
+    stage_camera_ray(A_, cnt, q, qbase, c_defer, cam_o, dir, draws, vx.id, [&] {
+        float one = 1.f;
+        if (WINDOW) asm volatile("" : "+v"(one));      // (made here, in the rare branch: as a constant, (0, 0, 0, 1) is hoisted in front of the row loop, where the draw-window kernel has no four registers for it - 72 VGPRs and a 16-byte spill)
+        return StagedRayWords{hr.t, hr.prim, hr.u, hr.v, 1.f, 0.f, one};
+    });
+    entry = valid && !c_defer; bool alive = entry && hr.prim >= 0;                       // nothing hit: the path ends where it began, nothing gathered
+    if (alive) {
+        vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
+        f3 rec_kd; float2 uv; uv.x = hr.u; uv.y = hr.v;
+        build_hit((A_->sc), hr.prim, hr.t, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+        alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), 1.f, uv, 0, WINDOW ? jitter_tail : nullptr);
+    }
+    return alive;
+}
+// ... live rows: a lane past the id space's end makes the ray of its pixel (a pixel of the film all the same, a sample no batch holds), and
+// a ray that hit nothing or is left to the reference-order code is shaded on whatever record the resolve gives it; `valid`, `c_defer`, `alive` mask the effects
+template <int BM, int SM, bool WINDOW, typename RNG>
+APT_D bool camera_vertex_live(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qbase, uint32_t pos, bool in_row, uint32_t cam_total, const unsigned long long* strips, Vertex& vx, RNG& rng, uint32_t* s_draws, uint32_t& t_samples, uint32_t& t_extend, bool& entry) {
+    const uint32_t w = cam_wave(A_, pos, q), id_ = w * 64u + lane_id(); const bool valid = in_row && id_ < cam_total;
+    uint32_t draws = 0, jitter_tail[2] = {0u, 0u}, s; int i, j;
+    vx.id = cam_path(A_, id_, valid, s, i, j);
+    const f3 dir = camera_ray_dir((A_->p), i, j, s, draws, WINDOW ? jitter_tail : nullptr);
+    if (valid && draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
+    const f3 cam_o = mk3((A_->p).cam_t[0], (A_->p).cam_t[1], (A_->p).cam_t[2]);
+    float c_t; int c_idx, hit_cls = 0;
+    const bool c_defer = cam_sweep(A_, strips, w, valid, cam_o, dir, c_t, c_idx);
+    HitRec hr;
+    flat_resolve((A_->sc).flat, max(c_idx, 0), c_t, cam_o, dir, hr, hit_cls);
+    { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
+    stage_camera_ray(A_, cnt, q, qbase, c_defer, cam_o, dir, draws, vx.id, [&] {      // with an empty hit record
+        float one = 1.f, far_ = 1e7f, zero = 0.f;
+        asm volatile("" : "+v"(one), "+v"(far_), "+v"(zero));      // (made here, in the rare branch: as constants the words are hoisted in front of the row loop and spilled there, see camera_vertex)
+        return StagedRayWords{far_, -1, zero, zero, one, zero, one};
+    });
+    entry = valid && !c_defer; bool alive = entry && c_idx >= 0 && hr.prim >= 0;          // nothing hit: the path ends where it began, nothing gathered
+    vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
+    f3 rec_kd; build_hit((A_->sc), max(hr.prim, 0), hr.t, hr.u, hr.v, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+    const bool opened = alive; alive = open_vertex_live<BM, SM>(A_, vx, rng, rec_kd, tr_pack(hr.prim, draws, false), 0, alive, WINDOW ? jitter_tail : nullptr);
+    if (opened && !alive && rng.draw != vx.draw0) tally_draws<false>(s_draws, rng.draw - vx.draw0);      // the roulette's word of a path it ended
+    return alive;
+}
+// ROW TAIL.  Emission of the surface the vertex is on, then the continuation (emit_and_scatter): new_d, its direction; -> a continuation
+// ray leaves.  The vertex's draws join the wave's tally (LDS_TALLY: tally_draws' unordered form).
+template <int BM, int SM, bool LDS_TALLY, typename RNG>
+APT_D bool scatter(const ShadeArgs3* A_, Vertex& vx, RNG& rng, bool alive, int bounce, uint32_t* s_draws, f3& Lc, f3& new_d, float& new_pdf, bool& is_spec) {
+    bool cont = false;
+    if (alive) { new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { Lc = Lc + add; }); cont = (bounce + 1) < (A_->p).max_bounce; }
+    if (rng.draw != vx.draw0) tally_draws<LDS_TALLY>(s_draws, rng.draw - vx.draw0);      // also paths that died in the roulette
+    return cont;
+}
+// ... live rows: the last bounce's continuation has no reader, its two words are passed over (wave-uniform)
+template <int BM, int SM, bool LDS_TALLY, typename RNG>
+APT_D bool scatter_live(const ShadeArgs3* A_, Vertex& vx, RNG& rng, bool alive, int bounce, uint32_t* s_draws, f3& Lc, f3& new_d, float& new_pdf, bool& is_spec) {
+    bool cont = false;
+    if ((bounce + 1) < (A_->p).max_bounce) { new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { Lc = Lc + add; }); cont = alive; }
+    else rng.draw += 2u;
+    if (alive) tally_draws<LDS_TALLY>(s_draws, rng.draw - vx.draw0);
+    return cont;
+}
+// The records the row's light samples are swept against (traverse.hpp flat_occ_list): the occluder list of the emitter that every lane of
+// the wave that wants a sample has sampled - the only one in a single-emitter scene - else the full stream (-1).  Decided before the
+// continuation, wave-uniform (scalar registers), so that the emitter index is not held in a lane register until the sweep.
+APT_D int pick_occluder_list(const ShadeArgs3* A_, const LightSample& f) {
+    int occ_e = 0;
+    if ((A_->sc).n_sources != 1) {
+        const unsigned long long wm = __ballot(f.want);
+        occ_e = -1;
+        if (wm != 0ull) { const int e0 = __builtin_amdgcn_readlane(f.src, __ffsll((long long)wm) - 1); if (!__any(f.want && f.src != e0)) occ_e = e0; }
+    }
+    return occ_e;
+}
+// The continuation ray meets the scene's records.  Only rays that hit something (or whose answer is left to the reference-order code:
+// listed, with a provisional record) enter the next queue (-> true); the tail atomic is on its way while the light sample is swept.
+struct Continuation { float t, u, v; int hit, q; TrAppend app; };      // hit distance, barycentrics, primitive; q: the queue the record joins (0; 1: the staging area at the top of its sub-queue's region; -1: none); its append ticket
+APT_D bool trace_continuation(const ShadeArgs3* A_, const Vertex& vx, f3 new_d, bool cont, uint32_t* next_counter, uint32_t& t_extend, Continuation& ct) {
+    ct.t = 0.f; ct.hit = -1; ct.u = ct.v = 0.f; int tr_idx = -1, tr_run = -1, hit_cls = 0;
+    if (__any(cont)) tr_idx = flat_closest1((A_->sc).flat, vx.hit_point, new_d, 1e7f, ct.t, tr_run);
+    const bool tr_defer = cont && (tr_run >= 0 || flat_needs_cull((A_->sc).flat, new_d));
+    t_extend += wave_count(cont);
+    cont = cont && (tr_idx >= 0 || tr_defer);
+    if (cont && !tr_defer) { HitRec hr; flat_resolve((A_->sc).flat, tr_idx, ct.t, vx.hit_point, new_d, hr, hit_cls); ct.hit = hr.prim; ct.u = hr.u; ct.v = hr.v; }
+    ct.q = !cont ? -1 : (tr_defer ? 1 : 0);
+    const Append a_ = append_issue(ct.q == 0, next_counter); ct.app.raw = a_.raw; ct.app.rank = rank_in(a_.m);      // (a staged ray - rare - moves the staging queue's tail by itself: append_record)
+    return cont;
+}
+// The row's light sample, swept in place against the list pick_occluder_list chose and added to Lc; a ray that needs the reference-order
+// sweep leaves as a shadow-queue entry for the next launch's prologue.  CAM: the pairs of the emitter's list that cannot lie between the
+// patch of surfaces the strip sees and the light are skipped (the mask is fetched here, scalar loads).
+template <bool CAM>
+APT_D void sweep_light_sample(const ShadeArgs3* A_, Counters* cnt, const Vertex& vx, const LightSample& f, int occ_e, int cur, int q, uint32_t sh_qbase, uint32_t pos, const unsigned long long* strips, f3& Lc, uint32_t& t_traced, uint32_t& t_lit) {
+    const bool defer = f.want && flat_needs_cull((A_->sc).flat, f.dir); bool occ = false;
+    if (__any(f.want && !defer)) {
+        const FlatList ls = (occ_e >= 0) ? flat_occ_list((A_->sc).flat, occ_e) : flat_full_list((A_->sc).flat);
+        if constexpr (CAM) {
+            unsigned long long lmask = ~0ull;
+            if (occ_e >= 0 && occ_e < APT_LIGHT_STRIP_EMITTERS) lmask = light_strip_mask((A_->p), strips, cam_wave(A_, pos, q), occ_e);
+            occ = flat_any1<true>(ls, vx.hit_point, f.dir, shadow_limit(f.dist), lmask);
+        } else occ = flat_any1(ls, vx.hit_point, f.dir, shadow_limit(f.dist));
+    }
+    if (__any(defer)) {
+        const uint32_t spos = wave_append(defer, &cnt->n_fix_sh[cur][q * CNT_PAD]);
+        if (defer && spos < (A_->q).sh_subcap) { const uint32_t so = (sh_qbase + spos) << 2; shadow_store((A_->q), so, vx.hit_point, f.dir, f.dist, f.contrib); stq((A_->q).sh_id, so, vx.l_off); }
+    }
+    const bool traced = f.want && !defer;
+    if (traced) {
+        // (an occluded sample still enters upstream's sum as 0 * contribution: NaN for a non-finite one, see k_shadow)
+        const bool weird = !(isfinite(f.contrib.x) && isfinite(f.contrib.y) && isfinite(f.contrib.z));
+        if (!occ || weird) Lc = Lc + (occ ? f.contrib * 0.f : f.contrib);
+    }
+    t_traced += wave_count(f.want); t_lit += wave_count(traced && !occ);
+}
+// the continuation's record joins the next queue; the path's radiance so far (Lc) travels with it
+APT_D void append_record(const ShadeArgs3* A_, int nxt, uint32_t qbase, uint32_t* next_counter, const Continuation& ct, bool cont, const Vertex& vx, f3 new_d, uint32_t draw, bool is_spec, f3 Lc, float new_pdf) {
+    uint32_t npos = (uint32_t)__builtin_amdgcn_readlane((int)ct.app.raw, 0) + ct.app.rank;
+    if (__any(ct.q == 1)) { const uint32_t dpos = wave_append(ct.q == 1, next_counter + APT_MAX_NQ * CNT_PAD); if (ct.q == 1) npos = dpos; }
+    if (cont) {
+        const uint32_t slot = (ct.q == 1) ? qbase + (A_->p).subcap - 1u - npos : qbase + npos, so = slot << 4;      // (staged rays grow down from the top of the sub-queue's region)
+        stq((A_->q).tr[nxt][0], so, make_float4(vx.hit_point.x, vx.hit_point.y, vx.hit_point.z, ct.t));
+        stq((A_->q).tr[nxt][1], so, make_float4(new_d.x, new_d.y, new_d.z, __uint_as_float(tr_pack(ct.hit, draw, is_spec))));
+        stq((A_->q).tr[nxt][2], so, make_float4(vx.thr.x, vx.thr.y, vx.thr.z, __uint_as_float(vx.id)));
+        stq((A_->q).tr[nxt][3], so, make_float4(Lc.x, Lc.y, Lc.z, new_pdf));
+        if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = ct.u; uv_.y = ct.v; stq((A_->q).tr_uv[nxt], slot << 3, uv_); }
+    }
+}
+// the path ends here (nothing hit, roulette, last bounce): its radiance goes to its slot - added, not stored: the prologue may have put a deferred sample's share there already
+APT_D void end_path(const ShadeArgs3* A_, bool ended, uint32_t id, f3 Lc) { if (ended && !(Lc.x == 0.f && Lc.y == 0.f && Lc.z == 0.f)) add_radiance((A_->q).L, (A_->p).cap, radiance_slot((A_->p), id), Lc, true); }
 template <int BM, int SM, int TEX, bool CAM = false, bool STAGE = false, bool LIVE_ = false>
 APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, const unsigned long long* strips = nullptr) {
     static_assert(!(CAM && STAGE), "a camera-fed row loads no record");
     static_assert(!LIVE_ || ((CAM || STAGE) && TEX == 0), "live rows: the staged and the camera-fed form of the lean kernels");
     constexpr bool LIVE = LIVE_ && APT_DRAW_WINDOW != 0;      // (live rows are written for the draw window: a build without it, -DAPT_DRAW_WINDOW=0, keeps the parent's form under the live kernels' names)
     const ShadeArgs3* A_ = args_fresh(A0);                      // scene, parameters, queues: read through the kernel-argument segment, re-fetched per phase (APT_ARGS_PHASE)
-    const int cur = CAM ? 0 : cur_, bounce = CAM ? 0 : bounce_;
-    const int nxt = cur ^ 1;
+    const int cur = CAM ? 0 : cur_, bounce = CAM ? 0 : bounce_, nxt = cur ^ 1;
     const SubLoop sl = sub_loop((A_->p).nq);
     const uint32_t qbase = (uint32_t)sl.q * (A_->p).subcap, sh_qbase = (uint32_t)sl.q * (A_->q).sh_subcap;
     uint32_t* next_counter = &cnt->n_tr[(bounce + 1) % 3][0][sl.q * CNT_PAD];      // (the first queue's tail)
-    if (sl.first == 0 && threadIdx.x == 0) {                   // (read by the previous bounce, appended to by the next one)
-        cnt->n_tr[(bounce + 2) % 3][0][sl.q * CNT_PAD] = 0;
-        cnt->n_tr[(bounce + 2) % 3][(A_->q).tr_ncls][sl.q * CNT_PAD] = 0;      // (the staging queue's tail)
-    }
+    if (sl.first == 0 && threadIdx.x == 0) { cnt->n_tr[(bounce + 2) % 3][0][sl.q * CNT_PAD] = 0; cnt->n_tr[(bounce + 2) % 3][(A_->q).tr_ncls][sl.q * CNT_PAD] = 0; }      // (read by the previous bounce, appended to by the next one; the second: the staging queue's tail)
     const EmitterGeom geom = {(A_->sc).precom, (A_->sc).normals, (A_->sc).obj_info};
     __shared__ uint32_t s_draws[BLOCK / 64];
     if (lane_id() == 0) s_draws[threadIdx.x >> 6] = 0;
-    ShadeTally tl = {0u, 0u, 0u};
-    uint32_t t_traced = 0, t_lit = 0, t_extend = 0, t_samples = 0;
+    ShadeTally tl = {0u, 0u, 0u}; uint32_t t_traced = 0, t_lit = 0, t_extend = 0, t_samples = 0;
 #ifdef APT_NEAR_STATS
     uint32_t t_near = 0;
 #endif
-#ifdef APT_ROWTOP_STATS      // diagnostic build: per wave, the clock ticks of the row loop and those of them spent waiting for the row's record at its top (stats[12..14])
-    unsigned long long t_rowtop = 0, t_rows = 0, t_loop0 = 0;
-#endif
-    // The next row's hit primitive is requested one row ahead (PFP: one register), so that a row's shading record can be requested together
-    // with its queue record instead of a round trip after it.  (Rounds 2-4 prefetched the Lambertian kernel's whole record: thirteen
-    // registers.  Without them the kernel allocates 91 VGPRs - five waves per SIMD instead of four - and three render lanes gain 6 %:
-    // C2 4 310 -> 4 560 Msamples/s on the same box.)
+    RowTop rt = {0ull, 0ull, 0ull};
     // the generator: without area lights a Lambertian vertex's draws are all decided when it is opened, and it reads them from a draw window (rng.hpp)
     constexpr bool WINDOW = APT_DRAW_WINDOW != 0 && BM == APT_BX_LAMBERTIAN && !(SM & APT_SRC_AREA);
     typedef typename std::conditional<WINDOW, DrawWindow, Philox>::type Rng;
     constexpr bool PFP = TEX == 0 && !CAM && !STAGE;          // (a camera-fed row knows its primitive when it has traced its ray: nothing to request ahead; a staged row's arrives with its plane B)
     static_assert(APT_FLAT_MAX_PRIMS < (int)TR_NO_PRIM, "the packed record keeps the hit primitive in 8 bits");
-    const float4* trA = (A_->q).tr[cur][0]; const float4* trB = (A_->q).tr[cur][1]; const float4* trC = (A_->q).tr[cur][2]; const float4* trD = (A_->q).tr[cur][3];
-    // the staged record: plane k of this wave's row at s_rec[64 * k + lane]; one buffer per wave - a row's loads are issued when the row has read the buffer
-    rec4* s_rec = nullptr; rec4* s_prim = nullptr;             // ... and the scene's shading records (DevScene::prim_shade), one copy per workgroup, filled below
-    if constexpr (STAGE) {
-        __shared__ rec4 s_stage[(BLOCK / 64) * 4 * 64]; __shared__ rec4 s_shade[2 * APT_FLAT_MAX_PRIMS];
-        s_rec = s_stage + (threadIdx.x >> 6) * (4 * 64); s_prim = s_shade;
-    }
-    if constexpr (STAGE) {                                     // (before the prologue: every wave of the workgroup passes here, none has a staged load in flight)
-        static_assert(2 * APT_FLAT_MAX_PRIMS <= BLOCK, "one shading-record word per thread");
-        if ((int)threadIdx.x < 2 * min((A_->sc).n_prims, APT_FLAT_MAX_PRIMS)) { const float4 w_ = (A_->sc).prim_shade[threadIdx.x]; s_prim[threadIdx.x] = rec4{w_.x, w_.y, w_.z, w_.w}; }
-        __syncthreads();
-    }
+    const RecordPlanes tr = {(A_->q).tr[cur][0], (A_->q).tr[cur][1], (A_->q).tr[cur][2], (A_->q).tr[cur][3]};
+    StagedRecord stage = {nullptr, nullptr};
+    if constexpr (STAGE) stage = staged_record_open(A_);
     uint32_t n, cam_total = 0;
     if constexpr (CAM) {
         // rows of this sub-queue: 64 per id-space wave w with w % nq == q
@@ -465,305 +685,85 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         fix_prologue((A_->sc), (A_->p), (A_->q), cnt, cur, sl.q, bounce);       // before the queue's length is read: the prologue may append to it
         n = __hip_atomic_load(&cnt->n_tr[bounce % 3][0][sl.q * CNT_PAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    uint32_t pf_pm = 0;                                        // (the packed word: primitive, draw index, specular flag)
-    auto prefetch_prim = [&](uint32_t b) { pf_pm = ldq(reinterpret_cast<const uint32_t*>(trB), ((qbase + min(b + threadIdx.x, n - 1u)) << 4) + 12u); };      // (lanes past the end re-read the last entry: never used)
-    if (PFP && n > 0) prefetch_prim(sl.first);
-    auto stage_row = [&](uint32_t b) {                         // (wave-uniform: b < n)
-        const uint32_t off = (qbase + min(b + threadIdx.x, n - 1u)) << 4;      // (lanes past the end stage the last entry: never used)
-        stage_plane(trA, off, s_rec); stage_plane(trB, off, s_rec + 64); stage_plane(trC, off, s_rec + 128);
-        if (bounce > 0) stage_plane(trD, off, s_rec + 192);
-    };
-    if (STAGE && sl.first < n) {
-        stage_row(sl.first);
+    uint32_t pf_pm = 0;                                        // (PFP: the next row's packed word)
+    if (PFP && n > 0) pf_pm = prefetch_prim(tr, qbase, sl.first, n);
+    if (STAGE && sl.first < n) { stage_row(stage, tr, qbase, sl.first, n, bounce); staged_wait_stamped(rt, false); }      // (the first row's record: the only one whose round trip the wave sits out)
 #ifdef APT_ROWTOP_STATS
-        const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-#endif
-        staged_wait();                                         // (the first row's record: the only one whose round trip the wave sits out)
-#ifdef APT_ROWTOP_STATS
-        t_rowtop += __builtin_amdgcn_s_memtime() - t0_;
-#endif
-    }
-#ifdef APT_ROWTOP_STATS
-    t_loop0 = __builtin_amdgcn_s_memtime();
+    rt.loop0 = __builtin_amdgcn_s_memtime();
 #endif
     for (uint32_t base = sl.first; base < n; base += sl.stride) {
         APT_ARGS_PHASE();
         const uint32_t pos = base + threadIdx.x, idx = qbase + pos;                    // (unsorted renders: one queue for the scene)
         bool alive = pos < n;
-        const uint32_t cu_pm = pf_pm;
-        float4 cu_ra = make_float4(0.f, 0.f, 0.f, 0.f), cu_rb = cu_ra;
-        if (PFP) { const int rp = max(tr_prim(cu_pm), 0); cu_ra = (A_->sc).prim_shade[2 * rp]; cu_rb = (A_->sc).prim_shade[2 * rp + 1]; prefetch_prim(base + sl.stride); }
-        Vertex vx; vertex_reset(vx);
-        Rng rng; rng_init(rng, 0u, 0u, 0u, 0u);
+        const uint32_t cu_pm = pf_pm; float4 cu_ra = make_float4(0.f, 0.f, 0.f, 0.f), cu_rb = cu_ra;
+        if (PFP) { const int rp = max(tr_prim(cu_pm), 0); cu_ra = (A_->sc).prim_shade[2 * rp]; cu_rb = (A_->sc).prim_shade[2 * rp + 1]; pf_pm = prefetch_prim(tr, qbase, base + sl.stride, n); }
+        Vertex vx; vertex_reset(vx); Rng rng; rng_init(rng, 0u, 0u, 0u, 0u);
         f3 Lc = splat3(0.f);                                   // the radiance the path has gathered so far (camera rays carry none: nothing is read at bounce 0)
-        bool entry = alive;
-        float ray_pdf = 1.f;
-        if constexpr (CAM && LIVE) {
-            // ---- the camera vertex, live rows: a lane past the id space's end makes the ray of its pixel, and a ray that hit nothing or is left
-            // to the reference-order code is shaded on whatever record the resolve gives it; `valid`, `c_defer`, `alive` mask the effects
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)sl.q;
-            const uint32_t id_ = w * 64u + lane_id();
-            const bool valid = alive && id_ < cam_total;
-            uint32_t draws = 0;
-            uint32_t jitter_tail[2] = {0u, 0u};
-            const uint32_t lp = id_ % (uint32_t)(A_->p).npix, s = id_ / (uint32_t)(A_->p).npix;      // (past the end: a pixel of the film all the same, a sample no batch holds)
-            int i, j; local_to_global((A_->p), lp, i, j);
-            if (valid) for (int pl = 0; pl < (A_->p).l_planes; pl++) stL((A_->q).L, (A_->p).cap, (id_ << 2) | (uint32_t)pl, splat3(0.f));
-            const f3 dir = camera_ray_dir((A_->p), i, j, s, draws, WINDOW ? jitter_tail : nullptr);
-            vx.id = (s << (A_->p).pix_bits) | lp;
-            if (valid && draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
-            const f3 cam_o = mk3((A_->p).cam_t[0], (A_->p).cam_t[1], (A_->p).cam_t[2]);
-            float c_t = 0.f; int c_run = -1, c_idx = -1;
-            if (__any(valid)) c_idx = flat_closest1<true>((A_->sc).flat, cam_o, dir, 1e7f, c_t, c_run, camera_strip_mask((A_->p), strips, w));
-            const bool c_defer = valid && (c_run >= 0 || flat_needs_cull((A_->sc).flat, dir));
-            HitRec hr; int hit_cls = 0;
-            flat_resolve((A_->sc).flat, max(c_idx, 0), c_t, cam_o, dir, hr, hit_cls);
-            { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
-            if (__any(c_defer)) {                             // left to the reference-order code: staged with an empty hit record, as k_generate_trace stages it
-                const int ncls = (A_->q).tr_ncls;
-                const uint32_t dpos = wave_append(c_defer, &cnt->n_tr[0][ncls][sl.q * CNT_PAD]);
-                if (c_defer) {
-                    const uint32_t slot = (A_->q).tr_stage_top ? qbase + (A_->p).subcap - 1u - dpos : (uint32_t)ncls * (A_->p).cap + qbase + dpos, so = slot << 4;
-                    float one = 1.f, far_ = 1e7f, zero = 0.f;
-                    asm volatile("" : "+v"(one), "+v"(far_), "+v"(zero));      // (made here, in the rare branch: as constants the words are hoisted in front of the row loop and spilled there, see the parent's form below)
-                    stq((A_->q).tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, far_));
-                    stq((A_->q).tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(-1, draws, false))));
-                    stq((A_->q).tr[0][2], so, make_float4(one, one, one, __uint_as_float(vx.id)));
-                    stq((A_->q).tr[0][3], so, make_float4(zero, zero, zero, one));
-                    if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = zero; uv_.y = zero; stq((A_->q).tr_uv[0], slot << 3, uv_); }
-                }
+        bool entry = alive; float ray_pdf = 1.f;
+        // ---- the row's head: its opened vertex
+        if constexpr (CAM && LIVE) alive = camera_vertex_live<BM, SM, WINDOW>(A_, cnt, sl.q, qbase, pos, alive, cam_total, strips, vx, rng, s_draws, t_samples, t_extend, entry);
+        else if constexpr (CAM) alive = camera_vertex<BM, SM, TEX, WINDOW>(A_, cnt, sl.q, qbase, pos, alive, cam_total, strips, vx, rng, s_draws, t_samples, t_extend, entry);
+        else if constexpr (STAGE) {
+            float4 a, b_, c, d;                                // this lane's words of the row's record
+            staged_row_read(stage, a, b_, c, d, cu_ra, cu_rb);
+            if constexpr (LIVE) alive = open_record_live<BM, SM>(A_, vx, rng, a, b_, c, d, cu_ra, cu_rb, cur, idx, bounce, alive, s_draws, Lc);
+            else if (alive) {
+                if (bounce > 0) { Lc = mk3(d.x, d.y, d.z); if (SM & APT_SRC_AREA) ray_pdf = d.w; }
+                alive = open_record<BM, SM, TEX, true>(A_, vx, rng, a, b_, c, __float_as_uint(b_.w), cu_ra, cu_rb, cur, idx, ray_pdf, bounce);
             }
-            entry = valid && !c_defer;
-            alive = entry && c_idx >= 0 && hr.prim >= 0;      // nothing hit: the path ends where it began, nothing gathered
-            vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
-            f3 rec_kd;
-            build_hit((A_->sc), max(hr.prim, 0), hr.t, hr.u, hr.v, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
-            const bool opened = alive;
-            alive = open_vertex_live<BM, SM>(A_, vx, rng, rec_kd, tr_pack(hr.prim, draws, false), 0, alive, WINDOW ? jitter_tail : nullptr);
-            if (opened && !alive && rng.draw != vx.draw0) atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);      // the roulette's word of a path it ended
-        }
-        if constexpr (CAM && !LIVE) {
-            // ---- the camera vertex: the ray is made, swept against its strip's records and, where that settles it, shaded right here
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)sl.q;
-            const uint32_t id_ = w * 64u + lane_id();
-            const bool valid = alive && id_ < cam_total;
-            f3 dir = mk3(0.f, 0.f, 1.f);
-            uint32_t draws = 0;
-            uint32_t jitter_tail[2] = {0u, 0u};
-            if (valid) {
-                const uint32_t lp = id_ % (uint32_t)(A_->p).npix, s = id_ / (uint32_t)(A_->p).npix;
-                int i, j; local_to_global((A_->p), lp, i, j);
-                for (int pl = 0; pl < (A_->p).l_planes; pl++) stL((A_->q).L, (A_->p).cap, (id_ << 2) | (uint32_t)pl, splat3(0.f));
-                dir = camera_ray_dir((A_->p), i, j, s, draws, WINDOW ? jitter_tail : nullptr);
-                vx.id = (s << (A_->p).pix_bits) | lp;
-            }
-            if (draws) atomicAdd(&s_draws[threadIdx.x >> 6], draws);      // (the jitter's draws: k_generate_trace's share of ST_DRAWS)
-            const f3 cam_o = mk3((A_->p).cam_t[0], (A_->p).cam_t[1], (A_->p).cam_t[2]);
-            float c_t = 0.f; int c_run = -1, c_idx = -1;
-            if (__any(valid)) c_idx = flat_closest1<true>((A_->sc).flat, cam_o, dir, 1e7f, c_t, c_run, camera_strip_mask((A_->p), strips, w));
-            const bool c_defer = valid && (c_run >= 0 || flat_needs_cull((A_->sc).flat, dir));
-            HitRec hr; hr.t = 1e7f; hr.prim = -1; hr.u = hr.v = 0.f;
-            int hit_cls = 0;
-            if (valid && !c_defer && c_idx >= 0) flat_resolve((A_->sc).flat, c_idx, c_t, cam_o, dir, hr, hit_cls);
-            { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
-            if (__any(c_defer)) {                             // left to the reference-order code: staged for the bounce-0 launch behind this one, as k_generate_trace stages it
-                const int ncls = (A_->q).tr_ncls;
-                const uint32_t dpos = wave_append(c_defer, &cnt->n_tr[0][ncls][sl.q * CNT_PAD]);
-                if (c_defer) {
-                    const uint32_t slot = (A_->q).tr_stage_top ? qbase + (A_->p).subcap - 1u - dpos : (uint32_t)ncls * (A_->p).cap + qbase + dpos, so = slot << 4;
-                    stq((A_->q).tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, hr.t));
-                    stq((A_->q).tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(hr.prim, draws, false))));
-                    stq((A_->q).tr[0][2], so, make_float4(1.f, 1.f, 1.f, __uint_as_float(vx.id)));
-                    float one = 1.f;
-                    if (WINDOW) asm volatile("" : "+v"(one));      // (made here, in the rare branch: as a constant, (0, 0, 0, 1) is hoisted in front of the row loop, where the draw-window kernel has no four registers for it - 72 VGPRs and a 16-byte spill)
-                    stq((A_->q).tr[0][3], so, make_float4(0.f, 0.f, 0.f, one));
-                    if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = hr.u; uv_.y = hr.v; stq((A_->q).tr_uv[0], slot << 3, uv_); }
-                }
-            }
-            entry = valid && !c_defer;
-            alive = entry && hr.prim >= 0;                    // nothing hit: the path ends where it began, nothing gathered
+        } else {                                               // the direct loads: plane D has a reader behind the first bounce only
+            if (alive && bounce > 0) { const float4 d = ldq(tr.d, idx << 4); Lc = mk3(d.x, d.y, d.z); if (SM & APT_SRC_AREA) ray_pdf = d.w; }
             if (alive) {
-                vx.o = cam_o; vx.d = dir; vx.thr = splat3(1.f);
-                f3 rec_kd; float2 uv; uv.x = hr.u; uv.y = hr.v;
-                build_hit((A_->sc), hr.prim, hr.t, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
-                alive = open_vertex<BM, SM, TEX>(A_, vx, rng, hr.prim, rec_kd, tr_meta(tr_pack(hr.prim, draws, false), 0u), ray_pdf, uv, 0, WINDOW ? jitter_tail : nullptr);
-            }
-        }
-        rec4 sa = {0.f, 0.f, 0.f, 0.f}, sb = sa, sc_ = sa, sd = sa;      // (STAGE: this lane's words of the row's record)
-        if constexpr (STAGE) {
-            // (the record landed before the row in front of this one stored its own - staged_wait below; nothing at a row's top waits on vector memory)
-            staged_read(s_rec + lane_id(), sa, sb, sc_, sd);    // (plane D's words are read at bounce 0 too, where nothing was staged into them: never used)
-            { const int rp = max(tr_prim(__float_as_uint(sb.w)), 0); rec4 pa, pb; staged_read2(s_prim + 2 * rp, pa, pb); cu_ra = make_float4(pa.x, pa.y, pa.z, pa.w); cu_rb = make_float4(pb.x, pb.y, pb.z, pb.w); }
-            if constexpr (!LIVE) if (alive && bounce > 0) { Lc = mk3(sd.x, sd.y, sd.z); if (SM & APT_SRC_AREA) ray_pdf = sd.w; }
-        }
-        if constexpr (LIVE && STAGE) {
-            // every lane unpacks the record it staged; `alive` goes on to mask the row's effects
-            if (bounce > 0) Lc = mk3(sd.x, sd.y, sd.z);
-            vx.o = mk3(sa.x, sa.y, sa.z); vx.d = mk3(sb.x, sb.y, sb.z); vx.thr = mk3(sc_.x, sc_.y, sc_.z); vx.id = __float_as_uint(sc_.w);
-            const uint32_t pm = __float_as_uint(sb.w);
-            const int prim = tr_prim(pm);
-            alive = alive && prim >= 0;                          // nothing hit: path ends (vanilla_renderer.py:49)
-            f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
-            if ((A_->sc).has_vn) { if (alive) uv = ldq((A_->q).tr_uv[cur], idx << 3); }
-            build_hit_rec((A_->sc), cu_ra, cu_rb, max(prim, 0), sa.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
-            const bool opened = alive;
-            alive = open_vertex_live<BM, SM>(A_, vx, rng, rec_kd, pm, bounce, alive);
-            if (opened && !alive && rng.draw != vx.draw0) lds_add_unordered(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);      // the roulette's word of a path it ended
-        }
-        if (!CAM && !STAGE && alive && bounce > 0) { const float4 dd = ldq(trD, idx << 4); Lc = mk3(dd.x, dd.y, dd.z); if (SM & APT_SRC_AREA) ray_pdf = dd.w; }
-        if (!CAM && !LIVE && alive) {
-            float4 a, b_, c;
-            if constexpr (STAGE) { a = make_float4(sa.x, sa.y, sa.z, sa.w); b_ = make_float4(sb.x, sb.y, sb.z, sb.w); c = make_float4(sc_.x, sc_.y, sc_.z, sc_.w); }
-            else { a = ldq(trA, idx << 4); b_ = ldq(trB, idx << 4); c = ldq(trC, idx << 4); }
+                const float4 a = ldq(tr.a, idx << 4), b_ = ldq(tr.b, idx << 4), c = ldq(tr.c, idx << 4);
 #ifdef APT_ROWTOP_STATS      // (direct loads: everything the row has requested - record, shading record - is waited for between two stamps; the staged form's wait is stamped where it stands)
-            if constexpr (!STAGE) { const unsigned long long t0_ = __builtin_amdgcn_s_memtime(); staged_wait(); t_rowtop += __builtin_amdgcn_s_memtime() - t0_; t_rows++; }
+                staged_wait_stamped(rt, true);
 #endif
-            vx.o = mk3(a.x, a.y, a.z); vx.d = mk3(b_.x, b_.y, b_.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = __float_as_uint(c.w);
-            const uint32_t pm = PFP ? cu_pm : __float_as_uint(b_.w);
-            const int prim = tr_prim(pm);
-            if (prim < 0) alive = false;                         // nothing hit: path ends (vanilla_renderer.py:49)
-            else {
-                f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
-                if ((A_->sc).has_vn || (TEX && (A_->sc).tex_i != nullptr)) uv = ldq((A_->q).tr_uv[cur], idx << 3);      // otherwise nobody reads the barycentrics (and nobody wrote them)
-                if (PFP || STAGE) build_hit_rec((A_->sc), cu_ra, cu_rb, prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
-                else build_hit((A_->sc), prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
-                alive = open_vertex<BM, SM, TEX>(A_, vx, rng, prim, rec_kd, tr_meta(pm, (uint32_t)bounce), ray_pdf, uv, bounce);
+                alive = open_record<BM, SM, TEX, PFP>(A_, vx, rng, a, b_, c, PFP ? cu_pm : __float_as_uint(b_.w), cu_ra, cu_rb, cur, idx, ray_pdf, bounce);
             }
         }
         tl.shade += wave_count(alive);
 #ifdef APT_NEAR_STATS      // diagnostic build (tools/gpu_near_probe.py): shaded vertices that sit within 2e-3 of the vertex before them - rays that re-hit the surface they left
         t_near += wave_count(alive && bounce > 0 && vx.it.min_depth < 2e-3f);
 #endif
-        if (LIVE || alive) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
-
+        if constexpr (LIVE) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
+        else if (alive) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
         APT_ARGS_PHASE();
         // ---- next-event estimation: the vertex's light sample waits in registers and is swept at the end of the row, when little else is live
-        bool break_flag = false;
-        DevSrc src_only;                                      // the scene's only light, read once through the scalar path
+        bool break_flag = false; DevSrc src_only;             // the scene's only light, read once through the scalar path
         if ((A_->sc).n_sources == 1) src_only = ld_src_uniform((A_->sc).src);
         LightSample f;                                         // (one light sample per vertex: api.hip pick_shading, PIPE_TRACED)
         if constexpr (LIVE) f = sample_light_live<BM, SM>(A_, vx, rng, geom, src_only, alive);
         else f = sample_light<BM, SM, false>(A_, vx, rng, geom, src_only, alive, break_flag);
         if (f.poisoned) Lc = splat3(f.mis_w);
         tl.shadow += wave_count(f.sampled); tl.poison += wave_count(f.poisoned);
-        // the records the row's light samples are swept against (traverse.hpp flat_occ_list): the occluder list of the emitter that every
-        // lane of the wave that wants a sample has sampled - the only one in a single-emitter scene - else the full stream (occ_e = -1).
-        // Decided here, wave-uniform (scalar registers), so that the emitter index is not held in a lane register until the sweep.
-        int occ_e = 0;
-        if ((A_->sc).n_sources != 1) {
-            const unsigned long long wm = __ballot(f.want);
-            occ_e = -1;
-            if (wm != 0ull) {
-                const int e0 = __builtin_amdgcn_readlane(f.src, __ffsll((long long)wm) - 1);
-                if (!__any(f.want && f.src != e0)) occ_e = e0;
-            }
-        }
+        const int occ_e = pick_occluder_list(A_, f);
         // The next row's record starts on its way HERE, behind the last load that the row's shading waits for: loads come back in the order
         // they were issued, so the wait for any load issued behind the staged ones is a wait for them - the round trip this form takes out
         // of the row.  In front of them lie the continuation's sample and its sweep: time enough to land.
-        if constexpr (STAGE) if (base + sl.stride < n) stage_row(base + sl.stride);
+        if constexpr (STAGE) if (base + sl.stride < n) stage_row(stage, tr, qbase, base + sl.stride, n, bounce);
         APT_ARGS_PHASE();
-        // ---- emission of the surface we are on, then the continuation
-        bool cont = false, is_spec = false;
-        f3 new_d = mk3(0.f, 1.f, 0.f);
-        float new_pdf = 1.f;
-        if constexpr (LIVE) {
-            // the last bounce's continuation has no reader: its two words are passed over (wave-uniform)
-            if ((bounce + 1) < (A_->p).max_bounce) { new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { Lc = Lc + add; }); cont = alive; }
-            else rng.draw += 2u;
-            if (alive) {
-                if constexpr (STAGE) lds_add_unordered(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
-                else atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
-            }
-        } else if (alive) {
-            new_d = emit_and_scatter<BM, SM>(A_, vx, rng, new_pdf, is_spec, [&](f3 add) { Lc = Lc + add; });
-            cont = (bounce + 1) < (A_->p).max_bounce;
-        }
-        if (!LIVE && rng.draw != vx.draw0) {                   // also paths that died in the roulette
-            if constexpr (STAGE) lds_add_unordered(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
-            else atomicAdd(&s_draws[threadIdx.x >> 6], rng.draw - vx.draw0);
-        }
+        // ---- emission of the surface we are on, then the continuation, which meets the scene's records
+        bool cont, is_spec = false; float new_pdf = 1.f; f3 new_d = mk3(0.f, 1.f, 0.f);
+        if constexpr (LIVE) cont = scatter_live<BM, SM, STAGE>(A_, vx, rng, alive, bounce, s_draws, Lc, new_d, new_pdf, is_spec);
+        else cont = scatter<BM, SM, STAGE>(A_, vx, rng, alive, bounce, s_draws, Lc, new_d, new_pdf, is_spec);
         APT_ARGS_PHASE();
-        // the continuation ray meets the scene's records here.  Only rays that hit something (or whose answer is left to the reference-order
-        // code: listed, with a provisional record) enter the next queue; the tail atomic is on its way while the light sample is swept below.
-        float tr_t = 0.f; int tr_hit = -1; float tr_u = 0.f, tr_v = 0.f; int tr_q = -1;      // tr_q: the queue the record joins (-1: none)
-        TrAppend tr_app; tr_app.raw = 0u; tr_app.rank = 0u;
-        {
-            int tr_idx = -1, tr_run = -1, hit_cls = 0;
-            if (__any(cont)) tr_idx = flat_closest1((A_->sc).flat, vx.hit_point, new_d, 1e7f, tr_t, tr_run);
-            const bool tr_defer = cont && (tr_run >= 0 || flat_needs_cull((A_->sc).flat, new_d));
-            t_extend += wave_count(cont);
-            cont = cont && (tr_idx >= 0 || tr_defer);
-            if (cont && !tr_defer) { HitRec hr; flat_resolve((A_->sc).flat, tr_idx, tr_t, vx.hit_point, new_d, hr, hit_cls); tr_hit = hr.prim; tr_u = hr.u; tr_v = hr.v; }
-            tr_q = !cont ? -1 : (tr_defer ? 1 : 0);            // (the queue, or the staging area at the top of its sub-queue's region)
-            { const Append a_ = append_issue(tr_q == 0, next_counter); tr_app.raw = a_.raw; tr_app.rank = rank_in(a_.m); }      // (a staged ray - rare - moves the staging queue's tail by itself, below)
-        }
+        Continuation ct; cont = trace_continuation(A_, vx, new_d, cont, next_counter, t_extend, ct);
         APT_ARGS_PHASE();
-        {
-            // the row's light sample, swept in place; a ray that needs the reference-order sweep leaves as a shadow-queue entry for the next launch's prologue
-            const bool defer = f.want && flat_needs_cull((A_->sc).flat, f.dir);
-            bool occ = false;
-            if (__any(f.want && !defer)) {
-                const FlatList ls = (occ_e >= 0) ? flat_occ_list((A_->sc).flat, occ_e) : flat_full_list((A_->sc).flat);
-                if constexpr (CAM) {
-                    // a camera vertex's light samples leave from the patch of surfaces its strip sees: the pairs of the emitter's list that
-                    // cannot lie between that patch and the light are skipped (flat_build.cpp light_strips); fetched here, scalar loads
-                    unsigned long long lmask = ~0ull;
-                    if (occ_e >= 0 && occ_e < APT_LIGHT_STRIP_EMITTERS)
-                        lmask = light_strip_mask((A_->p), strips, (uint32_t)__builtin_amdgcn_readfirstlane((int)(pos >> 6)) * (uint32_t)(A_->p).nq + (uint32_t)sl.q, occ_e);
-                    occ = flat_any1<true>(ls, vx.hit_point, f.dir, shadow_limit(f.dist), lmask);
-                } else occ = flat_any1(ls, vx.hit_point, f.dir, shadow_limit(f.dist));
-            }
-            if (__any(defer)) {
-                const uint32_t spos = wave_append(defer, &cnt->n_fix_sh[cur][sl.q * CNT_PAD]);
-                if (defer && spos < (A_->q).sh_subcap) { const uint32_t so = (sh_qbase + spos) << 2; shadow_store((A_->q), so, vx.hit_point, f.dir, f.dist, f.contrib); stq((A_->q).sh_id, so, vx.l_off); }
-            }
-            const bool traced = f.want && !defer;
-            if (traced) {
-                // (an occluded sample still enters upstream's sum as 0 * contribution: NaN for a non-finite one, see k_shadow)
-                const bool weird = !(isfinite(f.contrib.x) && isfinite(f.contrib.y) && isfinite(f.contrib.z));
-                if (!occ || weird) Lc = Lc + (occ ? f.contrib * 0.f : f.contrib);
-            }
-            t_traced += wave_count(f.want); t_lit += wave_count(traced && !occ);
-        }
-        if constexpr (STAGE) {
-            // the next row's record has landed - it has had both sweeps - before this row's stores are issued: a wait at the next row's top
-            // would be a wait for these stores to be acknowledged as well (one counter, in order)
-#ifdef APT_ROWTOP_STATS
-            const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-#endif
-            staged_wait();
-#ifdef APT_ROWTOP_STATS
-            t_rowtop += __builtin_amdgcn_s_memtime() - t0_; t_rows++;
-#endif
-        }
-        uint32_t npos = (uint32_t)__builtin_amdgcn_readlane((int)tr_app.raw, 0) + tr_app.rank;
-        if (__any(tr_q == 1)) { const uint32_t dpos = wave_append(tr_q == 1, next_counter + APT_MAX_NQ * CNT_PAD); if (tr_q == 1) npos = dpos; }
-        if (cont) {
-            const uint32_t slot = (tr_q == 1) ? qbase + (A_->p).subcap - 1u - npos : qbase + npos, so = slot << 4;      // (staged rays grow down from the top of the sub-queue's region)
-            stq((A_->q).tr[nxt][0], so, make_float4(vx.hit_point.x, vx.hit_point.y, vx.hit_point.z, tr_t));
-            stq((A_->q).tr[nxt][1], so, make_float4(new_d.x, new_d.y, new_d.z, __uint_as_float(tr_pack(tr_hit, rng.draw, is_spec))));
-            stq((A_->q).tr[nxt][2], so, make_float4(vx.thr.x, vx.thr.y, vx.thr.z, __uint_as_float(vx.id)));
-            stq((A_->q).tr[nxt][3], so, make_float4(Lc.x, Lc.y, Lc.z, new_pdf));
-            if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = tr_u; uv_.y = tr_v; stq((A_->q).tr_uv[nxt], slot << 3, uv_); }
-        }
-        if (!cont && entry && !(Lc.x == 0.f && Lc.y == 0.f && Lc.z == 0.f)) {
-            // the path ends here (nothing hit, roulette, last bounce): its radiance goes to its slot - added, not stored: the prologue may have put a deferred sample's share there already
-            const uint32_t lp_ = vx.id & ((1u << (A_->p).pix_bits) - 1u), s_ = vx.id >> (A_->p).pix_bits;
-            add_radiance((A_->q).L, (A_->p).cap, (s_ * (uint32_t)(A_->p).npix + lp_) << 2, Lc, true);
-        }
+        sweep_light_sample<CAM>(A_, cnt, vx, f, occ_e, cur, sl.q, sh_qbase, pos, strips, Lc, t_traced, t_lit);
+        // the next row's record has landed - it has had both sweeps - before this row's stores are issued: a wait at the next row's top
+        // would be a wait for these stores to be acknowledged as well (one counter, in order)
+        if constexpr (STAGE) staged_wait_stamped(rt, true);
+        append_record(A_, nxt, qbase, next_counter, ct, cont, vx, new_d, rng.draw, is_spec, Lc, new_pdf);
+        end_path(A_, !cont && entry, vx.id, Lc);
     }
-    flush_uniform(t_traced, &cnt->stats[sl.q][ST_SHADOW_TRACED]); flush_uniform(t_lit, &cnt->stats[sl.q][ST_LIT]);
-    flush_uniform(t_extend, &cnt->stats[sl.q][ST_EXTEND]);
+    flush_uniform(t_traced, &cnt->stats[sl.q][ST_SHADOW_TRACED]); flush_uniform(t_lit, &cnt->stats[sl.q][ST_LIT]); flush_uniform(t_extend, &cnt->stats[sl.q][ST_EXTEND]);
     if (CAM) flush_uniform(t_samples, &cnt->stats[sl.q][ST_SAMPLES]);
     tally_flush(tl, s_draws, cnt, sl.q);
 #ifdef APT_NEAR_STATS
     flush_uniform(t_near, &cnt->stats[sl.q][14]);
 #endif
 #ifdef APT_ROWTOP_STATS
-    if (!CAM && lane_id() == 0 && t_rows) {
-        atomicAdd(&cnt->stats[sl.q][12], t_rowtop); atomicAdd(&cnt->stats[sl.q][13], (unsigned long long)__builtin_amdgcn_s_memtime() - t_loop0); atomicAdd(&cnt->stats[sl.q][14], t_rows);
-    }
+    if (!CAM && lane_id() == 0 && rt.rows) { atomicAdd(&cnt->stats[sl.q][12], rt.wait); atomicAdd(&cnt->stats[sl.q][13], (unsigned long long)__builtin_amdgcn_s_memtime() - rt.loop0); atomicAdd(&cnt->stats[sl.q][14], rt.rows); }
 #endif
 }
 #endif

@@ -231,6 +231,9 @@ APT_D uint32_t lane_id() { return threadIdx.x & 63u; }
 APT_D float* L_slot(float* L, uint32_t cap, uint32_t code) { return L + (size_t)(code & 3u) * 4 * cap + (size_t)(code & ~3u); }      // (slot << 2 floats = 16 bytes per slot)
 APT_D f3 ldL(float* L, uint32_t cap, uint32_t code) { const float4 v = *reinterpret_cast<const float4*>(L_slot(L, cap, code)); return mk3(v.x, v.y, v.z); }
 APT_D void stL(float* L, uint32_t cap, uint32_t code, f3 v) { *reinterpret_cast<float4*>(L_slot(L, cap, code)) = make_float4(v.x, v.y, v.z, 0.f); }
+// The radiance slot of the path with id word `id` - (sample in batch << pix_bits) | local pixel - as the byte offset of its first word in
+// a plane of 32-bit values: what add_radiance and stL take as `code` (the two low bits name the radiance plane), Vertex::l_off.
+APT_D uint32_t radiance_slot(const Params& p, uint32_t id) { return ((id >> p.pix_bits) * (uint32_t)p.npix + (id & ((1u << p.pix_bits) - 1u))) << 2; }
 // A light sample's contribution into its path's radiance slot.  With ONE light sample per
 // path vertex (p.S == 1) no two entries of a shadow launch share a slot and nothing else writes L while the launch runs, so the add is
 // a plain read-modify-write: deterministic, and not an L2 atomic per component.  With several samples per vertex the entries of one

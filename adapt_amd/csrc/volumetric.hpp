@@ -325,7 +325,7 @@ APT_D void vshade_ev_body(const DevScene& sc, const Params& p, const Queues& q, 
         float emission_weight = rd.y;
         uint32_t bounce = (meta >> 23) & 0xffu; const uint32_t draw0 = meta & 0x7fffffu; const bool vol_event = (meta >> 31) != 0u;
         const uint32_t lp = id & ((1u << p.pix_bits) - 1u), s_ = id >> p.pix_bits;
-        const uint32_t l_off = (s_ * (uint32_t)p.npix + lp) << 2;
+        const uint32_t l_off = radiance_slot(p, id);
         Philox rng; rng_init(rng, (p.world == 1) ? lp : ldq(p.pix_key, lp << 2), p.seed, (uint32_t)(p.cnt_base + (int)s_ + 1), draw0);
         Hit it; it.obj_id = -1; it.prim_id = -1; it.n_s = it.n_g = mk3(1.f, 0.f, 0.f); it.min_depth = 0.f;
         int hit_light = -1, rec_light = -1;

@@ -1,17 +1,9 @@
 """Occupancy guard for the hot kernels.  A kernel's register allocation decides how many waves a SIMD holds (512 VGPRs per lane: <= 128 ->
 four waves, <= 96 -> five, <= 72 -> seven), and it is the maximum over every path the compiler sees, including ones a config never takes: an innocent
 change elsewhere in the stage headers can cost C2's shade kernel its fourth wave (-10 %: it happened, profiles/NOTES.md).  This test compiles the
-hot instantiations for gfx950 with -Rpass-analysis=kernel-resource-usage (hipcc cross-compiles without a GPU; ~10 s) and holds each to
+hot instantiations for gfx950 with -Rpass-analysis=kernel-resource-usage (tests/kernel_probe.py; ~10 s) and holds each to
 the budget it ships with."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_probe import SHADE_HEADERS, compile_probe, resources
 
 # (explicit instantiation, mangled-name prefix, VGPR budget, why)
 KERNELS = [
@@ -25,25 +17,11 @@ KERNELS = [
 ]
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
-def test_hot_kernels_keep_their_register_budget(tmp_path):
-    src = tmp_path / "probe.hip"
-    src.write_text("#include <hip/hip_runtime.h>\n#include <algorithm>\n#include <cmath>\n#include <cstdio>\n#include <cstdlib>\n#include <cstring>\n"
-                   f'#include "{ROOT}/include/adapt_mi.h"\n#include "{ROOT}/adapt_amd/csrc/bvh_build.hpp"\n#include "{ROOT}/adapt_amd/csrc/shade_stage.hpp"\n#include "{ROOT}/adapt_amd/csrc/volumetric.hpp"\n'
-                   + "".join(f"template __global__ void {inst};\n" for inst, *_ in KERNELS))
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-fast-math", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fno-slp-vectorize", "-ffp-contract=off",
-           "-DAPT_FAST=1", "-DAPT_EXACT_MATH=0", "-DAPT_FAST_DIV=1", "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", str(src), "-o", str(tmp_path / "probe.o")]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    usage = {}
-    for blk in out.stderr.split("Function Name: ")[1:]:
-        name = blk.split("\n")[0].split(" [")[0].strip()
-        v = re.search(r"VGPRs: (\d+)", blk); s = re.search(r"VGPRs Spill: (\d+)", blk); sc = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blk)
-        usage[name] = (int(v.group(1)), int(s.group(1)) if s else 0, int(sc.group(1)) if sc else 0)
+def test_hot_kernels_keep_their_register_budget():
+    remarks = compile_probe([inst for inst, *_ in KERNELS], SHADE_HEADERS + ("adapt_amd/csrc/volumetric.hpp",))
     for inst, prefix, budget, why in KERNELS:
-        hit = [(n, u) for n, u in usage.items() if n.startswith(prefix)]
-        assert len(hit) == 1, (prefix, sorted(usage))
-        vgprs, spilled, scratch = hit[0][1]
+        u = resources(remarks, prefix)
+        vgprs, spilled, scratch = u["vgprs"], u["spilled"], u["scratch"]
         # a scratch budget of 16 bytes per lane: the lean group with area lights parks ONE 8-byte constant there under its five-wave
         # bound; anything beyond that is a spill in a hot loop
         assert vgprs <= budget and spilled <= 1 and scratch <= 16, f"{inst}: {vgprs} VGPRs, {spilled} spilled, {scratch} B of scratch; budget {budget} ({why})"
