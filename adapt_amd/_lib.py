@@ -135,6 +135,7 @@ SYMBOLS = {
     "apt_renderer_light_strips": (C.c_int, [C.c_void_p, i32p]),
     "apt_renderer_record_staged": (C.c_int, [C.c_void_p, i32p]),
     "apt_renderer_live_rows": (C.c_int, [C.c_void_p, i32p]),
+    "apt_renderer_record_compact": (C.c_int, [C.c_void_p, i32p]),
     "apt_measure_sclk_mhz": (C.c_int, [C.c_int32, f32p]),
     "apt_last_error": (C.c_char_p, []),
     "apt_version": (C.c_char_p, []),

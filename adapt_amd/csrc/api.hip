@@ -47,8 +47,8 @@ typedef void (*shade_tr_fn)(DevScene, Params, Queues, Counters*, ShadeIn, int, i
 //   queue[stage][live]  the queue-fed kernel: [0][0] direct loads (k_shade_traced), [1][0] its record staged in LDS a row ahead (STAGE), [1][1] staged with live rows (LIVE)
 //   cam[live]           the camera-fed twin (CAM: bounce 0 of a steady full-film batch, no k_generate_trace in front of it), [1] with live rows
 struct TracedKernels { shade_traced_fn queue[2][2]; shade_cam_fn cam[2]; };
-// transient: fn's time-resolved twin (k_shade_tr)
-struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; TracedKernels traced; };
+// transient: fn's time-resolved twin (k_shade_tr); traced56: the traced kernels on the 56-byte path record (stages.hpp TrRecord; all null: the variant has no such form)
+struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn transient; TracedKernels traced, traced56; };
 #if APT_FAST
 #define APT_FLAT_FN(...) __VA_ARGS__
 #else
@@ -57,7 +57,10 @@ struct ShadeVariant { int bm, sm; const char* name; shade_fn fn; shade_tr_fn tra
 #define APT_TRACED_PLAIN(BM, SM, TEX) {{{APT_FLAT_FN(k_shade_traced<BM, SM, TEX>), nullptr}, {nullptr, nullptr}}, {APT_FLAT_FN(k_shade_traced_cam<BM, SM, TEX>), nullptr}}
 #define APT_TRACED_LEAN(BM, SM, TEX) {{{APT_FLAT_FN(k_shade_traced_lean<BM, SM>), nullptr}, {APT_FLAT_FN(k_shade_traced_lean_staged<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_staged_live<BM, SM>)}}, \
                                       {APT_FLAT_FN(k_shade_traced_lean_cam<BM, SM>), APT_FLAT_FN(k_shade_traced_lean_cam_live<BM, SM>)}}
-#define APT_SHADE_VARIANT(BM, SM, TEX, NAME, TRACED) {BM, SM, NAME, k_shade<BM, SM, TEX>, k_shade_tr<BM, SM, TEX>, APT_TRACED_##TRACED(BM, SM, TEX)}
+#define APT_TRACED56_PLAIN(BM, SM, TEX) {{{nullptr, nullptr}, {nullptr, nullptr}}, {nullptr, nullptr}}
+#define APT_TRACED56_LEAN(BM, SM, TEX) {{{APT_FLAT_FN(k_shade_traced_lean56<BM, SM>), nullptr}, {APT_FLAT_FN(k_shade_traced_lean56_staged<BM, SM>), APT_FLAT_FN(k_shade_traced_lean56_staged_live<BM, SM>)}}, \
+                                        {APT_FLAT_FN(k_shade_traced_lean56_cam<BM, SM>), APT_FLAT_FN(k_shade_traced_lean56_cam_live<BM, SM>)}}
+#define APT_SHADE_VARIANT(BM, SM, TEX, NAME, TRACED) {BM, SM, NAME, k_shade<BM, SM, TEX>, k_shade_tr<BM, SM, TEX>, APT_TRACED_##TRACED(BM, SM, TEX), APT_TRACED56_##TRACED(BM, SM, TEX)}
 static const ShadeVariant kShadeVariants[] = {
     APT_SHADE_VARIANT(APT_BX_LAMBERTIAN, APT_SRC_POINT, 0, "lambertian/point", LEAN),
     APT_SHADE_VARIANT(APT_BX_BLINN_PHONG | APT_BX_LAMBERTIAN, APT_SRC_POINT_AREA, 0, "phong+lambertian/point+area", PLAIN),
@@ -262,6 +265,7 @@ struct apt_renderer {
     shade_traced_fn traced_fn = nullptr;      // the queue-fed kernel of a PIPE_TRACED render (pick_traced_kernels)
     int live_rows = 0;            // rays traced in place: 1 = the staged and the camera-fed shade kernel run their live-row form (TracedKernels::queue[1][1], cam[1]; APT_LIVE_ROWS=0 switches it off)
     shade_cam_fn traced_cam_fn = nullptr;     // the camera-fed kernel of a PIPE_TRACED render (pick_traced_kernels)
+    int record_compact = 0;       // rays traced in place: 1 = every launch of a batch reads and writes the 56-byte path record (ShadeVariant::traced56, k_generate_trace56; APT_RECORD_COMPACT=0 switches it off)
     int camera_fuse = 0;          // rays traced in place: 1 = the camera vertex is shaded by the kernel that traces the camera ray (k_shade_traced_cam; steady full-film renders with max_bounce >= 1, APT_CAMERA_FUSE=0 switches it off)
     int light_strips = 0;         // rays traced in place, camera-fed: 1 = some strip mask of the camera vertex's light samples leaves a pair out (cam_strips' second part, flat_build.cpp light_strips; APT_LIGHT_STRIPS=0 switches them off)
     Counters host_counters{};
@@ -840,9 +844,12 @@ static void pick_traversal(apt_renderer* r) {
 
 // The traced kernels of a render: which forms of the variant's (TracedKernels) run.  The staged record and live rows are on wherever the
 // variant has the form; APT_RECORD_STAGE=0 / APT_LIVE_ROWS=0 switch them off (live rows need both live kernels; unstaged, only the camera-fed one runs).
+// The 56-byte record is on wherever the variant has its kernels (the lean one: all five forms); APT_RECORD_COMPACT=0 keeps the 64-byte record.
 static void pick_traced_kernels(apt_renderer* r) {
-    const TracedKernels& t = r->shade->traced;
     const bool traced = r->pipeline == PIPE_TRACED;
+    const bool want_compact = !(getenv("APT_RECORD_COMPACT") && atoi(getenv("APT_RECORD_COMPACT")) == 0);
+    r->record_compact = (traced && want_compact && r->shade->traced56.queue[0][0] != nullptr) ? 1 : 0;
+    const TracedKernels& t = r->record_compact ? r->shade->traced56 : r->shade->traced;
     const bool want_stage = !(getenv("APT_RECORD_STAGE") && atoi(getenv("APT_RECORD_STAGE")) == 0);
     const bool want_live = !(getenv("APT_LIVE_ROWS") && atoi(getenv("APT_LIVE_ROWS")) == 0);
     r->record_stage = (traced && want_stage && t.queue[1][0] != nullptr) ? 1 : 0;
@@ -1040,7 +1047,7 @@ static int make_lanes(apt_renderer* r) {
         for (int k = 0; k < 2; k++) { q.ray_o[k] = (k == 0 || staged) ? take(3 * cap) : nullptr; q.ray_d[k] = (k == 0 || staged) ? take(3 * cap) : nullptr; }
         q.hit_t = take(cap); q.hit_prim = (int*)take(cap); q.hit_u = take(cap); q.hit_v = take(cap);
         for (int k = 0; k < 2; k++) {
-            for (int a = 0; a < 4; a++) q.tr[k][a] = staged ? nullptr : (float4*)take(4 * cap);
+            for (int a = 0; a < 4; a++) q.tr[k][a] = staged ? nullptr : (float4*)take((a == 3 && r->record_compact ? 2 : 4) * cap);      // (the 56-byte record's plane D: 8 bytes per entry)
             q.tr_uv[k] = tr_uv ? (float2*)take(2 * cap) : nullptr;
         }
         q.tr_ncls = staged ? 0 : 1; q.tr_stage_top = staged ? 0 : 1;
@@ -1536,8 +1543,8 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
                 cur = 1; b0 = 1;
             } else {
                 LaunchTimer t(r, APT_K_GENERATE, st);
-                if (r->adaptive) hipLaunchKernelGGL(k_generate_trace_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, (const uint8_t*)r->aq.active, strips);
-                else hipLaunchKernelGGL(k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips);
+                if (r->adaptive) hipLaunchKernelGGL(r->record_compact ? k_generate_trace56_ad : k_generate_trace_ad, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, (const uint8_t*)r->aq.active, strips);
+                else hipLaunchKernelGGL(r->record_compact ? k_generate_trace56 : k_generate_trace, dim3(grid_for(total, r->grid_small, 1)), dim3(BLOCK), 0, st, sc, p, q, cnt, strips);
             }
             for (int b = b0; b < p.max_bounce; b++) {
                 { LaunchTimer t(r, APT_K_SHADE, st); hipLaunchKernelGGL(r->traced_fn, dim3(grid_for(total, r->grid_small, nq)), dim3(BLOCK), 0, st, sc, p, q, cnt, cur, b); }      // (the records are Queues::tr[cur]: one queue for the scene)
@@ -2192,6 +2199,11 @@ APT_EXPORT int apt_renderer_record_staged(const apt_renderer* r, int32_t* out) {
 APT_EXPORT int apt_renderer_live_rows(const apt_renderer* r, int32_t* out) {
     if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_live_rows: null argument");
     *out = r->live_rows;
+    return APT_OK;
+}
+APT_EXPORT int apt_renderer_record_compact(const apt_renderer* r, int32_t* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_renderer_record_compact: null argument");
+    *out = r->record_compact;
     return APT_OK;
 }
 APT_EXPORT int apt_renderer_info(const apt_renderer* r, int32_t* spp_batch, int32_t* n_subqueues, int64_t* queue_bytes, int32_t* lds_bytes, const char** shade_variant, int32_t* trace_mode) {

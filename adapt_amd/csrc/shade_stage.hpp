@@ -62,10 +62,13 @@ APT_D int surface_maps(const DevScene& sc, Hit& it, int prim, float bu, float bv
 }
 
 // -------------------------------------------------------------------- shade
+// AT: `o` is the hit point itself (the 56-byte path record carries it, stages.hpp TrRecord); d and t are not read
+template <bool AT = false>
 APT_D void build_hit_rec(const DevScene& sc, float4 ra, float4 rb, int prim, float t, float u, float v, f3 o, f3 d, Hit& it, int& hit_light, f3& k_d, bool with_vn = true);
 APT_D void build_hit(const DevScene& sc, int prim, float t, float u, float v, f3 o, f3 d, Hit& it, int& hit_light, f3& k_d) {
     build_hit_rec(sc, sc.prim_shade[2 * prim], sc.prim_shade[2 * prim + 1], prim, t, u, v, o, d, it, hit_light, k_d);
 }
+template <bool AT>
 APT_D void build_hit_rec(const DevScene& sc, float4 ra, float4 rb, int prim, float t, float u, float v, f3 o, f3 d, Hit& it, int& hit_light, f3& k_d, bool with_vn) {
     const int code = __float_as_int(ra.w);
     it.prim_id = prim; it.min_depth = t;
@@ -74,7 +77,7 @@ APT_D void build_hit_rec(const DevScene& sc, float4 ra, float4 rb, int prim, flo
     k_d = mk3(rb.y, rb.z, rb.w);
     if (code < 0) {
         // sphere: the record holds the centre; normal from the hit point (tracer_base.py:217-223)
-        it.n_g = normalize((o + d * t) - mk3(ra.x, ra.y, ra.z));
+        it.n_g = normalize((AT ? o : (o + d * t)) - mk3(ra.x, ra.y, ra.z));
         it.n_s = it.n_g;
     } else {
         it.n_g = mk3(ra.x, ra.y, ra.z);
@@ -103,7 +106,10 @@ APT_D void build_hit(const DevScene& sc, int prim, float t, float u, float v, f3
 // launches per render, where the whole protocol is two scalar loads per wave; the serving code sits in front of the kernel's main loop,
 // where almost no register is live, so it costs the hot loop nothing (k_fix_flat alone allocates 84 VGPRs, the shade kernel 122).
 // Nothing depends on how workgroups are placed: whichever wave claims a list is running, hence the waiters cannot starve it.
+// C56: the launch's records are 56 bytes (stages.hpp TrRecord) - a staged ray's origin becomes the resolved record's hit point here.
+template <bool C56 = false>
 APT_D void fix_prologue(const DevScene& sc, const Params& p, const Queues& q, Counters* cnt, int cur, int sq, int bounce) {
+    typedef TrRecord<C56> Rec;
     const uint32_t epoch = (uint32_t)bounce + 1u;
     const int ncls = q.tr_ncls;
     uint32_t* n_def_p = &cnt->n_tr[bounce % 3][ncls][sq * CNT_PAD]; uint32_t* n_sh_p = &cnt->n_fix_sh[cur ^ 1][sq * CNT_PAD];
@@ -134,22 +140,31 @@ APT_D void fix_prologue(const DevScene& sc, const Params& p, const Queues& q, Co
         // (staging at the top of the sub-queue's own region: served from its LOWEST slot upwards - a resolved record is appended at or below the
         // slot its ray was just read from, never onto a staged ray that is still to be served)
         const uint32_t lj = valid ? li : n_def - 1u;
-        const uint32_t io = (q.tr_stage_top ? qbase + p.subcap - n_def + lj : (uint32_t)ncls * p.cap + qbase + lj) << 4;
-        const float4 ra = ldq(q.tr[cur][0], io), rb = ldq(q.tr[cur][1], io), rc = ldq(q.tr[cur][2], io), rd = ldq(q.tr[cur][3], io);
-        const f3 o = mk3(ra.x, ra.y, ra.z), d = mk3(rb.x, rb.y, rb.z);
+        const uint32_t is = q.tr_stage_top ? qbase + p.subcap - n_def + lj : (uint32_t)ncls * p.cap + qbase + lj, io = is << 4;
+        const float4 ra = ldq(q.tr[cur][0], io), rb = ldq(q.tr[cur][1], io), rc = ldq(q.tr[cur][2], io);
+        float4 rd = make_float4(0.f, 0.f, 0.f, 0.f);      // (a 56-byte camera ray has no plane D)
+        if (!C56 || bounce > 0) rd = Rec::load_d(q.tr[cur][3], is);
+        const f3 o = mk3(ra.x, ra.y, ra.z), d = mk3(rb.x, rb.y, rb.z), lc = Rec::Lc(rc, rd);      // (staged: the three words of plane A hold the ray's origin in either form)
         HitRec r0, r1; r0.t = r1.t = 1e7f; r0.prim = r1.prim = -1; r0.u = r0.v = r1.u = r1.v = 0.f;
         int c0, c1;
         flat_closest2(sc.flat, sc.sweep, sc.prim_class, o, d, o, d, r0, r1, c0, c1);
         if (valid && r0.prim >= 0) {
             const int oc = ncls > 1 ? c0 : 0;
             const uint32_t pos = atomicAdd(&cnt->n_tr[bounce % 3][oc][sq * CNT_PAD], 1u);      // (one atomic per entry: this path is a handful of rays per million)
-            const uint32_t slot = (uint32_t)oc * p.cap + qbase + pos, so = slot << 4;
-            stq(q.tr[cur][0], so, make_float4(ra.x, ra.y, ra.z, r0.t));
-            stq(q.tr[cur][1], so, make_float4(rb.x, rb.y, rb.z, __uint_as_float((__float_as_uint(rb.w) & ~0xffu) | (uint32_t)r0.prim)));
-            stq(q.tr[cur][2], so, rc); stq(q.tr[cur][3], so, rd);
+            const uint32_t slot = (uint32_t)oc * p.cap + qbase + pos;
+            // (the 64-byte form's two stores stay as they were written: through put_a / put_b the hit record's fields are read in another order and
+            // the parent's kernels come out with two registers swapped)
+            if constexpr (C56) {
+                auto pm = [pm0 = Rec::pm(ra, rb), prim = r0.prim] { return (pm0 & ~0xffu) | (uint32_t)prim; };
+                Rec::put_a(q.tr[cur][0], slot, hit_point_of(o, d, r0.t), r0.t, pm); Rec::put_b(q.tr[cur][1], slot, d, pm, Rec::id(rb, rc));
+            } else {
+                stq(q.tr[cur][0], slot << 4, make_float4(ra.x, ra.y, ra.z, r0.t));
+                stq(q.tr[cur][1], slot << 4, make_float4(rb.x, rb.y, rb.z, __uint_as_float((__float_as_uint(rb.w) & ~0xffu) | (uint32_t)r0.prim)));
+            }
+            Rec::copy_c(q.tr[cur][2], slot, rc); if (!C56 || bounce > 0) Rec::copy_d(q.tr[cur][3], slot, rd);      // (throughput, id, radiance, pdf: as they were staged)
             if (need_uv) { float2 uv_; uv_.x = r0.u; uv_.y = r0.v; stq(q.tr_uv[cur], slot << 3, uv_); }
-        } else if (valid && !(rd.x == 0.f && rd.y == 0.f && rd.z == 0.f)) {      // nothing hit: the path ends, its radiance goes to its slot
-            add_radiance(q.L, p.cap, radiance_slot(p, __float_as_uint(rc.w)), mk3(rd.x, rd.y, rd.z), true);
+        } else if (valid && !(lc.x == 0.f && lc.y == 0.f && lc.z == 0.f)) {      // nothing hit: the path ends, its radiance goes to its slot
+            add_radiance(q.L, p.cap, radiance_slot(p, Rec::id(rb, rc)), lc, true);
         }
     }
     uint32_t t_lit = 0;
@@ -391,7 +406,8 @@ struct RecordPlanes { const float4 *a, *b, *c, *d; };             // planes A to
 // shading record can be requested together with its queue record instead of a round trip after it.  (Rounds 2-4 prefetched the Lambertian
 // kernel's whole record: thirteen registers.  Without them the kernel allocates 91 VGPRs - five waves per SIMD instead of four - and three
 // render lanes gain 6 %: C2 4 310 -> 4 560 Msamples/s on the same box.)
-APT_D uint32_t prefetch_prim(const RecordPlanes& tr, uint32_t qbase, uint32_t b, uint32_t n) { return ldq(reinterpret_cast<const uint32_t*>(tr.b), ((qbase + row_lane(b, n)) << 4) + 12u); }
+template <bool C56 = false>
+APT_D uint32_t prefetch_prim(const RecordPlanes& tr, uint32_t qbase, uint32_t b, uint32_t n) { return ldq(TrRecord<C56>::pm_plane(tr.a, tr.b), ((qbase + row_lane(b, n)) << 4) + 12u); }
 // STAGE, the staged record (queue-fed form only): a row's record - planes A to D, 64 entries of 16 bytes each: 1 KiB per
 // plane and wave - is requested a row AHEAD, by loads that write LDS directly (global_load_lds_dwordx4: no register holds the data in
 // flight), into 4 KiB that the wave owns; the scene's shading records (at most 96 x 32 bytes) sit in LDS too, one copy per workgroup.
@@ -401,24 +417,38 @@ APT_D uint32_t prefetch_prim(const RecordPlanes& tr, uint32_t qbase, uint32_t b,
 // the row, before its stores (a wait at the next row's top would also wait for those stores to be acknowledged: one in-order counter).
 // Nothing is staged for an empty sub-queue or behind the last row.  STAGE = false is the kernel with the direct loads, instruction for instruction.
 struct StagedRecord { rec4* rec; rec4* prim; };                   // plane k of this wave's row at rec[64 * k + lane]; the shading records (DevScene::prim_shade)
+// (the 56-byte record, C56: 3.5 KiB per wave, laid out by thread - stages.hpp staged_read56 - and `rec` is the workgroup's area: plane k of
+// the row of thread t at rec[BLOCK * k + t], plane D's two words as word planes behind plane C)
+template <bool C56 = false>
 APT_D StagedRecord staged_record_open(const ShadeArgs3* A_) {      // (before the prologue: every wave of the workgroup passes here, none has a staged load in flight)
-    __shared__ rec4 s_stage[(BLOCK / 64) * 4 * 64]; __shared__ rec4 s_shade[2 * APT_FLAT_MAX_PRIMS];
+    constexpr int WAVE_RECS = C56 ? 3 * 64 + 32 : 4 * 64;
+    __shared__ rec4 s_stage[(BLOCK / 64) * WAVE_RECS]; __shared__ rec4 s_shade[2 * APT_FLAT_MAX_PRIMS];
     static_assert(2 * APT_FLAT_MAX_PRIMS <= BLOCK, "one shading-record word per thread");
     if ((int)threadIdx.x < 2 * min((A_->sc).n_prims, APT_FLAT_MAX_PRIMS)) { const float4 w_ = (A_->sc).prim_shade[threadIdx.x]; s_shade[threadIdx.x] = rec4{w_.x, w_.y, w_.z, w_.w}; }
     __syncthreads();
-    return StagedRecord{s_stage + (threadIdx.x >> 6) * (4 * 64), s_shade};
+    return StagedRecord{s_stage + (C56 ? 0 : (threadIdx.x >> 6) * WAVE_RECS), s_shade};
 }
+template <bool C56 = false>
 APT_D void stage_row(const StagedRecord& s, const RecordPlanes& tr, uint32_t qbase, uint32_t b, uint32_t n, int bounce) {      // (wave-uniform: b < n)
     const uint32_t off = (qbase + row_lane(b, n)) << 4;
+    if constexpr (C56) {
+        rec4* row = s.rec + (threadIdx.x >> 6) * 64;
+        stage_plane(tr.a, off, row); stage_plane(tr.b, off, row + BLOCK); stage_plane(tr.c, off, row + 2 * BLOCK);
+        // (plane D, 8 bytes per entry: its two words, 64 lanes of 4 bytes each)
+        if (bounce > 0) { float* w_ = reinterpret_cast<float*>(s.rec + 3 * BLOCK) + (threadIdx.x >> 6) * 64; stage_word(reinterpret_cast<const float*>(tr.d), off >> 1, w_); stage_word(reinterpret_cast<const float*>(tr.d), (off >> 1) + 4u, w_ + BLOCK); }
+        return;
+    }
     stage_plane(tr.a, off, s.rec); stage_plane(tr.b, off, s.rec + 64); stage_plane(tr.c, off, s.rec + 128);
     if (bounce > 0) stage_plane(tr.d, off, s.rec + 192);
 }
 // this lane's words of the row's record and the shading record of its hit primitive (plane D's words are read at bounce 0 too, where
 // nothing was staged into them: never used)
+template <bool C56 = false>
 APT_D void staged_row_read(const StagedRecord& s, float4& a, float4& b, float4& c, float4& d, float4& ra, float4& rb) {
     rec4 sa, sb, sc_, sd, pa, pb;
-    staged_read(s.rec + lane_id(), sa, sb, sc_, sd);
-    staged_read2(s.prim + 2 * max(tr_prim(__float_as_uint(sb.w)), 0), pa, pb);
+    if constexpr (C56) { float d0, d1; staged_read56(s.rec, sa, sb, sc_, d0, d1); sd = rec4{d0, d1, 0.f, 0.f}; }
+    else staged_read(s.rec + lane_id(), sa, sb, sc_, sd);
+    staged_read2(s.prim + 2 * max(tr_prim(__float_as_uint(C56 ? sa.w : sb.w)), 0), pa, pb);
     a = make_float4(sa.x, sa.y, sa.z, sa.w); b = make_float4(sb.x, sb.y, sb.z, sb.w); c = make_float4(sc_.x, sc_.y, sc_.z, sc_.w); d = make_float4(sd.x, sd.y, sd.z, sd.w);
     ra = make_float4(pa.x, pa.y, pa.z, pa.w); rb = make_float4(pb.x, pb.y, pb.z, pb.w);
 }
@@ -435,16 +465,23 @@ APT_D void staged_wait_stamped(RowTop& rt, bool row) {
 // a vertex's draws into the wave's tally; UNORDERED (the kernels that stage their record): by an LDS add that waits for no staged load
 template <bool UNORDERED> APT_D void tally_draws(uint32_t* s_draws, uint32_t n) { if constexpr (UNORDERED) lds_add_unordered(&s_draws[threadIdx.x >> 6], n); else atomicAdd(&s_draws[threadIdx.x >> 6], n); }
 // planes A to C of a record -> the vertex's ray, throughput and path id (A.w, the hit distance, and B.w, the packed word, go to the hit)
-APT_D void unpack_record(float4 a, float4 b, float4 c, Vertex& vx) { vx.o = mk3(a.x, a.y, a.z); vx.d = mk3(b.x, b.y, b.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = __float_as_uint(c.w); }
+// (the 56-byte record, C56: plane A's point is the vertex itself - vx.hit_point; the ray's origin did not travel and has no reader)
+template <bool C56 = false>
+APT_D void unpack_record(float4 a, float4 b, float4 c, Vertex& vx) {
+    if constexpr (C56) vx.hit_point = mk3(a.x, a.y, a.z); else vx.o = mk3(a.x, a.y, a.z);
+    vx.d = mk3(b.x, b.y, b.z); vx.thr = mk3(c.x, c.y, c.z); vx.id = TrRecord<C56>::id(b, c);
+}
 // a record's words -> its opened vertex; false: the path ends here.  pm: the packed word; REC: ra, rb hold the hit primitive's shading record
-template <int BM, int SM, int TEX, bool REC, typename RNG>
+template <int BM, int SM, int TEX, bool REC, bool C56 = false, typename RNG>
 APT_D bool open_record(const ShadeArgs3* A_, Vertex& vx, RNG& rng, float4 a, float4 b, float4 c, uint32_t pm, float4 ra, float4 rb, int cur, uint32_t idx, float ray_pdf, int bounce) {
-    unpack_record(a, b, c, vx);
+    static_assert(!C56 || REC, "the 56-byte record's kernels hold the hit primitive's shading record");
+    unpack_record<C56>(a, b, c, vx);
     const int prim = tr_prim(pm);
     if (prim < 0) return false;                              // nothing hit: path ends (vanilla_renderer.py:49)
     f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
     if ((A_->sc).has_vn || (TEX && (A_->sc).tex_i != nullptr)) uv = ldq((A_->q).tr_uv[cur], idx << 3);      // otherwise nobody reads the barycentrics (and nobody wrote them)
-    if (REC) build_hit_rec((A_->sc), ra, rb, prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+    if constexpr (C56) build_hit_rec<true>((A_->sc), ra, rb, prim, 0.f, uv.x, uv.y, vx.hit_point, vx.d, vx.it, vx.hit_light, rec_kd);
+    else if (REC) build_hit_rec((A_->sc), ra, rb, prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
     else build_hit((A_->sc), prim, a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
     return open_vertex<BM, SM, TEX>(A_, vx, rng, prim, rec_kd, tr_meta(pm, (uint32_t)bounce), ray_pdf, uv, bounce);
 }
@@ -454,15 +491,16 @@ APT_D bool open_record(const ShadeArgs3* A_, Vertex& vx, RNG& rng, float4 a, flo
 // above).  vertex_reset is no default provider there: what it writes is overwritten for every lane, or a constant of the Lambertian
 // kernel.  At the last bounce the continuation is not sampled; `draw` moves on by its two words.  LIVE = false is the parent's kernel,
 // instruction for instruction.
-template <int BM, int SM, typename RNG>
+template <int BM, int SM, bool C56 = false, typename RNG>
 APT_D bool open_record_live(const ShadeArgs3* A_, Vertex& vx, RNG& rng, float4 a, float4 b, float4 c, float4 d, float4 ra, float4 rb, int cur, uint32_t idx, int bounce, bool alive, uint32_t* s_draws, f3& Lc) {
-    if (bounce > 0) Lc = mk3(d.x, d.y, d.z);
-    unpack_record(a, b, c, vx);
-    const uint32_t pm = __float_as_uint(b.w); const int prim = tr_prim(pm);
+    if (bounce > 0) Lc = TrRecord<C56>::Lc(c, d);
+    unpack_record<C56>(a, b, c, vx);
+    const uint32_t pm = TrRecord<C56>::pm(a, b); const int prim = tr_prim(pm);
     alive = alive && prim >= 0;                              // nothing hit: path ends (vanilla_renderer.py:49)
     f3 rec_kd; float2 uv; uv.x = uv.y = 0.f;
     if ((A_->sc).has_vn) { if (alive) uv = ldq((A_->q).tr_uv[cur], idx << 3); }
-    build_hit_rec((A_->sc), ra, rb, max(prim, 0), a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
+    if constexpr (C56) build_hit_rec<true>((A_->sc), ra, rb, max(prim, 0), 0.f, uv.x, uv.y, vx.hit_point, vx.d, vx.it, vx.hit_light, rec_kd);
+    else build_hit_rec((A_->sc), ra, rb, max(prim, 0), a.w, uv.x, uv.y, vx.o, vx.d, vx.it, vx.hit_light, rec_kd);
     const bool opened = alive; alive = open_vertex_live<BM, SM>(A_, vx, rng, rec_kd, pm, bounce, alive);
     if (opened && !alive && rng.draw != vx.draw0) tally_draws<true>(s_draws, rng.draw - vx.draw0);      // the roulette's word of a path it ended
     return alive;
@@ -494,23 +532,25 @@ APT_D bool cam_sweep(const ShadeArgs3* A_, const unsigned long long* strips, uin
 // a camera ray left to the reference-order code is staged.  The words the two callers store differently come from `words`, called in the
 // rare branch, where their register notes want them made: A.w; B.w's primitive; the barycentrics; planes C (one, one, one, id) and D (zero, zero, zero, one_d)
 struct StagedRayWords { float t; int prim; float u, v, one, zero, one_d; };
-template <typename Words>
+template <bool C56 = false, typename Words>
 APT_D void stage_camera_ray(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qbase, bool c_defer, f3 cam_o, f3 dir, uint32_t draws, uint32_t id, Words&& words) {
     if (!__any(c_defer)) return;
     const int ncls = (A_->q).tr_ncls; const uint32_t dpos = wave_append(c_defer, &cnt->n_tr[0][ncls][q * CNT_PAD]);
     if (c_defer) {
-        const uint32_t slot = (A_->q).tr_stage_top ? qbase + (A_->p).subcap - 1u - dpos : (uint32_t)ncls * (A_->p).cap + qbase + dpos, so = slot << 4;
+        const uint32_t slot = (A_->q).tr_stage_top ? qbase + (A_->p).subcap - 1u - dpos : (uint32_t)ncls * (A_->p).cap + qbase + dpos;
         const StagedRayWords w = words();
-        stq((A_->q).tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, w.t));
-        stq((A_->q).tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(w.prim, draws, false))));
-        stq((A_->q).tr[0][2], so, make_float4(w.one, w.one, w.one, __uint_as_float(id)));
-        stq((A_->q).tr[0][3], so, make_float4(w.zero, w.zero, w.zero, w.one_d));
+        typedef TrRecord<C56> Rec;
+        auto pm = [&] { return tr_pack(w.prim, draws, false); };
+        Rec::put_a((A_->q).tr[0][0], slot, cam_o, w.t, pm);
+        Rec::put_b((A_->q).tr[0][1], slot, dir, pm, id);
+        Rec::put_c((A_->q).tr[0][2], slot, mk3(w.one, w.one, w.one), id, mk3(w.zero, w.zero, w.zero));
+        if constexpr (!C56) Rec::put_d((A_->q).tr[0][3], slot, mk3(w.zero, w.zero, w.zero), w.one_d);      // (56 bytes: a camera ray has no plane D, stages.hpp TrRecord)
         if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = w.u; uv_.y = w.v; stq((A_->q).tr_uv[0], slot << 3, uv_); }
     }
 }
 // the camera vertex: the ray is made, swept against its strip's records and, where that settles it, shaded right here.
 // -> alive; entry: the lane holds a path this launch shades (valid, not left to the reference-order code)
-template <int BM, int SM, int TEX, bool WINDOW, typename RNG>
+template <int BM, int SM, int TEX, bool WINDOW, bool C56 = false, typename RNG>
 APT_D bool camera_vertex(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qbase, uint32_t pos, bool in_row, uint32_t cam_total, const unsigned long long* strips, Vertex& vx, RNG& rng, uint32_t* s_draws, uint32_t& t_samples, uint32_t& t_extend, bool& entry) {
     const uint32_t w = cam_wave(A_, pos, q), id_ = w * 64u + lane_id(); const bool valid = in_row && id_ < cam_total;
     f3 dir = mk3(0.f, 0.f, 1.f); uint32_t draws = 0, jitter_tail[2] = {0u, 0u};
@@ -522,10 +562,12 @@ APT_D bool camera_vertex(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qb
     HitRec hr; hr.t = 1e7f; hr.prim = -1; hr.u = hr.v = 0.f;
     if (valid && !c_defer && c_idx >= 0) flat_resolve((A_->sc).flat, c_idx, c_t, cam_o, dir, hr, hit_cls);
     { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
-    stage_camera_ray(A_, cnt, q, qbase, c_defer, cam_o, dir, draws, vx.id, [&] {
+    stage_camera_ray<C56>(A_, cnt, q, qbase, c_defer, cam_o, dir, draws, vx.id, [&] {
         float one = 1.f;
-        if (WINDOW) asm volatile("" : "+v"(one));      // (made here, in the rare branch: as a constant, (0, 0, 0, 1) is hoisted in front of the row loop, where the draw-window kernel has no four registers for it - 72 VGPRs and a 16-byte spill)
-        return StagedRayWords{hr.t, hr.prim, hr.u, hr.v, 1.f, 0.f, one};
+        if (WINDOW && !C56) asm volatile("" : "+v"(one));      // (made here, in the rare branch: as a constant, (0, 0, 0, 1) is hoisted in front of the row loop, where the draw-window kernel has no four registers for it - 72 VGPRs and a 16-byte spill)
+        float zero = 0.f;
+        if constexpr (C56) { if (WINDOW) asm volatile("" : "+v"(zero)); }      // (the 56-byte record's plane D is (zero, zero): hoisted and spilled likewise)
+        return StagedRayWords{hr.t, C56 ? -1 : hr.prim, hr.u, hr.v, 1.f, zero, one};      // (a staged ray was not resolved: its hit record is the empty one)
     });
     entry = valid && !c_defer; bool alive = entry && hr.prim >= 0;                       // nothing hit: the path ends where it began, nothing gathered
     if (alive) {
@@ -538,7 +580,7 @@ APT_D bool camera_vertex(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qb
 }
 // ... live rows: a lane past the id space's end makes the ray of its pixel (a pixel of the film all the same, a sample no batch holds), and
 // a ray that hit nothing or is left to the reference-order code is shaded on whatever record the resolve gives it; `valid`, `c_defer`, `alive` mask the effects
-template <int BM, int SM, bool WINDOW, typename RNG>
+template <int BM, int SM, bool WINDOW, bool C56 = false, typename RNG>
 APT_D bool camera_vertex_live(const ShadeArgs3* A_, Counters* cnt, int q, uint32_t qbase, uint32_t pos, bool in_row, uint32_t cam_total, const unsigned long long* strips, Vertex& vx, RNG& rng, uint32_t* s_draws, uint32_t& t_samples, uint32_t& t_extend, bool& entry) {
     const uint32_t w = cam_wave(A_, pos, q), id_ = w * 64u + lane_id(); const bool valid = in_row && id_ < cam_total;
     uint32_t draws = 0, jitter_tail[2] = {0u, 0u}, s; int i, j;
@@ -551,9 +593,10 @@ APT_D bool camera_vertex_live(const ShadeArgs3* A_, Counters* cnt, int q, uint32
     HitRec hr;
     flat_resolve((A_->sc).flat, max(c_idx, 0), c_t, cam_o, dir, hr, hit_cls);
     { const uint32_t nv = wave_count(valid); t_samples += nv; t_extend += nv; }
-    stage_camera_ray(A_, cnt, q, qbase, c_defer, cam_o, dir, draws, vx.id, [&] {      // with an empty hit record
+    stage_camera_ray<C56>(A_, cnt, q, qbase, c_defer, cam_o, dir, draws, vx.id, [&] {      // with an empty hit record
         float one = 1.f, far_ = 1e7f, zero = 0.f;
-        asm volatile("" : "+v"(one), "+v"(far_), "+v"(zero));      // (made here, in the rare branch: as constants the words are hoisted in front of the row loop and spilled there, see camera_vertex)
+        if constexpr (C56) asm volatile("" : "+v"(one), "+v"(zero));      // (the 56-byte record carries no hit distance)
+        else asm volatile("" : "+v"(one), "+v"(far_), "+v"(zero));      // (made here, in the rare branch: as constants the words are hoisted in front of the row loop and spilled there, see camera_vertex)
         return StagedRayWords{far_, -1, zero, zero, one, zero, one};
     });
     entry = valid && !c_defer; bool alive = entry && c_idx >= 0 && hr.prim >= 0;          // nothing hit: the path ends where it began, nothing gathered
@@ -634,23 +677,51 @@ APT_D void sweep_light_sample(const ShadeArgs3* A_, Counters* cnt, const Vertex&
     t_traced += wave_count(f.want); t_lit += wave_count(traced && !occ);
 }
 // the continuation's record joins the next queue; the path's radiance so far (Lc) travels with it
+// (the 56-byte record, C56: the NEXT vertex - this ray's hit point, made here from what the reader would have loaded; a staged ray keeps its origin)
+// TURN (56 bytes): a staged ray's position is turned round in its rare branch and the row has one slot expression, instead of a select in
+// the row.  Which of the two the compiler makes the shorter row loop of differs by kernel (the scalar registers it keeps in lanes move):
+// the camera-fed form without live rows takes this one, the other four the select (tests/test_kernel_record_compact.py holds all five).
+template <bool C56 = false, bool TURN = false>
 APT_D void append_record(const ShadeArgs3* A_, int nxt, uint32_t qbase, uint32_t* next_counter, const Continuation& ct, bool cont, const Vertex& vx, f3 new_d, uint32_t draw, bool is_spec, f3 Lc, float new_pdf) {
     uint32_t npos = (uint32_t)__builtin_amdgcn_readlane((int)ct.app.raw, 0) + ct.app.rank;
+    auto pm = [&] { return tr_pack(ct.hit, draw, is_spec); };
+    if constexpr (C56) {
+        // a staged ray's plane A - its origin - is stored in the rare branch, whole; behind it the vertex's own position has no reader left
+        typedef TrRecord<true> Rec;
+        if (__any(ct.q == 1)) {
+            const uint32_t dpos = wave_append(ct.q == 1, next_counter + APT_MAX_NQ * CNT_PAD);
+            if (ct.q == 1) { npos = TURN ? (A_->p).subcap - 1u - dpos : dpos; Rec::put_a((A_->q).tr[nxt][0], qbase + (A_->p).subcap - 1u - dpos, vx.hit_point, ct.t, [&] { return tr_pack(-1, draw, is_spec); }); }      // (no hit yet)
+        }
+        const uint32_t slot = (!TURN && ct.q == 1) ? qbase + (A_->p).subcap - 1u - npos : qbase + npos;      // (staged rays grow down from the top of the sub-queue's region)
+        float t_hit = ct.t;
+        asm volatile("" : "+v"(t_hit));      // (the point is made HERE, into the registers of the vertex's own: made ahead of the light sample's sweep it costs three registers the budget does not have)
+        // (a resolved ray has its primitive: the packed word needs no "nothing hit" test here - the staged rays' word was made above)
+        if (ct.q == 0) Rec::put_a((A_->q).tr[nxt][0], slot, hit_point_of(vx.hit_point, new_d, t_hit), t_hit, [&] { return (uint32_t)ct.hit | ((draw & 0xffffu) << 8) | (is_spec ? (1u << 24) : 0u); });
+        if (cont) {
+            Rec::put_b((A_->q).tr[nxt][1], slot, new_d, pm, vx.id);
+            Rec::put_c((A_->q).tr[nxt][2], slot, vx.thr, vx.id, Lc); Rec::put_d((A_->q).tr[nxt][3], slot, Lc, new_pdf);
+            if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = ct.u; uv_.y = ct.v; stq((A_->q).tr_uv[nxt], slot << 3, uv_); }
+        }
+        return;
+    }
     if (__any(ct.q == 1)) { const uint32_t dpos = wave_append(ct.q == 1, next_counter + APT_MAX_NQ * CNT_PAD); if (ct.q == 1) npos = dpos; }
     if (cont) {
-        const uint32_t slot = (ct.q == 1) ? qbase + (A_->p).subcap - 1u - npos : qbase + npos, so = slot << 4;      // (staged rays grow down from the top of the sub-queue's region)
-        stq((A_->q).tr[nxt][0], so, make_float4(vx.hit_point.x, vx.hit_point.y, vx.hit_point.z, ct.t));
-        stq((A_->q).tr[nxt][1], so, make_float4(new_d.x, new_d.y, new_d.z, __uint_as_float(tr_pack(ct.hit, draw, is_spec))));
-        stq((A_->q).tr[nxt][2], so, make_float4(vx.thr.x, vx.thr.y, vx.thr.z, __uint_as_float(vx.id)));
-        stq((A_->q).tr[nxt][3], so, make_float4(Lc.x, Lc.y, Lc.z, new_pdf));
+        const uint32_t slot = (ct.q == 1) ? qbase + (A_->p).subcap - 1u - npos : qbase + npos;      // (staged rays grow down from the top of the sub-queue's region)
+        typedef TrRecord<false> Rec;
+        Rec::put_a((A_->q).tr[nxt][0], slot, vx.hit_point, ct.t, pm); Rec::put_b((A_->q).tr[nxt][1], slot, new_d, pm, vx.id);
+        Rec::put_c((A_->q).tr[nxt][2], slot, vx.thr, vx.id, Lc); Rec::put_d((A_->q).tr[nxt][3], slot, Lc, new_pdf);
         if ((A_->sc).has_vn || (A_->sc).tex_i != nullptr) { float2 uv_; uv_.x = ct.u; uv_.y = ct.v; stq((A_->q).tr_uv[nxt], slot << 3, uv_); }
     }
 }
 // the path ends here (nothing hit, roulette, last bounce): its radiance goes to its slot - added, not stored: the prologue may have put a deferred sample's share there already
 APT_D void end_path(const ShadeArgs3* A_, bool ended, uint32_t id, f3 Lc) { if (ended && !(Lc.x == 0.f && Lc.y == 0.f && Lc.z == 0.f)) add_radiance((A_->q).L, (A_->p).cap, radiance_slot((A_->p), id), Lc, true); }
-template <int BM, int SM, int TEX, bool CAM = false, bool STAGE = false, bool LIVE_ = false>
+// C56: the launch reads and writes the 56-byte record (stages.hpp TrRecord: the hit point travels, origin, distance and pdf do not); C56 =
+// false is the kernel with the 64-byte record, instruction for instruction.
+template <int BM, int SM, int TEX, bool CAM = false, bool STAGE = false, bool LIVE_ = false, bool C56 = false>
 APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, const unsigned long long* strips = nullptr) {
     static_assert(!(CAM && STAGE), "a camera-fed row loads no record");
+    static_assert(!C56 || (TEX == 0 && BM == APT_BX_LAMBERTIAN && !(SM & APT_SRC_AREA)), "the 56-byte record: Lambertian surfaces, no area light - nobody reads the ray's origin, its hit distance or its pdf");
+    typedef TrRecord<C56> Rec;
     static_assert(!LIVE_ || ((CAM || STAGE) && TEX == 0), "live rows: the staged and the camera-fed form of the lean kernels");
     constexpr bool LIVE = LIVE_ && APT_DRAW_WINDOW != 0;      // (live rows are written for the draw window: a build without it, -DAPT_DRAW_WINDOW=0, keeps the parent's form under the live kernels' names)
     const ShadeArgs3* A_ = args_fresh(A0);                      // scene, parameters, queues: read through the kernel-argument segment, re-fetched per phase (APT_ARGS_PHASE)
@@ -674,7 +745,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
     static_assert(APT_FLAT_MAX_PRIMS < (int)TR_NO_PRIM, "the packed record keeps the hit primitive in 8 bits");
     const RecordPlanes tr = {(A_->q).tr[cur][0], (A_->q).tr[cur][1], (A_->q).tr[cur][2], (A_->q).tr[cur][3]};
     StagedRecord stage = {nullptr, nullptr};
-    if constexpr (STAGE) stage = staged_record_open(A_);
+    if constexpr (STAGE) stage = staged_record_open<C56>(A_);
     uint32_t n, cam_total = 0;
     if constexpr (CAM) {
         // rows of this sub-queue: 64 per id-space wave w with w % nq == q
@@ -682,12 +753,12 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         const uint32_t n_waves = (cam_total + 63u) / 64u, nq_ = (uint32_t)(A_->p).nq;
         n = n_waves > (uint32_t)sl.q ? ((n_waves - (uint32_t)sl.q + nq_ - 1u) / nq_) * 64u : 0u;
     } else {
-        fix_prologue((A_->sc), (A_->p), (A_->q), cnt, cur, sl.q, bounce);       // before the queue's length is read: the prologue may append to it
+        fix_prologue<C56>((A_->sc), (A_->p), (A_->q), cnt, cur, sl.q, bounce);       // before the queue's length is read: the prologue may append to it
         n = __hip_atomic_load(&cnt->n_tr[bounce % 3][0][sl.q * CNT_PAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     uint32_t pf_pm = 0;                                        // (PFP: the next row's packed word)
-    if (PFP && n > 0) pf_pm = prefetch_prim(tr, qbase, sl.first, n);
-    if (STAGE && sl.first < n) { stage_row(stage, tr, qbase, sl.first, n, bounce); staged_wait_stamped(rt, false); }      // (the first row's record: the only one whose round trip the wave sits out)
+    if (PFP && n > 0) pf_pm = prefetch_prim<C56>(tr, qbase, sl.first, n);
+    if (STAGE && sl.first < n) { stage_row<C56>(stage, tr, qbase, sl.first, n, bounce); staged_wait_stamped(rt, false); }      // (the first row's record: the only one whose round trip the wave sits out)
 #ifdef APT_ROWTOP_STATS
     rt.loop0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -696,37 +767,41 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         const uint32_t pos = base + threadIdx.x, idx = qbase + pos;                    // (unsorted renders: one queue for the scene)
         bool alive = pos < n;
         const uint32_t cu_pm = pf_pm; float4 cu_ra = make_float4(0.f, 0.f, 0.f, 0.f), cu_rb = cu_ra;
-        if (PFP) { const int rp = max(tr_prim(cu_pm), 0); cu_ra = (A_->sc).prim_shade[2 * rp]; cu_rb = (A_->sc).prim_shade[2 * rp + 1]; pf_pm = prefetch_prim(tr, qbase, base + sl.stride, n); }
+        if (PFP) { const int rp = max(tr_prim(cu_pm), 0); cu_ra = (A_->sc).prim_shade[2 * rp]; cu_rb = (A_->sc).prim_shade[2 * rp + 1]; pf_pm = prefetch_prim<C56>(tr, qbase, base + sl.stride, n); }
         Vertex vx; vertex_reset(vx); Rng rng; rng_init(rng, 0u, 0u, 0u, 0u);
         f3 Lc = splat3(0.f);                                   // the radiance the path has gathered so far (camera rays carry none: nothing is read at bounce 0)
         bool entry = alive; float ray_pdf = 1.f;
         // ---- the row's head: its opened vertex
-        if constexpr (CAM && LIVE) alive = camera_vertex_live<BM, SM, WINDOW>(A_, cnt, sl.q, qbase, pos, alive, cam_total, strips, vx, rng, s_draws, t_samples, t_extend, entry);
-        else if constexpr (CAM) alive = camera_vertex<BM, SM, TEX, WINDOW>(A_, cnt, sl.q, qbase, pos, alive, cam_total, strips, vx, rng, s_draws, t_samples, t_extend, entry);
+        if constexpr (CAM && LIVE) alive = camera_vertex_live<BM, SM, WINDOW, C56>(A_, cnt, sl.q, qbase, pos, alive, cam_total, strips, vx, rng, s_draws, t_samples, t_extend, entry);
+        else if constexpr (CAM) alive = camera_vertex<BM, SM, TEX, WINDOW, C56>(A_, cnt, sl.q, qbase, pos, alive, cam_total, strips, vx, rng, s_draws, t_samples, t_extend, entry);
         else if constexpr (STAGE) {
             float4 a, b_, c, d;                                // this lane's words of the row's record
-            staged_row_read(stage, a, b_, c, d, cu_ra, cu_rb);
-            if constexpr (LIVE) alive = open_record_live<BM, SM>(A_, vx, rng, a, b_, c, d, cu_ra, cu_rb, cur, idx, bounce, alive, s_draws, Lc);
+            staged_row_read<C56>(stage, a, b_, c, d, cu_ra, cu_rb);
+            if constexpr (LIVE) alive = open_record_live<BM, SM, C56>(A_, vx, rng, a, b_, c, d, cu_ra, cu_rb, cur, idx, bounce, alive, s_draws, Lc);
             else if (alive) {
-                if (bounce > 0) { Lc = mk3(d.x, d.y, d.z); if (SM & APT_SRC_AREA) ray_pdf = d.w; }
-                alive = open_record<BM, SM, TEX, true>(A_, vx, rng, a, b_, c, __float_as_uint(b_.w), cu_ra, cu_rb, cur, idx, ray_pdf, bounce);
+                if (bounce > 0) { Lc = Rec::Lc(c, d); if (SM & APT_SRC_AREA) ray_pdf = d.w; }
+                alive = open_record<BM, SM, TEX, true, C56>(A_, vx, rng, a, b_, c, Rec::pm(a, b_), cu_ra, cu_rb, cur, idx, ray_pdf, bounce);
             }
         } else {                                               // the direct loads: plane D has a reader behind the first bounce only
-            if (alive && bounce > 0) { const float4 d = ldq(tr.d, idx << 4); Lc = mk3(d.x, d.y, d.z); if (SM & APT_SRC_AREA) ray_pdf = d.w; }
+            if constexpr (!C56) if (alive && bounce > 0) { const float4 d = Rec::load_d(tr.d, idx); Lc = Rec::Lc(d, d); if (SM & APT_SRC_AREA) ray_pdf = d.w; }
             if (alive) {
                 const float4 a = ldq(tr.a, idx << 4), b_ = ldq(tr.b, idx << 4), c = ldq(tr.c, idx << 4);
+                if constexpr (C56) if (bounce > 0) Lc = Rec::Lc(c, Rec::load_d(tr.d, idx));      // (the 56-byte record's radiance lies in planes C and D)
 #ifdef APT_ROWTOP_STATS      // (direct loads: everything the row has requested - record, shading record - is waited for between two stamps; the staged form's wait is stamped where it stands)
                 staged_wait_stamped(rt, true);
 #endif
-                alive = open_record<BM, SM, TEX, PFP>(A_, vx, rng, a, b_, c, PFP ? cu_pm : __float_as_uint(b_.w), cu_ra, cu_rb, cur, idx, ray_pdf, bounce);
+                alive = open_record<BM, SM, TEX, PFP, C56>(A_, vx, rng, a, b_, c, PFP ? cu_pm : Rec::pm(a, b_), cu_ra, cu_rb, cur, idx, ray_pdf, bounce);
             }
         }
         tl.shade += wave_count(alive);
 #ifdef APT_NEAR_STATS      // diagnostic build (tools/gpu_near_probe.py): shaded vertices that sit within 2e-3 of the vertex before them - rays that re-hit the surface they left
-        t_near += wave_count(alive && bounce > 0 && vx.it.min_depth < 2e-3f);
+        if constexpr (!C56) t_near += wave_count(alive && bounce > 0 && vx.it.min_depth < 2e-3f);      // (56-byte record: the hit distance does not travel - counted where the record is appended, below)
 #endif
-        if constexpr (LIVE) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
-        else if (alive) vx.hit_point = vx.d * vx.it.min_depth + vx.o;
+        // the vertex's position (a 56-byte record carried it: unpack_record)
+        if constexpr (!C56 || CAM) {
+            if constexpr (LIVE) vx.hit_point = hit_point_of(vx.o, vx.d, vx.it.min_depth);
+            else if (alive) vx.hit_point = hit_point_of(vx.o, vx.d, vx.it.min_depth);
+        }
         APT_ARGS_PHASE();
         // ---- next-event estimation: the vertex's light sample waits in registers and is swept at the end of the row, when little else is live
         bool break_flag = false; DevSrc src_only;             // the scene's only light, read once through the scalar path
@@ -740,7 +815,7 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         // The next row's record starts on its way HERE, behind the last load that the row's shading waits for: loads come back in the order
         // they were issued, so the wait for any load issued behind the staged ones is a wait for them - the round trip this form takes out
         // of the row.  In front of them lie the continuation's sample and its sweep: time enough to land.
-        if constexpr (STAGE) if (base + sl.stride < n) stage_row(stage, tr, qbase, base + sl.stride, n, bounce);
+        if constexpr (STAGE) if (base + sl.stride < n) stage_row<C56>(stage, tr, qbase, base + sl.stride, n, bounce);
         APT_ARGS_PHASE();
         // ---- emission of the surface we are on, then the continuation, which meets the scene's records
         bool cont, is_spec = false; float new_pdf = 1.f; f3 new_d = mk3(0.f, 1.f, 0.f);
@@ -753,7 +828,10 @@ APT_D void shade_traced(args3_ptr A0, Counters* cnt, int cur_, int bounce_, cons
         // the next row's record has landed - it has had both sweeps - before this row's stores are issued: a wait at the next row's top
         // would be a wait for these stores to be acknowledged as well (one counter, in order)
         if constexpr (STAGE) staged_wait_stamped(rt, true);
-        append_record(A_, nxt, qbase, next_counter, ct, cont, vx, new_d, rng.draw, is_spec, Lc, new_pdf);
+#ifdef APT_NEAR_STATS
+        if constexpr (C56) t_near += wave_count(cont && ct.q == 0 && ct.t < 2e-3f);
+#endif
+        append_record<C56, C56 && CAM && !LIVE>(A_, nxt, qbase, next_counter, ct, cont, vx, new_d, rng.draw, is_spec, Lc, new_pdf);
         end_path(A_, !cont && entry, vx.id, Lc);
     }
     flush_uniform(t_traced, &cnt->stats[sl.q][ST_SHADOW_TRACED]); flush_uniform(t_lit, &cnt->stats[sl.q][ST_LIT]); flush_uniform(t_extend, &cnt->stats[sl.q][ST_EXTEND]);
@@ -952,6 +1030,14 @@ template <int BM, int SM>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(APT_TRACED_CAM_WAVES, APT_TRACED_CAM_WAVES))) k_shade_traced_lean_cam_live(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) {
     shade_traced<BM, SM, 0, true, false, true>(kernel_args3(), cnt, 0, 0, strips);
 }
+// ... and the five lean forms on the 56-byte record (shade_traced, C56; stages.hpp TrRecord): what a Lambertian / point-light render runs
+// unless APT_RECORD_COMPACT=0.  A renderer runs one record form in every launch of a batch (k_generate_trace56 feeds these).
+#define APT_LEAN56_KERNEL(NAME, WAVES) template <int BM, int SM> __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) NAME
+APT_LEAN56_KERNEL(k_shade_traced_lean56, APT_TRACED_WAVES)(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) { shade_traced<BM, SM, 0, false, false, false, true>(kernel_args3(), cnt, cur, bounce); }
+APT_LEAN56_KERNEL(k_shade_traced_lean56_staged, APT_TRACED_WAVES)(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) { shade_traced<BM, SM, 0, false, true, false, true>(kernel_args3(), cnt, cur, bounce); }
+APT_LEAN56_KERNEL(k_shade_traced_lean56_staged_live, APT_TRACED_WAVES)(DevScene sc, Params p, Queues q, Counters* cnt, int cur, int bounce) { shade_traced<BM, SM, 0, false, true, true, true>(kernel_args3(), cnt, cur, bounce); }
+APT_LEAN56_KERNEL(k_shade_traced_lean56_cam, APT_TRACED_CAM_WAVES)(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) { shade_traced<BM, SM, 0, true, false, false, true>(kernel_args3(), cnt, 0, 0, strips); }
+APT_LEAN56_KERNEL(k_shade_traced_lean56_cam_live, APT_TRACED_CAM_WAVES)(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) { shade_traced<BM, SM, 0, true, false, true, true>(kernel_args3(), cnt, 0, 0, strips); }
 #endif
 
 // ---- class kernels in groups: ONE launch shades several material classes.

@@ -357,6 +357,11 @@ typedef float rec4 __attribute__((ext_vector_type(4)));
 APT_D void stage_plane(const float4* plane, uint32_t off, rec4* dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(plane) + off), (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
 }
+// ... and one 4-byte word per lane -> dst[lane] (global_load_lds_dword; the direct-to-LDS loads come 4, 12 and 16 bytes wide: an 8-byte
+// entry is staged as two word planes)
+APT_D void stage_word(const float* plane, uint32_t off, float* dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(plane) + off), (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
+}
 // every staged load of this wave has landed in LDS
 APT_D void staged_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // LDS reads by statements of their own, complete when the statement ends (from there on the buffer may be staged into again).  In front
@@ -368,6 +373,18 @@ APT_D uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __at
 APT_D void staged_read(const rec4* rec, rec4& a, rec4& b, rec4& c, rec4& d) {
     asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
                  : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(lds_addr(rec)) : "memory");
+}
+// ... of the 56-byte record (TrRecord<true>).  Its area is laid out by THREAD, plane after plane for the whole workgroup - planes A to C at
+// area + 16 * BLOCK * k + 16 * thread, plane D's two words, staged as word planes, at area + 48 * BLOCK + 4 * BLOCK * k + 4 * thread - so
+// that both lane addresses, 16- and 4-byte strided, come from the thread index (live in any case) by one instruction each, made here: a
+// second address held in a register across the row loop is one register more than the seven-wave budget has (an 8-byte scratch slot).
+// A wave's 64 entries of a plane are still 1 KiB (256 bytes) in a row, what one direct-to-LDS load writes.
+APT_D void staged_read56(const rec4* area, rec4& a, rec4& b, rec4& c, float& d0, float& d1) {
+    uint32_t at16, at4;
+    asm volatile("v_lshl_add_u32 %5, %7, 4, %8\n\tv_lshl_add_u32 %6, %7, 2, %8\n\t"
+                 "ds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:%9\n\tds_read_b128 %2, %5 offset:%10\n\tds_read_b32 %3, %6 offset:%11\n\tds_read_b32 %4, %6 offset:%12\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d0), "=&v"(d1), "=&v"(at16), "=&v"(at4)
+                 : "v"(threadIdx.x), "s"(lds_addr(area)), "i"(16 * BLOCK), "i"(32 * BLOCK), "i"(48 * BLOCK), "i"(52 * BLOCK) : "memory");
 }
 // two consecutive 16-byte words
 APT_D void staged_read2(const rec4* p, rec4& a, rec4& b) {
@@ -381,6 +398,51 @@ APT_D void lds_add_unordered(uint32_t* word, uint32_t v) {
 }
 APT_D f3 ld3q(const float* base, uint32_t stride, uint32_t off) { return mk3(ldq(base, off), ldq(base + stride, off), ldq(base + 2 * stride, off)); }
 APT_D void st3q(float* base, uint32_t stride, uint32_t off, f3 v) { stq(base, off, v.x); stq(base + stride, off, v.y); stq(base + 2 * stride, off, v.z); }
+// ---- the path record of the rays traced in place (Queues::tr), in its two forms; every site that writes or reads one goes through here.
+//   C56 = false, 64 bytes: A = (ray origin, hit distance)  B = (direction, pm)  C = (throughput, id)  D = (radiance so far, pdf of the ray)
+//   C56 = true,  56 bytes: A = (hit point, pm)             B = (direction, id)  C = (throughput, Lc.x)  D = (Lc.y, Lc.z), 8 bytes per entry
+// The 56-byte form is the lean kernels' (Lambertian surfaces, no area light): the ray's pdf has no reader there, and origin and distance
+// have one - the hit point - which the WRITER holds when it stores the record (hit_point_of below: the reader's own expression on the
+// same operands).  A ray left to the reference-order code (staged: top of the sub-queue's region) has no hit yet and keeps its ORIGIN
+// in the three words; fix_prologue turns it into the hit point when it resolves the ray.
+// A camera ray's 56-byte record has no plane D: the ray carries no radiance, Lc.x in plane C is its zero, and nothing reads plane D at
+// bounce 0 (the prologue included).
+// Planes are addressed by slot; Queues::tr keeps its type, plane D's pointer is reinterpreted.
+APT_D f3 hit_point_of(f3 o, f3 d, float t) { return d * t + o; }
+template <bool C56> struct TrRecord {
+    static constexpr uint32_t D_BYTES = C56 ? 8u : 16u;
+    APT_D static float4 load_d(const float4* d, uint32_t slot) {
+        if constexpr (C56) { const float2 v = ldq(reinterpret_cast<const float2*>(d), slot << 3); return make_float4(v.x, v.y, 0.f, 0.f); }
+        else return ldq(d, slot << 4);
+    }
+    // byte offset of the packed word pm inside its plane's entry, and which plane that is
+    APT_D static const uint32_t* pm_plane(const float4* a, const float4* b) { return reinterpret_cast<const uint32_t*>(C56 ? a : b); }
+    APT_D static uint32_t pm(float4 a, float4 b) { return __float_as_uint(C56 ? a.w : b.w); }
+    APT_D static uint32_t id(float4 b, float4 c) { return __float_as_uint(C56 ? b.w : c.w); }
+    APT_D static f3 Lc(float4 c, float4 d) { if constexpr (C56) return mk3(c.w, d.x, d.y); else return mk3(d.x, d.y, d.z); }
+    // A writer stores plane by plane, A to D, each with the fields either form keeps in it (p: the ray's origin - 64 bytes, staged rays - or
+    // the hit point); a plane's words are made where it is stored, as the sites did before there was a second form - pm: a callable, so
+    // that the packed word too is made in front of the plane that holds it.
+    template <typename PM> APT_D static void put_a(float4* plane, uint32_t slot, f3 p, float t, PM&& pm) {
+        const uint32_t so = slot << 4;
+        if constexpr (C56) stq(plane, so, make_float4(p.x, p.y, p.z, __uint_as_float(pm()))); else stq(plane, so, make_float4(p.x, p.y, p.z, t));
+    }
+    template <typename PM> APT_D static void put_b(float4* plane, uint32_t slot, f3 d, PM&& pm, uint32_t id) {
+        if constexpr (C56) stq(plane, slot << 4, make_float4(d.x, d.y, d.z, __uint_as_float(id))); else stq(plane, slot << 4, make_float4(d.x, d.y, d.z, __uint_as_float(pm())));
+    }
+    APT_D static void put_c(float4* plane, uint32_t slot, f3 thr, uint32_t id, f3 Lc) { stq(plane, slot << 4, make_float4(thr.x, thr.y, thr.z, C56 ? Lc.x : __uint_as_float(id))); }
+    // ... and planes C and D as they were loaded (load_d's words), for the site that moves a record
+    APT_D static void copy_a(float4* plane, uint32_t slot, float4 a) { stq(plane, slot << 4, a); }
+    APT_D static void copy_c(float4* plane, uint32_t slot, float4 c) { stq(plane, slot << 4, c); }
+    APT_D static void copy_d(float4* plane, uint32_t slot, float4 d) {
+        if constexpr (C56) { float2 d_; d_.x = d.x; d_.y = d.y; stq(reinterpret_cast<float2*>(plane), slot << 3, d_); }
+        else stq(plane, slot << 4, d);
+    }
+    APT_D static void put_d(float4* plane, uint32_t slot, f3 Lc, float pdf) {
+        if constexpr (C56) { float2 d_; d_.x = Lc.y; d_.y = Lc.z; stq(reinterpret_cast<float2*>(plane), slot << 3, d_); }
+        else stq(plane, slot << 4, make_float4(Lc.x, Lc.y, Lc.z, pdf));
+    }
+};
 // wave-uniform tally: how many lanes of the wave have `flag` set (lives in an SGPR)
 APT_D uint32_t wave_count(bool flag) { return (uint32_t)__popcll(__ballot(flag)); }
 APT_D void flush_uniform(uint32_t v, unsigned long long* counter) { if (lane_id() == 0 && v) atomicAdd(counter, (unsigned long long)v); }
@@ -516,7 +578,7 @@ APT_D unsigned long long light_strip_mask(const Params& p, const unsigned long l
 // strips (TRACE): per block of 64 consecutive local pixels, the record pairs a camera ray of the block can hit (flat_build.cpp
 // camera_strips).  A wave's 64 entries are consecutive local pixels modulo npix: they lie in the block of the first, the
 // block of the last before the film's end and - where the wave wraps into the next sample - block 0; the wave sweeps the union.
-template <bool TRACE, bool ADAPTIVE = false>
+template <bool TRACE, bool ADAPTIVE = false, bool C56 = false>
 APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, Counters* cnt, const uint8_t* active = nullptr, const unsigned long long* strips = nullptr) {
     const uint32_t total = (uint32_t)p.npix * (uint32_t)p.spp_batch;
     const uint32_t n_waves = (total + 63u) / 64u;
@@ -565,11 +627,15 @@ APT_D void generate_body(const DevScene* sc, const Params& p, const Queues& q, C
             pos = tr_append_pos(app, ocls);
             if (alive) t_samples++;
             if (ocls >= 0) {
-                const uint32_t slot = (q.tr_stage_top && ocls == q.tr_ncls) ? (uint32_t)sq * p.subcap + p.subcap - 1u - pos : (uint32_t)ocls * p.cap + (uint32_t)sq * p.subcap + pos, so = slot << 4;
-                stq(q.tr[0][0], so, make_float4(cam_o.x, cam_o.y, cam_o.z, hr.t));
-                stq(q.tr[0][1], so, make_float4(dir.x, dir.y, dir.z, __uint_as_float(tr_pack(hr.prim, draws, false))));
-                stq(q.tr[0][2], so, make_float4(1.f, 1.f, 1.f, __uint_as_float(((idx / (uint32_t)p.npix) << p.pix_bits) | (idx % (uint32_t)p.npix))));
-                stq(q.tr[0][3], so, make_float4(0.f, 0.f, 0.f, 1.f));
+                const uint32_t slot = (q.tr_stage_top && ocls == q.tr_ncls) ? (uint32_t)sq * p.subcap + p.subcap - 1u - pos : (uint32_t)ocls * p.cap + (uint32_t)sq * p.subcap + pos;
+                // (the 56-byte record carries the hit point; a ray left to the reference-order code keeps its origin there)
+                const f3 rec_p = (C56 && ocls != q.tr_ncls) ? hit_point_of(cam_o, dir, hr.t) : cam_o;
+                typedef TrRecord<C56> Rec;
+                auto pm = [&] { return tr_pack(hr.prim, draws, false); };
+                Rec::put_a(q.tr[0][0], slot, rec_p, hr.t, pm);
+                Rec::put_b(q.tr[0][1], slot, dir, pm, ((idx / (uint32_t)p.npix) << p.pix_bits) | (idx % (uint32_t)p.npix));
+                Rec::put_c(q.tr[0][2], slot, splat3(1.f), ((idx / (uint32_t)p.npix) << p.pix_bits) | (idx % (uint32_t)p.npix), splat3(0.f));
+                if constexpr (!C56) Rec::put_d(q.tr[0][3], slot, splat3(0.f), 1.f);      // (a camera ray carries no radiance: the 56-byte record's plane D has no reader at bounce 0, TrRecord)
                 if (sc->has_vn || sc->tex_i != nullptr) { float2 uv_; uv_.x = hr.u; uv_.y = hr.v; stq(q.tr_uv[0], slot << 3, uv_); }
             }
         }
@@ -596,6 +662,9 @@ __global__ void __launch_bounds__(BLOCK) k_generate_ad(Params p, Queues q, Count
 #if APT_FAST
 __global__ void __launch_bounds__(BLOCK) k_generate_trace(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) { generate_body<true>(&sc, p, q, cnt, nullptr, strips); }
 __global__ void __launch_bounds__(BLOCK) k_generate_trace_ad(DevScene sc, Params p, Queues q, Counters* cnt, const uint8_t* active, const unsigned long long* strips) { generate_body<true, true>(&sc, p, q, cnt, active, strips); }
+// ... writing the 56-byte record (TrRecord<true>): what feeds the lean shade kernels' 56-byte forms where no camera-fed launch does
+__global__ void __launch_bounds__(BLOCK) k_generate_trace56(DevScene sc, Params p, Queues q, Counters* cnt, const unsigned long long* strips) { generate_body<true, false, true>(&sc, p, q, cnt, nullptr, strips); }
+__global__ void __launch_bounds__(BLOCK) k_generate_trace56_ad(DevScene sc, Params p, Queues q, Counters* cnt, const uint8_t* active, const unsigned long long* strips) { generate_body<true, true, true>(&sc, p, q, cnt, active, strips); }
 #endif
 
 // ------------------------------------------------------------------- extend

@@ -732,6 +732,13 @@ class Renderer:
         _lib.check(self.lib.apt_renderer_live_rows(self.handle, C.byref(f)), "apt_renderer_live_rows", self.lib)
         return bool(f.value)
 
+    def record_compact(self) -> bool:
+        """apt_renderer_record_compact: the traced kernels carry the 56-byte path record - hit point instead of ray origin and hit distance,
+        no pdf (rays traced in place, Lambertian surfaces under point lights; APT_RECORD_COMPACT=0 at creation keeps the 64-byte record)."""
+        f = C.c_int32(0)
+        _lib.check(self.lib.apt_renderer_record_compact(self.handle, C.byref(f)), "apt_renderer_record_compact", self.lib)
+        return bool(f.value)
+
     # ------------------------------------------------------------ checkpoint
     def get_check_point(self) -> dict:
         """Same keys as the reference's pickle (path_tracer.py:181-193)."""

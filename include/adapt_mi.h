@@ -367,6 +367,10 @@ int apt_renderer_record_staged(const apt_renderer*, int32_t* staged);
  * valid record, a dead lane's effects are masked (the Lambertian / point-light kernels; env APT_LIVE_ROWS=0, read at apt_renderer_create,
  * selects the kernels that give dead lanes default values), else 0. */
 int apt_renderer_live_rows(const apt_renderer*, int32_t* live);
+/* Rays traced in place: *compact = 1 when every launch of a batch reads and writes the 56-byte path record - the hit point instead of the
+ * ray's origin and hit distance, no pdf of the ray (the Lambertian / point-light kernels, which read neither; env APT_RECORD_COMPACT=0,
+ * read at apt_renderer_create, keeps the 64-byte record), else 0. */
+int apt_renderer_record_compact(const apt_renderer*, int32_t* compact);
 
 /* Shader clock (MHz) with every CU busy: cycle counter against the 100 MHz wall clock over a full-grid FMA chain (~1 ms).
  * bench.py prices the VALU roofline of the trace kernels with it.  (No reference counterpart.) */
