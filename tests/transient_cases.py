@@ -65,3 +65,15 @@ def _rounding_up_window():
     t = np.nextafter(top, np.float32(-np.inf))
     k = int(np.flatnonzero((t - lo) / steps >= np.float32(n))[0])
     return lo, steps[k], n, t[k]
+
+
+ALL_TIME = {"sample_count": 1, "min_time": -1.0, "interval": 1e6}      # one bin that holds every path
+
+
+def bins_sum_to_framebuffer(bins, framebuffer):
+    """The rule tests/test_gpu_transient.py::test_bins_sum_to_steady_image holds a transient render's own framebuffer to: it is the sum
+    of the bins, bounce by bounce, so with a window that holds every path the two agree to 1e-5 relative on every finite pixel.
+    bins: the cube summed over time, times the sample count; framebuffer: the renderer's accumulation (both float64, (w, h, 3))."""
+    fin = np.isfinite(framebuffer).all(axis=2)
+    bad = np.abs(framebuffer - bins)[fin] > 1e-5 * np.abs(bins)[fin] + 1e-12
+    assert not bad.any(), (int(bad.sum()), float(np.abs(framebuffer - bins)[fin].max()))
