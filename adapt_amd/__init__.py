@@ -9,7 +9,7 @@ The render path is hand-written HIP reached through the C-ABI in include/adapt_m
 """
 from .parsers.xml_parser import scene_parsing  # noqa: F401
 
-__all__ = ["scene_parsing", "Renderer", "VolumeRenderer", "load_renderer"]
+__all__ = ["scene_parsing", "Renderer", "VolumeRenderer", "AORenderer", "SSAORenderer", "load_renderer"]
 __version__ = "0.1.0"
 
 
@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "VolumeRenderer":
         from .renderer import VolumeRenderer
         return VolumeRenderer
+    if name in ("AORenderer", "SSAORenderer"):
+        from .renderer import AORenderer
+        return AORenderer
     raise AttributeError(name)
 
 

@@ -23,6 +23,7 @@
 #include "shade_stage.hpp"
 #include "unit_kernels.hpp"
 #include "aov.hpp"
+#include "ao.hpp"
 #include "volumetric.hpp"
 
 #define APT_EXPORT extern "C" __attribute__((visibility("default")))
@@ -229,8 +230,9 @@ struct Lane {
 //   PIPE_SORTED      extend into per-class queues, the class kernels in groups, shadow  (render_surface)
 //   PIPE_TRACED      the shade kernel traces its rays itself: one launch per bounce     (render_surface; product build, shade_stage.hpp "rays traced in place")
 //   PIPE_VOLUMETRIC  extend, k_vevent, one kernel per event queue, transmittance walk   (render_volumetric)
+//   PIPE_AO          ambient occlusion: one trace-and-occlude kernel and one ordered sum per batch, no shade, shadow or class launch (render_ao; ao.hpp)
 // A split render (apt_renderer::split_mode) and an adaptive one (::adaptive) are modifiers on top of it.
-enum Pipeline { PIPE_STAGED, PIPE_SORTED, PIPE_TRACED, PIPE_VOLUMETRIC };
+enum Pipeline { PIPE_STAGED, PIPE_SORTED, PIPE_TRACED, PIPE_VOLUMETRIC, PIPE_AO };
 
 // A split render keeps a surface render's contributions apart: by arrival time, by segment count or by emitter.  One
 // mechanism - the TR shade twins, the per-path records (stages.hpp TransQ), a binning kernel per settled bounce, one render lane - and per
@@ -324,6 +326,9 @@ struct apt_renderer {
     DevBuf aov_rec, aov_sum;              // the AOV pass's per-slot records (aov_batch samples in flight) and per-pixel sums
     int aov_batch = 0;
     DevBuf dn_rgb, dn_planes;             // the denoiser's packed colour in / out (3 floats per pixel) and its four float4 planes (colour x 2, guides x 2)
+    // ambient occlusion (apt_render_cfg.ao; ao.hpp): the depth map is made once, by apt_renderer_create
+    DevBuf ao_rec, ao_depth, ao_hits, ao_last;      // per-slot records (spp_batch samples in flight), the depth map, the depth pass's hit counts, per pixel whether the last sample hit
+    AoQ aoq{};
 };
 
 static int count_device(int* n) {
@@ -765,6 +770,8 @@ static int owned_columns(const apt_render_cfg& c) {
     return n;
 }
 
+constexpr int APT_AO_MAX_BATCH = 16;                   // ambient occlusion: samples in flight per batch ...
+constexpr size_t APT_AO_MAX_SLOTS = (size_t)8 << 20;   // ... fewer where the film is larger than 512 x 1024
 // Film, render lanes, sub-queues and batch size; the film / camera part of Params and the pixel -> RNG key table.
 static int plan_film(apt_renderer* r) {
     const apt_scene* sc = r->scene;
@@ -775,11 +782,13 @@ static int plan_film(apt_renderer* r) {
     if (r->npix <= 0) { return fail(APT_E_INVALID, "apt_renderer_create: this rank owns no pixels"); }
     r->n_lanes = 3;   // measured on C2: 1 lane 1 827, 2 lanes 2 196, 3 lanes 2 268, 4 lanes 2 178 Msamples/s (round 2, 64 spp per lane-batch); round 5, 32 Mi paths per lane-batch: C2 4 559 / 4 590 / 4 287 with 2 / 3 / 4, C5 1 844 / 2 028 / 2 129 with 1 / 2 / 3; volumetric scenes with null surfaces ran four lanes in rounds 3-4 (the fourth hid the host read-backs of their tails): at this batch size V1 1 374 with three, 1 299 with four
     if (const char* nl = getenv("APT_LANES")) r->n_lanes = std::min(4, std::max(1, atoi(nl)));
+    if (c.ao) r->n_lanes = 1;            // ambient occlusion: one kernel per batch on one stream
     if (r->split()) r->n_lanes = 1;      // a split render's cells are shared by every batch and added to per bounce: one lane keeps the adds in order
     const size_t nq = (size_t)r->nq;
     // queue capacity of a batch of b: whole waves, dealt over the sub-queues (generate: wave w -> sub-queue w % nq)
     auto subcap_of = [&](int b) { const size_t n_waves = ((size_t)r->npix * (size_t)b + 63) / 64; return ((n_waves + nq - 1) / nq) * 64; };
     int B = c.spp_per_batch;
+    if (c.ao && B <= 0) B = std::max(1, std::min(APT_AO_MAX_BATCH, (int)(APT_AO_MAX_SLOTS / (size_t)r->npix)));      // a slot is 8 bytes and a gather-bound kernel: a few samples in flight fill the device
     if (B <= 0) {
         // ~32 Mi paths per lane-batch (5-17 GB of queues each, of 288 GB) whatever the tile size: an 8-GPU rank owns 1/8 of the pixels and takes
         // 8x the samples per batch.  Measured 16 Mi -> 32 Mi on one box: C2 4 547 -> 4 685, C3 1 150 -> 1 177, C4 1 840 -> 1 922, C5 1 971 ->
@@ -887,6 +896,7 @@ static int pick_shading(apt_renderer* r) {
     }
     const bool can_trace = r->trace_mode == TRACE_FLAT && S == 1 && !r->split() && r->shade->traced.queue[0][0] != nullptr;
     r->pipeline = c.volumetric ? PIPE_VOLUMETRIC : (sorted ? PIPE_SORTED : ((can_trace && want_traced) ? PIPE_TRACED : PIPE_STAGED));
+    if (c.ao) r->pipeline = PIPE_AO;
     p.traced = (r->pipeline == PIPE_TRACED) ? 1 : 0;
     pick_traced_kernels(r);
     // flat sweep with several light samples per vertex: the samples are queued by vertex and the shadow kernel adds a vertex's samples with
@@ -928,6 +938,7 @@ static int pick_shading(apt_renderer* r) {
     } else {
         r->shade_name = r->shade->name;
         if (r->pipeline == PIPE_TRACED) r->shade_name += " [rays traced in place]";
+        if (r->pipeline == PIPE_AO) r->shade_name = "ambient occlusion: screen-space, against the camera's depth map";
     }
     r->shade_name += kSplit[r->split_mode].tag;
     if (r->adaptive) r->shade_name += " [adaptive]";
@@ -1210,7 +1221,7 @@ static int plan_lds_and_grids(apt_renderer* r) {
     }
     // streaming stages: persistent grid in 256-thread workgroups per CU.  (rays traced in place: the kernel holds FIVE workgroups per CU since round 5 - one lane 3 440 -> 3 630 Msamples/s on C2 with 5 per CU, three lanes level)  streaming stages, persistent grid in 256-thread workgroups per CU.  Measured (tools/grid_sweep.sh, 2 / 3 / 4 / 5 / 8 per CU): C2 3 385 / 3 350 / 3 378 / 3 312 / 3 279 Msamples/s (a shade kernel holds 4 workgroups per CU; a second round of workgroups only adds a tail), C1 / C3 / C4 / C5 within 1 %, V1 823 / 838 / 842 / 840 / 858
     // (round 6: class-sorted renders too - their lean group holds five workgroups per CU now: C5 2 243 -> 2 261, C3 one lane 1 035 -> 1 103, three lanes level)
-    static const int kSmallPerCu[4] = {4, 5, 5, 8};           // [Pipeline]
+    static const int kSmallPerCu[5] = {4, 5, 5, 8, 5};        // [Pipeline]
     r->grid_small = cus * kSmallPerCu[r->pipeline];
     if (const char* g = getenv("APT_GRID_SMALL")) r->grid_small = cus * std::max(1, atoi(g));       // tuning knobs: workgroups per CU
     if (const char* g = getenv("APT_GRID_TRACE")) r->grid_trace = cus * std::max(1, atoi(g));
@@ -1296,6 +1307,20 @@ static int check_split(const apt_scene* sc, const apt_render_cfg& c, SplitMode* 
     }
     return APT_OK;
 }
+// Ambient occlusion (ao = 1): its settings' ranges and what it does not combine with.
+static int check_ao(const apt_render_cfg& c, SplitMode split_mode) {
+    if (c.ao != 0 && c.ao != 1) return fail(APT_E_INVALID, "apt_renderer_create: ao must be 0 (off) or 1");
+    if (!c.ao) return APT_OK;
+    if (c.ao_smp_hemisphere <= 0 || c.ao_depth_samples < 0 || !(c.ao_sample_extent > 0.f) || !std::isfinite(c.ao_sample_extent))
+        return fail(APT_E_INVALID, "apt_renderer_create: ambient occlusion needs ao_smp_hemisphere > 0, ao_depth_samples >= 0 and a positive, finite ao_sample_extent");
+    if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: ambient occlusion is a surface-renderer mode (volumetric = 0)");
+    if (split_mode != SPLIT_NONE)
+        return fail(APT_E_INVALID, std::string("apt_renderer_create: ambient occlusion and ") + kSplit[split_mode].subject + " do not combine (" + kSplit[split_mode].field + " must be 0 when ao = 1)");
+    if (c.adaptive_threshold > 0.f) return fail(APT_E_INVALID, "apt_renderer_create: ambient occlusion and adaptive sampling do not combine (adaptive_threshold must be 0 when ao = 1)");
+    if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: ambient occlusion runs on one rank (world_size = 1): a sample's depth-map lookups cross the column shards");
+    return APT_OK;
+}
+static int make_ao(apt_renderer* r);
 APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cfg, apt_renderer** out) {
     if (!sc || !cfg || !out) return fail(APT_E_INVALID, "apt_renderer_create: null argument");
     apt_render_cfg c = *cfg;
@@ -1316,6 +1341,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
         if (c.adaptive_min_spp <= 0 || c.adaptive_step <= 0)
             return fail(APT_E_INVALID, "apt_renderer_create: adaptive sampling needs adaptive_min_spp > 0 and adaptive_step > 0");
     }
+    if (int rc = check_ao(c, split_mode)) return rc;
     HIP_TRY(hipSetDevice(c.device));
     apt_renderer* r = new apt_renderer();
     struct Owner { apt_renderer* r; ~Owner() { if (r) apt_renderer_destroy(r); } } owner{r};     // every early return below releases streams, events and queue pools
@@ -1330,6 +1356,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     if (int rc = make_adaptive(r)) return rc;
     if (int rc = plan_lds_and_grids(r)) return rc;
     if (int rc = make_overflow_stacks(r)) return rc;
+    if (int rc = make_ao(r)) return rc;
     for (Lane& ln : r->lanes) HIP_TRY(hipStreamSynchronize(ln.stream));
     owner.r = nullptr;
     *out = r;
@@ -1617,7 +1644,67 @@ static int render_surface(apt_renderer* r, int32_t n_spp) {
 }
 
 // n_spp samples over every pixel that takes them, by the renderer's pipeline
-static int render_steady(apt_renderer* r, int32_t n_spp) { return r->pipeline == PIPE_VOLUMETRIC ? render_volumetric(r, n_spp) : render_surface(r, n_spp); }
+// Ambient occlusion (SSAORenderer.render x n_spp; ao.hpp): per batch one kernel that traces the camera rays and runs their hemisphere loops,
+// and the ordered sum into channel 0 - the batch loop of apt_render_aov on the renderer's own stream.
+typedef void (*ao_fn)(DevScene, Params, AoQ, LdsPlan);
+static const ao_fn kAoTrace[4] = {k_ao_trace<TRACE_BVH>, k_ao_trace<TRACE_SWEEP>, k_ao_trace<TRACE_TILE>, /* TRACE_FLAT */ APT_FLAT_FN(k_ao_trace_flat)};
+static const ao_fn kAoDepth[4] = {k_ao_depth<TRACE_BVH>, k_ao_depth<TRACE_SWEEP>, k_ao_depth<TRACE_TILE>, /* TRACE_FLAT */ APT_FLAT_FN(k_ao_depth_flat)};
+static int render_ao(apt_renderer* r, int32_t n_spp) {
+    Lane& ln = r->lanes[0];
+    for (int done = 0; done < n_spp;) {
+        const int B = std::min(r->spp_batch, n_spp - done);
+        Params p = r->par; p.cnt_base = r->cnt; p.spp_batch = B;
+        const size_t total = (size_t)r->npix * (size_t)B;
+        { LaunchTimer t(r, APT_K_EXTEND, ln.stream); hipLaunchKernelGGL(kAoTrace[r->trace_mode], dim3(grid_for(total, r->grid_trace, 1, r->trace_items)), dim3(r->trace_nt), r->lds_bytes, ln.stream, r->scene->dev, p, r->aoq, ln.plan); }
+        { LaunchTimer t(r, APT_K_FINALIZE, ln.stream); hipLaunchKernelGGL(k_ao_sum, dim3(grid_for((size_t)r->npix, r->grid_small, 1)), dim3(BLOCK), 0, ln.stream, p, r->aoq, r->accum.as<float>()); }
+        HIP_TRY(hipGetLastError());
+        r->cnt += B; done += B;
+    }
+    return APT_OK;
+}
+// The depth map (SSAORenderer.get_depth_map, run by upstream's constructor): depth_samples camera rays per pixel at sample counter 0, in
+// batches of the render's size; the running sums live in the map itself until the last batch divides them.
+static int make_ao(apt_renderer* r) {
+    if (!r->cfg.ao) return APT_OK;
+    const apt_render_cfg& c = r->cfg;
+    const size_t np = (size_t)r->npix;
+    hipError_t e;
+    if ((e = r->ao_rec.alloc(np * (size_t)r->spp_batch * 8)) != hipSuccess || (e = r->ao_depth.alloc(np * 4)) != hipSuccess ||
+        (e = r->ao_hits.alloc(np * 4)) != hipSuccess || (e = r->ao_last.alloc(np * 4)) != hipSuccess)
+        return fail(APT_E_NOMEM, std::string("ambient occlusion buffers: ") + hipGetErrorString(e));
+    AoQ& a = r->aoq;
+    a.rec = r->ao_rec.as<float2>(); a.t = r->ao_rec.as<float>(); a.depth = r->ao_depth.as<float>(); a.hits = r->ao_hits.as<int32_t>(); a.last_hit = r->ao_last.as<int32_t>();
+    a.smp = c.ao_smp_hemisphere; a.extent = c.ao_sample_extent; a.k_base = 0;
+    // inv_cam_r = cam_r.inverse(): adjugate x (1 / det), and cam_normal = (cam_r @ (0, 0, 1)).normalized(), in float32 and Taichi's operation order (ssao.py:39-40)
+    const float* m = c.cam_r;
+    auto E = [&](int x, int y) { return m[3 * (x % 3) + (y % 3)]; };
+    const float det = (m[0] * (m[4] * m[8] - m[7] * m[5]) - m[3] * (m[1] * m[8] - m[7] * m[2])) + m[6] * (m[1] * m[5] - m[4] * m[2]);
+    const float inv_det = 1.0f / det;
+    for (int row = 0; row < 3; row++) for (int col = 0; col < 3; col++) a.inv_cam_r[3 * col + row] = inv_det * (E(row + 1, col + 1) * E(row + 2, col + 2) - E(row + 2, col + 1) * E(row + 1, col + 2));
+    const float nx = m[2], ny = m[5], nz = m[8];      // (0 * a + 0 * b + 1 * c: the products with 0 and the sums with them change nothing)
+    const float inv_len = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
+    a.cam_normal[0] = inv_len * nx; a.cam_normal[1] = inv_len * ny; a.cam_normal[2] = inv_len * nz;
+    a.x0 = c.do_crop ? std::max(0, c.start_x) : 0; a.x1 = c.do_crop ? std::min(c.width, c.end_x) : c.width;      // (rasterize_pinhole tests start / end whether or not the render is cropped: uncropped they are the film)
+    a.y0 = c.do_crop ? std::max(0, c.start_y) : 0; a.y1 = c.do_crop ? std::min(c.height, c.end_y) : c.height;
+    if (r->lds_bytes > 64 * 1024) {
+        HIP_TRY(hipFuncSetAttribute((const void*)kAoTrace[r->trace_mode], hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)kAoDepth[r->trace_mode], hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
+    }
+    hipStream_t st = r->stream();
+    HIP_TRY(hipMemsetAsync(r->ao_depth.p, 0, np * 4, st)); HIP_TRY(hipMemsetAsync(r->ao_hits.p, 0, np * 4, st)); HIP_TRY(hipMemsetAsync(r->ao_last.p, 0, np * 4, st));
+    for (int done = 0; done < c.ao_depth_samples;) {
+        const int B = std::min(r->spp_batch, c.ao_depth_samples - done);
+        Params p = r->par; p.cnt_base = 0; p.spp_batch = B;
+        AoQ q = r->aoq; q.k_base = done;
+        const size_t total = np * (size_t)B;
+        hipLaunchKernelGGL(kAoDepth[r->trace_mode], dim3(grid_for(total, r->grid_trace, 1, r->trace_items)), dim3(r->trace_nt), r->lds_bytes, st, r->scene->dev, p, q, r->lanes[0].plan);
+        hipLaunchKernelGGL(k_ao_depth_mean, dim3(grid_for(np, r->grid_small, 1)), dim3(BLOCK), 0, st, p, q, r->accum.as<float>(), (done + B == c.ao_depth_samples) ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        done += B;
+    }
+    return APT_OK;
+}
+static int render_steady(apt_renderer* r, int32_t n_spp) { return r->pipeline == PIPE_AO ? render_ao(r, n_spp) : (r->pipeline == PIPE_VOLUMETRIC ? render_volumetric(r, n_spp) : render_surface(r, n_spp)); }
 
 // the live count of the last decision, once its read-back has landed
 static int adaptive_settle(apt_renderer* r) {
@@ -1700,7 +1787,8 @@ APT_EXPORT int apt_read_pixels(apt_renderer* r, float* out) {
     HIP_TRY(hipSetDevice(r->cfg.device));
     const uint32_t n = (uint32_t)r->npix * 3u;
     const float inv = (float)(r->cnt > 0 ? r->cnt : 1);     // before the first sample the image is all zero
-    if (r->adaptive) hipLaunchKernelGGL(k_divide_ad, dim3((n + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), (const int32_t*)r->ad_n.p, r->scratch.as<float>(), n);
+    if (r->pipeline == PIPE_AO) hipLaunchKernelGGL(k_ao_pixels, dim3(((uint32_t)r->npix + 255) / 256), dim3(256), 0, r->stream(), (const float*)r->accum.as<float>(), (const int32_t*)r->aoq.last_hit, r->scratch.as<float>(), (uint32_t)r->npix, inv);
+    else if (r->adaptive) hipLaunchKernelGGL(k_divide_ad, dim3((n + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), (const int32_t*)r->ad_n.p, r->scratch.as<float>(), n);
     else hipLaunchKernelGGL(k_divide, dim3((n + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), r->scratch.as<float>(), n, inv);
     HIP_TRY(hipMemcpyAsync(out, r->scratch.p, (size_t)n * 4, hipMemcpyDeviceToHost, r->stream()));
     return resolve_events(r);
@@ -1716,6 +1804,10 @@ APT_EXPORT int apt_set_accum(apt_renderer* r, const float* in, int32_t cnt) {
     if (!r || !in || cnt < 0) return fail(APT_E_INVALID, "apt_set_accum: bad argument");
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemcpyAsync(r->accum.p, in, (size_t)r->npix * 12, hipMemcpyHostToDevice, r->stream()));
+    if (r->pipeline == PIPE_AO) {      // channel 2 is the depth map (upstream's checkpoint layout); `pixels` shows every pixel until the next sample says otherwise
+        hipLaunchKernelGGL(k_ao_take_depth, dim3(((uint32_t)r->npix + 255) / 256), dim3(256), 0, r->stream(), (const float*)r->accum.as<float>(), r->aoq.depth, (uint32_t)r->npix);
+        HIP_TRY(hipMemsetAsync(r->ao_last.p, 0xff, r->ao_last.bytes, r->stream()));
+    }
     r->cnt = cnt;
     return resolve_events(r);
 }
@@ -1751,7 +1843,8 @@ APT_EXPORT int apt_relight(apt_renderer* r, const float* gains, float* out) {
 APT_EXPORT int apt_reset(apt_renderer* r) {
     if (!r) return fail(APT_E_INVALID, "apt_reset: null handle");
     HIP_TRY(hipSetDevice(r->cfg.device));
-    HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
+    if (r->pipeline == PIPE_AO) hipLaunchKernelGGL(k_ao_reset, dim3(((uint32_t)r->npix + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), (const float*)r->aoq.depth, r->aoq.last_hit, (uint32_t)r->npix);      // (the depth map stays: channel 2 is put back from it)
+    else HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
     if (r->split()) HIP_TRY(hipMemsetAsync(r->split_cells.p, 0, r->split_cells.bytes, r->stream()));
     if (r->split_mode == SPLIT_LIGHTS) HIP_TRY(hipMemsetAsync(r->lg_aux.p, 0, 16, r->stream()));
     if (r->aov_sum.p) HIP_TRY(hipMemsetAsync(r->aov_sum.p, 0, r->aov_sum.bytes, r->stream()));
@@ -1856,10 +1949,20 @@ APT_EXPORT int apt_stream(apt_renderer* r, void** hip_stream) {
     return APT_OK;
 }
 
+// ---- ambient occlusion: the depth map apt_renderer_create made (or apt_set_accum handed in), [local col][y], n_cols * height floats
+APT_EXPORT int apt_read_ao_depth(apt_renderer* r, float* out) {
+    if (!r || !out) return fail(APT_E_INVALID, "apt_read_ao_depth: bad argument");
+    if (r->pipeline != PIPE_AO) return fail(APT_E_STATE, "apt_read_ao_depth: the renderer was created with ao = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipMemcpyAsync(out, r->ao_depth.p, (size_t)r->npix * 4, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
+
 // ---- feature buffers (AOV pass) and denoiser: aov.hpp, DESIGN.md 4.7
 // Both describe the camera ray's first SURFACE hit of one rank's whole film: the volumetric tracer's first event through null surfaces and
 // fog is another question, and a rank owns bands of the film, not the neighbourhoods a filter reads.
 static int aov_refuse(const apt_renderer* r, const char* who) {
+    if (r->cfg.ao) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser belong to the path tracer (ao = 0): an ambient-occlusion renderer keeps a depth map of its own (apt_read_ao_depth)");
     if (r->cfg.volumetric) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser belong to the surface renderer (volumetric = 0)");
     if (r->cfg.world_size > 1) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser run on one rank (world_size = 1)");
     return APT_OK;

@@ -65,7 +65,7 @@ from . import _lib
 from .scene_pack import FlatScene, RenderConfig, make_config, pack_scene
 from .tiles import TilePlan
 
-__all__ = ["Renderer", "VolumeRenderer", "DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error", "DENOISE_DEFAULTS"]
+__all__ = ["Renderer", "VolumeRenderer", "AORenderer", "SSAORenderer","DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error", "DENOISE_DEFAULTS"]
 
 ADAPTIVE_DEFAULTS = {"min_spp": 64, "step": 32}
 # apt_denoise_cfg's defaults (include/adapt_mi.h; DESIGN.md §4.7 says how they were chosen)
@@ -347,6 +347,7 @@ class Renderer:
         if self.adaptive:
             cfg.adaptive_threshold = self.adaptive["threshold"]
             cfg.adaptive_min_spp, cfg.adaptive_step = self.adaptive["min_spp"], self.adaptive["step"]
+        self._configure(cfg, prop)
         h = C.c_void_p()
         _lib.check(self.lib.apt_renderer_create(self.scene.handle, C.byref(cfg), C.byref(h)), "apt_renderer_create", self.lib)
         self.handle = h
@@ -357,6 +358,9 @@ class Renderer:
         self.cnt = _Counter(self)
         self.pixels = _FieldView(self, True)
         self.color = _FieldView(self, False)
+
+    def _configure(self, cfg, prop: dict):
+        """what a subclass adds to the apt_render_cfg before the handle is made (AORenderer: the ao block)"""
 
     # ------------------------------------------------------------ rendering
     def render(self, _t_start: int = 0, _t_end: int = 0, _s_start: int = 0, _s_end: int = 0, _a: int = 0, _b: int = 0,
@@ -807,6 +811,63 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+
+AO_DEFAULTS = {"smp_hemisphere": 32, "depth_samples": 64, "sample_extent": 0.1}      # ssao.py:36-38
+
+
+def ao_settings(prop: dict, **over) -> dict:
+    """The three settings of the ambient-occlusion renderer: a keyword that is not None, else the sensor's key, else upstream's default"""
+    unknown = set(over) - set(AO_DEFAULTS)
+    if unknown:
+        raise ValueError(f"ambient occlusion: unknown setting(s) {sorted(unknown)}")
+    return {k: type(d)(over[k] if over.get(k) is not None else prop.get(k, d)) for k, d in AO_DEFAULTS.items()}
+
+
+class AORenderer(Renderer):
+    """Drop-in for the reference's `SSAORenderer` (renderer/ssao.py; `--type ao`): same constructor and surface as `Renderer`, screen-space
+    ambient occlusion instead of path tracing.  Creation renders the depth map; every sample traces the camera ray,
+    draws `smp_hemisphere` directions about the hit's shading normal and holds the points `sample_extent` along them against the depth map.
+
+        rdr = AORenderer(emitters, array_info, objects, prop)      # reads the sensor's smp_hemisphere / depth_samples / sample_extent
+        rdr.render(0, 0, 0, 0, 0, 0)   # +1 spp (or render(n_spp=...))
+        rdr.pixels.to_numpy()          # (w, h, 3): channel 0 of color / cnt on all three channels where the last sample's ray hit, else 0
+        rdr.color.to_numpy()           # (w, h, 3): the sum of (1 - occlusion), zero, the depth map - upstream's checkpoint layout
+        rdr.depth_map()                # (w, h): the mean hit distance of each pixel's depth_samples camera rays (0: none hit)
+
+    The three settings can be overridden by keyword.  `reset()` leaves the render alone like upstream's; `clear()` zeroes channel 0 and the
+    counter and keeps the depth map.  One rank, no split mode, no adaptive sampling, no feature buffers: apt_renderer_create refuses the rest."""
+
+    def __init__(self, emitters: List, array_info: dict, objects: List, prop: dict, *, smp_hemisphere: Optional[int] = None,
+                 depth_samples: Optional[int] = None, sample_extent: Optional[float] = None, **kw):
+        if kw.get("aov_spp"):
+            raise ValueError("AORenderer: ambient occlusion keeps no feature buffers (aov_spp must be 0); depth_map() is its depth")
+        kw["aov_spp"] = 0
+        self.ao = ao_settings(prop, smp_hemisphere=smp_hemisphere, depth_samples=depth_samples, sample_extent=sample_extent)
+        self.smp_hemisphere, self.depth_samples, self.sample_extent = self.ao["smp_hemisphere"], self.ao["depth_samples"], self.ao["sample_extent"]
+        super().__init__(emitters, array_info, objects, prop, **kw)
+
+    def _configure(self, cfg, prop: dict):
+        cfg.ao = 1
+        cfg.ao_smp_hemisphere, cfg.ao_depth_samples, cfg.ao_sample_extent = self.smp_hemisphere, self.depth_samples, float(self.sample_extent)
+
+    def depth_map(self) -> np.ndarray:
+        """(w, h) float32, index [x, y]: the depth map (apt_read_ao_depth)"""
+        out = np.empty((self.n_cols, self.h), np.float32)
+        _lib.check(self.lib.apt_read_ao_depth(self.handle, _fp(out)), "apt_read_ao_depth", self.lib)
+        return out
+
+    def info(self) -> dict:
+        return {**super().info(), "pipeline": "ao", "ao": dict(self.ao)}
+
+    def summary(self) -> str:
+        self.synchronize()
+        msg = f"SSAO SPP = {self._cnt}. Rendering time: {time.time() - self._t0:.3f} s"
+        print(msg)
+        return msg
+
+
+SSAORenderer = AORenderer
 
 
 class VolumeRenderer(Renderer):

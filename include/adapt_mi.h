@@ -25,6 +25,7 @@
  *   apt_read_light_groups / apt_set_light_groups / apt_relight   (none; the `pt` render split by emitter - light groups - and relit on the device)
  *   apt_read_sample_counts / apt_read_moments / apt_set_adaptive_state   (none; adaptive sampling)
  *   apt_render_aov / apt_read_aov / apt_set_aov / apt_clear_aov   (none; per-pixel albedo, normal and depth of the camera rays' first hits)
+ *   apt_renderer_create with ao = 1, apt_read_ao_depth   renderer/ssao.py:31-130  SSAORenderer (`--type ao`): depth map at creation, screen-space occlusion per sample
  *   apt_denoise                    post_processing.py:15-32 (the firefly filter: stage 1) + an edge-avoiding a-trous filter guided by those buffers (stage 2; none upstream)
  *   apt_get_stats                  (none; the reference only has ti.profiler, render.py:154-160)
  *   apt_device_ptr                 (none; hands the tile framebuffer to RCCL for the multi-GPU gather)
@@ -112,6 +113,19 @@ typedef struct apt_render_cfg {
     int32_t volumetric;                           /* 0 = Renderer.render (renderer/vanilla_renderer.py:32-120); 1 = VolumeRenderer.render
                                                      (renderer/vpt.py:145-258): free-path sampling in homogeneous media, null surfaces,
                                                      transmittance-tracked light samples */
+    /* Ambient occlusion: ao = 1 makes the handle upstream's SSAORenderer (renderer/ssao.py, `--type ao`) instead of a path
+       tracer.  apt_renderer_create renders the depth map - ao_depth_samples camera rays per pixel at sample counter 0, the mean distance of
+       those that hit - and every sample of apt_render traces the camera ray, draws ao_smp_hemisphere directions about the hit's shading normal,
+       re-projects the points ao_sample_extent along them onto the film and holds their distance against the depth map there.  The accumulation
+       has upstream's layout: channel 0 the sum of (1 - occlusion), channel 1 zero, channel 2 the depth map (apt_set_accum takes it back from
+       there; apt_reset keeps it); apt_read_pixels hands out channel 0 / cnt on all three channels where the LAST sample's ray hit, else 0.
+       Needs volumetric = 0, light_groups = path_lengths = transient_bins = 0, adaptive_threshold = 0 and world_size = 1 (a sample's depth
+       lookups cross the column shards); max_bounce, num_shadow_ray and the roulette are not read.  (These four sit before the blocks that were
+       there when they were added.) */
+    int32_t ao;                                   /* 0 = off, 1 = ambient occlusion */
+    int32_t ao_smp_hemisphere;                    /* > 0; the sensor's smp_hemisphere (upstream's default 32) */
+    int32_t ao_depth_samples;                     /* >= 0; the sensor's depth_samples (64) */
+    float   ao_sample_extent;                     /* > 0, finite; the sensor's sample_extent (0.1) */
     /* Light groups, surface renderer only: every path contribution is also added to the plane of the emitter its light came
        from - emitter e is row e of apt_scene_desc.src_f - and, within it, to the part that says how the emitter was reached (0: by a sampled
        ray, 1: by a light sample).  Needs volumetric = 0, num_shadow_ray <= 4, world_size = 1, path_lengths = 0, transient_bins = 0 and
@@ -304,6 +318,9 @@ int apt_clear_aov(apt_renderer*);
 /* Denoise colour_in ([x][y][rgb], width*height*3 floats; NULL: the renderer's current pixels, as apt_read_pixels hands them out) into out, guided by
    the feature buffers as they stand.  The settings are checked before the handle and the device.  Same refusals as the feature buffers. */
 int apt_denoise(apt_renderer*, const apt_denoise_cfg* cfg, const float* colour_in, float* out);
+/* ambient-occlusion renders (ao = 1; APT_E_STATE otherwise): the depth map, [local col][y], n_cols * height floats - the mean hit distance of the
+   pixel's ao_depth_samples camera rays, 0 where none hit or outside a crop window */
+int apt_read_ao_depth(apt_renderer*, float* out);
 int apt_get_stats(apt_renderer*, apt_stats* out);
 int apt_device_ptr(apt_renderer*, void** accum_dev, int32_t* cnt); /* device float[n_cols*height*3] accumulation buffer */
 int apt_stream(apt_renderer*, void** hip_stream);         /* the hipStream_t every kernel of this renderer runs on */
