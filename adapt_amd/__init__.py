@@ -9,7 +9,7 @@ The render path is hand-written HIP reached through the C-ABI in include/adapt_m
 """
 from .parsers.xml_parser import scene_parsing  # noqa: F401
 
-__all__ = ["scene_parsing", "Renderer", "VolumeRenderer", "AORenderer", "SSAORenderer", "load_renderer"]
+__all__ = ["scene_parsing", "Renderer", "VolumeRenderer", "AORenderer", "SSAORenderer", "BlinnPhongTracer", "load_renderer"]
 __version__ = "0.1.0"
 
 
@@ -23,6 +23,9 @@ def __getattr__(name):
     if name in ("AORenderer", "SSAORenderer"):
         from .renderer import AORenderer
         return AORenderer
+    if name == "BlinnPhongTracer":
+        from .renderer import BlinnPhongTracer
+        return BlinnPhongTracer
     raise AttributeError(name)
 
 

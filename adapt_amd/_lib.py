@@ -47,7 +47,8 @@ class RenderCfg(C.Structure):
                 ("cam_r", C.c_float * 9), ("cam_t", C.c_float * 3),
                 ("inv_focal", C.c_float), ("half_w", C.c_float), ("half_h", C.c_float), ("seed", C.c_uint32),
                 ("band_width", C.c_int32), ("rank", C.c_int32), ("world_size", C.c_int32),
-                ("spp_per_batch", C.c_int32), ("device", C.c_int32), ("profile", C.c_int32), ("volumetric", C.c_int32),
+                ("spp_per_batch", C.c_int32), ("device", C.c_int32), ("profile", C.c_int32),
+                ("direct", C.c_int32), ("direct_intensity", C.c_float * 3), ("volumetric", C.c_int32),
                 ("ao", C.c_int32), ("ao_smp_hemisphere", C.c_int32), ("ao_depth_samples", C.c_int32), ("ao_sample_extent", C.c_float),
                 ("light_groups", C.c_int32), ("path_lengths", C.c_int32),
                 ("adaptive_threshold", C.c_float), ("adaptive_min_spp", C.c_int32), ("adaptive_step", C.c_int32),
@@ -119,6 +120,8 @@ SYMBOLS = {
     "apt_clear_aov": (C.c_int, [C.c_void_p]),
     "apt_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseCfg), f32p, f32p]),
     "apt_read_ao_depth": (C.c_int, [C.c_void_p, f32p]),
+    "apt_render_direct": (C.c_int, [C.c_void_p, f32p, C.c_int32, f32p]),
+    "apt_read_direct_maps": (C.c_int, [C.c_void_p, f32p, f32p]),
     "apt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "apt_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), i32p]),
     "apt_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

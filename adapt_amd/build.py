@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libadapt_mi.so")                 # default build: fast arithmetic (APT_FAST=1)
 LIB_EXACT = os.path.join(HERE, "libadapt_mi_exact.so")     # bit-parity build: the reference's float32 arithmetic, operation for operation
 SOURCES = ["api.hip", "bvh_gpu.hip", "bvh_build.cpp", "bvh_linear.cpp", "bvh_wide.cpp", "flat_build.cpp"]
-HEADERS = ["vec.hpp", "rng.hpp", "shading.hpp", "traverse.hpp", "stages.hpp", "shade_stage.hpp", "unit_kernels.hpp", "aov.hpp", "ao.hpp","bvh_build.hpp", os.path.join("..", "..", "include", "adapt_mi.h"), "volumetric.hpp"]
+HEADERS = ["vec.hpp", "rng.hpp", "shading.hpp", "traverse.hpp", "stages.hpp", "shade_stage.hpp", "unit_kernels.hpp", "aov.hpp", "ao.hpp", "direct.hpp", "bvh_build.hpp", os.path.join("..", "..", "include", "adapt_mi.h"), "volumetric.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-fast-math",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
          # every queue/list append here is already aggregated per wave by hand (ballot + one atomic from lane 0);

@@ -24,6 +24,7 @@
 #include "unit_kernels.hpp"
 #include "aov.hpp"
 #include "ao.hpp"
+#include "direct.hpp"
 #include "volumetric.hpp"
 
 #define APT_EXPORT extern "C" __attribute__((visibility("default")))
@@ -232,7 +233,8 @@ struct Lane {
 //   PIPE_VOLUMETRIC  extend, k_vevent, one kernel per event queue, transmittance walk   (render_volumetric)
 //   PIPE_AO          ambient occlusion: one trace-and-occlude kernel and one ordered sum per batch, no shade, shadow or class launch (render_ao; ao.hpp)
 // A split render (apt_renderer::split_mode) and an adaptive one (::adaptive) are modifiers on top of it.
-enum Pipeline { PIPE_STAGED, PIPE_SORTED, PIPE_TRACED, PIPE_VOLUMETRIC, PIPE_AO };
+//   PIPE_DIRECT      direct-light viewer: one hit kernel at creation, one shade kernel per apt_render_direct launch, no sample loop (render_direct; direct.hpp)
+enum Pipeline { PIPE_STAGED, PIPE_SORTED, PIPE_TRACED, PIPE_VOLUMETRIC, PIPE_AO, PIPE_DIRECT };
 
 // A split render keeps a surface render's contributions apart: by arrival time, by segment count or by emitter.  One
 // mechanism - the TR shade twins, the per-path records (stages.hpp TransQ), a binning kernel per settled bounce, one render lane - and per
@@ -329,6 +331,10 @@ struct apt_renderer {
     // ambient occlusion (apt_render_cfg.ao; ao.hpp): the depth map is made once, by apt_renderer_create
     DevBuf ao_rec, ao_depth, ao_hits, ao_last;      // per-slot records (spp_batch samples in flight), the depth map, the depth pass's hit counts, per pixel whether the last sample hit
     AoQ aoq{};
+    // direct-light viewer (apt_render_cfg.direct; direct.hpp): the hit pass runs once, in apt_renderer_create
+    DevBuf dr_depth, dr_normal, dr_obj, dr_emit, dr_frames;      // the hit pass's three words per pixel; a launch's light positions and its frames (dr_cap of each)
+    int dr_cap = 0, dr_last = 0;          // frames the buffers hold; which of them apt_read_pixels hands out (the last one shaded)
+    DirectQ drq{};
 };
 
 static int count_device(int* n) {
@@ -783,12 +789,14 @@ static int plan_film(apt_renderer* r) {
     r->n_lanes = 3;   // measured on C2: 1 lane 1 827, 2 lanes 2 196, 3 lanes 2 268, 4 lanes 2 178 Msamples/s (round 2, 64 spp per lane-batch); round 5, 32 Mi paths per lane-batch: C2 4 559 / 4 590 / 4 287 with 2 / 3 / 4, C5 1 844 / 2 028 / 2 129 with 1 / 2 / 3; volumetric scenes with null surfaces ran four lanes in rounds 3-4 (the fourth hid the host read-backs of their tails): at this batch size V1 1 374 with three, 1 299 with four
     if (const char* nl = getenv("APT_LANES")) r->n_lanes = std::min(4, std::max(1, atoi(nl)));
     if (c.ao) r->n_lanes = 1;            // ambient occlusion: one kernel per batch on one stream
+    if (c.direct) r->n_lanes = 1;        // direct-light viewer: one kernel per call
     if (r->split()) r->n_lanes = 1;      // a split render's cells are shared by every batch and added to per bounce: one lane keeps the adds in order
     const size_t nq = (size_t)r->nq;
     // queue capacity of a batch of b: whole waves, dealt over the sub-queues (generate: wave w -> sub-queue w % nq)
     auto subcap_of = [&](int b) { const size_t n_waves = ((size_t)r->npix * (size_t)b + 63) / 64; return ((n_waves + nq - 1) / nq) * 64; };
     int B = c.spp_per_batch;
     if (c.ao && B <= 0) B = std::max(1, std::min(APT_AO_MAX_BATCH, (int)(APT_AO_MAX_SLOTS / (size_t)r->npix)));      // a slot is 8 bytes and a gather-bound kernel: a few samples in flight fill the device
+    if (c.direct) B = 1;                 // direct-light viewer: no samples in flight; the lane's queues serve apt_intersect alone
     if (B <= 0) {
         // ~32 Mi paths per lane-batch (5-17 GB of queues each, of 288 GB) whatever the tile size: an 8-GPU rank owns 1/8 of the pixels and takes
         // 8x the samples per batch.  Measured 16 Mi -> 32 Mi on one box: C2 4 547 -> 4 685, C3 1 150 -> 1 177, C4 1 840 -> 1 922, C5 1 971 ->
@@ -897,6 +905,7 @@ static int pick_shading(apt_renderer* r) {
     const bool can_trace = r->trace_mode == TRACE_FLAT && S == 1 && !r->split() && r->shade->traced.queue[0][0] != nullptr;
     r->pipeline = c.volumetric ? PIPE_VOLUMETRIC : (sorted ? PIPE_SORTED : ((can_trace && want_traced) ? PIPE_TRACED : PIPE_STAGED));
     if (c.ao) r->pipeline = PIPE_AO;
+    if (c.direct) r->pipeline = PIPE_DIRECT;
     p.traced = (r->pipeline == PIPE_TRACED) ? 1 : 0;
     pick_traced_kernels(r);
     // flat sweep with several light samples per vertex: the samples are queued by vertex and the shadow kernel adds a vertex's samples with
@@ -939,6 +948,7 @@ static int pick_shading(apt_renderer* r) {
         r->shade_name = r->shade->name;
         if (r->pipeline == PIPE_TRACED) r->shade_name += " [rays traced in place]";
         if (r->pipeline == PIPE_AO) r->shade_name = "ambient occlusion: screen-space, against the camera's depth map";
+        if (r->pipeline == PIPE_DIRECT) r->shade_name = "direct-light viewer: Blinn-Phong under one point light";
     }
     r->shade_name += kSplit[r->split_mode].tag;
     if (r->adaptive) r->shade_name += " [adaptive]";
@@ -1221,7 +1231,7 @@ static int plan_lds_and_grids(apt_renderer* r) {
     }
     // streaming stages: persistent grid in 256-thread workgroups per CU.  (rays traced in place: the kernel holds FIVE workgroups per CU since round 5 - one lane 3 440 -> 3 630 Msamples/s on C2 with 5 per CU, three lanes level)  streaming stages, persistent grid in 256-thread workgroups per CU.  Measured (tools/grid_sweep.sh, 2 / 3 / 4 / 5 / 8 per CU): C2 3 385 / 3 350 / 3 378 / 3 312 / 3 279 Msamples/s (a shade kernel holds 4 workgroups per CU; a second round of workgroups only adds a tail), C1 / C3 / C4 / C5 within 1 %, V1 823 / 838 / 842 / 840 / 858
     // (round 6: class-sorted renders too - their lean group holds five workgroups per CU now: C5 2 243 -> 2 261, C3 one lane 1 035 -> 1 103, three lanes level)
-    static const int kSmallPerCu[5] = {4, 5, 5, 8, 5};        // [Pipeline]
+    static const int kSmallPerCu[6] = {4, 5, 5, 8, 5, 5};     // [Pipeline]
     r->grid_small = cus * kSmallPerCu[r->pipeline];
     if (const char* g = getenv("APT_GRID_SMALL")) r->grid_small = cus * std::max(1, atoi(g));       // tuning knobs: workgroups per CU
     if (const char* g = getenv("APT_GRID_TRACE")) r->grid_trace = cus * std::max(1, atoi(g));
@@ -1321,6 +1331,21 @@ static int check_ao(const apt_render_cfg& c, SplitMode split_mode) {
     return APT_OK;
 }
 static int make_ao(apt_renderer* r);
+// Direct-light viewer (direct = 1): what it does not combine with.
+static int check_direct(const apt_render_cfg& c, SplitMode split_mode) {
+    if (c.direct != 0 && c.direct != 1) return fail(APT_E_INVALID, "apt_renderer_create: direct must be 0 (off) or 1");
+    if (!c.direct) return APT_OK;
+    if (!(std::isfinite(c.direct_intensity[0]) && std::isfinite(c.direct_intensity[1]) && std::isfinite(c.direct_intensity[2])))
+        return fail(APT_E_INVALID, "apt_renderer_create: the direct-light viewer needs a finite direct_intensity");
+    if (c.volumetric) return fail(APT_E_INVALID, "apt_renderer_create: the direct-light viewer is a surface-renderer mode (volumetric = 0)");
+    if (c.ao) return fail(APT_E_INVALID, "apt_renderer_create: the direct-light viewer and ambient occlusion do not combine (ao must be 0 when direct = 1)");
+    if (split_mode != SPLIT_NONE)
+        return fail(APT_E_INVALID, std::string("apt_renderer_create: the direct-light viewer and ") + kSplit[split_mode].subject + " do not combine (" + kSplit[split_mode].field + " must be 0 when direct = 1)");
+    if (c.adaptive_threshold > 0.f) return fail(APT_E_INVALID, "apt_renderer_create: the direct-light viewer and adaptive sampling do not combine (adaptive_threshold must be 0 when direct = 1)");
+    if (c.world_size > 1) return fail(APT_E_INVALID, "apt_renderer_create: the direct-light viewer runs on one rank (world_size = 1): its frames are whole films");
+    return APT_OK;
+}
+static int make_direct(apt_renderer* r);
 APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cfg, apt_renderer** out) {
     if (!sc || !cfg || !out) return fail(APT_E_INVALID, "apt_renderer_create: null argument");
     apt_render_cfg c = *cfg;
@@ -1341,6 +1366,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
         if (c.adaptive_min_spp <= 0 || c.adaptive_step <= 0)
             return fail(APT_E_INVALID, "apt_renderer_create: adaptive sampling needs adaptive_min_spp > 0 and adaptive_step > 0");
     }
+    if (int rc = check_direct(c, split_mode)) return rc;
     if (int rc = check_ao(c, split_mode)) return rc;
     HIP_TRY(hipSetDevice(c.device));
     apt_renderer* r = new apt_renderer();
@@ -1357,6 +1383,7 @@ APT_EXPORT int apt_renderer_create(const apt_scene* sc, const apt_render_cfg* cf
     if (int rc = plan_lds_and_grids(r)) return rc;
     if (int rc = make_overflow_stacks(r)) return rc;
     if (int rc = make_ao(r)) return rc;
+    if (int rc = make_direct(r)) return rc;
     for (Lane& ln : r->lanes) HIP_TRY(hipStreamSynchronize(ln.stream));
     owner.r = nullptr;
     *out = r;
@@ -1704,6 +1731,47 @@ static int make_ao(apt_renderer* r) {
     }
     return APT_OK;
 }
+// Direct-light viewer (BlinnPhongTracer; direct.hpp).  The hit pass, once: the centre ray of every pixel with the renderer's own traversal.
+typedef void (*direct_fn)(DevScene, Params, DirectQ, LdsPlan);
+static const direct_fn kDirectHit[4] = {k_direct_hit<TRACE_BVH>, k_direct_hit<TRACE_SWEEP>, k_direct_hit<TRACE_TILE>, /* TRACE_FLAT */ APT_FLAT_FN(k_direct_hit_flat)};
+static const direct_fn kDirectShade[4] = {k_direct_shade<TRACE_BVH>, k_direct_shade<TRACE_SWEEP>, k_direct_shade<TRACE_TILE>, /* TRACE_FLAT */ APT_FLAT_FN(k_direct_shade_flat)};
+constexpr size_t APT_DIRECT_FRAME_BYTES = (size_t)1 << 30;      // the frame buffer of a sweep: at most 1 GiB (85 frames of 1024 x 1024), at least one frame
+static int direct_frames(apt_renderer* r, int want, int* chunk_out) {      // room for min(want, the chunk) frames; *chunk_out: frames per launch
+    const size_t frame = (size_t)r->npix * 12;
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>(APT_DIRECT_FRAME_BYTES / frame, (size_t)1 << 16));
+    if (const char* e = getenv("APT_DIRECT_CHUNK")) chunk = std::max(1, atoi(e));      // tuning knob, and how the tests reach the several-launch path on a tiny film
+    *chunk_out = chunk;
+    const int need = std::min(want, chunk);
+    if (need > r->dr_cap) {
+        hipError_t e;
+        if ((e = r->dr_frames.alloc(frame * (size_t)need)) != hipSuccess || (e = r->dr_emit.alloc((size_t)need * 12)) != hipSuccess) {
+            r->dr_cap = 0; r->dr_last = 0;
+            return fail(APT_E_NOMEM, std::string("direct-light viewer frames: ") + hipGetErrorString(e));
+        }
+        r->dr_cap = need; r->dr_last = 0;
+        HIP_TRY(hipMemsetAsync(r->dr_frames.p, 0, frame, r->stream()));
+    }
+    return APT_OK;
+}
+static int make_direct(apt_renderer* r) {
+    if (!r->cfg.direct) return APT_OK;
+    const size_t np = (size_t)r->npix;
+    if (!kDirectHit[r->trace_mode] || !kDirectShade[r->trace_mode]) return fail(APT_E_STATE, "apt_renderer_create: the direct-light viewer has no kernel for this traversal in this build");
+    hipError_t e;
+    if ((e = r->dr_depth.alloc(np * 4)) != hipSuccess || (e = r->dr_normal.alloc(np * 12)) != hipSuccess || (e = r->dr_obj.alloc(np * 4)) != hipSuccess)
+        return fail(APT_E_NOMEM, std::string("direct-light viewer buffers: ") + hipGetErrorString(e));
+    DirectQ& q = r->drq;
+    q.depth = r->dr_depth.as<float>(); q.normal = r->dr_normal.as<float>(); q.obj = r->dr_obj.as<int32_t>();
+    q.emit = nullptr; q.frames = nullptr; q.n_frames = 0;
+    for (int k = 0; k < 3; k++) q.intensity[k] = r->cfg.direct_intensity[k];
+    int chunk = 0;
+    if (int rc = direct_frames(r, 1, &chunk)) return rc;   // the frame apt_read_pixels shows before the first call: zeros
+    if (r->lds_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kDirectHit[r->trace_mode], hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
+    if (r->lds_bytes_any > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kDirectShade[r->trace_mode], hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes_any));
+    hipLaunchKernelGGL(kDirectHit[r->trace_mode], dim3(grid_for(np, r->grid_trace, 1, r->trace_items)), dim3(r->trace_nt), r->lds_bytes, r->stream(), r->scene->dev, r->par, r->drq, r->lanes[0].plan);
+    HIP_TRY(hipGetLastError());
+    return APT_OK;
+}
 static int render_steady(apt_renderer* r, int32_t n_spp) { return r->pipeline == PIPE_AO ? render_ao(r, n_spp) : (r->pipeline == PIPE_VOLUMETRIC ? render_volumetric(r, n_spp) : render_surface(r, n_spp)); }
 
 // the live count of the last decision, once its read-back has landed
@@ -1758,6 +1826,7 @@ static int render_impl(apt_renderer* r, int32_t n_spp) {
 }
 APT_EXPORT int apt_render(apt_renderer* r, int32_t n_spp) {
     if (!r || n_spp < 0) return fail(APT_E_INVALID, "apt_render: bad argument");
+    if (r->pipeline == PIPE_DIRECT) return fail(APT_E_STATE, "apt_render: a direct-light viewer takes no samples (direct = 1): apt_render_direct shades it for a light position");
     HIP_TRY(hipSetDevice(r->cfg.device));
     if (r->render_pending) { if (int rc = resolve_events(r)) return rc; }
     const int cnt0 = r->cnt;
@@ -1786,6 +1855,10 @@ APT_EXPORT int apt_read_pixels(apt_renderer* r, float* out) {
     if (!r || !out) return fail(APT_E_INVALID, "apt_read_pixels: bad argument");
     HIP_TRY(hipSetDevice(r->cfg.device));
     const uint32_t n = (uint32_t)r->npix * 3u;
+    if (r->pipeline == PIPE_DIRECT) {      // the last frame shaded (zeros before the first call); nothing to divide
+        HIP_TRY(hipMemcpyAsync(out, r->dr_frames.as<float>() + (size_t)r->dr_last * n, (size_t)n * 4, hipMemcpyDeviceToHost, r->stream()));
+        return resolve_events(r);
+    }
     const float inv = (float)(r->cnt > 0 ? r->cnt : 1);     // before the first sample the image is all zero
     if (r->pipeline == PIPE_AO) hipLaunchKernelGGL(k_ao_pixels, dim3(((uint32_t)r->npix + 255) / 256), dim3(256), 0, r->stream(), (const float*)r->accum.as<float>(), (const int32_t*)r->aoq.last_hit, r->scratch.as<float>(), (uint32_t)r->npix, inv);
     else if (r->adaptive) hipLaunchKernelGGL(k_divide_ad, dim3((n + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), (const int32_t*)r->ad_n.p, r->scratch.as<float>(), n);
@@ -1795,6 +1868,7 @@ APT_EXPORT int apt_read_pixels(apt_renderer* r, float* out) {
 }
 APT_EXPORT int apt_get_accum(apt_renderer* r, float* out, int32_t* cnt) {
     if (!r || !out) return fail(APT_E_INVALID, "apt_get_accum: bad argument");
+    if (r->pipeline == PIPE_DIRECT) return fail(APT_E_STATE, "apt_get_accum: a direct-light viewer keeps no accumulation (direct = 1)");
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemcpyAsync(out, r->accum.p, (size_t)r->npix * 12, hipMemcpyDeviceToHost, r->stream()));
     if (cnt) *cnt = r->cnt;
@@ -1802,6 +1876,7 @@ APT_EXPORT int apt_get_accum(apt_renderer* r, float* out, int32_t* cnt) {
 }
 APT_EXPORT int apt_set_accum(apt_renderer* r, const float* in, int32_t cnt) {
     if (!r || !in || cnt < 0) return fail(APT_E_INVALID, "apt_set_accum: bad argument");
+    if (r->pipeline == PIPE_DIRECT) return fail(APT_E_STATE, "apt_set_accum: a direct-light viewer keeps no accumulation (direct = 1)");
     HIP_TRY(hipSetDevice(r->cfg.device));
     HIP_TRY(hipMemcpyAsync(r->accum.p, in, (size_t)r->npix * 12, hipMemcpyHostToDevice, r->stream()));
     if (r->pipeline == PIPE_AO) {      // channel 2 is the depth map (upstream's checkpoint layout); `pixels` shows every pixel until the next sample says otherwise
@@ -1842,6 +1917,7 @@ APT_EXPORT int apt_relight(apt_renderer* r, const float* gains, float* out) {
 }
 APT_EXPORT int apt_reset(apt_renderer* r) {
     if (!r) return fail(APT_E_INVALID, "apt_reset: null handle");
+    if (r->pipeline == PIPE_DIRECT) return APT_OK;      // (upstream's reset is an empty kernel, and a viewer has nothing that adds up)
     HIP_TRY(hipSetDevice(r->cfg.device));
     if (r->pipeline == PIPE_AO) hipLaunchKernelGGL(k_ao_reset, dim3(((uint32_t)r->npix + 255) / 256), dim3(256), 0, r->stream(), r->accum.as<float>(), (const float*)r->aoq.depth, r->aoq.last_hit, (uint32_t)r->npix);      // (the depth map stays: channel 2 is put back from it)
     else HIP_TRY(hipMemsetAsync(r->accum.p, 0, (size_t)r->npix * 12, r->stream()));
@@ -1939,6 +2015,7 @@ APT_EXPORT int apt_get_stats(apt_renderer* r, apt_stats* out) {
 }
 APT_EXPORT int apt_device_ptr(apt_renderer* r, void** accum_dev, int32_t* cnt) {
     if (!r || !accum_dev) return fail(APT_E_INVALID, "apt_device_ptr: bad argument");
+    if (r->pipeline == PIPE_DIRECT) return fail(APT_E_STATE, "apt_device_ptr: a direct-light viewer keeps no accumulation (direct = 1)");
     *accum_dev = r->accum.p;
     if (cnt) *cnt = r->cnt;
     return APT_OK;
@@ -1958,10 +2035,44 @@ APT_EXPORT int apt_read_ao_depth(apt_renderer* r, float* out) {
     return resolve_events(r);
 }
 
+// ---- direct-light viewer: n light positions shaded in ceil(n / chunk) launches; each launch reads a pixel's hit once (direct.hpp k_direct_shade)
+APT_EXPORT int apt_render_direct(apt_renderer* r, const float* emit_pos, int32_t n, float* out) {
+    if (!r) return fail(APT_E_INVALID, "apt_render_direct: null handle");
+    if (r->pipeline != PIPE_DIRECT) return fail(APT_E_STATE, "apt_render_direct: the renderer was created with direct = 0");
+    if (!emit_pos || n <= 0) return fail(APT_E_INVALID, "apt_render_direct: needs n >= 1 light positions");
+    for (size_t k = 0; k < (size_t)n * 3; k++)
+        if (!std::isfinite(emit_pos[k])) return fail(APT_E_INVALID, "apt_render_direct: a light position has a non-finite coordinate");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    int chunk = 0;
+    if (int rc = direct_frames(r, n, &chunk)) return rc;
+    const size_t frame = (size_t)r->npix * 3;
+    hipStream_t st = r->stream();
+    for (int done = 0; done < n;) {
+        const int F = std::min(std::min(chunk, r->dr_cap), n - done);
+        HIP_TRY(hipMemcpyAsync(r->dr_emit.p, emit_pos + 3 * (size_t)done, (size_t)F * 12, hipMemcpyHostToDevice, st));
+        DirectQ q = r->drq; q.emit = r->dr_emit.as<float>(); q.frames = r->dr_frames.as<float>(); q.n_frames = F;
+        { LaunchTimer t(r, APT_K_SHADOW, st); hipLaunchKernelGGL(kDirectShade[r->trace_mode], dim3(grid_for((size_t)r->npix, r->grid_shadow, 1, r->trace_items)), dim3(r->trace_nt), r->lds_bytes_any, st, r->scene->dev, r->par, q, r->lanes[0].plan); }
+        HIP_TRY(hipGetLastError());
+        r->dr_last = F - 1;
+        if (out) HIP_TRY(hipMemcpyAsync(out + (size_t)done * frame, r->dr_frames.p, (size_t)F * frame * 4, hipMemcpyDeviceToHost, st));
+        done += F;
+    }
+    return resolve_events(r);
+}
+APT_EXPORT int apt_read_direct_maps(apt_renderer* r, float* depth, float* normal) {
+    if (!r) return fail(APT_E_INVALID, "apt_read_direct_maps: null handle");
+    if (r->pipeline != PIPE_DIRECT) return fail(APT_E_STATE, "apt_read_direct_maps: the renderer was created with direct = 0");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (depth) HIP_TRY(hipMemcpyAsync(depth, r->dr_depth.p, (size_t)r->npix * 4, hipMemcpyDeviceToHost, r->stream()));
+    if (normal) HIP_TRY(hipMemcpyAsync(normal, r->dr_normal.p, (size_t)r->npix * 12, hipMemcpyDeviceToHost, r->stream()));
+    return resolve_events(r);
+}
+
 // ---- feature buffers (AOV pass) and denoiser: aov.hpp, DESIGN.md 4.7
 // Both describe the camera ray's first SURFACE hit of one rank's whole film: the volumetric tracer's first event through null surfaces and
 // fog is another question, and a rank owns bands of the film, not the neighbourhoods a filter reads.
 static int aov_refuse(const apt_renderer* r, const char* who) {
+    if (r->cfg.direct) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser belong to the path tracer (direct = 0): a direct-light viewer keeps a depth and a normal map of its own (apt_read_direct_maps)");
     if (r->cfg.ao) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser belong to the path tracer (ao = 0): an ambient-occlusion renderer keeps a depth map of its own (apt_read_ao_depth)");
     if (r->cfg.volumetric) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser belong to the surface renderer (volumetric = 0)");
     if (r->cfg.world_size > 1) return fail(APT_E_INVALID, std::string(who) + ": feature buffers and the denoiser run on one rank (world_size = 1)");

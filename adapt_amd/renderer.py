@@ -65,7 +65,7 @@ from . import _lib
 from .scene_pack import FlatScene, RenderConfig, make_config, pack_scene
 from .tiles import TilePlan
 
-__all__ = ["Renderer", "VolumeRenderer", "AORenderer", "SSAORenderer","DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error", "DENOISE_DEFAULTS"]
+__all__ = ["Renderer", "VolumeRenderer", "AORenderer", "SSAORenderer", "BlinnPhongTracer", "DeviceScene", "bxdf_probe", "medium_probe", "volume_probe", "rng_stream", "adaptive_config", "adaptive_segments", "relative_error", "DENOISE_DEFAULTS"]
 
 ADAPTIVE_DEFAULTS = {"min_spp": 64, "step": 32}
 # apt_denoise_cfg's defaults (include/adapt_mi.h; DESIGN.md §4.7 says how they were chosen)
@@ -868,6 +868,114 @@ class AORenderer(Renderer):
 
 
 SSAORenderer = AORenderer
+
+
+class _MapView:
+    """`rdr.depth_map` / `rdr.norm_map`: objects with .to_numpy(), as upstream's fields"""
+
+    def __init__(self, read): self._read = read
+    def to_numpy(self): return self._read()
+
+
+def light_positions(positions) -> np.ndarray:
+    """(F, 3) float32 from one position or a sequence of them; a ValueError for any other shape or a non-finite coordinate"""
+    p = np.ascontiguousarray(positions, np.float32)
+    if p.ndim == 1:
+        p = p.reshape(1, -1)
+    if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] == 0:
+        raise ValueError(f"light positions: expected (3,) or (F, 3) with F >= 1, got {np.shape(positions)}")
+    if not np.isfinite(p).all():
+        raise ValueError("light positions: every coordinate must be finite")
+    return p
+
+
+def unlit_objects(objects: List) -> List:
+    """copies of the objects with no emitter attached: the viewer shades emissive objects like any other (direct_render.py:49-60 reads no
+    emitter reference), and its scene holds one light, the point source"""
+    import copy
+    out = []
+    for o in objects:
+        o = copy.copy(o)
+        o.emitter_ref_id = -1
+        out.append(o)
+    return out
+
+
+class BlinnPhongTracer(Renderer):
+    """Drop-in for the reference's `BlinnPhongTracer` (renderer/direct_render.py): the direct-light viewer.  One ray
+    through the centre of every pixel of the whole film - no jitter, no crop, no random number -, traced once, when the object is made;
+    every `render(emit_pos)` then shades those hits with a Blinn-Phong highlight under ONE point light at `emit_pos`, dimmed to a tenth
+    where the light is occluded.  Nothing accumulates.
+
+        bpt = BlinnPhongTracer(emitter, array_info, objects, prop)     # a point source: its intensity is used, its position is not
+        bpt.render(emitter.pos)
+        bpt.pixels.to_numpy()          # (w, h, 3): the frame of the last position shaded
+        bpt.depth_map.to_numpy()       # (w, h): hit distance, 0 for a miss;   bpt.norm_map.to_numpy(): (w, h, 3), the shading normal
+        bpt.render_sweep(positions)    # (F, w, h, 3): F positions in one launch, the hits read once
+
+    `Renderer.direct()` is something else: the path-length split's direct light."""
+
+    def __init__(self, emitter, array_info: dict, objects: List, prop: dict, *, device: int = 0, exact: Optional[bool] = None, profile: bool = False):
+        if isinstance(emitter, (list, tuple)) or getattr(emitter, "type", None) != "point":
+            what = f"{len(emitter)} emitters" if isinstance(emitter, (list, tuple)) else f"a '{getattr(emitter, 'type', type(emitter).__name__)}' emitter"
+            raise ValueError(f"BlinnPhongTracer: this tracer only supports one point source (renderer/direct_render.py:30), got {what}")
+        self.emit_int = np.float32(emitter.intensity).reshape(3)
+        super().__init__([emitter], array_info, unlit_objects(objects), prop, device=device, exact=exact, profile=profile, aov_spp=0)
+        # what TracerBase fixes whatever the sensor says (tracer_base.py:60-61); the loop of direct_render.py:64 has no crop test
+        self.anti_alias = self.stratified_sample = False
+        self.depth_map = _MapView(lambda: self._maps()[0])
+        self.norm_map = _MapView(lambda: self._maps()[1])
+
+    def _configure(self, cfg, prop: dict):
+        cfg.direct = 1
+        cfg.direct_intensity = (C.c_float * 3)(*self.emit_int.tolist())
+        cfg.anti_alias = cfg.stratified = cfg.do_crop = 0
+        cfg.start_x = cfg.start_y = 0
+        cfg.end_x, cfg.end_y = cfg.width, cfg.height
+
+    def _maps(self):
+        depth, normal = np.empty((self.w, self.h), np.float32), np.empty((self.w, self.h, 3), np.float32)
+        _lib.check(self.lib.apt_read_direct_maps(self.handle, _fp(depth), _fp(normal)), "apt_read_direct_maps", self.lib)
+        return depth, normal
+
+    def render(self, emit_pos):
+        """Shade the film for a light at `emit_pos`; `pixels` holds the frame afterwards (direct_render.py:63-88)"""
+        p = light_positions(emit_pos)
+        if p.shape[0] != 1:
+            raise ValueError("BlinnPhongTracer.render takes one light position; render_sweep takes several")
+        _lib.check(self.lib.apt_render_direct(self.handle, _fp(p), 1, None), "apt_render_direct", self.lib)
+
+    def render_sweep(self, positions, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """(F, w, h, 3) float32: the frames of F light positions, shaded in one launch (or a few, where the frame buffer sets a chunk);
+        `pixels` holds the last one afterwards.  out: a C-contiguous float32 array of that shape to fill instead of a new one"""
+        p = light_positions(positions)
+        shape = (p.shape[0], self.w, self.h, 3)
+        if out is None:
+            out = np.empty(shape, np.float32)
+        elif out.shape != shape or out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"render_sweep: out must be a C-contiguous float32 array of shape {shape}")
+        _lib.check(self.lib.apt_render_direct(self.handle, _fp(p), p.shape[0], _fp(out)), "apt_render_direct", self.lib)
+        return out
+
+    def reset(self):
+        """An empty kernel upstream (tracer_base.py:284-286): nothing to do"""
+
+    clear = reset
+
+    def get_check_point(self):
+        raise NotImplementedError("Checkpoint saver is not implemented in TracerBase.")       # (tracer_base.py:104-106)
+
+    def load_check_point(self, check_point: dict):
+        raise NotImplementedError("BlinnPhongTracer keeps nothing a checkpoint could restore")
+
+    def info(self) -> dict:
+        return {**super().info(), "pipeline": "direct", "intensity": self.emit_int.tolist()}
+
+    def summary(self) -> str:
+        self.synchronize()
+        msg = f"Blinn-Phong viewer, {self.w} x {self.h}. Time since creation: {time.time() - self._t0:.3f} s"
+        print(msg)
+        return msg
 
 
 class VolumeRenderer(Renderer):

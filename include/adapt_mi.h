@@ -26,6 +26,7 @@
  *   apt_read_sample_counts / apt_read_moments / apt_set_adaptive_state   (none; adaptive sampling)
  *   apt_render_aov / apt_read_aov / apt_set_aov / apt_clear_aov   (none; per-pixel albedo, normal and depth of the camera rays' first hits)
  *   apt_renderer_create with ao = 1, apt_read_ao_depth   renderer/ssao.py:31-130  SSAORenderer (`--type ao`): depth map at creation, screen-space occlusion per sample
+ *   apt_renderer_create with direct = 1, apt_render_direct, apt_read_direct_maps   renderer/direct_render.py:26-88  BlinnPhongTracer: hits at creation, one point light per call
  *   apt_denoise                    post_processing.py:15-32 (the firefly filter: stage 1) + an edge-avoiding a-trous filter guided by those buffers (stage 2; none upstream)
  *   apt_get_stats                  (none; the reference only has ti.profiler, render.py:154-160)
  *   apt_device_ptr                 (none; hands the tile framebuffer to RCCL for the multi-GPU gather)
@@ -110,6 +111,18 @@ typedef struct apt_render_cfg {
                                                      per lane; the image does not depend on the split */
     int32_t device;                               /* HIP device ordinal */
     int32_t profile;                              /* 1 = time every kernel launch with HIP events */
+    /* Direct-light viewer: direct = 1 makes the handle upstream's BlinnPhongTracer (renderer/direct_render.py) instead of a
+       path tracer.  apt_renderer_create traces the ray through the CENTRE of every pixel of the WHOLE film - anti_alias, stratified and the
+       crop window are not read, no random number is drawn - and keeps each pixel's hit distance, shading normal and object
+       (apt_read_direct_maps).  apt_render_direct then shades the film for one or more positions of ONE point light of intensity
+       direct_intensity: a Blinn-Phong highlight pow(max(dot(h, n_s), 0), k_g) per channel, times min(1 / (1e-5 + d^2), 1e5), times 0.1 where
+       the light is occluded, times the intensity and the material's k_d; a miss is 0.  There is no accumulation: apt_render, apt_get_accum,
+       apt_set_accum and apt_device_ptr return APT_E_STATE, apt_reset does nothing, apt_read_pixels hands out the last frame shaded.
+       Needs volumetric = 0, ao = 0, light_groups = path_lengths = transient_bins = 0, adaptive_threshold = 0 and world_size = 1; max_bounce,
+       num_shadow_ray, the roulette and the jitter flags are not read.  (These two sit before the blocks that were there when they were added
+       and before `volumetric`, which tests/test_ao_host.py pins as the ao block's neighbour.) */
+    int32_t direct;                               /* 0 = off, 1 = direct-light viewer */
+    float   direct_intensity[3];                  /* finite; the point source's rgb intensity (upstream's emit_int) */
     int32_t volumetric;                           /* 0 = Renderer.render (renderer/vanilla_renderer.py:32-120); 1 = VolumeRenderer.render
                                                      (renderer/vpt.py:145-258): free-path sampling in homogeneous media, null surfaces,
                                                      transmittance-tracked light samples */
@@ -321,6 +334,14 @@ int apt_denoise(apt_renderer*, const apt_denoise_cfg* cfg, const float* colour_i
 /* ambient-occlusion renders (ao = 1; APT_E_STATE otherwise): the depth map, [local col][y], n_cols * height floats - the mean hit distance of the
    pixel's ao_depth_samples camera rays, 0 where none hit or outside a crop window */
 int apt_read_ao_depth(apt_renderer*, float* out);
+/* direct-light viewers (direct = 1; APT_E_STATE otherwise).  apt_render_direct shades the film once per light position: emit_pos holds n >= 1
+   positions (n * 3 floats, every one finite: n <= 0, NULL or a non-finite coordinate is APT_E_INVALID); out, where not NULL, takes the n frames,
+   [frame][x][y][rgb], n * width * height * 3 floats.  The per-pixel hits are read once per launch, whatever n is; a sweep too large for the
+   frame buffer runs in several launches.  apt_read_pixels hands out the last frame afterwards.  apt_read_direct_maps copies out what the
+   creation's hit pass kept: depth ([x][y], width * height floats: the hit distance, 0 for a miss) and normal ([x][y][xyz]: the shading normal,
+   not normalised where it is a mix of vertex normals; zero for a miss); either pointer may be NULL. */
+int apt_render_direct(apt_renderer*, const float* emit_pos, int32_t n, float* out);
+int apt_read_direct_maps(apt_renderer*, float* depth, float* normal);
 int apt_get_stats(apt_renderer*, apt_stats* out);
 int apt_device_ptr(apt_renderer*, void** accum_dev, int32_t* cnt); /* device float[n_cols*height*3] accumulation buffer */
 int apt_stream(apt_renderer*, void** hip_stream);         /* the hipStream_t every kernel of this renderer runs on */
